@@ -12,14 +12,19 @@ copy stream) + greedy rollout + sampled rollout (dropout on) + CIDEr-D reward + 
 batches whose features are resident in HBM before the timed region (round 3; one batch, references cooked once
 outside the loop before).  Weak scaling: every rank runs its own 10 images.  Prints ONE JSON line (rank 0).
 
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the line.  --dump-outputs DIR also writes
+what the last timed step computed (dump_outputs).  --full adds everything else, after the timed steps.
+
 --config selects the other BASELINE.json configurations with the same JSON schema (their own `metric` name):
 updown_xe (configs[1], bs64), transformer_xe (configs[3], bs64), aoa_nsc (configs[4], bs10 x 5), newfc_xe (configs[0]).
 
-Extra objects on the line:
+Extra objects on the line with --full:
   roofline      dominant kernel (skinny weight-streaming MFMA GEMM of the decode step): algorithmic bytes
                 / average launch duration from HIP events recorded inside the timed region
   attention     the same for the fused region-attention kernel named by north_star
   cpu_baseline  the oracle's SCST iteration (oracle/scst_step.py, kind "port") on this box's host cores
+  other_configs the other BASELINE configurations (N = 1), or the two DDP ones on the same process group (N > 1)
+  collective    N > 1: all-reduce time and every gradient-exchange mode
 """
 import argparse
 import ctypes as C
@@ -122,6 +127,34 @@ def prof_read(lib, cls):
     return ms.value, n.value, b.value, f.value
 
 
+DUMP_SAMPLE = 1 << 22        # parameter / gradient elements in a dump (2 x 16 MB as float32)
+
+
+def dump_outputs(path, loss, out, flat):
+    """What the last timed step handed its caller, as float32 DIR/<name>.npy: `loss`, the LossWrapper's other tensor outputs
+    (`out_<key>`), and the updated parameters (`params`) with the gradients the step left on them (`grads`).  Parameters are
+    indexed in model.parameters() order, so two builds compare element for element whatever their flat-buffer layout; a model
+    above DUMP_SAMPLE elements contributes a fixed sample: one position drawn (seed 0) from each of DUMP_SAMPLE equal strata."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {'loss': loss}
+    arrays.update(('out_' + k, v) for k, v in out.items() if k != 'loss')
+    sizes = np.array([p.numel() for p in flat.params], dtype=np.int64)
+    starts = np.concatenate(([0], np.cumsum(sizes)[:-1]))
+    total = int(sizes.sum())
+    if total > DUMP_SAMPLE:
+        edges = np.arange(DUMP_SAMPLE + 1, dtype=np.int64) * total // DUMP_SAMPLE
+        pos = edges[:-1] + np.random.default_rng(0).integers(0, edges[1:] - edges[:-1])
+    else:
+        pos = np.arange(total, dtype=np.int64)
+    seg = np.searchsorted(starts, pos, side='right') - 1
+    at = torch.from_numpy(np.asarray(flat.offsets, dtype=np.int64)[seg] + pos - starts[seg]).to(flat.flat.device)
+    arrays['params'] = flat.flat[at]
+    arrays['grads'] = flat.grad[at]
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), np.atleast_1d(t.detach().float().cpu().numpy()))
+
+
 def _opt(name):
     from imagecaptioning.pytorch_amd import synthetic
     if name == 'updown':
@@ -204,7 +237,8 @@ def other_configs(budget_s=150.0):
     # default here) -- reported beside the faithful line because r5's Transformer numbers were measured that way
     runs = [(n, n, {}) for n in OTHER_CONFIGS] + [('transformer_xe_tied_encoder', 'transformer_xe', {'CAPMI_TIE_ENC': '1'})]
     for name, cfg_name, extra_env in runs:
-        cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--config', cfg_name, '--steps', '8', '--warmup', '3', '--brief']
+        cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--config', cfg_name, '--steps', '8', '--warmup', '3', '--full',
+               '--brief']
         if extra_env:
             cmd.append('--no-cpu-baseline')
         t0 = time.perf_counter()
@@ -325,13 +359,21 @@ def main():
     ap.add_argument('--cpu-iters', type=int, default=5)
     ap.add_argument('--config', default='updown_scst', choices=sorted(CONFIGS),
                     help='BASELINE.json configuration (default: configs[2], the one the headline metric is quoted on)')
+    ap.add_argument('--full', action='store_true',
+                    help='beside the headline: roofline and per-kernel samples, HBM copy rate, large-batch attention, the early-exit '
+                         'line, the CPU baseline, the other BASELINE configurations; N > 1: all-reduce time, every exchange mode and '
+                         'the DDP configurations (all after the timed steps)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed as DIR/<name>.npy (float32; see dump_outputs)')
     ap.add_argument('--brief', action='store_true',
-                    help='the headline objects only: no large-batch attention pass, no copy measurement, no early-exit line, no other '
-                         'configurations, a 1-iteration CPU sample (how the default run times the other BASELINE configurations)')
+                    help='with --full, the headline objects only: no large-batch attention pass, no copy measurement, no early-exit '
+                         'line, no other configurations, a 1-iteration CPU sample (how --full times the other BASELINE configurations)')
     ap.add_argument('--no-other-configs', action='store_true', help='do not append the other BASELINE configurations to the line')
     ap.add_argument('--eos-bias', type=float, default=0.0,
                     help='add this to logit.bias[EOS]: a model that ends its captions (random weights never do), for the early-exit line')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     cfg = CONFIGS[args.config]
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -460,10 +502,12 @@ def main():
             ev[1].record()
         return scale
     ts = TrainStep(lw, flat, opt, dev, world=world, all_reduce=_all_reduce if multi else None)
+    last_out = {}           # the LossWrapper's tensor outputs of the latest step (--dump-outputs)
 
     def step():
         if not (mode_now['overlap'] or mode_now['sharded']):
-            loss, _ = ts(pf.get_batch('train'), sc_flag, struc_flag)
+            loss, out = ts(pf.get_batch('train'), sc_flag, struc_flag)
+            last_out.update(out)
             return loss
         return step_legacy()
 
@@ -474,6 +518,7 @@ def main():
         data = pf.get_batch('train')
         out = lw(data['fc_feats'], data['att_feats'], data['labels'], data['masks'], None, data['gts'], gt_indices, sc_flag,
                  struc_flag, False)
+        last_out.update((k, v.detach()) for k, v in out.items() if torch.is_tensor(v))
         loss = out['loss']
         if loss.dim():
             loss = loss.mean()
@@ -538,7 +583,7 @@ def main():
     xe_cfg = args.config in ('updown_xe', 'transformer_xe', 'newfc_xe')
     prof_mask = (1 << 2) if xe_cfg else (1 << 9)        # fat GEMMs (XE steps) / the weight-streaming decode GEMMs
     extra_mask = (1 << 0) | (1 << 3) | ((1 << 9) if xe_cfg else 0)      # small decode GEMMs, fused attention (+ streaming ones of an XE step)
-    if args.no_prof:
+    if args.no_prof or not args.full:
         sampled = set()
     elif args.steps >= 40:
         sampled = {args.steps // 3, (2 * args.steps) // 3}
@@ -574,6 +619,9 @@ def main():
             buf = io.StringIO()
             pstats.Stats(host_prof, stream=buf).sort_stats(key).print_stats(30)
             print('\n'.join(l[:160] for l in buf.getvalue().split('\n') if l.strip()), file=sys.stderr)
+    if args.dump_outputs and rank == 0:
+        # before any further step of --full moves the parameters on
+        dump_outputs(args.dump_outputs, loss, last_out, flat)
     lib.capmi_prof_enable(0)
     graph_sample = None
     if sampled and ts.replays and not (mode_now['overlap'] or mode_now['sharded']):
@@ -602,7 +650,7 @@ def main():
     n_extra = 1                                                   # ... behind the companion classes'
     n_g = n_extra if xe_cfg else n_sampled                        # ... behind the streaming decode GEMMs'
     allreduce_ms = None
-    if dist is not None and not overlap and not sharded:
+    if dist is not None and not overlap and not sharded and args.full:
         # collective time of the single flat all-reduce: HIP events around it on 5 extra (untimed) steps
         ms = []
         for _ in range(5):
@@ -655,7 +703,7 @@ def main():
     captions = B * n * world * args.steps
     value = captions / dt
 
-    if rank == 0:
+    if rank == 0 and args.full:
         copy_gbs = 0.0 if (args.no_prof or args.brief) else measured_copy_gbs(dev)     # kept out of rocprofv3 kernel tables
         # the dominant kernel = ONE instance, gemm_lc_kernel<true,2> (round 3): the decode-step GEMMs that stream >= 24 MB of weights
         # (the language-LSTM gate GEMM, the logit GEMM and the first / un-fused attention-LSTM gate GEMMs; class 9).  The small decode
@@ -752,6 +800,7 @@ def main():
         early = None
         if args.config == 'updown_scst' and world == 1 and not args.no_prof and not args.brief and os.environ.get('CAPMI_EARLY_EXIT', '4') != '0':
             early = early_exit_line(model, flat, lw, pf, gt_indices, opt, B, n)
+    if rank == 0:
         names = {'updown_scst': 'captions/sec/node (UpDown SCST, bs10xsample_n5, 36x2048 feats)',
                  'updown_xe': 'captions/sec/node (UpDown XE, bs64 x 5 captions, 36x2048 feats)',
                  'transformer_xe': 'captions/sec/node (Transformer XE, bs64 x 5 captions, 36x2048 feats)',
@@ -778,14 +827,16 @@ def main():
                                                            '"none" = no gradient exchange (compute only); exposed = mode - none'},
             'step_issue': {'mode': 'hipGraph replay (graph_step.TrainStep)' if ts.replays else 'stepped launch by launch',
                            'captures': ts.captures, 'replays': ts.replays, 'stepped': ts.stepped, 'capture_failed': ts.failed},
-            'loss': float(loss.detach()), 'roofline': roofline, 'attention': attention, 'kernel_ms_per_step': per_class,
-            'early_exit_eos_biased': early, 'cpu_baseline': cpu}
+            'loss': float(loss.detach())}
+        if args.full:
+            line.update({'roofline': roofline, 'attention': attention, 'kernel_ms_per_step': per_class, 'early_exit_eos_biased': early,
+                         'cpu_baseline': cpu})
         WATCH['line'] = line
-        if (args.config == 'updown_scst' and world == 1 and not (args.brief or args.no_prof or args.no_other_configs)
+        if (args.full and args.config == 'updown_scst' and world == 1 and not (args.brief or args.no_prof or args.no_other_configs)
                 and os.environ.get('CAPMI_BENCH_OTHER_CONFIGS', '1') != '0'):
             # every BASELINE configuration on the driver's line, measured after the headline is complete
             line['other_configs'] = other_configs()
-    if multi and os.environ.get('CAPMI_BENCH_MODES', '1') != '0':
+    if multi and args.full and os.environ.get('CAPMI_BENCH_MODES', '1') != '0':
         # every exchange mode in the same run, AFTER the measurement and its line are complete: if a mode hangs on a topology that
         # could not be tested here, the watchdog prints the line without the sweep instead of losing it
         WATCH['phase'] = 'mode sweep'
@@ -796,7 +847,7 @@ def main():
             c['ms_per_step_by_mode'] = {k: (round(v, 3) if isinstance(v, float) else v) for k, v in mode_ms.items()}
             if isinstance(mode_ms.get('none'), float):
                 c['exposed_comm_ms'] = {k: round(v - mode_ms['none'], 3) for k, v in mode_ms.items() if isinstance(v, float) and k != 'none'}
-    if multi and args.config == 'updown_scst' and not (args.brief or args.no_other_configs) \
+    if multi and args.full and args.config == 'updown_scst' and not (args.brief or args.no_other_configs) \
             and os.environ.get('CAPMI_BENCH_DDP_CONFIGS', '1') != '0':
         # ONE N-GPU run answers everything -- the two configurations BASELINE.json names for 8-GPU data parallel,
         # on this process group, after the headline line and the sweep are complete (a hang here: the watchdog prints the line as it is)

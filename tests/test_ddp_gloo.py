@@ -47,7 +47,9 @@ def _worker(rank, world, port, q):
     assert calls['n'] == 1, 'exactly one collective per step'
     assert abs(scale - 1.0 / world) < 1e-12
     avg = [p.grad * scale for p in net.parameters()]
-    q.put((rank, [t.clone() for t in local], [t.clone() for t in avg]))
+    # (numpy copies: a torch tensor in a Queue is shared by file descriptor, which the parent can no longer fetch once this
+    #  process has exited)
+    q.put((rank, [t.numpy().copy() for t in local], [t.numpy().copy() for t in avg]))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -72,7 +74,7 @@ def _worker_buckets(rank, world, port, q):
     flat.on_grads_ready(['0.bias', '1.bias'])          # two non-adjacent parameters -> two collectives
     flat.collect_grads()
     scale = flat.finish_overlap()                      # leftovers: 0.weight, 1.weight
-    q.put((rank, local, flat.grad.clone() * scale, flat.last_collectives))
+    q.put((rank, local.numpy().copy(), (flat.grad * scale).numpy().copy(), flat.last_collectives))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -88,7 +90,7 @@ def test_bucketed_overlapped_allreduce_equals_flat_allreduce():
     got = {}
     for _ in range(world):
         rank, local, avg, n_coll = q.get(timeout=120)
-        got[rank] = (local, avg, n_coll)
+        got[rank] = (torch.from_numpy(local), torch.from_numpy(avg), n_coll)
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
@@ -109,7 +111,7 @@ def test_single_flat_allreduce_averages_gradients():
     got = {}
     for _ in range(world):
         rank, local, avg = q.get(timeout=120)
-        got[rank] = (local, avg)
+        got[rank] = ([torch.from_numpy(t) for t in local], [torch.from_numpy(t) for t in avg])
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
@@ -159,7 +161,7 @@ def _worker_sharded(rank, world, port, q):
                 flat.sharded_step(1e-2, clip_value=0.1, adam=_cpu_adam)
         out.append(flat.flat.clone())
         assert all(torch.equal(p.data, flat.flat[o:o + p.numel()].view_as(p)) for p, o in zip(flat.params, flat.offsets))
-    q.put((rank, out[0], out[1]))
+    q.put((rank, out[0].numpy().copy(), out[1].numpy().copy()))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -177,7 +179,7 @@ def test_sharded_step_reduce_scatter_adam_all_gather_equals_all_reduce():
     got = {}
     for _ in range(world):
         rank, a, b = q.get(timeout=120)
-        got[rank] = (a, b)
+        got[rank] = (torch.from_numpy(a), torch.from_numpy(b))
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0

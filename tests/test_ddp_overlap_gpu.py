@@ -116,7 +116,7 @@ def test_bench_multi_gpu_code_path_on_rccl_with_one_rank(mode):
         env['CAPMI_DDP_OVERLAP'] = '1'
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '1',
-           '--no-cpu-baseline', '--no-prof']
+           '--full', '--no-cpu-baseline', '--no-prof']
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=170 if mode != 'allreduce' else 350)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][-1])
