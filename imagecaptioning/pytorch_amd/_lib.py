@@ -135,6 +135,36 @@ class NewFCBwdScratch(C.Structure):
                 [('partial_capacity', C.c_int64), ('sparse', C.POINTER(SparseLogpGrad))])
 
 
+class Att2in2Weights(C.Structure):
+    _fields_ = [(k, c_f) for k in ('embed', 'i2h_w', 'i2h_b', 'h2h_w', 'h2h_b', 'a2c_w', 'a2c_b', 'h2att_w', 'h2att_b', 'alpha_w',
+                                   'alpha_b', 'logit_w', 'logit_b')]
+
+
+class Att2in2Rollout(C.Structure):
+    _fields_ = ([(k, C.c_int) for k in ('B', 'n', 'N', 'K', 'A', 'R', 'E', 'V1', 'T', 'L')] +
+                [(k, c_f) for k in ('att', 'p_att', 'att_mask', 'drop_xt', 'drop_out')] +
+                [('mode', C.c_int), ('temperature', C.c_float), ('gumbel', c_f), ('seed', C.c_uint64), ('forced', c_f),
+                 ('forced_ld', C.c_int), ('teacher', C.c_int), ('ss_mode', c_f)] +
+                [(k, c_f) for k in ('h', 'c', 'x', 'it_all', 'xin', 'att_h', 'alpha', 'ctx', 'saved', 'h_drop', 'seq', 'seq_logp',
+                                    'sel_logp', 'live', 'it', 'unfinished', 'partial')] + [('partial_capacity', C.c_int64)])
+
+
+class Att2in2Grads(C.Structure):
+    _fields_ = [(k, c_f) for k in ('embed', 'i2h_w', 'i2h_b', 'h2h_w', 'h2h_b', 'a2c_w', 'a2c_b', 'h2att_w', 'h2att_b', 'alpha_w',
+                                   'alpha_b', 'logit_w', 'logit_b', 'd_att', 'd_p_att')]
+
+
+class Att2in2BwdScratch(C.Structure):
+    _fields_ = ([(k, c_f) for k in ('dlogits', 'd_hdrop', 'd_sums', 'd_ctx', 'd_att_h', 'd_e', 'dc', 'd_x', 'partial')] +
+                [('partial_capacity', C.c_int64), ('sparse', C.POINTER(SparseLogpGrad))])
+
+
+class Att2in2Step(C.Structure):
+    _fields_ = ([(k, C.c_int) for k in ('B', 'K', 'A', 'R', 'E', 'V1')] +
+                [(k, c_f) for k in ('att', 'p_att', 'att_mask', 'it', 'xt', 'att_h', 'alpha', 'ctx', 'saved', 'logits', 'partial')] +
+                [('partial_capacity', C.c_int64)])
+
+
 _I, _F, _P, _U64, _I64 = C.c_int, C.c_float, C.c_void_p, C.c_uint64, C.c_int64
 DECODE_NO_REPEAT, DECODE_NO_BAD_ENDING, DECODE_BLOCK_TRIGRAMS = 1, 2, 4      # capmi.h CAPMI_DECODE_*
 SELECT_RAW = 256       # capmi.h CAPMI_SELECT_RAW: OR into the select `mode` -- the stored rows are the logits, not the log-probabilities
@@ -236,6 +266,12 @@ SIGNATURES = {
     'capmi_newfc_rollout_fwd': [C.POINTER(NewFCWeights), C.POINTER(NewFCRollout), _P],
     'capmi_newfc_rollout_bwd': [C.POINTER(NewFCWeights), C.POINTER(NewFCRollout), _P, C.POINTER(NewFCBwdScratch),
                                 C.POINTER(NewFCGrads), _P],
+    'capmi_att2in2_cell_fwd': [_P, _I, _P, _I] + [_P] * 10 + [_I, _I, _P],
+    'capmi_att2in2_cell_bwd': [_P, _P, _P, _I, _I64] + [_P] * 6 + [_I, _I, _P],
+    'capmi_att2in2_rollout_fwd': [C.POINTER(Att2in2Weights), C.POINTER(Att2in2Rollout), _P],
+    'capmi_att2in2_rollout_bwd': [C.POINTER(Att2in2Weights), C.POINTER(Att2in2Rollout), _P, C.POINTER(Att2in2BwdScratch),
+                                  C.POINTER(Att2in2Grads), _P],
+    'capmi_att2in2_decode_step': [C.POINTER(Att2in2Weights), C.POINTER(Att2in2Step), _I, _I, _P, _P, _P, _P, _P],
     'capmi_updown_rollout_fwd': [C.POINTER(UpDownWeights), C.POINTER(UpDownRollout), _P],
     'capmi_updown_rollout_bwd': [C.POINTER(UpDownWeights), C.POINTER(UpDownRollout), _P, C.POINTER(UpDownBwdScratch),
                                  C.POINTER(UpDownGrads), _P],

@@ -1,7 +1,7 @@
 """Model factory (reference captioning/models/__init__.py:20-73), hot-path models only."""
 from .AttModel import AttModel, UpDownModel  # noqa: F401
 
-_OUT_OF_SCOPE = ('fc', 'show_tell', 'language_model', 'att2in', 'att2in2', 'att2all2', 'adaatt', 'adaattmo', 'stackatt',
+_OUT_OF_SCOPE = ('fc', 'show_tell', 'language_model', 'att2in', 'att2all2', 'adaatt', 'adaattmo', 'stackatt',
                  'denseatt', 'bert', 'm2transformer')
 
 
@@ -15,6 +15,9 @@ def setup(opt):
     if name == 'transformer':
         from .TransformerModel import TransformerModel
         return TransformerModel(opt)
+    if name == 'att2in2':
+        from .Att2in2Model import Att2in2Model
+        return Att2in2Model(opt)
     if name == 'aoa':
         from .AoAModel import AoAModel
         return AoAModel(opt)

@@ -12,6 +12,7 @@ The fast paths (one native call per rollout / per beam search) do not go through
 
   UpDownStepper   capmi_updown_decode_step  (UpDownCore.forward, AttModel.py:615-640, eval numerics)
   NewFCStepper    maxout LSTMCore.forward   (FCModel.py:13-42 via AttModel.py:904-945)
+  Att2in2Stepper  capmi_att2in2_decode_step (Att2in2Core.forward, AttModel.py:750-790, eval numerics)
 """
 import ctypes as C
 
@@ -128,6 +129,65 @@ class NewFCStepper:
         src, dst = self.state[self.cur], self.state[1 - self.cur]
         beam.reorder_rows(src, dst, parent, self.B, cur, parent.shape[1])
         self.cur = 1 - self.cur
+
+
+class Att2in2Stepper:
+    """Att2in2Model (AttModel.py:854-859): BOS first, no image step; the state is (h, c) of the one cell."""
+
+    def __init__(self, P, pr, rows_per_image_max):
+        from . import att2in2_engine
+        dev = pr.att.device
+        B, K, R = pr.att.shape
+        A = pr.p_att.shape[2]
+        V1, E = P['embed.0.weight'].shape
+        self.P, self.pr = P, pr
+        self.B, self.R, self.V1, self.cap = B, R, V1, int(rows_per_image_max)
+        self.N = N = B * self.cap
+        z = lambda *s: torch.empty(*s, dtype=_f32, device=dev)       # noqa: E731
+        self.ws = ops.default_workspace(dev)
+        self.state = torch.zeros(2, 2, N, R, dtype=_f32, device=dev)   # ping-pong of (h, c)
+        self.cur = 0
+        self.bufs = dict(it=torch.zeros(N, dtype=torch.long, device=dev), xt=z(N, E), att_h=z(N, A), alpha=z(N, K), ctx=z(N, R),
+                         saved=z(N, 5 * R), logits=z(N, V1))
+        s = _lib.Att2in2Step()
+        s.B, s.K, s.A, s.R, s.E, s.V1 = B, K, A, R, E, V1
+        s.att, s.p_att, s.att_mask = ptr(pr.att), ptr(pr.p_att), ptr(pr.att_masks)
+        for k, t in self.bufs.items():
+            setattr(s, k, t.data_ptr())
+        s.partial, s.partial_capacity = self.ws.buf.data_ptr(), self.ws.capacity
+        self.s, self.w = s, att2in2_engine.weights_struct(P)
+
+    def step(self, t, it, rows_per_image):
+        rows = self.B * rows_per_image
+        assert it.shape[0] == rows and rows_per_image <= self.cap
+        self.bufs['it'][:rows].copy_(it)
+        src, dst = self.state[self.cur], self.state[1 - self.cur]
+        check(lib.capmi_att2in2_decode_step(C.byref(self.w), C.byref(self.s), rows, rows_per_image, ptr(src[0]), ptr(src[1]),
+                                            ptr(dst[0]), ptr(dst[1]), stream_ptr()), 'capmi_att2in2_decode_step')
+        self.cur = 1 - self.cur
+        return self.bufs['logits'][:rows]
+
+    def reorder(self, parent, cur):
+        from . import beam
+        src, dst = self.state[self.cur], self.state[1 - self.cur]
+        beam.reorder_rows(src, dst, parent, self.B, cur, parent.shape[1])
+        self.cur = 1 - self.cur
+
+    def snapshot(self):
+        return self.state[self.cur].clone()
+
+    def restore(self, snap):
+        self.state[self.cur].copy_(snap)
+
+    # reference layout of the recurrent state: (h [layers,N,R], c [layers,N,R]); the core reads the last layer and returns one
+    def load_state(self, state, rows):
+        h, c = state
+        s = self.state[self.cur]
+        s[0, :rows], s[1, :rows] = h[-1], c[-1]
+
+    def export_state(self, rows):
+        s = self.state[self.cur]
+        return (s[0, :rows].clone().unsqueeze(0), s[1, :rows].clone().unsqueeze(0))
 
 
 def updown_step(model, it, fc_feats, att_feats, p_att_feats, att_masks, state, output_logsoftmax=1):

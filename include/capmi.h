@@ -951,6 +951,86 @@ int capmi_newfc_rollout_fwd(const capmi_newfc_weights *w, capmi_newfc_rollout *r
 int capmi_newfc_rollout_bwd(const capmi_newfc_weights *w, const capmi_newfc_rollout *r, const float *g_seq_logp,
                             capmi_newfc_bwd_scratch *s, capmi_newfc_grads *g, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Att2in2 decoder (configs/a2i2*.yml): Att2in2Model (AttModel.py:854-859) over Att2in2Core (:750-790).
+ * Per step: att_res = Attention(h_prev) (the capmi_attention_* kernels, queried with the state BEFORE the
+ * step); sums = i2h(x) + h2h(h_prev) [N,5R]; the candidate half (columns 3R..5R) also gets a2c(att_res);
+ * then the maxout cell of NewFC.  Embedding = ReLU + dropout (AttModel.py:74-76), BOS first, no image step.
+ * ------------------------------------------------------------------------------------------- */
+/* cell: sums = sum_s partial[s] (+ addend) + b_i2h + b_h2h ([N,5R] slabs, stride N*5R), and on columns 3R..5R also
+ * sum_s partial2[s] + b_a2c ([N,2R] slabs of the a2c GEMM, stride N*2R; splits2 = 0: none).  Outputs as
+ * capmi_maxout_cell_fwd: h, c, saved [N,5R] = (sig(in), sig(f), sig(out), cand_a, cand_b), h_drop = h * out_mask. */
+int capmi_att2in2_cell_fwd(const float *partial, int splits, const float *partial2, int splits2, const float *addend,
+                           const float *b_i2h, const float *b_h2h, const float *b_a2c, const float *c_prev, float *h,
+                           float *c, float *saved, const float *out_mask, float *h_drop, int N, int R, void *stream);
+/* dh = dh_a (* dh_a_mask) + sum_{s<b_splits} dh_b[s*b_stride + r*R + j] (a dX GEMM left as slabs; NULL: none);
+ * writes d_sums [N,5R] (whose columns 3R..5R are also the gradient of the a2c output) and dc_prev [N,R]. */
+int capmi_att2in2_cell_bwd(const float *dh_a, const float *dh_a_mask, const float *dh_b, int b_splits, int64_t b_stride,
+                           const float *dc_next, const float *saved, const float *c_prev, const float *c_new, float *d_sums,
+                           float *dc_prev, int N, int R, void *stream);
+
+typedef struct capmi_att2in2_weights {
+    const float *embed;                /* [V1,E]  embed.0.weight */
+    const float *i2h_w, *i2h_b;        /* [5R,E],[5R]  core.i2h */
+    const float *h2h_w, *h2h_b;        /* [5R,R],[5R]  core.h2h */
+    const float *a2c_w, *a2c_b;        /* [2R,R],[2R]  core.a2c */
+    const float *h2att_w, *h2att_b;    /* [A,R],[A]    core.attention.h2att */
+    const float *alpha_w, *alpha_b;    /* [A],[1]      core.attention.alpha_net */
+    const float *logit_w, *logit_b;    /* [V1,R],[V1]  logit */
+} capmi_att2in2_weights;
+
+typedef struct capmi_att2in2_rollout {
+    int B, n, N, K, A, R, E, V1, T, L;
+    const float *att, *p_att, *att_mask;   /* [B,K,R] att_embed output, [B,K,A] ctx2att output, [B,K] or NULL */
+    const float *drop_xt, *drop_out;       /* [T,N,E], [T,N,R] keep masks (embedding / core output dropout) or NULL */
+    int mode; float temperature; const float *gumbel; uint64_t seed;
+    const int64_t *forced; int forced_ld; int teacher;
+    const uint8_t *ss_mode;   /* [T,N] or NULL (teacher only): scheduled sampling, as capmi_updown_rollout.ss_mode */
+    float *h, *c;             /* [T+1,N,R]  slot 0 = zero state, slot t+1 after step t */
+    float *x;                 /* [T,N,E]    input embeddings */
+    int64_t *it_all;          /* [T,N]      input tokens */
+    float *xin;               /* [T,N,5R]   teacher forcing: i2h product of all steps (one GEMM), or NULL */
+    float *att_h, *alpha, *ctx;   /* [T,N,A], [T,N,K], [T,N,R] */
+    float *saved, *h_drop;    /* [T,N,5R], [T,N,R] */
+    int64_t *seq; float *seq_logp; float *sel_logp; uint8_t *live;   /* [N,L], [N,L,V1], [N,L], [N,L] */
+    int64_t *it; uint8_t *unfinished;
+    float *partial; int64_t partial_capacity;
+} capmi_att2in2_rollout;
+
+typedef struct capmi_att2in2_grads {
+    float *embed, *i2h_w, *i2h_b, *h2h_w, *h2h_b, *a2c_w, *a2c_b, *h2att_w, *h2att_b, *alpha_w, *alpha_b, *logit_w, *logit_b;
+    float *d_att, *d_p_att;   /* [B,K,R], [B,K,A]: for the prefill backward (att_embed, ctx2att) */
+} capmi_att2in2_grads;
+
+typedef struct capmi_att2in2_bwd_scratch {
+    float *dlogits;   /* [T,N,V1] */
+    float *d_hdrop;   /* [T,N,R]  */
+    float *d_sums;    /* [T,N,5R] */
+    float *d_ctx;     /* [T,N,R]  */
+    float *d_att_h;   /* [T,N,A]  */
+    float *d_e;       /* [T,N,K]  */
+    float *dc;        /* [2][N,R] */
+    float *d_x;       /* [T,N,E]  */
+    float *partial; int64_t partial_capacity;
+    const capmi_sparse_logp_grad *sparse;   /* as in capmi_updown_bwd_scratch */
+} capmi_att2in2_bwd_scratch;
+
+int capmi_att2in2_rollout_fwd(const capmi_att2in2_weights *w, capmi_att2in2_rollout *r, void *stream);
+int capmi_att2in2_rollout_bwd(const capmi_att2in2_weights *w, const capmi_att2in2_rollout *r, const float *g_seq_logp,
+                              capmi_att2in2_bwd_scratch *s, capmi_att2in2_grads *g, void *stream);
+
+/* one decode step in eval numerics (AttModel.get_logprobs_state up to the logits) for the host-stepped samplers:
+ * rows = B * rows_per_image image-major rows, state (h, c) read from *_src and written to *_dst ([rows,R] each). */
+typedef struct capmi_att2in2_step {
+    int B, K, A, R, E, V1;
+    const float *att, *p_att, *att_mask;   /* [B,K,R], [B,K,A], [B,K] or NULL */
+    const int64_t *it;                      /* [rows] input tokens */
+    float *xt, *att_h, *alpha, *ctx, *saved, *logits;   /* [rows, E | A | K | R | 5R | V1] */
+    float *partial; int64_t partial_capacity;
+} capmi_att2in2_step;
+int capmi_att2in2_decode_step(const capmi_att2in2_weights *w, capmi_att2in2_step *s, int rows, int rows_per_image,
+                              const float *h_src, const float *c_src, float *h_dst, float *c_dst, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
