@@ -165,6 +165,15 @@ class Att2in2Step(C.Structure):
                 [('partial_capacity', C.c_int64)])
 
 
+ENSEMBLE_MAX = 8       # capmi.h CAPMI_ENSEMBLE_MAX
+
+
+class Ensemble(C.Structure):
+    """capmi_ensemble (include/capmi.h): M member rows -> their mixture log-probability"""
+    _fields_ = ([(k, C.c_int) for k in ('M', 'rows', 'V1', 'ld_in', 'ld_out')] + [('in', c_f * ENSEMBLE_MAX),
+                ('w', C.c_float * ENSEMBLE_MAX), ('out', c_f)])
+
+
 _I, _F, _P, _U64, _I64 = C.c_int, C.c_float, C.c_void_p, C.c_uint64, C.c_int64
 DECODE_NO_REPEAT, DECODE_NO_BAD_ENDING, DECODE_BLOCK_TRIGRAMS = 1, 2, 4      # capmi.h CAPMI_DECODE_*
 SELECT_RAW = 256       # capmi.h CAPMI_SELECT_RAW: OR into the select `mode` -- the stored rows are the logits, not the log-probabilities
@@ -272,6 +281,7 @@ SIGNATURES = {
     'capmi_att2in2_rollout_bwd': [C.POINTER(Att2in2Weights), C.POINTER(Att2in2Rollout), _P, C.POINTER(Att2in2BwdScratch),
                                   C.POINTER(Att2in2Grads), _P],
     'capmi_att2in2_decode_step': [C.POINTER(Att2in2Weights), C.POINTER(Att2in2Step), _I, _I, _P, _P, _P, _P, _P],
+    'capmi_ensemble_logprobs': [C.POINTER(Ensemble), _P],
     'capmi_updown_rollout_fwd': [C.POINTER(UpDownWeights), C.POINTER(UpDownRollout), _P],
     'capmi_updown_rollout_bwd': [C.POINTER(UpDownWeights), C.POINTER(UpDownRollout), _P, C.POINTER(UpDownBwdScratch),
                                  C.POINTER(UpDownGrads), _P],

@@ -157,6 +157,23 @@ class AoAModel(CaptionModel):
         _, logp = self._run(dict(n=N // B, T=T_eff, L=T, forced=seq, teacher=True), att_feats, att_masks)
         return logp
 
+    def _decode_stepper(self, fc_feats, att_feats, att_masks, L):
+        """make(rows_per_image) -> aoa_engine.BeamDecoder, the factory _sample builds inline for the decode options (masks clipped to
+        the longest row).  Used by AttEnsemble; L is the caller's decode length (the decoder has none)."""
+        if not att_feats.is_cuda:
+            raise CapmiError('the capmi backend runs on a HIP device only; there is no CPU path')
+        if att_masks is not None:
+            ml = clip_len(att_masks)
+            att_feats, att_masks = att_feats[:, :ml], att_masks[:, :ml].float().contiguous()
+        P = dict(zip(self._param_names, [p.detach() for p in self._param_list()]))
+        att_feats = att_feats.float().contiguous()
+
+        def make(rows):
+            g = engine.AoAGraph(P, {}, self.num_heads, 0.0, 0.0, False, 0)
+            g.prepare(att_feats, att_masks)
+            return engine.BeamDecoder(g, rows)
+        return make
+
     def _sample(self, fc_feats, att_feats, att_masks=None, opt={}):
         method = opt.get('sample_method', 'greedy')
         from imagecaptioning.pytorch_amd import decode

@@ -172,6 +172,12 @@ class Att2in2Model(CaptionModel):
         pr = engine.prepare(P, att_feats.float().contiguous(), None if att_masks is None else att_masks.float())
         return lambda rows: Att2in2Stepper(P, pr, rows)
 
+    def _decode_stepper(self, fc_feats, att_feats, att_masks, L):
+        """make(rows_per_image) -> Att2in2Stepper (= _stepper).  Used by AttEnsemble; L is the caller's decode length (the stepper
+        has none)."""
+        self._device_check(att_feats)
+        return self._stepper(att_feats, att_masks)
+
     def _sample(self, fc_feats, att_feats, att_masks=None, opt={}):
         """Greedy / sampling rollout (AttModel.py:258-352); beam search and the decode-time options on the stepper."""
         from imagecaptioning.pytorch_amd import decode, beam

@@ -339,6 +339,16 @@ class AttModel(CaptionModel):
             cache[key] = (row_img, row_mode, hyp_img)
         return cache[key][:2]
 
+    def _decode_stepper(self, fc_feats, att_feats, att_masks, L):
+        """make(rows_per_image) -> UpDownStepper: the single-step decoder factory _sample builds inline for the decode options
+        (eval numerics, features prepared once).  Used by AttEnsemble; L is the caller's decode length (the stepper has none)."""
+        from imagecaptioning.pytorch_amd.step import UpDownStepper
+        self._device_check(fc_feats)
+        P = {k: v.detach() for k, v in self._named_param_list()}
+        pr = engine.prepare(P, fc_feats.float().contiguous(), att_feats.float().contiguous(),
+                            None if att_masks is None else att_masks.float())
+        return lambda rows: UpDownStepper(P, pr, rows)
+
     def _sample_beam(self, fc_feats, att_feats, att_masks=None, opt={}):
         from imagecaptioning.pytorch_amd.beam import sample_beam
         return sample_beam(self, fc_feats, att_feats, att_masks, opt)

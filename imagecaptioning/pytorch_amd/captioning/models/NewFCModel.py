@@ -107,6 +107,15 @@ class NewFCModel(CaptionModel):
         _, logp = self._run(dict(n=N // B, T=T_eff, L=T, mode='forced', forced=seq, teacher=True), fc_feats)
         return logp
 
+    def _decode_stepper(self, fc_feats, att_feats, att_masks, L):
+        """make(rows_per_image) -> NewFCStepper, the factory _sample builds inline (the image step is taken per stepper).  Used by
+        AttEnsemble; L is the caller's decode length (the stepper has none)."""
+        from imagecaptioning.pytorch_amd.step import NewFCStepper
+        if not fc_feats.is_cuda:
+            raise CapmiError('the capmi backend runs on a HIP device only; there is no CPU path')
+        P = dict(zip(self._param_names, [p.detach() for p in self._param_list()]))
+        return lambda rows: NewFCStepper(P, fc_feats, rows)
+
     def _sample(self, fc_feats, att_feats, att_masks=None, opt={}):
         method = opt.get('sample_method', 'greedy')
         from .utils import parse_sample_method

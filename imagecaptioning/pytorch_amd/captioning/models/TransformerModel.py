@@ -233,6 +233,15 @@ class TransformerModel(CaptionModel):
         sink = sparse_logp.LogpSink()
         return sparse_logp.attach(_Fn.apply(self, att_feats, att_masks, seq, n, sink, _seed, bool(_raw), *params), sink)
 
+    def _decode_stepper(self, fc_feats, att_feats, att_masks, L):
+        """make(rows_per_image) -> transformer_engine.Decoder sized for L steps, the factory _sample builds inline for the decode
+        options (masks clipped by _clip).  Used by AttEnsemble, whose seq_length is the L given here."""
+        if not att_feats.is_cuda:
+            raise CapmiError('the capmi backend runs on a HIP device only; there is no CPU path')
+        att_feats, att_masks = self._clip(att_feats, att_masks)
+        P = self._pdict(self._param_list())
+        return lambda rows: engine.Decoder(P, att_feats, att_masks, self.h, self.N_enc, self.N_dec, int(L), rows)
+
     def _sample(self, fc_feats, att_feats, att_masks=None, opt={}):
         """AttModel._sample for the Transformer.  Tokens are drawn with the KV-cached decoder under no_grad; when a
         gradient is needed (SCST) the log-probs of the drawn tokens are recomputed by ONE teacher-forced pass.  In train

@@ -1,5 +1,6 @@
 """Model factory (reference captioning/models/__init__.py:20-73), hot-path models only."""
 from .AttModel import AttModel, UpDownModel  # noqa: F401
+from .AttEnsemble import AttEnsemble  # noqa: F401
 
 _OUT_OF_SCOPE = ('fc', 'show_tell', 'language_model', 'att2in', 'att2all2', 'adaatt', 'adaattmo', 'stackatt',
                  'denseatt', 'bert', 'm2transformer')

@@ -52,6 +52,14 @@ def load_infos(start_from, id_):
         return pickle.load(f)
 
 
+def load_infos_suffixed(log_dir, id_, suffix=''):
+    """infos_<id>[-suffix].pkl of a run's log directory, as tools/eval_ensemble.py reads it for every --ids entry (the suffix names
+    a checkpoint saved with misc.save_checkpoint(..., append=suffix)).  Unlike load_infos a missing file is an error."""
+    path = os.path.join(log_dir, 'infos_%s%s.pkl' % (id_, ('-' + suffix) if suffix else ''))
+    with open(path, 'rb') as f:
+        return pickle.load(f)
+
+
 def load_optimizer_state(start_from):
     """tools/train.py:112-119: optimizer.pth next to model.pth (None when absent)."""
     path = os.path.join(start_from, 'optimizer.pth')

@@ -1,0 +1,209 @@
+// Test-time ensemble (gfx950): the mixture log-probability of M members' rows.
+// Reference: AttEnsemble.get_logprobs_state (AttEnsemble.py:45-53), log(sum_i w_i softmax(logit_i) / sum_i w_i), here in
+// log space.  See include/capmi.h (capmi_ensemble_logprobs) for the contract and the edge cases.
+#include "capmi_common.h"
+#include "../../../include/capmi.h"
+
+using namespace capmi;
+
+namespace {
+
+constexpr int ENS_T = 256;             // 4 waves per row: 9.3 float4 per thread and member at V1 = 9488
+constexpr int ENS_W = ENS_T / 64;
+
+// what the launch needs, members with weight 0 already dropped (the array is indexed with unrolled constants only:
+// a dynamically indexed kernel-argument array would be copied to scratch)
+struct EnsArgs {
+    const float *in[CAPMI_ENSEMBLE_MAX];
+    float log_w[CAPMI_ENSEMBLE_MAX];
+    float *out;
+    int rows, V1, ld_in, ld_out;
+    int vec;                           // every member's rows share one alignment mod 16 bytes: float4 body
+};
+
+// (max, sum exp(x - max)) folded with x.  A NaN x leaves the max alone and reaches the sum; while the max is still -inf the
+// sum stays 0 without forming -inf - -inf.
+__device__ __forceinline__ void online1(float &m, float &s, float x) {
+    const float nm = fmaxf(m, x);
+    const float base = nm == -INFINITY ? 0.f : nm;
+    s = s * __expf(m - base) + __expf(x - base);
+    m = nm;
+}
+__device__ __forceinline__ void online4(float &m, float &s, f32x4 x) {
+    const float nm = fmaxf(m, fmaxf(fmaxf(x.x, x.y), fmaxf(x.z, x.w)));
+    const float base = nm == -INFINITY ? 0.f : nm;
+    s = s * __expf(m - base) + ((__expf(x.x - base) + __expf(x.y - base)) + (__expf(x.z - base) + __expf(x.w - base)));
+    m = nm;
+}
+
+// block-wide max of M values at once (one barrier pair instead of M), then the rescaled sums likewise
+template <int M>
+__device__ __forceinline__ void block_lse(float (&m)[M], float (&s)[M], float *scratch /* [2][M][ENS_W] */) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+        const float wm = wave_max(m[i]);
+        if (lane == 0) scratch[i * ENS_W + wid] = wm;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+        float r = scratch[i * ENS_W];
+#pragma unroll
+        for (int q = 1; q < ENS_W; ++q) r = fmaxf(r, scratch[i * ENS_W + q]);
+        const float base = r == -INFINITY ? 0.f : r;
+        const float ws = wave_sum(s[i] * __expf(m[i] - base));
+        if (lane == 0) scratch[(M + i) * ENS_W + wid] = ws;
+        m[i] = r;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+        float r = 0.f;
+#pragma unroll
+        for (int q = 0; q < ENS_W; ++q) r += scratch[(M + i) * ENS_W + q];
+        s[i] = r;
+    }
+}
+
+// out = log sum_i exp(a_i) with a_i = (x_i - max_i) - c_i, c_i = log(sum_i) - log w_i, as m + log sum_i exp(a_i - m).
+// x_i - max_i is exact for inputs near the row maximum (logits offset by 1e4 keep their digits); all a_i = -inf gives -inf.
+template <int M>
+__device__ __forceinline__ float mix(const float (&x)[M], const float (&mx)[M], const float (&c)[M]) {
+    float a[M];
+    float m = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+        a[i] = (x[i] - mx[i]) - c[i];
+        m = fmaxf(m, a[i]);
+    }
+    const float base = m == -INFINITY ? 0.f : m;
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < M; ++i) s += __expf(a[i] - base);
+    return base + __logf(s);
+}
+
+template <int M>
+__device__ __forceinline__ float mix_at(const float *const (&row)[M], int v, const float (&mx)[M], const float (&c)[M]) {
+    float x[M];
+#pragma unroll
+    for (int i = 0; i < M; ++i) x[i] = row[i][v];
+    return mix<M>(x, mx, c);
+}
+
+template <int M>
+__global__ __launch_bounds__(ENS_T) void ensemble_logprobs_kernel(const EnsArgs e) {
+    __shared__ float s_red[2 * M * ENS_W];
+    const size_t r = blockIdx.x;
+    const int V1 = e.V1, tid = threadIdx.x;
+    const float *row[M];     // members share ld_in and their base alignment mod 16, so one per-row head aligns them all
+#pragma unroll
+    for (int i = 0; i < M; ++i) row[i] = e.in[i] + r * (size_t)e.ld_in;
+    float *o = e.out + r * (size_t)e.ld_out;
+    // [0, head) scalar, [head, head + 4 nv) float4, [head + 4 nv, V1) scalar; head aligns member 0's row, hence all of them
+    int head = V1, nv = 0;
+    if (e.vec) {
+        head = (int)(((16 - (reinterpret_cast<uintptr_t>(row[0]) & 15)) & 15) >> 2);
+        head = head < V1 ? head : V1;
+        nv = (V1 - head) >> 2;
+    }
+    const int tail = head + 4 * nv;
+
+    // pass 1: per member online max and sum of exp over the row
+    float m[M], s[M];
+#pragma unroll
+    for (int i = 0; i < M; ++i) m[i] = -INFINITY, s[i] = 0.f;
+    for (int q = tid; q < nv; q += ENS_T) {
+        f32x4 x[M];
+#pragma unroll
+        for (int i = 0; i < M; ++i) x[i] = *reinterpret_cast<const f32x4 *>(row[i] + head + 4 * q);
+#pragma unroll
+        for (int i = 0; i < M; ++i) online4(m[i], s[i], x[i]);
+    }
+    for (int v = tid; v < head; v += ENS_T)
+#pragma unroll
+        for (int i = 0; i < M; ++i) online1(m[i], s[i], row[i][v]);
+    for (int v = tail + tid; v < V1; v += ENS_T)
+#pragma unroll
+        for (int i = 0; i < M; ++i) online1(m[i], s[i], row[i][v]);
+    block_lse<M>(m, s, s_red);
+    float c[M];
+#pragma unroll
+    for (int i = 0; i < M; ++i) c[i] = __logf(s[i]) - e.log_w[i];
+
+    // pass 2: re-read the member rows, write the mixture
+    const bool out_vec = ((reinterpret_cast<uintptr_t>(o) ^ reinterpret_cast<uintptr_t>(row[0])) & 15) == 0;
+    for (int q = tid; q < nv; q += ENS_T) {
+        f32x4 x[M];
+#pragma unroll
+        for (int i = 0; i < M; ++i) x[i] = *reinterpret_cast<const f32x4 *>(row[i] + head + 4 * q);
+        f32x4 y;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float xk[M];
+#pragma unroll
+            for (int i = 0; i < M; ++i) xk[i] = x[i][k];
+            y[k] = mix<M>(xk, m, c);
+        }
+        float *op = o + head + 4 * q;
+        if (out_vec) {
+            *reinterpret_cast<f32x4 *>(op) = y;
+        } else {
+            op[0] = y.x; op[1] = y.y; op[2] = y.z; op[3] = y.w;
+        }
+    }
+    for (int v = tid; v < head; v += ENS_T) o[v] = mix_at<M>(row, v, m, c);
+    for (int v = tail + tid; v < V1; v += ENS_T) o[v] = mix_at<M>(row, v, m, c);
+}
+
+template <int M>
+void launch(const EnsArgs &a, hipStream_t st) {
+    hipLaunchKernelGGL(ensemble_logprobs_kernel<M>, dim3(a.rows), dim3(ENS_T), 0, st, a);
+}
+
+bool overlaps(const float *a, size_t na, const float *b, size_t nb) { return a < b + nb && b < a + na; }
+
+}  // namespace
+
+extern "C" int capmi_ensemble_logprobs(const capmi_ensemble *e, void *stream) {
+    if (!e || e->M < 1 || e->M > CAPMI_ENSEMBLE_MAX || e->V1 <= 0 || e->rows < 0 || e->ld_in < e->V1 || e->ld_out < e->V1 || !e->out)
+        return CAPMI_EINVAL;
+    EnsArgs a{};
+    a.out = e->out;
+    a.rows = e->rows;
+    a.V1 = e->V1;
+    a.ld_in = e->ld_in;
+    a.ld_out = e->ld_out;
+    a.vec = 1;
+    const size_t span_in = (size_t)(e->rows > 0 ? e->rows - 1 : 0) * e->ld_in + e->V1;
+    const size_t span_out = (size_t)(e->rows > 0 ? e->rows - 1 : 0) * e->ld_out + e->V1;
+    int n = 0;
+    for (int i = 0; i < e->M; ++i) {
+        const float w = e->w[i];
+        if (!e->in[i] || !(w >= 0.f) || w == INFINITY) return CAPMI_EINVAL;      // (also NaN)
+        if ((reinterpret_cast<uintptr_t>(e->in[i]) & 3) != 0) return CAPMI_EINVAL;
+        if (overlaps(e->in[i], span_in, e->out, span_out)) return CAPMI_EINVAL;
+        if (w == 0.f) continue;
+        a.in[n] = e->in[i];
+        a.log_w[n] = logf(w);
+        if (((reinterpret_cast<uintptr_t>(a.in[n]) ^ reinterpret_cast<uintptr_t>(a.in[0])) & 15) != 0) a.vec = 0;
+        ++n;
+    }
+    if (n == 0) return CAPMI_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(e->out) & 3) != 0) return CAPMI_EINVAL;
+    if (e->rows == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    switch (n) {
+        case 1: launch<1>(a, st); break;
+        case 2: launch<2>(a, st); break;
+        case 3: launch<3>(a, st); break;
+        case 4: launch<4>(a, st); break;
+        case 5: launch<5>(a, st); break;
+        case 6: launch<6>(a, st); break;
+        case 7: launch<7>(a, st); break;
+        default: launch<8>(a, st); break;
+    }
+    CAPMI_CHECK_LAUNCH();
+    return 0;
+}

@@ -704,6 +704,69 @@ def caption_stats(seq_logp, seq):
     return ent, ppl
 
 
+def ensemble_weights(weights, M):
+    """AttEnsemble's weights as the kernel takes them: M floats, >= 0, normalised to sum 1 (None: all ones, AttEnsemble.py:25)."""
+    if not 1 <= M <= _lib.ENSEMBLE_MAX:
+        raise _lib.CapmiError('an ensemble has 1..%d members (got %d)' % (_lib.ENSEMBLE_MAX, M))
+    w = [1.0] * M if weights is None else [float(x) for x in (weights.tolist() if torch.is_tensor(weights) else weights)]
+    if len(w) != M:
+        raise _lib.CapmiError('%d weights for %d members' % (len(w), M))
+    if any(not (x >= 0.0) or x == float('inf') for x in w):
+        raise _lib.CapmiError('ensemble weights must be finite and >= 0 (got %s)' % w)
+    tot = sum(w)
+    if not tot > 0.0:
+        raise _lib.CapmiError('ensemble weights must have a positive sum (got %s)' % w)
+    return [x / tot for x in w]
+
+
+def ensemble_logprobs(inputs, weights=None, out=None):
+    """log( sum_i w_i softmax(inputs[i]) / sum_i w_i ) row-wise (AttEnsemble.get_logprobs_state, AttEnsemble.py:45-53) in one launch
+    of capmi_ensemble_logprobs.  inputs: M tensors of one shape [..., V1] (logits or log-probs: each member is normalised),
+    float32 device tensors whose rows are contiguous; weights: M numbers >= 0 with a positive sum (normalised here) or None."""
+    inputs = list(inputs)
+    w = ensemble_weights(weights, len(inputs))
+    shape = tuple(inputs[0].shape)
+    if len(shape) < 1 or shape[-1] < 1:
+        raise _lib.CapmiError('ensemble_logprobs: inputs [..., V1] expected (got %s)' % (shape,))
+    for t in inputs:
+        if tuple(t.shape) != shape:
+            raise _lib.CapmiError('ensemble_logprobs: every member needs the same shape (%s vs %s)' % (tuple(t.shape), shape))
+        if t.dtype != _f32:
+            raise _lib.CapmiError('ensemble_logprobs: float32 inputs expected (got %s)' % t.dtype)
+    V1 = shape[-1]
+
+    def rows2d(t):
+        if t.dim() == 2 and t.stride(1) == 1:
+            return t
+        if not t.is_contiguous():
+            raise _lib.CapmiError('ensemble_logprobs: rows must be contiguous')
+        return t.view(-1, V1)
+    xs = [rows2d(t) for t in inputs]
+    if not all(x.is_cuda for x in xs):
+        raise _lib.CapmiError('capmi ops need device tensors (got %s)' % [str(x.device) for x in xs])
+    if len({x.stride(0) for x in xs}) != 1:
+        xs = [x.contiguous() for x in xs]
+    if out is None:
+        out = torch.empty(shape, dtype=_f32, device=inputs[0].device)
+    if tuple(out.shape) != shape or out.dtype != _f32:
+        raise _lib.CapmiError('ensemble_logprobs: out must be float32 of shape %s' % (shape,))
+    o = rows2d(out)
+    if not o.is_cuda:
+        raise _lib.CapmiError('capmi ops need device tensors (got %s)' % o.device)
+    if xs[0].shape[0] == 0:
+        return out
+    e = _lib.Ensemble()
+    e.M, e.rows, e.V1 = len(xs), xs[0].shape[0], V1
+    e.ld_in = xs[0].stride(0) if xs[0].shape[0] > 1 else V1
+    e.ld_out = o.stride(0) if o.shape[0] > 1 else V1
+    for i, (x, wi) in enumerate(zip(xs, w)):
+        getattr(e, 'in')[i] = x.data_ptr()
+        e.w[i] = wi
+    e.out = o.data_ptr()
+    check(lib.capmi_ensemble_logprobs(C.byref(e), stream_ptr()), 'capmi_ensemble_logprobs')
+    return out
+
+
 def clip_len(att_masks, width=None):
     """Longest valid region count of the batch -- the K that clip_att (AttModel.py:106-112) truncates to.
 

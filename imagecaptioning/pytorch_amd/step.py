@@ -13,6 +13,7 @@ The fast paths (one native call per rollout / per beam search) do not go through
   UpDownStepper   capmi_updown_decode_step  (UpDownCore.forward, AttModel.py:615-640, eval numerics)
   NewFCStepper    maxout LSTMCore.forward   (FCModel.py:13-42 via AttModel.py:904-945)
   Att2in2Stepper  capmi_att2in2_decode_step (Att2in2Core.forward, AttModel.py:750-790, eval numerics)
+  EnsembleStepper M member steppers + capmi_ensemble_logprobs (AttEnsemble.get_logprobs_state, AttEnsemble.py:45-53)
 """
 import ctypes as C
 
@@ -188,6 +189,43 @@ class Att2in2Stepper:
     def export_state(self, rows):
         s = self.state[self.cur]
         return (s[0, :rows].clone().unsqueeze(0), s[1, :rows].clone().unsqueeze(0))
+
+
+class EnsembleStepper:
+    """AttEnsemble's decoder step over M member steppers of any family: every member takes the same tokens, then ONE launch of
+    capmi_ensemble_logprobs turns their M rows of logits into the mixture log-probability (a normalised row: the drivers'
+    log_softmax leaves it unchanged, and their temperature applies to the mixture, as CaptionModel.py:204 does).  Members with
+    weight 0 are stepped too.  snapshot / restore exist when every member has them."""
+
+    def __init__(self, members, weights=None):
+        self.members = list(members)
+        self.w = ops.ensemble_weights(weights, len(self.members))
+        V1 = {m.V1 for m in self.members}
+        B = {m.B for m in self.members}
+        if len(V1) != 1 or len(B) != 1:
+            raise _lib.CapmiError('ensemble members disagree on the vocabulary or the batch (V1 %s, B %s)' % (sorted(V1), sorted(B)))
+        self.V1, self.B = V1.pop(), B.pop()
+        self.out = None
+        if all(hasattr(m, 'snapshot') and hasattr(m, 'restore') for m in self.members):
+            self.snapshot, self.restore = self._snapshot, self._restore
+
+    def step(self, t, it, rows_per_image):
+        logits = [m.step(t, it, rows_per_image) for m in self.members]
+        rows = logits[0].shape[0]
+        if self.out is None or self.out.shape[0] < rows:
+            self.out = torch.empty(rows, self.V1, dtype=_f32, device=logits[0].device)
+        return ops.ensemble_logprobs(logits, self.w, out=self.out[:rows])
+
+    def reorder(self, parent, cur):
+        for m in self.members:
+            m.reorder(parent, cur)
+
+    def _snapshot(self):
+        return [m.snapshot() for m in self.members]
+
+    def _restore(self, snap):
+        for m, s in zip(self.members, snap):
+            m.restore(s)
 
 
 def updown_step(model, it, fc_feats, att_feats, p_att_feats, att_masks, state, output_logsoftmax=1):

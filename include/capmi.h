@@ -1031,6 +1031,29 @@ typedef struct capmi_att2in2_step {
 int capmi_att2in2_decode_step(const capmi_att2in2_weights *w, capmi_att2in2_step *s, int rows, int rows_per_image,
                               const float *h_src, const float *c_src, float *h_dst, float *c_dst, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Test-time ensemble: the mixture log-probability of M members (AttEnsemble.get_logprobs_state, AttEnsemble.py:45-53,
+ *   logprobs = log( sum_i w_i * softmax(logit_i) / sum_i w_i ) ).  For every row r:
+ *   lse_i     = logsumexp_v in_i[r, v]            (each member is normalised here: logits and log-probs give the same result)
+ *   out[r, v] = log sum_{i: w_i > 0} w_i * exp(in_i[r, v] - lse_i)
+ * computed in log space, as m + log sum_i exp(a_i - m) with a_i = (in_i - max_i) - log(sum_i) + log w_i.  Difference from the
+ * reference: its fp32 softmax -> weighted sum -> log underflows to -inf where every member's probability is below ~1e-38; here
+ * the output stays finite.  A column is -inf only where it is -inf in every member with weight; NaN propagates (a member row
+ * that is -inf everywhere gives NaN, as the reference's softmax does).  Members with weight 0 are not read.
+ * rows == 0: success, nothing launched.  CAPMI_EINVAL: M outside 1..CAPMI_ENSEMBLE_MAX, V1 <= 0, ld_in or ld_out below V1,
+ * a NULL pointer, a negative or non-finite weight, no positive weight, out overlapping an input.
+ * One workgroup per row, two sweeps over the member rows (float4 loads); the weights are used as given (the caller
+ * normalises them; log w_i is only an offset, so unnormalised weights shift the output by log sum_i w_i).
+ * ------------------------------------------------------------------------------------------- */
+#define CAPMI_ENSEMBLE_MAX 8
+typedef struct capmi_ensemble {
+    int M, rows, V1, ld_in, ld_out;
+    const float *in[CAPMI_ENSEMBLE_MAX];   /* member i: rows x V1 logits OR log-probs, row stride ld_in */
+    float w[CAPMI_ENSEMBLE_MAX];           /* >= 0, normalised by the caller (sum 1) */
+    float *out;                            /* rows x V1, row stride ld_out; may not alias an input */
+} capmi_ensemble;
+int capmi_ensemble_logprobs(const capmi_ensemble *e, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
