@@ -174,6 +174,13 @@ class Ensemble(C.Structure):
                 ('w', C.c_float * ENSEMBLE_MAX), ('out', c_f)])
 
 
+class Ppo(C.Structure):
+    """capmi_ppo (include/capmi.h): the PPO structure loss of one rollout, forward and backward"""
+    _fields_ = ([(k, C.c_int) for k in ('N', 'L', 'V1', 'n', 'ld_new', 'ld_old', 'ld_grad', 'per_row')] +
+                [('eps', C.c_float), ('kl_coef', C.c_float)] +
+                [(k, c_f) for k in ('lp_new', 'lp_old', 'seq', 'scores', 'row_stats', 'msum', 'out', 'loss_rows', 'g_out', 'grad')])
+
+
 _I, _F, _P, _U64, _I64 = C.c_int, C.c_float, C.c_void_p, C.c_uint64, C.c_int64
 DECODE_NO_REPEAT, DECODE_NO_BAD_ENDING, DECODE_BLOCK_TRIGRAMS = 1, 2, 4      # capmi.h CAPMI_DECODE_*
 SELECT_RAW = 256       # capmi.h CAPMI_SELECT_RAW: OR into the select `mode` -- the stored rows are the logits, not the log-probabilities
@@ -282,6 +289,8 @@ SIGNATURES = {
                                   C.POINTER(Att2in2Grads), _P],
     'capmi_att2in2_decode_step': [C.POINTER(Att2in2Weights), C.POINTER(Att2in2Step), _I, _I, _P, _P, _P, _P, _P],
     'capmi_ensemble_logprobs': [C.POINTER(Ensemble), _P],
+    'capmi_ppo_loss_fwd': [C.POINTER(Ppo), _P],
+    'capmi_ppo_loss_bwd': [C.POINTER(Ppo), _P],
     'capmi_updown_rollout_fwd': [C.POINTER(UpDownWeights), C.POINTER(UpDownRollout), _P],
     'capmi_updown_rollout_bwd': [C.POINTER(UpDownWeights), C.POINTER(UpDownRollout), _P, C.POINTER(UpDownBwdScratch),
                                  C.POINTER(UpDownGrads), _P],

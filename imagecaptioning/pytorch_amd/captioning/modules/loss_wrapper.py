@@ -18,6 +18,7 @@ class LossWrapper(torch.nn.Module):
             self.crit = losses.LanguageModelCriterion()
         self.rl_crit = losses.RewardCriterion()
         self.struc_crit = losses.StructureLosses(opt) if getattr(opt, 'structure_loss_type', None) else None
+        self.ppo_crit = losses.PPOLoss(opt, model) if getattr(opt, 'use_ppo', 0) else None
 
     def forward(self, fc_feats, att_feats, labels, masks, att_masks, gts, gt_indices, sc_flag, struc_flag,
                 drop_worst_flag):
@@ -25,8 +26,12 @@ class LossWrapper(torch.nn.Module):
         out = {}
         reduction = 'none' if drop_worst_flag else 'mean'
         if struc_flag:
-            if getattr(opt, 'use_ppo', 0):
-                raise NotImplementedError('PPO loss is out of scope (SURVEY.md 2.1 #12)')
+            use_ppo = bool(getattr(opt, 'use_ppo', 0))
+            if use_ppo and opt.structure_loss_type in losses.StructureLosses.LOGIT_TYPES \
+                    and not getattr(opt, 'struc_use_logsoftmax', False):
+                raise NotImplementedError('use_ppo reads the rollout output; with structure_loss_type %r (max_margin, multi_margin, '
+                                          'real_softmax_margin) and no struc_use_logsoftmax that is raw logits, which is not '
+                                          'supported' % opt.structure_loss_type)
             w = opt.structure_loss_weight
             if w < 1:
                 lm_loss = self.crit(self.model(fc_feats, att_feats, labels[..., :-1], att_masks), labels[..., 1:],
@@ -44,14 +49,21 @@ class LossWrapper(torch.nn.Module):
                                                   or 'margin' not in opt.structure_loss_type),
                          'sample_n': opt.train_sample_n}, mode='sample')
                 gts = select_gts(gts, gt_indices)
-                struc_loss = self.struc_crit(sample_logprobs, gen_result, gts, reduction=reduction)
+                if use_ppo:
+                    struc_loss = self.ppo_crit(sample_logprobs, gen_result, gts, fc_feats, att_feats, att_masks, reduction=reduction)
+                else:
+                    struc_loss = self.struc_crit(sample_logprobs, gen_result, gts, reduction=reduction)
             else:
                 z = (att_feats if att_feats is not None else fc_feats).new_zeros(())
-                struc_loss = {'loss': z, 'reward': z}
+                struc_loss = {'loss': z, 'reward': z, 'pg_loss': z, 'kl_loss': z, 'clipfrac': z}
             loss = (1 - w) * lm_loss + w * struc_loss['loss']
             out['lm_loss'] = lm_loss
             out['struc_loss'] = struc_loss['loss']
             out['reward'] = struc_loss['reward']
+            if use_ppo:
+                out['pg_loss'] = struc_loss['pg_loss']
+                out['kl_loss'] = struc_loss['kl_loss']
+                out['clipfrac'] = struc_loss['clipfrac']
         elif not sc_flag:
             loss = self.crit(self.model(fc_feats, att_feats, labels[..., :-1], att_masks), labels[..., 1:], masks[..., 1:],
                              reduction=reduction)

@@ -3,6 +3,7 @@ log-prob tensor the model API returns; the arithmetic is a gather + masked mean 
 (K14/K15 of SURVEY.md 2.3) -- device tensor ops on the same HIP stream, no host sync.  The gather goes
 through ``sparse_logp.select_logp``: when the tensor comes from a capmi rollout its gradient travels back
 as [N,L] values + token ids (``capmi_logsoftmax_bwd_sparse``), never as a dense [N,L,V1] tensor."""
+import logging
 import math
 
 import torch
@@ -147,4 +148,116 @@ class StructureLosses(nn.Module):
                     avg = avg + costs
                 output = nn.functional.cross_entropy(avg, costs.min(1)[1], reduction=reduction)
         out['loss'] = output
+        return out
+
+
+class _FusedPPO(torch.autograd.Function):
+    """PPOLoss's arithmetic on the device: forward = capmi_ppo_loss_fwd (two launches), backward = capmi_ppo_loss_bwd (one launch,
+    the dense [N,L,V1] gradient written once; it reaches the rollout backward as its dense `g_dense` input, sparse_logp.split_grad).
+    `stats` receives the [4] device tensor pg_loss, kl_loss, clipfrac, loss (no host sync)."""
+
+    @staticmethod
+    def forward(ctx, input, lo, seq, scores, n, eps, kl_coef, per_row, stats):
+        from imagecaptioning.pytorch_amd import ops
+        out, loss_rows, row_stats, msum = ops.ppo_loss_fwd(input.detach(), lo, seq, scores, n, eps, kl_coef, per_row)
+        ctx.save_for_backward(lo, seq, row_stats, msum)
+        ctx.cfg = (n, eps, kl_coef, per_row)
+        stats['out'] = out
+        return loss_rows if per_row else out[3]
+
+    @staticmethod
+    def backward(ctx, g):
+        from imagecaptioning.pytorch_amd import ops
+        lo, seq, row_stats, msum = ctx.saved_tensors
+        n, eps, kl_coef, per_row = ctx.cfg
+        # 'mean': the upstream gradient stays a device scalar (as in sparse_logp._FusedReward)
+        grad = ops.ppo_loss_bwd(lo, seq, row_stats, msum, g.reshape(-1).float(), n, eps, kl_coef, per_row)
+        return grad, None, None, None, None, None, None, None, None
+
+
+class PPOLoss(nn.Module):
+    """losses.py:267-357: the clipped policy ratio of the sampled tokens against a frozen old policy plus kl_coef times
+    KL(old || new) over the whole vocabulary, with new_self_critical's leave-one-out advantage.
+
+    The old model is the live model's family built anew (models.setup) with the weights of ``ppo_old_model_path``, on the live
+    model's device, frozen and in eval mode.  It is not deep-copied from the live model (whose native caches are keyed to its own
+    buffers), and it is not part of the live model's parameters, state_dict, flat Adam buffer or checkpoint.
+
+    Two routes compute the same numbers: device float32 inputs go through _FusedPPO (capmi_ppo_loss_fwd / _bwd: every dense
+    [N,L,V1] row is read once per pass, nothing dense goes through ATen); anything else (CPU tensors, float64) through
+    ``generic``, the reference's formula in plain torch."""
+
+    def __init__(self, opt, model):
+        super().__init__()
+        self.opt = opt
+        self.cliprange = getattr(opt, 'ppo_cliprange', 0.2)
+        self.kl_coef = getattr(opt, 'ppo_kl_coef', 0.02)
+        self.old_model = None
+        if getattr(opt, 'use_ppo', 0) == 1:
+            path = getattr(opt, 'ppo_old_model_path', None)
+            assert path is not None, 'Must provide old model path for PPO'
+            from .. import models
+            logging.warning('Make sure you are using the same model for PPO loss and the vocab must be the same.')
+            dev = next(model.parameters()).device
+            state_dict = torch.load(path, map_location=dev)
+            if 'pytorch-lightning_version' in state_dict:        # a Lightning checkpoint
+                state_dict = state_dict['state_dict']
+                del state_dict['_vocab']
+                del state_dict['_opt']
+            old = models.setup(opt).to(dev)
+            old.load_state_dict(state_dict)
+            old.eval()
+            for p in old.parameters():
+                p.requires_grad = False
+            self.old_model = old
+
+    def old_logprobs(self, fc_feats, att_feats, seq, att_masks):
+        """the old policy's teacher-forced log-probs [N, L, V1] of the sampled tokens (BOS prepended, the last token dropped)"""
+        model_input_seq = torch.cat([seq.new_zeros(seq.size(0), 1), seq[:, :-1]], 1)
+        with torch.no_grad():
+            self.old_model.eval()
+            return self.old_model(fc_feats, att_feats, model_input_seq, att_masks)
+
+    def forward(self, input, seq, data_gts, fc_feats, att_feats, att_masks, reduction='mean'):
+        """input: what the rollout returned, [N, L, V1] (log-probs; raw logits are read as they are, as the reference does)"""
+        N = input.size(0)
+        n = N // len(data_gts)
+        assert n == self.opt.train_sample_n, n
+        scores = get_scores(data_gts, seq, self.opt, as_tensor=True)
+        scores = (scores if torch.is_tensor(scores) else torch.as_tensor(scores)).to(device=input.device, dtype=input.dtype)
+        lo = self.old_logprobs(fc_feats, att_feats, seq, att_masks)
+        return self.loss(input, seq, scores.reshape(-1), lo, reduction)
+
+    def loss(self, input, seq, scores, lo, reduction='mean'):
+        """the loss dict of `input` [N, L, V1] against the old log-probs `lo` [N, L, V1] with rewards `scores` [N]"""
+        n = self.opt.train_sample_n
+        fused = (input.is_cuda and input.dtype == torch.float32 and lo.dtype == torch.float32 and lo.shape == input.shape
+                 and input.is_contiguous() and seq.dtype == torch.int64 and n >= 2 and input.size(0) % n == 0 and input.size(1) > 0)
+        if not fused:
+            return self.generic(input, seq, scores, lo, reduction)
+        stats = {}
+        loss = _FusedPPO.apply(input, lo.contiguous(), seq.contiguous(), scores.float().contiguous(), n, float(self.cliprange),
+                               float(self.kl_coef), reduction == 'none', stats)
+        st = stats['out']
+        return {'reward': scores.view(-1, n), 'loss': loss, 'pg_loss': st[0], 'kl_loss': st[1], 'clipfrac': st[2]}
+
+    def generic(self, input, seq, scores, lo, reduction='mean'):
+        """losses.py:306-357 in plain torch (the route of CPU and float64 tensors)"""
+        out = {}
+        n = self.opt.train_sample_n
+        mask = _shifted_mask(seq, input)
+        scores = scores.to(input).view(-1, n)
+        out['reward'] = scores
+        adv = (scores - (scores.sum(1, keepdim=True) - scores) / (scores.shape[1] - 1)).view(-1, 1)
+        ratio = torch.exp(input.gather(2, seq.unsqueeze(2)).squeeze(2) - lo.gather(2, seq.unsqueeze(2)).squeeze(2))
+        pg = torch.max(-adv * ratio, -adv * torch.clamp(ratio, 1.0 - self.cliprange, 1.0 + self.cliprange))
+        kl = nn.functional.kl_div(input, lo, reduction='none', log_target=True).sum(-1)
+        msum = mask.sum()
+        out['pg_loss'] = (pg * mask).sum() / msum
+        out['kl_loss'] = (kl * mask).sum() / msum
+        out['clipfrac'] = (((ratio - 1.0).abs() > self.cliprange).to(mask) * mask).sum() / msum
+        if reduction == 'none':
+            out['loss'] = ((pg + self.kl_coef * kl) * mask).sum(1) / mask.sum(1)
+        else:
+            out['loss'] = out['pg_loss'] + self.kl_coef * out['kl_loss']
         return out

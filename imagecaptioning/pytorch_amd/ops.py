@@ -767,6 +767,70 @@ def ensemble_logprobs(inputs, weights=None, out=None):
     return out
 
 
+def _ppo_desc(lp_old, seq, n, eps, kl_coef, per_row, what):
+    if lp_old.dim() != 3 or lp_old.dtype != _f32:
+        raise _lib.CapmiError('%s: old log-probs [N, L, V1] float32 expected (got %s %s)' % (what, tuple(lp_old.shape), lp_old.dtype))
+    N, L, V1 = lp_old.shape
+    if seq.dtype != torch.int64 or tuple(seq.shape) != (N, L):
+        raise _lib.CapmiError('%s: seq [N, L] = %s int64 expected (got %s %s)' % (what, (N, L), tuple(seq.shape), seq.dtype))
+    if L < 1 or V1 < 1 or int(n) < 2 or N % int(n):
+        raise _lib.CapmiError('%s: need L, V1 >= 1 and N = %d a multiple of n = %d >= 2' % (what, N, int(n)))
+    _chk(lp_old, seq)
+    p = _lib.Ppo()
+    p.N, p.L, p.V1, p.n = N, L, V1, int(n)
+    p.ld_new = p.ld_old = p.ld_grad = V1
+    p.per_row = int(bool(per_row))
+    p.eps, p.kl_coef = float(eps), float(kl_coef)
+    p.lp_old, p.seq = lp_old.data_ptr(), seq.data_ptr()
+    return p
+
+
+def ppo_loss_fwd(lp_new, lp_old, seq, scores, n, eps=0.2, kl_coef=0.02, per_row=False):
+    """PPOLoss.forward's arithmetic (losses.py:267-357) in two launches of capmi_ppo_loss_fwd.  lp_new (what the rollout returned)
+    and lp_old (the old policy's log-probs): [N, L, V1] float32; seq [N, L] int64; scores [N] float32 (n samples per image,
+    image-major).  Returns (out [4] = pg_loss, kl_loss, clipfrac, loss ('mean'); loss_rows [N] ('none') or None;
+    row_stats [4, N, L] = kl, r, pg, d pg / d lp_new[seq]; msum [1] or [N]).  All stay on the device."""
+    p = _ppo_desc(lp_old, seq, n, eps, kl_coef, per_row, 'ppo_loss_fwd')
+    if tuple(lp_new.shape) != tuple(lp_old.shape) or lp_new.dtype != _f32:
+        raise _lib.CapmiError('ppo_loss_fwd: lp_new must be float32 of shape %s (got %s %s)' % (tuple(lp_old.shape), tuple(lp_new.shape), lp_new.dtype))
+    N, L, _ = lp_old.shape
+    if scores.dtype != _f32 or tuple(scores.shape) != (N,):
+        raise _lib.CapmiError('ppo_loss_fwd: scores [%d] float32 expected (got %s %s)' % (N, tuple(scores.shape), scores.dtype))
+    _chk(lp_new, scores)
+    dev = lp_old.device
+    row_stats = torch.empty(4, N, L, dtype=_f32, device=dev)
+    msum = torch.empty(N if per_row else 1, dtype=_f32, device=dev)
+    out = torch.empty(4, dtype=_f32, device=dev)
+    loss_rows = torch.empty(N, dtype=_f32, device=dev) if per_row else None
+    p.lp_new, p.scores = lp_new.data_ptr(), scores.data_ptr()
+    p.row_stats, p.msum, p.out, p.loss_rows = row_stats.data_ptr(), msum.data_ptr(), out.data_ptr(), ptr(loss_rows)
+    check(lib.capmi_ppo_loss_fwd(C.byref(p), stream_ptr()), 'capmi_ppo_loss_fwd')
+    return out, loss_rows, row_stats, msum
+
+
+def ppo_loss_bwd(lp_old, seq, row_stats, msum, g_out, n, eps=0.2, kl_coef=0.02, per_row=False, out=None):
+    """d loss / d lp_new of ppo_loss_fwd (capmi_ppo_loss_bwd, one launch): lp_old / seq / n / eps / kl_coef / per_row as given to the
+    forward, row_stats and msum as it returned them, g_out the upstream gradient ([1] or 0-dim for 'mean', [N] for 'none', float32
+    on the device).  Returns the dense [N, L, V1] gradient (masked rows are zeros)."""
+    p = _ppo_desc(lp_old, seq, n, eps, kl_coef, per_row, 'ppo_loss_bwd')
+    N, L, V1 = lp_old.shape
+    g_out = g_out.reshape(-1)
+    if g_out.dtype != _f32 or g_out.numel() != (N if per_row else 1):
+        raise _lib.CapmiError('ppo_loss_bwd: upstream gradient of %d float32 values expected (got %s %s)'
+                              % (N if per_row else 1, tuple(g_out.shape), g_out.dtype))
+    if row_stats.dtype != _f32 or tuple(row_stats.shape) != (4, N, L) or msum.dtype != _f32 or msum.numel() != (N if per_row else 1):
+        raise _lib.CapmiError('ppo_loss_bwd: row_stats [4, N, L] and msum as returned by ppo_loss_fwd expected')
+    if out is None:
+        out = torch.empty(N, L, V1, dtype=_f32, device=lp_old.device)
+    if tuple(out.shape) != (N, L, V1) or out.dtype != _f32:
+        raise _lib.CapmiError('ppo_loss_bwd: out must be float32 of shape %s' % ((N, L, V1),))
+    g_out = g_out.contiguous()
+    _chk(row_stats, msum, g_out, out)
+    p.row_stats, p.msum, p.g_out, p.grad = row_stats.data_ptr(), msum.data_ptr(), g_out.data_ptr(), out.data_ptr()
+    check(lib.capmi_ppo_loss_bwd(C.byref(p), stream_ptr()), 'capmi_ppo_loss_bwd')
+    return out
+
+
 def clip_len(att_masks, width=None):
     """Longest valid region count of the batch -- the K that clip_att (AttModel.py:106-112) truncates to.
 

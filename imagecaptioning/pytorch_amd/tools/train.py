@@ -229,6 +229,9 @@ def train(opt):
             if struc_flag:
                 print('iter %d (epoch %d), train_loss = %.3f, lm_loss = %.3f, struc_loss = %.3f, time/batch = %.3f'
                       % (it, epoch, train_loss, out['lm_loss'].mean().item(), out['struc_loss'].mean().item(), t2 - t1))
+                if getattr(opt, 'use_ppo', 0):
+                    print('iter %d (epoch %d), pg_loss = %.3f, kl_loss = %.3f, clipfrac = %.3f'
+                          % (it, epoch, out['pg_loss'].item(), out['kl_loss'].item(), out['clipfrac'].item()))
             elif not sc_flag:
                 print('iter %d (epoch %d), train_loss = %.3f, time/batch = %.3f' % (it, epoch, train_loss, t2 - t1))
             else:

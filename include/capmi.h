@@ -1054,6 +1054,55 @@ typedef struct capmi_ensemble {
 } capmi_ensemble;
 int capmi_ensemble_logprobs(const capmi_ensemble *e, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * PPO structure loss (PPOLoss.forward, captioning/modules/losses.py:267-357): a clipped policy ratio plus a KL penalty against a
+ * frozen old policy, over the N = B * n sampled rows of one rollout (n samples per image, image-major).  Row (i, t), t < L:
+ *   m[i,t]  = 1 for t == 0, else (seq[i, t-1] > 0)                           (the end step still counts)
+ *   A[i]    = scores[i] - (sum_k scores[img(i), k] - scores[i]) / (n - 1)     (leave-one-out baseline, new_self_critical's)
+ *   r       = exp(ln[s] - lo[s]),  s = seq[i, t]                              (ln: lp_new row, lo: lp_old row)
+ *   pg      = max(-A r, -A clamp(r, 1 - eps, 1 + eps))                       (NaN if either side is NaN, as torch.maximum)
+ *   kl      = sum_v exp(lo[v]) (lo[v] - ln[v])                                 (F.kl_div(ln, lo, log_target=True).sum(-1))
+ * masked means (M = sum m): out = {pg_loss, kl_loss, clipfrac = mean(|r - 1| > eps), loss = pg_loss + kl_coef kl_loss}; with
+ * per_row ('none'): loss_rows[i] = sum_t (pg + kl_coef kl) m / sum_t m as well.
+ *
+ * capmi_ppo_loss_fwd: two launches (one workgroup per row reading the new and the old row once, float4 body; one workgroup for
+ *   the means in double).  Writes row_stats [4][N*L] = {kl, r, pg, g_pg} with g_pg = d pg / d ln[s]:
+ *     -A r where the unclipped side is the larger, -A r [1-eps <= r <= 1+eps] where the clamped side is, the mean of the two on a
+ *     tie (torch.maximum's backward; while the clamp is inactive the two sides tie).  The side that gets no gradient adds nothing:
+ *     r = inf with A > 0 gives pg = -A (1 + eps), finite, and g_pg = 0.  (The reference's fp32 autograd forms 0 * inf = NaN in
+ *     exp's backward there; 0 is the limit of the finite case.)
+ *   and msum: M ([1], 'mean') or sum_t m per sample ([N], per_row).
+ *   Masked rows (m = 0) are not read; their row_stats are 0.  The reference multiplies them by 0, so the two differ only where a
+ *   masked row holds an infinity or a NaN (the reference then gives NaN).  Everything else follows IEEE as the reference's fp32
+ *   ops do: a -inf in an old row gives a NaN kl (0 * -inf), a -inf new entry under a positive old probability an infinite kl.
+ *   A token outside [0, V1) gives r = NaN and is not read.
+ * capmi_ppo_loss_bwd: one launch, one workgroup per row; reads the old row, g_pg, msum and the upstream gradient g_out ([1] for
+ *   'mean': a device scalar, no host sync; [N] for per_row) and writes the dense gradient once:
+ *     grad[i,t,v] = c (-kl_coef exp(lo[v]) + [v == s] g_pg),  c = g_out m / M;  masked rows are written as zeros.
+ * Both: lp_new / lp_old / grad are [N*L, V1] row views with strides ld_new / ld_old / ld_grad (>= V1, 4-byte aligned), seq [N, L]
+ * int64 contiguous, scores [N] float.  N == 0: success, nothing launched.  CAPMI_EINVAL: n < 2, N not a multiple of n, L or V1
+ * below 1, a stride below V1, a NULL pointer that the call reads or writes, eps or kl_coef negative / not finite, row_stats
+ * overlapping an input row span, grad overlapping the old rows.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct capmi_ppo {
+    int N, L, V1, n;                 /* rows N*L; n samples per image */
+    int ld_new, ld_old, ld_grad;     /* row strides, floats */
+    int per_row;                     /* 0: reduction 'mean', 1: 'none' */
+    float eps, kl_coef;              /* ppo_cliprange, ppo_kl_coef */
+    const float *lp_new;             /* [N*L, V1] the rollout's output (fwd) */
+    const float *lp_old;             /* [N*L, V1] the old policy's log-probs */
+    const int64_t *seq;              /* [N, L] sampled tokens */
+    const float *scores;             /* [N] rewards (fwd) */
+    float *row_stats;                /* [4][N*L] kl, r, pg, g_pg (written by fwd, read by bwd) */
+    float *msum;                     /* [1] or [N] mask sums (written by fwd, read by bwd) */
+    float *out;                      /* [4] pg_loss, kl_loss, clipfrac, loss (fwd) */
+    float *loss_rows;                /* [N] per_row losses (fwd, per_row only) */
+    const float *g_out;              /* [1] or [N] upstream gradient (bwd) */
+    float *grad;                     /* [N*L, V1] d loss / d lp_new (bwd) */
+} capmi_ppo;
+int capmi_ppo_loss_fwd(const capmi_ppo *p, void *stream);
+int capmi_ppo_loss_bwd(const capmi_ppo *p, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
