@@ -1,18 +1,11 @@
 // Device-side batched beam search for the UpDown decoder (gfx950).
 // Reference: AttModel._sample_beam (AttModel.py:218-256) + CaptionModel.beam_search
 // (CaptionModel.py:35-209, group_size 1).  See include/capmi.h for what each kernel replaces.
-#include "capmi_common.h"
-#include "../../../include/capmi.h"
+#include "host_common.h"
 
 using namespace capmi;
 
 namespace {
-
-#define RC(x)                 \
-    do {                      \
-        int rc__ = (x);       \
-        if (rc__) return rc__;\
-    } while (0)
 
 constexpr int SEL_T = 1024;
 constexpr int BD_MAX = 16;
@@ -136,24 +129,6 @@ __global__ __launch_bounds__(SEL_T) void beam_logsoftmax_kernel(const float *__r
     }
 }
 
-struct SegSpec {
-    const float *A; int lda; const float *B; int ldb; int K; int a_row_div;
-};
-int gemm(void *stream, int M, int N, float *C, int ldc, const SegSpec *segs, int nseg, float *partial, int64_t cap,
-         int defer, int *splits_used, const float *bias = nullptr) {
-    capmi_gemm_desc d{};
-    d.nseg = nseg;
-    for (int i = 0; i < nseg; ++i) {
-        d.seg[i].A = segs[i].A; d.seg[i].lda = segs[i].lda; d.seg[i].B = segs[i].B; d.seg[i].ldb = segs[i].ldb;
-        d.seg[i].K = segs[i].K; d.seg[i].a_row_div = segs[i].a_row_div > 0 ? segs[i].a_row_div : 1;
-    }
-    d.M = M; d.N = N; d.C = C; d.ldc = ldc; d.bias = bias;
-    d.partial = partial; d.partial_capacity = cap; d.splits = 0; d.defer_reduce = defer;
-    const int rc = capmi_gemm_f32(&d, stream);
-    if (splits_used) *splits_used = d.splits_used;
-    return rc;
-}
-
 // one decoder step on `rows` rows, `n` rows per image (get_logprobs_state, AttModel.py:166-176)
 int decode_step(const capmi_updown_weights *w, capmi_updown_beam *b, int rows, int n, const float *st_in, float *st_out,
                 float *logp_out, float temperature, void *stream) {
@@ -168,26 +143,26 @@ int decode_step(const capmi_updown_weights *w, capmi_updown_beam *b, int rows, i
     {
         SegSpec s[3] = {{h_lang_p, R, w->att_w_ih, ld_att_ih, R, 1}, {b->xt, E, w->att_w_ih + 2 * R, ld_att_ih, E, 1},
                         {h_att_p, R, w->att_w_hh, R, R, 1}};
-        RC(gemm(stream, rows, 4 * R, b->partial, 4 * R, s, 3, b->partial, b->partial_capacity, 1, &splits));
+        RC(gemm(stream, 0, 0, rows, 4 * R, b->partial, 4 * R, s, 3, b->partial, b->partial_capacity, 1, &splits));
         RC(capmi_lstm_cell_fwd(slabs, splits, w->att_b_ih, w->att_b_hh, b->fc_gates, n, nullptr, c_att_p, h_att, c_att,
                                b->gates, nullptr, nullptr, rows, R, stream));
     }
     {
         SegSpec s{h_att, R, w->h2att_w, R, R, 1};
-        RC(gemm(stream, rows, A, b->att_h, A, &s, 1, b->partial, b->partial_capacity, 0, nullptr, w->h2att_b));
+        RC(gemm(stream, 0, 0, rows, A, b->att_h, A, &s, 1, b->partial, b->partial_capacity, 0, nullptr, w->h2att_b));
     }
     RC(capmi_attention_fwd(b->att_h, b->p_att, b->att, b->att_mask, w->alpha_w, w->alpha_b, b->ctx, b->alpha, B, n, K, A, R,
                            nullptr, rows, stream));
     {
         SegSpec s[3] = {{b->ctx, R, w->lang_w_ih, 2 * R, R, 1}, {h_att, R, w->lang_w_ih + R, 2 * R, R, 1},
                         {h_lang_p, R, w->lang_w_hh, R, R, 1}};
-        RC(gemm(stream, rows, 4 * R, b->partial, 4 * R, s, 3, b->partial, b->partial_capacity, 1, &splits));
+        RC(gemm(stream, 0, 0, rows, 4 * R, b->partial, 4 * R, s, 3, b->partial, b->partial_capacity, 1, &splits));
         RC(capmi_lstm_cell_fwd(slabs, splits, w->lang_b_ih, w->lang_b_hh, nullptr, 1, nullptr, c_lang_p, h_lang, c_lang,
                                b->gates, nullptr, nullptr, rows, R, stream));
     }
     {
         SegSpec s{h_lang, R, w->logit_w, R, R, 1};     // eval mode: no dropout on the output
-        RC(gemm(stream, rows, V1, b->logits, V1, &s, 1, b->partial, b->partial_capacity, 0, nullptr, w->logit_b));
+        RC(gemm(stream, 0, 0, rows, V1, b->logits, V1, &s, 1, b->partial, b->partial_capacity, 0, nullptr, w->logit_b));
     }
     if (!logp_out) return 0;      // raw logits wanted (capmi_updown_decode_step)
     return capmi_beam_logsoftmax(b->logits, logp_out, rows, V1, temperature, b->unk_col, stream);
@@ -240,7 +215,7 @@ int capmi_updown_decode_step(const capmi_updown_weights *w, capmi_updown_beam *b
         return CAPMI_EINVAL;
     if (first) {   // fc term of the attention LSTM, once per set of images
         SegSpec s{b->fc, b->R, w->att_w_ih + b->R, 2 * b->R + b->E, b->R, 1};
-        RC(gemm(stream, b->B, 4 * b->R, b->fc_gates, 4 * b->R, &s, 1, b->partial, b->partial_capacity, 0, nullptr));
+        RC(gemm(stream, 0, 0, b->B, 4 * b->R, b->fc_gates, 4 * b->R, &s, 1, b->partial, b->partial_capacity, 0, nullptr));
     }
     return decode_step(w, b, rows, rows_per_image, state_in, state_out, nullptr, 1.f, stream);
 }
@@ -251,13 +226,12 @@ int capmi_updown_beam_search(const capmi_updown_weights *w, capmi_updown_beam *b
     const int N = B * bd;
     hipStream_t st = (hipStream_t)stream;
     const size_t per = (size_t)N * R, st_sz = 4 * per;
-    hipError_t e;
-    if ((e = hipMemsetAsync(b->state, 0, 2 * st_sz * sizeof(float), st)) != hipSuccess) return (int)e;
-    if ((e = hipMemsetAsync(b->it, 0, (size_t)N * sizeof(int64_t), st)) != hipSuccess) return (int)e;   // BOS
-    if ((e = hipMemsetAsync(b->sums, 0, (size_t)2 * N * sizeof(float), st)) != hipSuccess) return (int)e;
+    HIP_RC(hipMemsetAsync(b->state, 0, 2 * st_sz * sizeof(float), st));
+    HIP_RC(hipMemsetAsync(b->it, 0, (size_t)N * sizeof(int64_t), st));   // BOS
+    HIP_RC(hipMemsetAsync(b->sums, 0, (size_t)2 * N * sizeof(float), st));
     {   // fc term of the attention LSTM
         SegSpec s{b->fc, R, w->att_w_ih + R, 2 * R + E, R, 1};
-        RC(gemm(stream, B, 4 * R, b->fc_gates, 4 * R, &s, 1, b->partial, b->partial_capacity, 0, nullptr));
+        RC(gemm(stream, 0, 0, B, 4 * R, b->fc_gates, 4 * R, &s, 1, b->partial, b->partial_capacity, 0, nullptr));
     }
     // first step from BOS on B rows (AttModel.py:235-239): rows b of the [B*bd]-row arrays, one row per image
     float *st_a = b->state, *st_b = b->state + st_sz;
@@ -273,8 +247,7 @@ int capmi_updown_beam_search(const capmi_updown_weights *w, capmi_updown_beam *b
                              b->token + o, b->score + o, sums_out, b->ended + o, stream));
         if (t == L - 1) break;
         RC(capmi_beam_reorder(cur_state, nxt_state, b->parent + o, 4, B, cur, bd, R, stream));
-        if ((e = hipMemcpyAsync(b->it, b->token + o, (size_t)N * sizeof(int64_t), hipMemcpyDeviceToDevice, st)) != hipSuccess)
-            return (int)e;
+        HIP_RC(hipMemcpyAsync(b->it, b->token + o, (size_t)N * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
         // step on B*bd rows, bd rows per image; writes the next state in place of the consumed one
         RC(decode_step(w, b, N, bd, nxt_state, cur_state, b->logp_rows + (size_t)(t + 1) * N * V1, b->temperature, stream));
         cur = bd;

@@ -19,9 +19,8 @@
 //    gate pre-activations never make a round trip of their own.
 //  * multi-segment K loop: [h_lang | xt | h_att] x [W_ih slices | W_hh] are walked in place -- the
 //    reference's torch.cat (AttModel.py:626,632) and repeat_tensors (a_row_div) copies disappear.
-#include "capmi_common.h"
+#include "host_common.h"
 #include "profile.h"
-#include "../../../include/capmi.h"
 #include "gemm_common.h"
 #include <atomic>
 #include <stdio.h>
@@ -394,8 +393,6 @@ int launch_cfg(const KArgs &a, int al, int bl, dim3 grid, hipStream_t st, const 
     CAPMI_CHECK_LAUNCH();
     return 0;
 }
-
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 

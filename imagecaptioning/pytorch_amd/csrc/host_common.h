@@ -1,0 +1,80 @@
+// Host-side helpers shared by the native drivers and launchers of libcapmi.  Internal: not part of the C ABI in
+// include/capmi.h.
+#pragma once
+#include "capmi_common.h"
+#include "../../../include/capmi.h"
+
+// return a nonzero status (CAPMI_* or hipError_t) to the caller
+#define RC(x)                 \
+    do {                      \
+        int rc__ = (x);       \
+        if (rc__) return rc__;\
+    } while (0)
+
+// the same for calls that return a hipError_t (memsets, copies)
+#define HIP_RC(x)                                 \
+    do {                                          \
+        hipError_t e__ = (x);                     \
+        if (e__ != hipSuccess) return (int)e__;   \
+    } while (0)
+
+// workgroups of a grid-stride launch over `work` items
+inline int grid_for(size_t work, int per_block = 256, int cap = 2048) {
+    size_t b = (work + per_block - 1) / per_block;
+    if (b > (size_t)cap) b = cap;
+    if (b < 1) b = 1;
+    return (int)b;
+}
+
+// all (possibly null) pointers 16-byte aligned
+template <typename... P>
+inline bool aligned16(P... p) {
+    return ((... | reinterpret_cast<uintptr_t>(p)) & 15) == 0;
+}
+
+// one K segment of a capmi_gemm_f32 call; a_row_div <= 0 means 1
+struct SegSpec {
+    const float *A;
+    int lda;
+    const float *B;
+    int ldb;
+    int K;
+    int a_row_div;
+    const void *Apl;        // the same activations as A planes (capmi.h capmi_planes_from_f32), or null
+};
+
+// C[M,N] = sum_s A_s op B_s ; thin wrapper filling capmi_gemm_desc.  The segments' A planes are used only with zero_planes.
+inline int gemm(void *stream, int a_layout, int b_layout, int M, int N, float *C, int ldc, const SegSpec *segs, int nseg,
+                float *partial, int64_t cap, int defer, int *splits_used, const float *bias = nullptr,
+                const float *bias2 = nullptr, int accumulate = 0, const void *zero_planes = nullptr, int splits_hint = 0) {
+    capmi_gemm_desc d{};
+    d.nseg = nseg;
+    for (int i = 0; i < nseg; ++i) {
+        d.seg[i].A = segs[i].A; d.seg[i].lda = segs[i].lda;
+        d.seg[i].B = segs[i].B; d.seg[i].ldb = segs[i].ldb;
+        d.seg[i].K = segs[i].K; d.seg[i].a_row_div = segs[i].a_row_div > 0 ? segs[i].a_row_div : 1;
+        d.a_planes[i] = zero_planes ? segs[i].Apl : nullptr;
+    }
+    d.a_layout = a_layout; d.b_layout = b_layout;
+    d.M = M; d.N = N; d.C = C; d.ldc = ldc;
+    d.bias = bias; d.bias2 = bias2;
+    d.accumulate = accumulate;
+    d.partial = partial; d.partial_capacity = cap;
+    d.splits = splits_hint; d.defer_reduce = defer;
+    const int rc = capmi_gemm_f32(&d, stream);
+    if (splits_used) *splits_used = d.splits_used;
+    return rc;
+}
+
+// d(logits) [T,N,V1] of a rollout's backward.  raw: the rollout returned logits, so d(logits) is the loss gradient itself
+// (sparse and / or dense part), no softmax Jacobian.
+inline int dlogits_bwd(bool raw, const capmi_sparse_logp_grad *sparse, const float *g_seq_logp, const float *seq_logp,
+                       const uint8_t *live, float *dlogits, int N, int L, int T, int V1, void *stream) {
+    if (raw) {
+        capmi_sparse_logp_grad sp = sparse ? *sparse : capmi_sparse_logp_grad{};
+        sp.raw = 1;
+        return capmi_logsoftmax_bwd_sparse(&sp, g_seq_logp, seq_logp, live, dlogits, N, L, T, V1, stream);
+    }
+    if (sparse) return capmi_logsoftmax_bwd_sparse(sparse, g_seq_logp, seq_logp, live, dlogits, N, L, T, V1, stream);
+    return capmi_logsoftmax_bwd(g_seq_logp, seq_logp, live, dlogits, N, L, T, V1, stream);
+}

@@ -2,46 +2,52 @@
 // Replaces NewFCModel.core / _prepare_feature (AttModel.py:904-945) over LSTMCore (FCModel.py:13-42)
 // and the time loops of AttModel._forward / _sample for that model.  Same structure as the UpDown
 // drivers (rollout.hip): one host call per rollout, no host sync, time-batched weight gradients.
-#include "capmi_common.h"
-#include "../../../include/capmi.h"
+// The cell kernels also serve Att2in2 (att2in2.hip), whose cell is this one with an a2c term on the candidate half:
+// capmi_att2in2_cell_fwd / _bwd are defined here beside capmi_maxout_cell_fwd / _bwd.
+#include "host_common.h"
 
 using namespace capmi;
 
 namespace {
 
-#define RC(x)                 \
-    do {                      \
-        int rc__ = (x);       \
-        if (rc__) return rc__;\
-    } while (0)
-
-inline int grid_for(size_t work) {
-    size_t b = (work + 255) / 256;
-    if (b > 2048) b = 2048;
-    return (int)(b < 1 ? 1 : b);
+// sum_s p[s * slab + off] over the K-slice slabs of a GEMM, four independent loads at a time
+__device__ __forceinline__ float slab_sum(const float *__restrict__ p, int splits, size_t slab, size_t off) {
+    float v = 0.f;
+    for (int k0 = 0; k0 < splits; k0 += 4) {
+        float tv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) tv[u] = (k0 + u < splits) ? p[(size_t)(k0 + u) * slab + off] : 0.f;
+        v += tv[0] + tv[1] + tv[2] + tv[3];
+    }
+    return v;
 }
 
-__global__ void maxout_cell_fwd_kernel(const float *__restrict__ partial, int splits, const float *__restrict__ b1,
-                                       const float *__restrict__ b2, const float *__restrict__ c_prev,
-                                       float *__restrict__ h, float *__restrict__ c, float *__restrict__ saved,
-                                       const float *__restrict__ out_mask, float *__restrict__ h_drop, int N, int R) {
-    const size_t total = (size_t)N * R, slab = (size_t)N * 5 * R;
+// sums[r, q*R + j] = sum_s partial[s][r][q*R + j] (+ addend) + b_i2h + b_h2h; Att2in2 (partial2 or b_a2c given) adds to the
+// candidate half, q = 3, 4: sum_s partial2[s][r][(q-3)*R + j] + b_a2c.  saved = (sig(in), sig(f), sig(out), cand_a, cand_b).
+__global__ void maxout_cell_fwd_kernel(const float *__restrict__ partial, int splits, const float *__restrict__ partial2,
+                                       int splits2, const float *__restrict__ addend, const float *__restrict__ b_i2h,
+                                       const float *__restrict__ b_h2h, const float *__restrict__ b_a2c,
+                                       const float *__restrict__ c_prev, float *__restrict__ h, float *__restrict__ c,
+                                       float *__restrict__ saved, const float *__restrict__ out_mask,
+                                       float *__restrict__ h_drop, int N, int R) {
+    const size_t total = (size_t)N * R, slab = (size_t)N * 5 * R, slab2 = (size_t)N * 2 * R;
+    const bool a2c = partial2 || b_a2c;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int r = (int)(i / R), j = (int)(i % R);
         float s[5];
 #pragma unroll
         for (int q = 0; q < 5; ++q) {
             const size_t col = (size_t)q * R + j;
-            float v = 0.f;
-            for (int k0 = 0; k0 < splits; k0 += 4) {
-                float tv[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    tv[u] = (k0 + u < splits) ? partial[(size_t)(k0 + u) * slab + (size_t)r * 5 * R + col] : 0.f;
-                v += tv[0] + tv[1] + tv[2] + tv[3];
+            float v = slab_sum(partial, splits, slab, (size_t)r * 5 * R + col);
+            if (addend) v += addend[(size_t)r * 5 * R + col];
+            if (b_i2h) v += b_i2h[col];
+            if (b_h2h) v += b_h2h[col];
+            if (q >= 3 && a2c) {
+                const size_t col2 = (size_t)(q - 3) * R + j;
+                float a = slab_sum(partial2, splits2, slab2, (size_t)r * 2 * R + col2);
+                if (b_a2c) a += b_a2c[col2];
+                v += a;
             }
-            if (b1) v += b1[col];
-            if (b2) v += b2[col];
             s[q] = v;
         }
         const float ig = sigmoid_f(s[0]), fg = sigmoid_f(s[1]), og = sigmoid_f(s[2]);
@@ -56,17 +62,20 @@ __global__ void maxout_cell_fwd_kernel(const float *__restrict__ partial, int sp
     }
 }
 
+// dh = dh_a (* dh_a_mask) + sum_s dh_b[s * b_stride + i] (the dX GEMM of the step after as K-slice slabs, or one finished buffer:
+// b_splits = 1); d_sums [N,5R], dc_prev.
 __global__ void maxout_cell_bwd_kernel(const float *__restrict__ dh_a, const float *__restrict__ dh_a_mask,
-                                       const float *__restrict__ dh_b, const float *__restrict__ dc_next,
-                                       const float *__restrict__ saved, const float *__restrict__ c_prev,
-                                       const float *__restrict__ c_new, float *__restrict__ d_sums,
-                                       float *__restrict__ dc_prev, int N, int R) {
+                                       const float *__restrict__ dh_b, int b_splits, int64_t b_stride,
+                                       const float *__restrict__ dc_next, const float *__restrict__ saved,
+                                       const float *__restrict__ c_prev, const float *__restrict__ c_new,
+                                       float *__restrict__ d_sums, float *__restrict__ dc_prev, int N, int R) {
     const size_t total = (size_t)N * R;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int r = (int)(i / R), j = (int)(i % R);
         float dh = 0.f;
         if (dh_a) dh += dh_a_mask ? dh_a[i] * dh_a_mask[i] : dh_a[i];
-        if (dh_b) dh += dh_b[i];
+        if (dh_b)
+            for (int k = 0; k < b_splits; ++k) dh += dh_b[(size_t)k * b_stride + i];
         const float *sv = saved + (size_t)r * 5 * R + j;
         const float ig = sv[0], fg = sv[R], og = sv[2 * R], ca = sv[3 * (size_t)R], cb = sv[4 * (size_t)R];
         const float cand = fmaxf(ca, cb);
@@ -84,46 +93,44 @@ __global__ void maxout_cell_bwd_kernel(const float *__restrict__ dh_a, const flo
     }
 }
 
-struct SegSpec {
-    const float *A; int lda; const float *B; int ldb; int K; int a_row_div;
-};
-int gemm(void *stream, int al, int bl, int M, int N, float *C, int ldc, const SegSpec *segs, int nseg, float *partial,
-         int64_t cap, int defer, int *splits_used, const float *bias = nullptr) {
-    capmi_gemm_desc d{};
-    d.nseg = nseg;
-    for (int i = 0; i < nseg; ++i) {
-        d.seg[i].A = segs[i].A; d.seg[i].lda = segs[i].lda; d.seg[i].B = segs[i].B; d.seg[i].ldb = segs[i].ldb;
-        d.seg[i].K = segs[i].K; d.seg[i].a_row_div = segs[i].a_row_div > 0 ? segs[i].a_row_div : 1;
-    }
-    d.a_layout = al; d.b_layout = bl; d.M = M; d.N = N; d.C = C; d.ldc = ldc; d.bias = bias;
-    d.partial = partial; d.partial_capacity = cap; d.splits = 0; d.defer_reduce = defer;
-    const int rc = capmi_gemm_f32(&d, stream);
-    if (splits_used) *splits_used = d.splits_used;
-    return rc;
-}
-
 }  // namespace
 
 extern "C" {
 
+int capmi_att2in2_cell_fwd(const float *partial, int splits, const float *partial2, int splits2, const float *addend,
+                           const float *b_i2h, const float *b_h2h, const float *b_a2c, const float *c_prev, float *h, float *c,
+                           float *saved, const float *out_mask, float *h_drop, int N, int R, void *stream) {
+    if (!partial || splits < 1 || splits2 < 0 || (splits2 > 0 && !partial2) || !c_prev || !h || !c || !saved || N <= 0 || R <= 0)
+        return CAPMI_EINVAL;
+    hipLaunchKernelGGL(maxout_cell_fwd_kernel, dim3(grid_for((size_t)N * R)), dim3(256), 0, (hipStream_t)stream, partial,
+                       splits, partial2, splits2, addend, b_i2h, b_h2h, b_a2c, c_prev, h, c, saved, out_mask, h_drop, N, R);
+    CAPMI_CHECK_LAUNCH();
+    return 0;
+}
+
+int capmi_att2in2_cell_bwd(const float *dh_a, const float *dh_a_mask, const float *dh_b, int b_splits, int64_t b_stride,
+                           const float *dc_next, const float *saved, const float *c_prev, const float *c_new, float *d_sums,
+                           float *dc_prev, int N, int R, void *stream) {
+    if (!saved || !c_prev || !c_new || !d_sums || !dc_prev || N <= 0 || R <= 0 || (dh_b && (b_splits < 1 || b_stride < (int64_t)N * R)))
+        return CAPMI_EINVAL;
+    hipLaunchKernelGGL(maxout_cell_bwd_kernel, dim3(grid_for((size_t)N * R)), dim3(256), 0, (hipStream_t)stream, dh_a,
+                       dh_a_mask, dh_b, b_splits, b_stride, dc_next, saved, c_prev, c_new, d_sums, dc_prev, N, R);
+    CAPMI_CHECK_LAUNCH();
+    return 0;
+}
+
 int capmi_maxout_cell_fwd(const float *partial, int splits, const float *b_i2h, const float *b_h2h, const float *c_prev,
                           float *h, float *c, float *saved, const float *out_mask, float *h_drop, int N, int R,
                           void *stream) {
-    if (!partial || splits < 1 || !c_prev || !h || !c || !saved || N <= 0 || R <= 0) return CAPMI_EINVAL;
-    hipLaunchKernelGGL(maxout_cell_fwd_kernel, dim3(grid_for((size_t)N * R)), dim3(256), 0, (hipStream_t)stream, partial,
-                       splits, b_i2h, b_h2h, c_prev, h, c, saved, out_mask, h_drop, N, R);
-    CAPMI_CHECK_LAUNCH();
-    return 0;
+    return capmi_att2in2_cell_fwd(partial, splits, nullptr, 0, nullptr, b_i2h, b_h2h, nullptr, c_prev, h, c, saved, out_mask,
+                                  h_drop, N, R, stream);
 }
 
 int capmi_maxout_cell_bwd(const float *dh_a, const float *dh_a_mask, const float *dh_b, const float *dc_next,
                           const float *saved, const float *c_prev, const float *c_new, float *d_sums, float *dc_prev,
                           int N, int R, void *stream) {
-    if (!saved || !c_prev || !c_new || !d_sums || !dc_prev || N <= 0 || R <= 0) return CAPMI_EINVAL;
-    hipLaunchKernelGGL(maxout_cell_bwd_kernel, dim3(grid_for((size_t)N * R)), dim3(256), 0, (hipStream_t)stream, dh_a,
-                       dh_a_mask, dh_b, dc_next, saved, c_prev, c_new, d_sums, dc_prev, N, R);
-    CAPMI_CHECK_LAUNCH();
-    return 0;
+    return capmi_att2in2_cell_bwd(dh_a, dh_a_mask, dh_b, 1, (int64_t)N * R, dc_next, saved, c_prev, c_new, d_sums, dc_prev, N,
+                                  R, stream);
 }
 
 int capmi_newfc_rollout_fwd(const capmi_newfc_weights *w, capmi_newfc_rollout *r, void *stream) {
@@ -132,14 +139,9 @@ int capmi_newfc_rollout_fwd(const capmi_newfc_weights *w, capmi_newfc_rollout *r
     if (B <= 0 || n <= 0 || N != B * n || T <= 0 || L < T || !r->partial) return CAPMI_EINVAL;
     // (r5: mode may carry CAPMI_SELECT_RAW -- a free-running rollout that stores the LOGITS, AttModel._sample(output_logsoftmax=0))
     if (((r->mode & 255) == 2 || r->teacher) && !r->forced) return CAPMI_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
     const size_t NR = (size_t)N * R;
     float *slabs = r->partial + CAPMI_WS_COUNTER_FLOATS;
-    hipError_t e;
-    if ((e = hipMemsetAsync(r->h, 0, NR * sizeof(float), st)) != hipSuccess) return (int)e;
-    if ((e = hipMemsetAsync(r->c, 0, NR * sizeof(float), st)) != hipSuccess) return (int)e;
-    if ((e = hipMemsetAsync(r->it, 0, (size_t)N * sizeof(int64_t), st)) != hipSuccess) return (int)e;
-    if ((e = hipMemsetAsync(r->unfinished, 1, (size_t)N, st)) != hipSuccess) return (int)e;
+    RC(capmi_rollout_init(r->h, r->c, nullptr, nullptr, (int64_t)NR, r->it, r->unfinished, N, stream));    // state 0, BOS
     int splits = 1;
     // step "-1": the image (AttModel.py:925-927); h = c = 0 so only the i2h term matters but keep the general form
     {
@@ -180,13 +182,8 @@ int capmi_newfc_rollout_bwd(const capmi_newfc_weights *w, const capmi_newfc_roll
     const int TN = T * N;
     float *P = s->partial;
     const int64_t cap = s->partial_capacity;
-    if ((r->mode & CAPMI_SELECT_RAW) && !r->teacher) {
-        // the rollout returned logits: d(logits) is the loss gradient itself (sparse and / or dense part), no softmax Jacobian
-        capmi_sparse_logp_grad sp = s->sparse ? *s->sparse : capmi_sparse_logp_grad{};
-        sp.raw = 1;
-        RC(capmi_logsoftmax_bwd_sparse(&sp, g_seq_logp, r->seq_logp, r->live, s->dlogits, N, L, T, V1, stream));
-    } else if (s->sparse) RC(capmi_logsoftmax_bwd_sparse(s->sparse, g_seq_logp, r->seq_logp, r->live, s->dlogits, N, L, T, V1, stream));
-    else RC(capmi_logsoftmax_bwd(g_seq_logp, r->seq_logp, r->live, s->dlogits, N, L, T, V1, stream));
+    RC(dlogits_bwd((r->mode & CAPMI_SELECT_RAW) && !r->teacher, s->sparse, g_seq_logp, r->seq_logp, r->live, s->dlogits, N, L, T,
+                   V1, stream));
     static const int env_group = capmi::knob("CAPMI_GEMM_GROUP", 1);
     const bool grouped = env_group != 0;
     capmi_group_gemm grp[3];
@@ -199,7 +196,7 @@ int capmi_newfc_rollout_bwd(const capmi_newfc_weights *w, const capmi_newfc_roll
         // the logit bias gradient rides in it.  CAPMI_GEMM_GROUP=0: one launch each, as before.
         if (grouped) {
             grp[n_grp++] = capmi_group_gemm{s->dlogits, r->h_drop, g->logit_w, V1, R, R, TN, V1, R, 0, 0,
-                                            (reinterpret_cast<uintptr_t>(g->logit_b) & 15) == 0 ? g->logit_b : nullptr};
+                                            aligned16(g->logit_b) ? g->logit_b : nullptr};
             if (!grp[n_grp - 1].colsum) RC(capmi_colsum(s->dlogits, TN, V1, V1, g->logit_b, 0, stream));
         } else {
             SegSpec b{s->dlogits, V1, r->h_drop, R, TN, 1};
@@ -229,17 +226,12 @@ int capmi_newfc_rollout_bwd(const capmi_newfc_weights *w, const capmi_newfc_roll
     {
         SegSpec a{ds_words, 5 * R, r->x, E, TN, 1};                       // dW_i2h (words)
         if (!grouped) RC(gemm(stream, 1, 1, 5 * R, E, g->i2h_w, E, &a, 1, P, cap, 0, nullptr));
-        // + image step: x = fc_emb[row / n]  -> materialise d_ximg and use the row-shared operand through a_row_div
+        // + image step: x = fc_emb[row / n] is shared by the n rows of an image, so their d_sums are summed first (d_x_all reused
+        // as [B,5R]) and the product has K = B rows
         // (grouped: the image step WRITES the gradient here and the words' product is added to it by the grouped launch)
-        capmi_gemm_desc d{};
-        d.nseg = 1; d.a_layout = 1; d.b_layout = 1; d.M = 5 * R; d.N = E; d.C = g->i2h_w; d.ldc = E; d.accumulate = grouped ? 0 : 1;
-        d.partial = P; d.partial_capacity = cap;
-        // A = d_sums(image) [N,5R] stored [K=N][M]; B must be [K=N][E] = fc_emb repeated: expand once into d_x scratch
-        // (N*E floats, tiny) with the embed kernel's gather: rows r -> fc_emb[r / n]
         RC(capmi_group_rowsum(s->d_sums, 1, 0, B, n, 5 * R, s->d_x_all /* reuse as [B,5R] sum */, stream));
-        d.seg[0].A = s->d_x_all; d.seg[0].lda = 5 * R; d.seg[0].B = r->fc_emb; d.seg[0].ldb = E; d.seg[0].K = B;
-        d.seg[0].a_row_div = 1;
-        RC(capmi_gemm_f32(&d, stream));
+        SegSpec img{s->d_x_all, 5 * R, r->fc_emb, E, B, 1};
+        RC(gemm(stream, 1, 1, 5 * R, E, g->i2h_w, E, &img, 1, P, cap, 0, nullptr, nullptr, nullptr, grouped ? 0 : 1));
         // d_fc_emb [B,E] = (sum over the n rows of the image of d_sums_img) W_i2h
         if (g->d_fc_emb) {
             SegSpec f{s->d_x_all, 5 * R, w->i2h_w, E, 5 * R, 1};
@@ -247,8 +239,7 @@ int capmi_newfc_rollout_bwd(const capmi_newfc_weights *w, const capmi_newfc_roll
         }
         // bias gradients: all T+1 steps
         RC(capmi_colsum(s->d_sums, (T + 1) * N, 5 * R, 5 * R, g->i2h_b, 0, stream));
-        hipError_t e = hipMemcpyAsync(g->h2h_b, g->i2h_b, (size_t)5 * R * sizeof(float), hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) return (int)e;
+        HIP_RC(hipMemcpyAsync(g->h2h_b, g->i2h_b, (size_t)5 * R * sizeof(float), hipMemcpyDeviceToDevice, st));
         // dW_h2h: h_prev of word step t is slot t+1; of the image step it is slot 0 (zeros) -> words only
         SegSpec c{ds_words, 5 * R, r->h + NR, R, TN, 1};
         if (grouped) {
@@ -258,8 +249,7 @@ int capmi_newfc_rollout_bwd(const capmi_newfc_weights *w, const capmi_newfc_roll
         // word embeddings (plain Embedding: no ReLU, no dropout)
         SegSpec x{ds_words, 5 * R, w->i2h_w, E, 5 * R, 1};
         RC(gemm(stream, 0, 1, TN, E, s->d_x_all, E, &x, 1, P, cap, 0, nullptr));
-        e = hipMemsetAsync(g->embed, 0, (size_t)V1 * E * sizeof(float), st);
-        if (e != hipSuccess) return (int)e;
+        HIP_RC(hipMemsetAsync(g->embed, 0, (size_t)V1 * E * sizeof(float), st));
         RC(capmi_embed_bwd(r->it_all, s->d_x_all, nullptr, nullptr, g->embed, TN, E, 0, stream));
     }
     if (n_grp) RC(capmi_gemm_group_tn(grp, n_grp, cap > CAPMI_WS_COUNTER_FLOATS ? P + CAPMI_WS_COUNTER_FLOATS : nullptr,

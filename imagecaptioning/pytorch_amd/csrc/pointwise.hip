@@ -2,11 +2,10 @@
 // cell pointwise stage (fused with the split-K reduction of the gate GEMM), their backward,
 // dropout-mask generation, column sums and the fused clip+Adam update.  All are HBM/latency bound:
 // 16-byte accesses where the layout allows, grid-stride loops capped at 2048 workgroups.
-#include "capmi_common.h"
 #include <cstdlib>
+#include "host_common.h"
 #include "profile.h"
 #include "embed_bwd_det.h"
-#include "../../../include/capmi.h"
 
 using namespace capmi;
 
@@ -18,19 +17,6 @@ const uint64_t *rng_epoch() { return g_rng_epoch.load(std::memory_order_relaxed)
 }
 
 namespace {
-
-inline int grid_for(size_t work, int per_block = 256, int cap = 2048) {
-    size_t b = (work + per_block - 1) / per_block;
-    if (b > (size_t)cap) b = cap;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
-// all (possibly null) pointers 16-byte aligned
-template <typename... P>
-inline bool aligned16(P... p) {
-    return ((... | reinterpret_cast<uintptr_t>(p)) & 15) == 0;
-}
 
 // ---------------------------------------------------------------- embedding
 __global__ void embed_fwd_kernel(const int64_t *__restrict__ it, int it_stride, int64_t *__restrict__ it_save,
@@ -907,10 +893,7 @@ int capmi_colsum(const float *in, int rows, int cols, int ld, float *out, int ac
         if (rsplit > max_by_rows) rsplit = max_by_rows;
         if (rsplit < 1) rsplit = 1;
     }
-    if (rsplit > 1 && !accumulate) {
-        hipError_t e = hipMemsetAsync(out, 0, (size_t)cols * sizeof(float), (hipStream_t)stream);
-        if (e != hipSuccess) return (int)e;
-    }
+    if (rsplit > 1 && !accumulate) HIP_RC(hipMemsetAsync(out, 0, (size_t)cols * sizeof(float), (hipStream_t)stream));
     hipLaunchKernelGGL(colsum_kernel, dim3(cblocks, rsplit), dim3(CS_Q * CS_R), 0, (hipStream_t)stream, in, rows, cols, ld, out,
                        accumulate, vec, rsplit);
     CAPMI_CHECK_LAUNCH();

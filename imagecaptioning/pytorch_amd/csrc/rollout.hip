@@ -13,54 +13,14 @@
 //    logit layer (forward-saved activations are stored time-major [T,N,...] for exactly this);
 //    only the 4 skinny "dX" GEMMs + the pointwise cells + the attention Jacobian stay in the loop.
 #include <chrono>
-#include "capmi_common.h"
 #include <cstdlib>
-#include "../../../include/capmi.h"
+#include "host_common.h"
 
 namespace {
-
-#define RC(x)                 \
-    do {                      \
-        int rc__ = (x);       \
-        if (rc__) return rc__;\
-    } while (0)
-
-struct SegSpec {
-    const float *A;
-    int lda;
-    const float *B;
-    int ldb;
-    int K;
-    int a_row_div;
-    const void *Apl;        // the same activations as A planes (capmi.h capmi_planes_from_f32), or null
-};
 
 // chunk images of a K-wide planes buffer
 inline int64_t pl_chunks(int K) { return (K + 31) / 32; }
 constexpr int64_t PL_CHUNK = 12288;
-
-// C[M,N] = sum_s A_s op B_s ; thin wrapper filling capmi_gemm_desc
-int gemm(void *stream, int a_layout, int b_layout, int M, int N, float *C, int ldc, const SegSpec *segs, int nseg,
-         float *partial, int64_t cap, int defer, int *splits_used, const float *bias = nullptr,
-         const float *bias2 = nullptr, int accumulate = 0, const void *zero_planes = nullptr, int splits_hint = 0) {
-    capmi_gemm_desc d{};
-    d.nseg = nseg;
-    for (int i = 0; i < nseg; ++i) {
-        d.seg[i].A = segs[i].A; d.seg[i].lda = segs[i].lda;
-        d.seg[i].B = segs[i].B; d.seg[i].ldb = segs[i].ldb;
-        d.seg[i].K = segs[i].K; d.seg[i].a_row_div = segs[i].a_row_div > 0 ? segs[i].a_row_div : 1;
-        d.a_planes[i] = zero_planes ? segs[i].Apl : nullptr;
-    }
-    d.a_layout = a_layout; d.b_layout = b_layout;
-    d.M = M; d.N = N; d.C = C; d.ldc = ldc;
-    d.bias = bias; d.bias2 = bias2;
-    d.accumulate = accumulate;
-    d.partial = partial; d.partial_capacity = cap;
-    d.splits = splits_hint; d.defer_reduce = defer;
-    const int rc = capmi_gemm_f32(&d, stream);
-    if (splits_used) *splits_used = d.splits_used;
-    return rc;
-}
 
 // teacher forcing: [T,N,R] (time-major, as the steps wrote it) -> [N,T,R] so that ONE fat GEMM over all T*N rows lands in
 // the [N,L,V1] layout of seqLogprobs
@@ -411,15 +371,13 @@ int capmi_updown_rollout_fwd(const capmi_updown_weights *w, capmi_updown_rollout
                 steps_run, T, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - ee_t0).count(), ee_wait_us);
     r->steps_run = steps_run;
     if (steps_run < T) {     // the steps never run leave pad tokens and zero log-probs like the reference's untouched columns
-        hipError_t e = hipSuccess;
         const size_t tail = (size_t)(L - steps_run);
-        if (r->seq_logp) e = hipMemset2DAsync(r->seq_logp + (size_t)steps_run * V1, (size_t)L * V1 * sizeof(float), 0,
-                                              tail * V1 * sizeof(float), N, st);
-        if (e == hipSuccess) e = hipMemset2DAsync(r->seq + steps_run, (size_t)L * sizeof(int64_t), 0, tail * sizeof(int64_t), N, st);
-        if (e == hipSuccess && r->sel_logp)
-            e = hipMemset2DAsync(r->sel_logp + steps_run, (size_t)L * sizeof(float), 0, tail * sizeof(float), N, st);
-        if (e == hipSuccess && r->live) e = hipMemset2DAsync(r->live + steps_run, (size_t)L, 0, tail, N, st);
-        if (e != hipSuccess) return (int)e;
+        if (r->seq_logp)
+            HIP_RC(hipMemset2DAsync(r->seq_logp + (size_t)steps_run * V1, (size_t)L * V1 * sizeof(float), 0, tail * V1 * sizeof(float),
+                                    N, st));
+        HIP_RC(hipMemset2DAsync(r->seq + steps_run, (size_t)L * sizeof(int64_t), 0, tail * sizeof(int64_t), N, st));
+        if (r->sel_logp) HIP_RC(hipMemset2DAsync(r->sel_logp + steps_run, (size_t)L * sizeof(float), 0, tail * sizeof(float), N, st));
+        if (r->live) HIP_RC(hipMemset2DAsync(r->live + steps_run, (size_t)L, 0, tail, N, st));
     }
     if (batched_logit) {
         float *hd_nt = r->partial + CAPMI_WS_COUNTER_FLOATS;          // the split-K workspace is idle here
@@ -569,8 +527,7 @@ int capmi_updown_rollout_bwd_phases(const capmi_updown_weights *w, const capmi_u
     int n_copies = 0;
     auto colsum = [&](const float *in, int rows, int ncol, float *out, float *out2) -> int {
         for (int i = 0; i < n_grp; ++i)
-            if (grp[i].A == in && grp[i].K == rows && grp[i].M == ncol && grp[i].lda == ncol && !grp[i].colsum && n_copies < 4 &&
-                (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
+            if (grp[i].A == in && grp[i].K == rows && grp[i].M == ncol && grp[i].lda == ncol && !grp[i].colsum && n_copies < 4 && aligned16(out)) {
                 grp[i].colsum = out;
                 if (out2) copies[n_copies++] = Copy2{out2, out, (size_t)ncol * sizeof(float)};
                 return 0;
@@ -581,22 +538,13 @@ int capmi_updown_rollout_bwd_phases(const capmi_updown_weights *w, const capmi_u
         }
         int rc = capmi_colsum(in, rows, ncol, ncol, out, 0, stream);
         if (rc) return rc;
-        if (out2) {
-            hipError_t e = hipMemcpyAsync(out2, out, (size_t)ncol * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream);
-            if (e != hipSuccess) return (int)e;
-        }
+        if (out2) HIP_RC(hipMemcpyAsync(out2, out, (size_t)ncol * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
         return 0;
     };
 
     // ---- logit layer, batched over all T*N rows ----------------------------------------------
     if (phases & CAPMI_BWD_LOGIT) {
-        if (r->raw_logits && !r->teacher) {
-            // the rollout returned logits: d(logits) is the loss gradient (sparse and / or dense parts), no softmax Jacobian
-            capmi_sparse_logp_grad sp = s->sparse ? *s->sparse : capmi_sparse_logp_grad{};
-            sp.raw = 1;
-            RC(capmi_logsoftmax_bwd_sparse(&sp, g_seq_logp, r->seq_logp, r->live, s->dlogits, N, L, T, V1, stream));
-        } else if (s->sparse) RC(capmi_logsoftmax_bwd_sparse(s->sparse, g_seq_logp, r->seq_logp, r->live, s->dlogits, N, L, T, V1, stream));
-        else RC(capmi_logsoftmax_bwd(g_seq_logp, r->seq_logp, r->live, s->dlogits, N, L, T, V1, stream));
+        RC(dlogits_bwd(r->raw_logits && !r->teacher, s->sparse, g_seq_logp, r->seq_logp, r->live, s->dlogits, N, L, T, V1, stream));
         SegSpec a{s->dlogits, V1, w->logit_w, R, V1, 1};   // d_hdrop = dlogits W_logit          [TN,R]
         RC(gemm(stream, 0, 1, TN, R, s->d_hdrop, R, &a, 1, P, cap, 0, nullptr));
         SegSpec b{s->dlogits, V1, a_hdrop, R, TN, 1};       // dW_logit = dlogits^T h_drop         [V1,R]
@@ -617,25 +565,19 @@ int capmi_updown_rollout_bwd_phases(const capmi_updown_weights *w, const capmi_u
     //      ~80 launches.
     if (phases & CAPMI_BWD_RECURRENT) {
         const bool al = R % 4 == 0 && ld_att_ih % 4 == 0 &&
-                        ((reinterpret_cast<uintptr_t>(w->lang_w_ih) | reinterpret_cast<uintptr_t>(w->lang_w_hh) |
-                          reinterpret_cast<uintptr_t>(w->att_w_ih) | reinterpret_cast<uintptr_t>(w->att_w_hh) |
-                          reinterpret_cast<uintptr_t>(s->w_lang_cat) | reinterpret_cast<uintptr_t>(s->w_att_cat)) & 15) == 0;
+                        aligned16(w->lang_w_ih, w->lang_w_hh, w->att_w_ih, w->att_w_hh, s->w_lang_cat, s->w_att_cat);
         if (al) {
             const int total = 4 * R * 5 * R;
             hipLaunchKernelGGL(pack_recurrent_kernel, dim3((total / 4 + 255) / 256), dim3(256), 0, st, w->lang_w_ih, w->lang_w_hh,
                                w->att_w_ih, w->att_w_hh, s->w_lang_cat, s->w_att_cat, R, ld_att_ih);
             CAPMI_CHECK_LAUNCH();
         } else {
-            hipError_t e;
             const size_t fb = sizeof(float);
-            if ((e = hipMemcpy2DAsync(s->w_lang_cat, 3 * R * fb, w->lang_w_ih, 2 * R * fb, 2 * R * fb, 4 * R,
-                                      hipMemcpyDeviceToDevice, st)) != hipSuccess) return (int)e;
-            if ((e = hipMemcpy2DAsync(s->w_lang_cat + 2 * R, 3 * R * fb, w->lang_w_hh, R * fb, R * fb, 4 * R,
-                                      hipMemcpyDeviceToDevice, st)) != hipSuccess) return (int)e;
-            if ((e = hipMemcpy2DAsync(s->w_att_cat, 2 * R * fb, w->att_w_ih, (size_t)ld_att_ih * fb, R * fb, 4 * R,
-                                      hipMemcpyDeviceToDevice, st)) != hipSuccess) return (int)e;
-            if ((e = hipMemcpy2DAsync(s->w_att_cat + R, 2 * R * fb, w->att_w_hh, R * fb, R * fb, 4 * R,
-                                      hipMemcpyDeviceToDevice, st)) != hipSuccess) return (int)e;
+            HIP_RC(hipMemcpy2DAsync(s->w_lang_cat, 3 * R * fb, w->lang_w_ih, 2 * R * fb, 2 * R * fb, 4 * R, hipMemcpyDeviceToDevice, st));
+            HIP_RC(hipMemcpy2DAsync(s->w_lang_cat + 2 * R, 3 * R * fb, w->lang_w_hh, R * fb, R * fb, 4 * R, hipMemcpyDeviceToDevice, st));
+            HIP_RC(hipMemcpy2DAsync(s->w_att_cat, 2 * R * fb, w->att_w_ih, (size_t)ld_att_ih * fb, R * fb, 4 * R, hipMemcpyDeviceToDevice,
+                                    st));
+            HIP_RC(hipMemcpy2DAsync(s->w_att_cat + R, 2 * R * fb, w->att_w_hh, R * fb, R * fb, 4 * R, hipMemcpyDeviceToDevice, st));
         }
     }
 
@@ -650,9 +592,8 @@ int capmi_updown_rollout_bwd_phases(const capmi_updown_weights *w, const capmi_u
     if (capm <= CAPMI_WS_COUNTER_FLOATS || cap1 <= CAPMI_WS_COUNTER_FLOATS || caph <= CAPMI_WS_COUNTER_FLOATS) return CAPMI_EINVAL;
     static const bool self_reduce = capmi::research("CAPMI_GEMM_SELF_REDUCE", 0) != 0;
     if (self_reduce) {   // ticket words of the carved regions start zeroed like the main one (only the in-launch reduction reads them)
-        hipError_t e = hipMemsetAsync(P1, 0, CAPMI_WS_COUNTER_FLOATS * sizeof(float), st);
-        if (e == hipSuccess) e = hipMemsetAsync(Ph, 0, CAPMI_WS_COUNTER_FLOATS * sizeof(float), st);
-        if (e != hipSuccess) return (int)e;
+        HIP_RC(hipMemsetAsync(P1, 0, CAPMI_WS_COUNTER_FLOATS * sizeof(float), st));
+        HIP_RC(hipMemsetAsync(Ph, 0, CAPMI_WS_COUNTER_FLOATS * sizeof(float), st));
     }
     // A planes of d_gates (round 3, <= 64 gradient rows): [dg_lang | dg_att | one zero image]
     unsigned char *pl_dg_lang = nullptr, *pl_dg_att = nullptr, *pl_zero = nullptr;
@@ -729,7 +670,6 @@ int capmi_updown_rollout_bwd_phases(const capmi_updown_weights *w, const capmi_u
     // attention LSTM
     if (phases & CAPMI_BWD_ATT_LSTM) {
         RC(colsum(s->dg_att, TN, 4 * R, g->att_b_ih, g->att_b_hh));
-        hipError_t e;
         // fc columns: sum over time and over the n rows of an image first
         RC(capmi_group_rowsum(s->dg_att, T, (int64_t)N * 4 * R, B, n, 4 * R, s->sum_dg_att, stream));
         // (K = B rows: listed for the grouped launch like the time-batched ones -- any K since r6)
@@ -741,8 +681,7 @@ int capmi_updown_rollout_bwd_phases(const capmi_updown_weights *w, const capmi_u
         // token embedding: d_xt = dg_att W_ih(:, 2R:) then scatter through ReLU/dropout
         SegSpec x{s->dg_att, 4 * R, w->att_w_ih + 2 * R, ld_att_ih, 4 * R, 1};
         RC(gemm(stream, 0, 1, TN, E, s->d_xt_all, E, &x, 1, P, cap, 0, nullptr));
-        e = hipMemsetAsync(g->embed, 0, (size_t)V1 * E * sizeof(float), st);
-        if (e != hipSuccess) return (int)e;
+        HIP_RC(hipMemsetAsync(g->embed, 0, (size_t)V1 * E * sizeof(float), st));
         RC(capmi_embed_bwd(a_it, s->d_xt_all, a_xt, a_dropxt, g->embed, TN, E, 1, stream));
     }
     // language LSTM
@@ -763,10 +702,8 @@ int capmi_updown_rollout_bwd_phases(const capmi_updown_weights *w, const capmi_u
         // behind alpha_net's partial rows, which the batched column sum below still has to read
         const int64_t skip = CAPMI_WS_COUNTER_FLOATS + (((int64_t)B * K * A + 1023) & ~(int64_t)1023);
         RC(capmi_gemm_group_tn(grp, n_grp, cap > skip ? P + skip : nullptr, cap > skip ? cap - skip : 0, stream));
-        for (int i = 0; i < n_copies; ++i) {
-            hipError_t e = hipMemcpyAsync(copies[i].dst, copies[i].src, copies[i].bytes, hipMemcpyDeviceToDevice, st);
-            if (e != hipSuccess) return (int)e;
-        }
+        for (int i = 0; i < n_copies; ++i)
+            HIP_RC(hipMemcpyAsync(copies[i].dst, copies[i].src, copies[i].bytes, hipMemcpyDeviceToDevice, st));
     }
     if (n_cols) RC(capmi_colsum_batch_args(cols, n_cols, stream));
     return 0;

@@ -3,9 +3,8 @@
 // workgroup's LDS; K = 36 regions / T <= 21 tokens in the BASELINE configs), token embedding + sinusoidal
 // position, row log-softmax.  Cross-attention reads the per-image memory K/V once per image and serves the n
 // caption rows of that image from LDS (no repeat_tensors, TransformerModel.py:330-334).
-#include "capmi_common.h"
+#include "host_common.h"
 #include "embed_bwd_det.h"
-#include "../../../include/capmi.h"
 
 using namespace capmi;
 
@@ -1022,12 +1021,6 @@ __global__ void meanpool_bwd_kernel(const float *__restrict__ dmean, const float
     }
 }
 
-inline int grid_for(size_t work) {
-    size_t b = (work + 255) / 256;
-    if (b > 4096) b = 4096;
-    return (int)(b < 1 ? 1 : b);
-}
-
 }  // namespace
 
 // ---- caption statistics of the evaluation loop (reference captioning/utils/eval_utils.py:173-174) --------------------------------
@@ -1291,7 +1284,7 @@ int capmi_mha_bwd_slabs(const float *d_o, int do_splits, int64_t do_stride, int 
 int capmi_embed_pe_fwd(const int64_t *tok, int tok_ld, const float *E, const float *pe, const float *drop, float *x, int N,
                        int T, int D, int pos0, void *stream) {
     if (!tok || !E || !pe || !x || N <= 0 || T <= 0 || D <= 0 || pos0 < 0) return CAPMI_EINVAL;
-    hipLaunchKernelGGL(embed_pe_fwd_kernel, dim3(grid_for((size_t)N * T * D)), dim3(256), 0, (hipStream_t)stream, tok, tok_ld,
+    hipLaunchKernelGGL(embed_pe_fwd_kernel, dim3(grid_for((size_t)N * T * D, 256, 4096)), dim3(256), 0, (hipStream_t)stream, tok, tok_ld,
                        E, pe, drop, x, N, T, D, pos0, sqrtf((float)D));
     CAPMI_CHECK_LAUNCH();
     return 0;
@@ -1310,7 +1303,7 @@ int capmi_embed_pe_bwd(const int64_t *tok, int tok_ld, const float *dx, const fl
         CAPMI_CHECK_LAUNCH();
         return 0;
     }
-    hipLaunchKernelGGL(embed_pe_bwd_kernel, dim3(grid_for((size_t)N * T * D)), dim3(256), 0, (hipStream_t)stream, tok, tok_ld,
+    hipLaunchKernelGGL(embed_pe_bwd_kernel, dim3(grid_for((size_t)N * T * D, 256, 4096)), dim3(256), 0, (hipStream_t)stream, tok, tok_ld,
                        dx, drop, dE, N, T, D, sqrtf((float)D));
     CAPMI_CHECK_LAUNCH();
     return 0;
@@ -1318,7 +1311,7 @@ int capmi_embed_pe_bwd(const int64_t *tok, int tok_ld, const float *dx, const fl
 
 int capmi_glu_fwd(const float *pre, const float *mask, const float *residual, float *out, int M, int R, void *stream) {
     if (!pre || !out || M <= 0 || R <= 0) return CAPMI_EINVAL;
-    hipLaunchKernelGGL(glu_fwd_kernel, dim3(grid_for((size_t)M * R)), dim3(256), 0, (hipStream_t)stream, pre, mask, residual, out,
+    hipLaunchKernelGGL(glu_fwd_kernel, dim3(grid_for((size_t)M * R, 256, 4096)), dim3(256), 0, (hipStream_t)stream, pre, mask, residual, out,
                        M, R);
     CAPMI_CHECK_LAUNCH();
     return 0;
@@ -1335,7 +1328,7 @@ int capmi_glu_fwd_fused(const float *slabs, int splits, int64_t stride, const fl
          reinterpret_cast<uintptr_t>(mask_b) | reinterpret_cast<uintptr_t>(out_b) | reinterpret_cast<uintptr_t>(planes_a) |
          reinterpret_cast<uintptr_t>(planes_b)) & 15)
         return CAPMI_EINVAL;
-    hipLaunchKernelGGL(glu_fwd_fused_kernel, dim3(grid_for((size_t)M * (R / 4))), dim3(256), 0, (hipStream_t)stream, slabs, splits,
+    hipLaunchKernelGGL(glu_fwd_fused_kernel, dim3(grid_for((size_t)M * (R / 4), 256, 4096)), dim3(256), 0, (hipStream_t)stream, slabs, splits,
                        (size_t)stride, bias, pre, out, mask_a, out_a, static_cast<unsigned char *>(planes_a), mask_b, out_b,
                        static_cast<unsigned char *>(planes_b), M, R);
     CAPMI_CHECK_LAUNCH();
@@ -1350,7 +1343,7 @@ int capmi_glu_bwd_add(const float *d_out, const float *mask, const float *add_sl
                       const float *add_mask, const float *pre, float *d_pre, int M, int R, void *stream) {
     if (!d_out || !pre || !d_pre || M <= 0 || R <= 0) return CAPMI_EINVAL;
     if (add_slabs && (add_splits < 1 || (add_splits > 1 && add_stride < (int64_t)M * R))) return CAPMI_EINVAL;
-    hipLaunchKernelGGL(glu_bwd_kernel, dim3(grid_for((size_t)M * R)), dim3(256), 0, (hipStream_t)stream, d_out, mask, pre, d_pre,
+    hipLaunchKernelGGL(glu_bwd_kernel, dim3(grid_for((size_t)M * R, 256, 4096)), dim3(256), 0, (hipStream_t)stream, d_out, mask, pre, d_pre,
                        M, R, add_slabs, add_splits, (size_t)add_stride, add_mask);
     CAPMI_CHECK_LAUNCH();
     return 0;
@@ -1359,7 +1352,7 @@ int capmi_glu_bwd_add(const float *d_out, const float *mask, const float *add_sl
 int capmi_split_halves(const float *slabs, int splits, int64_t stride, const float *mask_lo, const float *mask_hi, float *out_lo,
                        float *out_hi, int M, int R, void *stream) {
     if (!slabs || !out_lo || !out_hi || splits < 1 || M <= 0 || R <= 0) return CAPMI_EINVAL;
-    hipLaunchKernelGGL(split_halves_kernel, dim3(grid_for((size_t)M * 2 * R)), dim3(256), 0, (hipStream_t)stream, slabs, splits,
+    hipLaunchKernelGGL(split_halves_kernel, dim3(grid_for((size_t)M * 2 * R, 256, 4096)), dim3(256), 0, (hipStream_t)stream, slabs, splits,
                        (size_t)stride, mask_lo, mask_hi, out_lo, out_hi, M, R);
     CAPMI_CHECK_LAUNCH();
     return 0;
@@ -1374,7 +1367,7 @@ int capmi_meanpool_fwd(const float *x, const float *mask, float *mean, int B, in
 
 int capmi_meanpool_bwd(const float *dmean, const float *mask, float *dx, int accumulate, int B, int K, int D, void *stream) {
     if (!dmean || !dx || B <= 0 || K <= 0 || D <= 0) return CAPMI_EINVAL;
-    hipLaunchKernelGGL(meanpool_bwd_kernel, dim3(grid_for((size_t)B * K * D)), dim3(256), 0, (hipStream_t)stream, dmean, mask, dx,
+    hipLaunchKernelGGL(meanpool_bwd_kernel, dim3(grid_for((size_t)B * K * D, 256, 4096)), dim3(256), 0, (hipStream_t)stream, dmean, mask, dx,
                        accumulate, B, K, D);
     CAPMI_CHECK_LAUNCH();
     return 0;
