@@ -117,7 +117,7 @@ class NewFCRollout(C.Structure):
                 [('mode', C.c_int), ('temperature', C.c_float), ('gumbel', c_f), ('seed', C.c_uint64), ('forced', c_f),
                  ('forced_ld', C.c_int), ('teacher', C.c_int)] +
                 [(k, c_f) for k in ('h', 'c', 'x', 'it_all', 'saved', 'h_drop', 'seq', 'seq_logp', 'sel_logp', 'live',
-                                    'logits', 'it', 'unfinished', 'partial')] + [('partial_capacity', C.c_int64)])
+                                    'logits', 'it', 'unfinished', 'partial')] + [('partial_capacity', C.c_int64), ('ss_mode', c_f)])
 
 
 class NewFCGrads(C.Structure):

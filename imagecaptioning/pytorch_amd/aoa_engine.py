@@ -168,16 +168,22 @@ class AoAGraph:
 
     # ------------------------------------------------------------------ rollout
     def rollout(self, n, T, L, mode='forced', forced=None, teacher=False, temperature=1.0, seed=0, gumbel=None, keep=True,
-                top_k=0, top_p=0.0, raw=False):
+                top_k=0, top_p=0.0, raw=False, ss_mode=None):
         """T decoder steps on N = B*n rows.  teacher: inputs forced[:, t] (AttModel._forward); else AttModel._sample with
         mode greedy / sample / forced (tokens chosen at t are fed at t+1).  raw (free-running only): the returned rows are the LOGITS
         (AttModel._sample(output_logsoftmax=0), AttModel.py:171-175, 265: what the margin structure losses read), the choice of the
-        tokens is the same; the backward then takes the loss gradient as d(logits)."""
+        tokens is the same; the backward then takes the loss gradient as d(logits).
+        ss_mode (uint8 [T,N], teacher only): scheduled sampling (AttModel.py:145-154), 1 = the input of (step, row) is drawn from the
+        previous step's distribution (temperature 1, `seed` / `gumbel`), 2 = forced[row, step]; row 0 is not read.  The select launch
+        of step t chooses the input of step t+1; the outputs keep their teacher-forced meaning."""
         P, h, B, K, R = self.P, self.h, self.B, self.K, self.R
         N = B * n
         V1, E = P['embed.0.weight'].shape
         dev = self.dev
         self.n, self.N, self.T, self.L, self.keep = n, N, T, L, keep
+        if ss_mode is not None:
+            assert teacher and ss_mode.dtype == torch.uint8 and ss_mode.shape == (T, N) and ss_mode.is_contiguous()
+        sched = teacher and ss_mode is not None
         z = lambda *s: torch.empty(*s, dtype=_f32, device=dev)       # noqa: E731
         W_ih, W_hh = P['core.att_lstm.weight_ih'], P['core.att_lstm.weight_hh']
         ld_ih = E + R
@@ -227,11 +233,12 @@ class AoAGraph:
             pl_zero = ops.zero_planes(dev, max(nbR, nbE) // 12288)
             self.ctx_in[0].zero_()                               # out_0 = 0 (AoAModel.py:127-129)
         # r5: a free-running rollout gets the embedding of step t+1 from the select launch of step t (capmi_next_embed, as the UpDown
-        # driver does): one launch fewer per step; a teacher-forced one knows its tokens and keeps the per-step launch
-        fold_embed = SLAB_CONSUMERS and use_pl and not teacher
+        # driver does): one launch fewer per step; a teacher-forced one knows its tokens and keeps the per-step launch -- unless it
+        # is a scheduled-sampling one, whose tokens are chosen by the select launch of the step before
+        fold_embed = SLAB_CONSUMERS and use_pl and (not teacher or sched)
         for t in range(T):
             m_xt, m_ctx, m_out, m_p = self.m_xt[t], self.m_ctx[t], self.m_out[t], self.m_patt[t]
-            tok_src = (forced.data_ptr() + 8 * t, forced.shape[1]) if teacher else (ptr(it), 1)
+            tok_src = (forced.data_ptr() + 8 * t, forced.shape[1]) if (teacher and not (sched and t > 0)) else (ptr(it), 1)
             if fold_embed and t > 0:
                 pass                                              # written by the select launch of step t-1
             elif use_pl:
@@ -291,6 +298,13 @@ class AoAGraph:
             ne = None
             if fold_embed and t + 1 < T:
                 ne = dict(E=P['embed.0.weight'], mask=self.m_xt[t + 1], x=self.xt[t + 1], it_save=self.it_all[t + 1], relu=1, x_planes=pl_xt)
+            if sched and t + 1 < T:
+                # the token chosen here is the INPUT of step t+1: forced[:, t+1] (ss_mode 2 rows) or a draw from this step's
+                # log-probs (ss_mode 1 rows).  A drawn 0 does not end the row: the labels decide that (no_finish_mask).
+                ops.logsoftmax_select(ws.slabs, t, L, 2, 1.0, None if gumbel is None else gumbel[t], seed, forced[:, 1:], 1, self.seq, it,
+                                      unf, self.seq_logp, self.sel, self.live, splits=sp, stride=N * V1, bias=P['logit.bias'],
+                                      shape=(N, V1), next_embed=ne, ss_mode=ss_mode[t + 1])
+                continue
             ops.logsoftmax_select(ws.slabs, t, L, mode_i, temperature, None if gumbel is None else gumbel[t], seed, forced,
                                   1 if teacher else 0, self.seq, it, unf, self.seq_logp, self.sel, self.live, top_k, top_p,
                                   splits=sp, stride=N * V1, bias=P['logit.bias'], shape=(N, V1), next_embed=ne)

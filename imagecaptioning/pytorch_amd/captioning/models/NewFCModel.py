@@ -95,8 +95,6 @@ class NewFCModel(CaptionModel):
         return seq, sparse_logp.attach(logp, sink)
 
     def _forward(self, fc_feats, att_feats, seq, att_masks=None):
-        if self.training and self.ss_prob > 0:
-            raise NotImplementedError('scheduled sampling (ss_prob > 0) is only wired into the UpDown rollout')
         B = fc_feats.size(0)
         if seq.ndim == 3:
             seq = seq.reshape(-1, seq.shape[2])
@@ -104,7 +102,16 @@ class NewFCModel(CaptionModel):
         N, T = seq.shape
         zero_cols = (seq[:, 1:].sum(0) == 0).nonzero()
         T_eff = int(zero_cols[0]) + 1 if zero_cols.numel() else T
-        _, logp = self._run(dict(n=N // B, T=T_eff, L=T, mode='forced', forced=seq, teacher=True), fc_feats)
+        cfg = dict(n=N // B, T=T_eff, L=T, mode='forced', forced=seq, teacher=True)
+        if self.training and self.ss_prob > 0.0:
+            # AttModel.py:145-154: the coin flips of all steps here, the draws inside the rollout (_ss_coin / _ss_gumbel: test hooks)
+            coin = self._ss_coin if getattr(self, '_ss_coin', None) is not None else \
+                torch.rand(T_eff, N, device=fc_feats.device) < self.ss_prob
+            cfg['ss_mode'] = torch.where(coin, 1, 2).to(torch.uint8).contiguous()
+            cfg['seed'] = self._next_seed()
+            if getattr(self, '_ss_gumbel', None) is not None:
+                cfg['gumbel'] = self._ss_gumbel
+        _, logp = self._run(cfg, fc_feats)
         return logp
 
     def _decode_stepper(self, fc_feats, att_feats, att_masks, L):

@@ -139,7 +139,9 @@ int capmi_newfc_rollout_fwd(const capmi_newfc_weights *w, capmi_newfc_rollout *r
     if (B <= 0 || n <= 0 || N != B * n || T <= 0 || L < T || !r->partial) return CAPMI_EINVAL;
     // (r5: mode may carry CAPMI_SELECT_RAW -- a free-running rollout that stores the LOGITS, AttModel._sample(output_logsoftmax=0))
     if (((r->mode & 255) == 2 || r->teacher) && !r->forced) return CAPMI_EINVAL;
+    if (r->ss_mode && !r->teacher) return CAPMI_EINVAL;
     const size_t NR = (size_t)N * R;
+    const bool sched = r->teacher && r->ss_mode;
     float *slabs = r->partial + CAPMI_WS_COUNTER_FLOATS;
     RC(capmi_rollout_init(r->h, r->c, nullptr, nullptr, (int64_t)NR, r->it, r->unfinished, N, stream));    // state 0, BOS
     int splits = 1;
@@ -155,7 +157,9 @@ int capmi_newfc_rollout_fwd(const capmi_newfc_weights *w, capmi_newfc_rollout *r
         const float *h_prev = r->h + (size_t)(t + 1) * NR, *c_prev = r->c + (size_t)(t + 1) * NR;
         float *h = r->h + (size_t)(t + 2) * NR, *c = r->c + (size_t)(t + 2) * NR;
         float *h_drop = r->h_drop + (size_t)t * NR;
-        if (r->teacher)
+        if (sched && t > 0) {
+            // scheduled sampling: x[t] and it_all[t] were written by the select launch of step t-1
+        } else if (r->teacher)
             RC(capmi_embed_fwd(r->forced + t, r->forced_ld, r->it_all + (size_t)t * N, w->embed, nullptr, x, N, E, 0, stream));
         else
             RC(capmi_embed_fwd(r->it, 1, r->it_all + (size_t)t * N, w->embed, nullptr, x, N, E, 0, stream));
@@ -165,10 +169,24 @@ int capmi_newfc_rollout_fwd(const capmi_newfc_weights *w, capmi_newfc_rollout *r
                                  r->drop_out ? r->drop_out + (size_t)t * NR : nullptr, h_drop, N, R, stream));
         SegSpec sl{h_drop, R, w->logit_w, R, R, 1};
         RC(gemm(stream, 0, 0, N, V1, r->partial, V1, &sl, 1, r->partial, r->partial_capacity, 1, &splits));
+        const float *gum = r->gumbel ? r->gumbel + (size_t)t * N * V1 : nullptr;
+        if (sched && t + 1 < T) {
+            // AttModel.py:145-154: the token chosen here is the INPUT of step t+1 -- forced[:, t+1] (ss_mode 2 rows) or a categorical
+            // draw from this step's log-probs (ss_mode 1 rows); the same launch embeds it (plain Embedding: no ReLU, no mask).  A
+            // drawn 0 does not end the row: the labels decide that (no_finish_mask).
+            capmi_next_embed ne{};
+            ne.E = w->embed; ne.Edim = E; ne.relu = 0;
+            ne.x = r->x + (size_t)(t + 1) * N * E;
+            ne.it_save = r->it_all + (size_t)(t + 1) * N;
+            RC(capmi_logsoftmax_select_partial(slabs, splits, (int64_t)N * V1, w->logit_b, N, V1, t, L, 2,
+                                               r->ss_mode + (size_t)(t + 1) * N, 1.f, gum, r->seed, r->forced + 1, r->forced_ld, 1,
+                                               r->seq, L, r->it, r->unfinished, r->seq_logp, r->sel_logp, r->live, &ne, nullptr,
+                                               stream));
+            continue;
+        }
         RC(capmi_logsoftmax_select_partial(slabs, splits, (int64_t)N * V1, w->logit_b, N, V1, t, L, r->teacher ? 2 : r->mode,
-                                           nullptr, r->temperature, r->gumbel ? r->gumbel + (size_t)t * N * V1 : nullptr,
-                                           r->seed, r->forced, r->forced_ld, r->teacher ? 1 : 0, r->seq, L, r->it,
-                                           r->unfinished, r->seq_logp, r->sel_logp, r->live, nullptr, nullptr, stream));
+                                           nullptr, r->temperature, gum, r->seed, r->forced, r->forced_ld, r->teacher ? 1 : 0, r->seq,
+                                           L, r->it, r->unfinished, r->seq_logp, r->sel_logp, r->live, nullptr, nullptr, stream));
     }
     return 0;
 }

@@ -13,7 +13,9 @@ _W = (('embed', 'embed.weight'), ('i2h_w', '_core.i2h.weight'), ('i2h_b', '_core
 
 class Rollout:
     def __init__(self, P, fc_feats, n, T, L=None, mode='greedy', temperature=1.0, drop_out=None, gumbel=None, seed=0,
-                 forced=None, teacher=False, ws=None, raw=False):
+                 forced=None, teacher=False, ws=None, raw=False, ss_mode=None):
+        # ss_mode (uint8 [T,N], teacher only): scheduled sampling, 1 = the input of (step, row) is drawn from the previous step's
+        # distribution, 2 = teacher-forced (as att2in2_engine.Rollout; capmi.h capmi_newfc_rollout.ss_mode)
         # raw (free-running rollouts, r5): the stored rows are the LOGITS (AttModel._sample(output_logsoftmax=0), AttModel.py:171-175,
         # 265; CAPMI_SELECT_RAW in the select's mode), the backward takes the loss gradient as d(logits)
         dev = fc_feats.device
@@ -37,7 +39,9 @@ class Rollout:
         self.logits = z(N, V1)
         self.it = torch.empty(N, dtype=torch.long, device=dev)
         self.unfinished = torch.empty(N, dtype=torch.uint8, device=dev)
-        self.drop_out, self.gumbel, self.forced = drop_out, gumbel, forced
+        self.drop_out, self.gumbel, self.forced, self.ss_mode = drop_out, gumbel, forced, ss_mode
+        if ss_mode is not None:
+            assert teacher and ss_mode.dtype == torch.uint8 and ss_mode.shape == (T, N) and ss_mode.is_contiguous()
         r = _lib.NewFCRollout()
         r.B, r.n, r.N, r.R, r.E, r.V1, r.T, r.L = B, n, N, R, E, V1, T, L
         r.fc_emb, r.drop_out = ptr(self.fc_emb), ptr(drop_out)
@@ -45,7 +49,7 @@ class Rollout:
         r.temperature, r.gumbel, r.seed = float(temperature), ptr(gumbel), int(seed) & 0xFFFFFFFFFFFFFFFF
         if forced is not None:
             r.forced, r.forced_ld = ptr(forced), forced.shape[1]
-        r.teacher = int(teacher)
+        r.teacher, r.ss_mode = int(teacher), ptr(ss_mode)
         for k in ('h', 'c', 'x', 'it_all', 'saved', 'h_drop', 'seq', 'seq_logp', 'sel_logp', 'live', 'logits', 'it',
                   'unfinished'):
             setattr(r, k, getattr(self, k).data_ptr())

@@ -928,6 +928,12 @@ typedef struct capmi_newfc_rollout {
     int64_t *seq; float *seq_logp; float *sel_logp; uint8_t *live;   /* [N,L], [N,L,V1], [N,L], [N,L] */
     float *logits; int64_t *it; uint8_t *unfinished;
     float *partial; int64_t partial_capacity;
+    /* scheduled sampling (teacher == 1 only, else CAPMI_EINVAL; AttModel.py:145-154): [T,N] or NULL, same meaning as
+     * capmi_updown_rollout.ss_mode.  ss_mode[t*N + r] says where the INPUT token of row r at step t comes from: 2 = forced[r, t],
+     * 1 = a draw (Gumbel-max, temperature 1, `seed` / `gumbel`) from the model's own distribution of step t-1.  Row t = 0 is not
+     * read: the first input is always forced[:, 0].  The select launch of step t < T-1 chooses and embeds the input of step t+1
+     * (x[t+1], it_all[t+1]), so such a step has no embedding launch.  Last field: older callers' layout is unchanged. */
+    const uint8_t *ss_mode;
 } capmi_newfc_rollout;
 
 typedef struct capmi_newfc_grads {
