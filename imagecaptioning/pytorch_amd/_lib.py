@@ -165,6 +165,46 @@ class Att2in2Step(C.Structure):
                 [('partial_capacity', C.c_int64)])
 
 
+class TileDrop(C.Structure):
+    """capmi_tile_drop (include/capmi.h): dropout of the sentinel attention's tanh tile, injected or drawn in the kernels"""
+    _fields_ = [('mask', c_f), ('p', C.c_float), ('seed', C.c_uint64), ('row0', C.c_int64)]
+
+
+class AdaAttWeights(C.Structure):
+    _fields_ = [(k, c_f) for k in ('embed', 'xw', 'hw', 'fr_w', 'fr_b', 'ho_w', 'ho_b', 'fre_w', 'fre_b', 'hoe_w', 'hoe_b', 'alpha_w',
+                                   'alpha_b', 'att2h_w', 'att2h_b', 'logit_w', 'logit_b')]
+
+
+class AdaAttRollout(C.Structure):
+    _fields_ = ([(k, C.c_int) for k in ('B', 'n', 'N', 'K', 'A', 'R', 'E', 'V1', 'T', 'L', 'maxout')] +
+                [(k, c_f) for k in ('fc_gates', 'att', 'p_att', 'att_mask', 'drop_xt', 'drop_h', 'drop_fake', 'drop_fr', 'drop_ho',
+                                    'drop_out', 'drop_tile')] +
+                [('tile_p', C.c_float), ('tile_seed', C.c_uint64), ('mode', C.c_int), ('temperature', C.c_float), ('gumbel', c_f),
+                 ('seed', C.c_uint64), ('forced', c_f), ('forced_ld', C.c_int), ('teacher', C.c_int), ('ss_mode', c_f)] +
+                [(k, c_f) for k in ('h', 'c', 'x', 'it_all', 'xin', 'saved', 'h_drop', 'fake_drop', 'fr', 'ho_t', 'ho', 'fr_e', 'ho_e',
+                                    'pi', 'ctx', 'out_t', 'out_drop', 'seq', 'seq_logp', 'sel_logp', 'live', 'it', 'unfinished',
+                                    'partial')] + [('partial_capacity', C.c_int64)])
+
+
+class AdaAttGrads(C.Structure):
+    _fields_ = [(k, c_f) for k in ('embed', 'w2h_w', 'r_w2h_w', 'h2h_w', 'r_h2h_w', 'gate_b', 'd_fc_gates', 'fr_w', 'fr_b', 'ho_w',
+                                   'ho_b', 'fre_w', 'fre_b', 'hoe_w', 'hoe_b', 'alpha_w', 'alpha_b', 'att2h_w', 'att2h_b', 'logit_w',
+                                   'logit_b', 'd_att', 'd_p_att')]
+
+
+class AdaAttBwdScratch(C.Structure):
+    _fields_ = ([(k, c_f) for k in ('dlogits', 'd_out', 'd_ctx', 'd_e', 'd_hoe', 'd_fre', 'd_fr', 'd_ho', 'd_hdrop', 'd_fakedrop',
+                                    'd_sums', 'dc', 'd_x', 'partial')] +
+                [('partial_capacity', C.c_int64), ('sparse', C.POINTER(SparseLogpGrad))])
+
+
+class AdaAttStep(C.Structure):
+    _fields_ = ([(k, C.c_int) for k in ('B', 'K', 'A', 'R', 'E', 'V1', 'maxout')] +
+                [(k, c_f) for k in ('fc_gates', 'att', 'p_att', 'att_mask', 'it', 'xt', 'saved', 'h_drop', 'fake_drop', 'fr', 'ho_t',
+                                    'ho', 'fr_e', 'ho_e', 'pi', 'ctx', 'out_t', 'out_drop', 'logits', 'partial')] +
+                [('partial_capacity', C.c_int64)])
+
+
 ENSEMBLE_MAX = 8       # capmi.h CAPMI_ENSEMBLE_MAX
 
 
@@ -288,6 +328,15 @@ SIGNATURES = {
     'capmi_att2in2_rollout_bwd': [C.POINTER(Att2in2Weights), C.POINTER(Att2in2Rollout), _P, C.POINTER(Att2in2BwdScratch),
                                   C.POINTER(Att2in2Grads), _P],
     'capmi_att2in2_decode_step': [C.POINTER(Att2in2Weights), C.POINTER(Att2in2Step), _I, _I, _P, _P, _P, _P, _P],
+    'capmi_sentinel_attention_fwd': [_P, _I, _I64, _P, _P, _I, _I64, _P] + [_P] * 9 + [C.POINTER(TileDrop), _P, _P] + [_I] * 5 + [_P],
+    'capmi_sentinel_attention_bwd': [_P] * 8 + [C.POINTER(TileDrop)] + [_P] * 4 + [_I] * 6 + [_P],
+    'capmi_sentinel_attention_bwd_batched': [_P] * 7 + [C.POINTER(TileDrop)] + [_P] * 4 + [_I] * 6 + [_P, _P],
+    'capmi_adaatt_cell_fwd': [_P, _I, _P, _P, _I] + [_P] * 8 + [_I, _I, _I, _P],
+    'capmi_adaatt_cell_bwd': [_P, _P, _P, _P, _P, _I, _I64] + [_P] * 6 + [_I, _I, _I, _P],
+    'capmi_adaatt_rollout_fwd': [C.POINTER(AdaAttWeights), C.POINTER(AdaAttRollout), _P],
+    'capmi_adaatt_rollout_bwd': [C.POINTER(AdaAttWeights), C.POINTER(AdaAttRollout), _P, C.POINTER(AdaAttBwdScratch),
+                                 C.POINTER(AdaAttGrads), _P],
+    'capmi_adaatt_decode_step': [C.POINTER(AdaAttWeights), C.POINTER(AdaAttStep), _I, _I, _P, _P, _P, _P, _P],
     'capmi_ensemble_logprobs': [C.POINTER(Ensemble), _P],
     'capmi_ppo_loss_fwd': [C.POINTER(Ppo), _P],
     'capmi_ppo_loss_bwd': [C.POINTER(Ppo), _P],

@@ -2,8 +2,7 @@
 from .AttModel import AttModel, UpDownModel  # noqa: F401
 from .AttEnsemble import AttEnsemble  # noqa: F401
 
-_OUT_OF_SCOPE = ('fc', 'show_tell', 'language_model', 'att2in', 'att2all2', 'adaatt', 'adaattmo', 'stackatt',
-                 'denseatt', 'bert', 'm2transformer')
+_OUT_OF_SCOPE = ('fc', 'show_tell', 'language_model', 'att2in', 'att2all2', 'stackatt', 'denseatt', 'bert', 'm2transformer')
 
 
 def setup(opt):
@@ -19,6 +18,9 @@ def setup(opt):
     if name == 'att2in2':
         from .Att2in2Model import Att2in2Model
         return Att2in2Model(opt)
+    if name in ('adaatt', 'adaattmo'):
+        from .AdaAttModel import AdaAttModel, AdaAttMOModel
+        return (AdaAttMOModel if name == 'adaattmo' else AdaAttModel)(opt)
     if name == 'aoa':
         from .AoAModel import AoAModel
         return AoAModel(opt)

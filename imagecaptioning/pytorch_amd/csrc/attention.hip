@@ -1075,3 +1075,558 @@ int capmi_attention_bwd_batched_ws(const float *d_ctx_all, int ld_dctx, const fl
 }
 
 }  // extern "C"
+
+// =====================================================================================================================
+// Sentinel attention (AdaAtt_attention.forward, AttModel.py:565-602, "Knowing when to look"): the additive attention
+// above over K + 1 rows.  Row 0 is the visual sentinel of the CAPTION ROW (its projection fr_e [A] as the score input, fr [R]
+// as the value); rows 1..K are the image's regions, shared by the image's n caption rows exactly as above: a workgroup owns
+// `rpb` rows of one image, reads p_att[b] / att[b] once and keeps the XCD mapping of decode_block.  The query is ho_e; the tanh
+// tile [K + 1, A] of a row takes an optional dropout keep-mask (AttModel.py:585), injected or drawn from Philox by
+// (row, score row, column) so that the backward kernels regenerate the same bits; with att_masks the sentinel takes the mask of
+// region 0 (:590-593).  The forward also adds the residual ho (:598), so the att2h GEMM reads one buffer.
+#include "host_common.h"
+
+namespace {
+
+constexpr uint64_t TILE_STREAM = 0x74696c65ULL;      // "tile": the Philox stream of the tanh-tile dropout
+constexpr int SSG = 4;                               // score rows a wave keeps in flight
+
+struct TileDrop {
+    const float *mask;      // [rows, K+1, A] pre-scaled keep mask, or null
+    float p, scale;         // mask == null and p > 0: Philox, keep = u01 >= p, scale = 1 / (1 - p)
+    uint64_t seed;
+    uint64_t row0;          // row index of the launch's first row in the Philox numbering (step * N)
+    int on;
+};
+
+inline TileDrop tile_drop(const capmi_tile_drop *d) {
+    TileDrop t{};
+    if (d && (d->mask || d->p > 0.f)) {
+        t.on = 1;
+        t.mask = d->mask;
+        t.p = d->p;
+        t.scale = 1.f / (1.f - d->p);
+        t.seed = d->seed;
+        t.row0 = (uint64_t)d->row0;
+    }
+    return t;
+}
+
+template <int V>
+__device__ __forceinline__ void ldv(const float *__restrict__ p, float (&o)[V]) {
+    if constexpr (V == 4) {
+        const f32x4 t = *reinterpret_cast<const f32x4 *>(p);
+        o[0] = t[0]; o[1] = t[1]; o[2] = t[2]; o[3] = t[3];
+    } else {
+        o[0] = p[0];
+    }
+}
+
+// keep factors of tile elements (row, kk, a .. a + V - 1) of a launch whose rows have K1 * A elements each
+template <int V>
+__device__ __forceinline__ void tile_keep(const TileDrop &td, const Philox &ph, uint64_t row, int kk, int a, int K1, int A,
+                                          float (&m)[V]) {
+    if (td.mask) {
+        ldv<V>(td.mask + (row * K1 + kk) * (uint64_t)A + a, m);
+        return;
+    }
+    const uint64_t idx = ((td.row0 + row) * K1 + kk) * (uint64_t)A + a;
+    uint32_t o[4];
+    ph.gen(idx >> 2, TILE_STREAM, o);
+    if constexpr (V == 4) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) m[e] = (u01(o[e]) < td.p) ? 0.f : td.scale;
+    } else {
+        const uint32_t x = (idx & 2) ? ((idx & 1) ? o[3] : o[2]) : ((idx & 1) ? o[1] : o[0]);
+        m[0] = (u01(x) < td.p) ? 0.f : td.scale;
+    }
+}
+
+__device__ __forceinline__ float slab_sum8(const float *__restrict__ p, int splits, size_t stride) {
+    float v = 0.f;
+    for (int s0 = 0; s0 < splits; s0 += 8) {
+        float part[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) part[u] = (s0 + u < splits) ? p[(size_t)(s0 + u) * stride] : 0.f;
+        v += ((part[0] + part[1]) + (part[2] + part[3])) + ((part[4] + part[5]) + (part[6] + part[7]));
+    }
+    return v;
+}
+
+// scores of the workgroup's n rows over the K1 score rows: s_e[j * K1 + kk] = w . (tanh(pe_kk + q_j) * keep) + bias
+template <int V>
+__device__ __forceinline__ void sentinel_scores(const float *__restrict__ pb, const float *__restrict__ w, float bias,
+                                                const float *s_q, const float *s_f, float *s_e, const TileDrop &td,
+                                                const Philox &ph, uint64_t grow0, int n, int K1, int A) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    for (int base = 0; base < K1; base += nw * SSG) {
+        float acc[SSG][NMAX];
+#pragma unroll
+        for (int g = 0; g < SSG; ++g)
+#pragma unroll
+            for (int j = 0; j < NMAX; ++j) acc[g][j] = 0.f;
+        for (int a = lane * V; a < A; a += 64 * V) {
+            float pv[SSG][V], wv[V];
+#pragma unroll
+            for (int g = 0; g < SSG; ++g) {            // all region loads of the group before the first tanh
+                const int kk = base + wid + g * nw;
+                if (kk > 0 && kk < K1) ldv<V>(pb + (size_t)(kk - 1) * A + a, pv[g]);
+                else
+#pragma unroll
+                    for (int e = 0; e < V; ++e) pv[g][e] = 0.f;
+            }
+            ldv<V>(w + a, wv);
+#pragma unroll
+            for (int g = 0; g < SSG; ++g) {
+                const int kk = base + wid + g * nw;
+                if (kk >= K1) continue;              // wave-uniform
+#pragma unroll
+                for (int j = 0; j < NMAX; ++j) {
+                    if (j >= n) continue;
+                    float m[V];
+                    if (td.on) tile_keep<V>(td, ph, grow0 + j, kk, a, K1, A, m);
+#pragma unroll
+                    for (int e = 0; e < V; ++e) {
+                        const float pe = kk == 0 ? s_f[j * A + a + e] : pv[g][e];
+                        float t = tanh_f(pe + s_q[j * A + a + e]);
+                        if (td.on) t *= m[e];
+                        acc[g][j] += wv[e] * t;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < SSG; ++g) {
+            const int kk = base + wid + g * nw;
+            if (kk >= K1) continue;
+#pragma unroll
+            for (int j = 0; j < NMAX; ++j) {
+                if (j >= n) continue;
+                const float e = wave_sum(acc[g][j]) + bias;
+                if (lane == 0) s_e[j * K1 + kk] = e;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(ATT_THREADS) void sentinel_fwd_kernel(
+    const float *__restrict__ fre_in, int fre_splits, size_t fre_stride, const float *__restrict__ fre_bias,
+    const float *__restrict__ hoe_in, int hoe_splits, size_t hoe_stride, const float *__restrict__ hoe_bias,
+    float *__restrict__ fre_out, float *__restrict__ hoe_out, const float *__restrict__ fr, const float *__restrict__ ho,
+    const float *__restrict__ p_att, const float *__restrict__ att, const float *__restrict__ mask,
+    const float *__restrict__ w, const float *__restrict__ bptr, TileDrop td, const uint64_t *__restrict__ epoch,
+    float *__restrict__ pi, float *__restrict__ ctx, int B, int n_img, int rpb, int chunks, int K, int A, int R, int G,
+    int vecA, int vecR) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int K1 = K + 1, R4 = (R + 3) & ~3, A4 = (A + 3) & ~3;
+    float *s_q = lds;                                // [rpb][A4]  the query ho_e
+    float *s_f = s_q + (size_t)rpb * A4;             // [rpb][A4]  the sentinel's projection fr_e
+    float *s_c = s_f + (size_t)rpb * A4;             // [G - 1][rpb][R4] context partial sums of the region groups
+    float *s_e = s_c + (size_t)(G - 1) * rpb * R4;   // [rpb][K1]
+    int b, chunk;
+    if (!decode_block(B, chunks, b, chunk)) return;
+    const int row0 = b * n_img + chunk * rpb;
+    const int n = min(rpb, n_img - chunk * rpb);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    (void)A4;
+    // the two projections: finish the split-K reduction (+ bias) and keep the rows for the backward pass
+    for (int i = threadIdx.x; i < n * A; i += blockDim.x) {
+        const int j = i / A, a = i - j * A;
+        const size_t o = (size_t)(row0 + j) * A + a;
+        float q = hoe_splits > 0 ? slab_sum8(hoe_in + o, hoe_splits, hoe_stride) : hoe_in[o];
+        float f = fre_splits > 0 ? slab_sum8(fre_in + o, fre_splits, fre_stride) : fre_in[o];
+        if (hoe_splits > 0 && hoe_bias) q += hoe_bias[a];
+        if (fre_splits > 0 && fre_bias) f += fre_bias[a];
+        s_q[j * A + a] = q;
+        s_f[j * A + a] = f;
+        if (hoe_out) hoe_out[o] = q;
+        if (fre_out) fre_out[o] = f;
+    }
+    __syncthreads();
+    const Philox ph(epoch_seed(td.seed, epoch));
+    const float bias = bptr ? bptr[0] : 0.f;
+    const float *pb = p_att + (size_t)b * K * A;
+    if (vecA) sentinel_scores<4>(pb, w, bias, s_q, s_f, s_e, td, ph, (uint64_t)row0, n, K1, A);
+    else sentinel_scores<1>(pb, w, bias, s_q, s_f, s_e, td, ph, (uint64_t)row0, n, K1, A);
+    __syncthreads();
+
+    // softmax over the K + 1 rows (+ mask renormalisation; the sentinel takes the mask of region 0), one wave per caption row
+    for (int j = wid; j < n; j += nw) {
+        float *e = s_e + j * K1;
+        float m = -INFINITY;
+        for (int k = lane; k < K1; k += 64) m = fmaxf(m, e[k]);
+        m = wave_max(m);
+        float s = 0.f;
+        for (int k = lane; k < K1; k += 64) {
+            const float x = __expf(e[k] - m);
+            e[k] = x;
+            s += x;
+        }
+        s = wave_sum(s);
+        const float inv = 1.f / s;
+        if (mask) {
+            const float *mb = mask + (size_t)b * K;
+            float s2 = 0.f;
+            for (int k = lane; k < K1; k += 64) {
+                const float x = e[k] * inv * mb[k > 0 ? k - 1 : 0];
+                e[k] = x;
+                s2 += x;
+            }
+            s2 = wave_sum(s2);
+            for (int k = lane; k < K1; k += 64) e[k] = e[k] / s2;
+        } else {
+            for (int k = lane; k < K1; k += 64) e[k] = e[k] * inv;
+        }
+        for (int k = lane; k < K1; k += 64) pi[(size_t)(row0 + j) * K1 + k] = e[k];
+    }
+    __syncthreads();
+
+    // context + residual: ctx[row] = pi[0] fr[row] + sum_k pi[k] att[b, k - 1] + ho[row]
+    const float *ab = att + (size_t)b * K * R;
+    if (vecR) {
+        // thread (cg, grp): column quad cg, regions grp, grp + G, ...; group 0 also takes the sentinel row and the residual
+        const int Q = R >> 2;
+        const int cg = threadIdx.x % Q, grp = threadIdx.x / Q, r = cg * 4;
+        const bool act = grp < G;
+        float c[NMAX][4];
+#pragma unroll
+        for (int j = 0; j < NMAX; ++j) c[j][0] = c[j][1] = c[j][2] = c[j][3] = 0.f;
+        if (act) {
+            constexpr int CG4 = 6;               // 6 x 16 B in flight per lane
+            if (grp == 0) {
+#pragma unroll
+                for (int j = 0; j < NMAX; ++j) {
+                    if (j >= n) continue;
+                    const f32x4 f = *reinterpret_cast<const f32x4 *>(fr + (size_t)(row0 + j) * R + r);
+                    const f32x4 h = *reinterpret_cast<const f32x4 *>(ho + (size_t)(row0 + j) * R + r);
+                    const float p0 = s_e[j * K1];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) c[j][e] = p0 * f[e] + h[e];
+                }
+            }
+#pragma unroll 1
+            for (int k0 = grp; k0 < K; k0 += G * CG4) {
+                f32x4 v[CG4];
+#pragma unroll
+                for (int u = 0; u < CG4; ++u) {
+                    const int k = k0 + u * G;
+                    v[u] = k < K ? *reinterpret_cast<const f32x4 *>(ab + (size_t)k * R + r) : f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+#pragma unroll
+                for (int u = 0; u < CG4; ++u) {
+                    const int k = k0 + u * G;
+                    if (k >= K) continue;
+#pragma unroll
+                    for (int j = 0; j < NMAX; ++j) {
+                        if (j >= n) continue;
+                        const float al = s_e[j * K1 + k + 1];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) c[j][e] += al * v[u][e];
+                    }
+                }
+            }
+            if (grp > 0) {
+#pragma unroll
+                for (int j = 0; j < NMAX; ++j)
+                    if (j < n) *reinterpret_cast<f32x4 *>(s_c + ((size_t)(grp - 1) * rpb + j) * R4 + r) = f32x4{c[j][0], c[j][1], c[j][2], c[j][3]};
+            }
+        }
+        __syncthreads();
+        if (act && grp == 0) {
+#pragma unroll
+            for (int j = 0; j < NMAX; ++j) {
+                if (j >= n) continue;
+                f32x4 cv = f32x4{c[j][0], c[j][1], c[j][2], c[j][3]};
+                for (int q = 1; q < G; ++q) cv += *reinterpret_cast<const f32x4 *>(s_c + ((size_t)(q - 1) * rpb + j) * R4 + r);
+                *reinterpret_cast<f32x4 *>(ctx + (size_t)(row0 + j) * R + r) = cv;
+            }
+        }
+    } else {
+        for (int r = threadIdx.x; r < R; r += blockDim.x) {
+            float c[NMAX];
+#pragma unroll
+            for (int j = 0; j < NMAX; ++j)
+                c[j] = j < n ? s_e[j * K1] * fr[(size_t)(row0 + j) * R + r] + ho[(size_t)(row0 + j) * R + r] : 0.f;
+            for (int k = 0; k < K; ++k) {
+                const float v = ab[(size_t)k * R + r];
+#pragma unroll
+                for (int j = 0; j < NMAX; ++j)
+                    if (j < n) c[j] += s_e[j * K1 + k + 1] * v;
+            }
+#pragma unroll
+            for (int j = 0; j < NMAX; ++j)
+                if (j < n) ctx[(size_t)(row0 + j) * R + r] = c[j];
+        }
+    }
+}
+
+// ---- backward of the rows of T steps (blockIdx.y = step; rows of step t start at t * N): the attention output of a step feeds
+// only that step's logits, so its whole backward is time-batched.  d_ctx -> d_e [K + 1] (softmax + renorm Jacobian as above),
+// d_fr = pi[0] d_ctx, d_fre (the sentinel's score input), d_hoe = sum over the K + 1 rows (the query).
+__global__ __launch_bounds__(ATT_THREADS) void sentinel_bwd_kernel(
+    const float *__restrict__ d_ctx, const float *__restrict__ fr, const float *__restrict__ fre, const float *__restrict__ hoe,
+    const float *__restrict__ pi, const float *__restrict__ p_att, const float *__restrict__ att, const float *__restrict__ w,
+    TileDrop td, const uint64_t *__restrict__ epoch, float *__restrict__ d_e, float *__restrict__ d_hoe,
+    float *__restrict__ d_fre, float *__restrict__ d_fr, int B, int n_img, int rpb, int chunks, int K, int A, int R, int N) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int K1 = K + 1;
+    float *s_dc = lds;                               // [rpb][R]
+    float *s_de = s_dc + (size_t)rpb * R;            // [rpb][K1] d_pi, then d_e
+    int b, chunk;
+    if (!decode_block(B, chunks, b, chunk)) return;
+    const size_t grow0 = (size_t)blockIdx.y * N + b * n_img + chunk * rpb;
+    const int n = min(rpb, n_img - chunk * rpb);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    for (int i = threadIdx.x; i < n * R; i += blockDim.x) s_dc[i] = d_ctx[grow0 * R + i];
+    __syncthreads();
+    // d_pi[kk] = value row kk . d_ctx
+    const float *ab = att + (size_t)b * K * R;
+    for (int kk = wid; kk < K1; kk += nw) {
+        float acc[NMAX];
+#pragma unroll
+        for (int j = 0; j < NMAX; ++j) acc[j] = 0.f;
+        for (int r0 = lane; r0 < R; r0 += 256) {
+            float v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = (kk > 0 && r0 + 64 * u < R) ? ab[(size_t)(kk - 1) * R + r0 + 64 * u] : 0.f;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int r = r0 + 64 * u;
+                if (r >= R) continue;
+#pragma unroll
+                for (int j = 0; j < NMAX; ++j) {
+                    if (j >= n) continue;
+                    const float x = kk > 0 ? v[u] : fr[(grow0 + j) * R + r];
+                    acc[j] += x * s_dc[j * R + r];
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NMAX; ++j) {
+            if (j >= n) continue;
+            const float s = wave_sum(acc[j]);
+            if (lane == 0) s_de[j * K1 + kk] = s;
+        }
+    }
+    __syncthreads();
+    for (int j = wid; j < n; j += nw) {
+        const float *al = pi + (grow0 + j) * K1;
+        float c = 0.f;
+        for (int k = lane; k < K1; k += 64) c += al[k] * s_de[j * K1 + k];
+        c = wave_sum(c);
+        for (int k = lane; k < K1; k += 64) {
+            const float de = al[k] * (s_de[j * K1 + k] - c);
+            s_de[j * K1 + k] = de;
+            d_e[(grow0 + j) * K1 + k] = de;
+        }
+    }
+    for (int i = threadIdx.x; i < n * R; i += blockDim.x) d_fr[grow0 * R + i] = pi[(grow0 + i / R) * K1] * s_dc[i];
+    __syncthreads();
+    const Philox ph(epoch_seed(td.seed, epoch));
+    const float *pb = p_att + (size_t)b * K * A;
+    for (int a = threadIdx.x; a < A; a += blockDim.x) {
+        float acc[NMAX], qq[NMAX];
+#pragma unroll
+        for (int j = 0; j < NMAX; ++j) {
+            acc[j] = 0.f;
+            qq[j] = j < n ? hoe[(grow0 + j) * A + a] : 0.f;
+        }
+        for (int k0 = 0; k0 < K; k0 += CG) {
+            float pv[CG];
+#pragma unroll
+            for (int g = 0; g < CG; ++g) pv[g] = (k0 + g < K) ? pb[(size_t)(k0 + g) * A + a] : 0.f;
+#pragma unroll
+            for (int g = 0; g < CG; ++g) {
+                if (k0 + g >= K) continue;
+#pragma unroll
+                for (int j = 0; j < NMAX; ++j) {
+                    if (j >= n) continue;
+                    const float t = tanh_f(pv[g] + qq[j]);
+                    float gr = s_de[j * K1 + k0 + g + 1] * (1.f - t * t);
+                    if (td.on) {
+                        float m[1];
+                        tile_keep<1>(td, ph, grow0 + j, k0 + g + 1, a, K1, A, m);
+                        gr *= m[0];
+                    }
+                    acc[j] += gr;
+                }
+            }
+        }
+        const float wa = w[a];
+#pragma unroll
+        for (int j = 0; j < NMAX; ++j) {
+            if (j >= n) continue;
+            const float t = tanh_f(fre[(grow0 + j) * A + a] + qq[j]);
+            float g0 = s_de[j * K1] * (1.f - t * t);
+            if (td.on) {
+                float m[1];
+                tile_keep<1>(td, ph, grow0 + j, 0, a, K1, A, m);
+                g0 *= m[0];
+            }
+            d_fre[(grow0 + j) * A + a] = wa * g0;
+            d_hoe[(grow0 + j) * A + a] = wa * (acc[j] + g0);
+        }
+    }
+}
+
+// ---- time-batched feature / parameter gradients -----------------------------------------------------------------------
+// d_att[b, k, :] = sum over steps and the image's rows of pi[row, k + 1] d_ctx[row, :]: attn_datt_kernel with the K + 1 pitch
+__global__ __launch_bounds__(DATT_T) void sentinel_datt_kernel(const float *__restrict__ d_ctx_all, const float *__restrict__ pi_all,
+                                                              float *__restrict__ d_att, int T, int N, int n, int K, int R) {
+    const int b = blockIdx.x, kc = blockIdx.y * KCH, K1 = K + 1;
+    const int r = blockIdx.z * DATT_T + threadIdx.x;
+    const int total = T * n;
+    extern __shared__ float s_al[];          // [total][KCH]
+    for (int i = threadIdx.x; i < total * KCH; i += DATT_T) {
+        const int row_i = i / KCH, q = i - row_i * KCH;
+        const size_t row = (size_t)(row_i / n) * N + b * n + (row_i % n);
+        s_al[i] = (kc + q < K) ? pi_all[row * K1 + kc + q + 1] : 0.f;
+    }
+    __syncthreads();
+    if (r >= R) return;
+    float acc[KCH];
+#pragma unroll
+    for (int q = 0; q < KCH; ++q) acc[q] = 0.f;
+    for (int i0 = 0; i0 < total; i0 += 4) {
+        float d[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int i = min(i0 + u, total - 1);
+            const size_t row = (size_t)(i / n) * N + b * n + (i % n);
+            d[u] = (i0 + u < total) ? d_ctx_all[row * R + r] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float *al = s_al + min(i0 + u, total - 1) * KCH;
+#pragma unroll
+            for (int q = 0; q < KCH; ++q) acc[q] += al[q] * d[u];
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < KCH; ++q)
+        if (kc + q < K) d_att[((size_t)b * K + kc + q) * R + r] = acc[q];
+}
+
+// grid B * (K + 1): one workgroup per (image, score row), threads over a.  Score row 0 (the sentinel) has no p_att gradient but
+// its share of alpha_net's weight gradient.  dw_part [B * (K + 1), A] (optional): one row per workgroup, column-summed by the caller.
+__global__ void sentinel_dpatt_kernel(const float *__restrict__ fre_all, const float *__restrict__ hoe_all,
+                                      const float *__restrict__ d_e_all, const float *__restrict__ p_att,
+                                      const float *__restrict__ w, TileDrop td, const uint64_t *__restrict__ epoch,
+                                      float *__restrict__ d_p_att, float *__restrict__ d_w, float *__restrict__ dw_part, int T,
+                                      int N, int n, int K, int A) {
+    const int K1 = K + 1;
+    const int b = blockIdx.x / K1, kk = blockIdx.x % K1;
+    const int total = T * n;
+    const Philox ph(epoch_seed(td.seed, epoch));
+    for (int a = threadIdx.x; a < A; a += blockDim.x) {
+        const float p = kk > 0 ? p_att[((size_t)b * K + kk - 1) * A + a] : 0.f;
+        float acc = 0.f, accw = 0.f;
+        for (int i0 = 0; i0 < total; i0 += 8) {
+            float de[8], pe[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = min(i0 + u, total - 1);
+                const size_t row = (size_t)(i / n) * N + b * n + (i % n);
+                de[u] = d_e_all[row * K1 + kk];
+                pe[u] = hoe_all[row * A + a] + (kk > 0 ? p : fre_all[row * A + a]);
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                if (i0 + u >= total) continue;
+                const float th = tanh_f(pe[u]);
+                float g = de[u];
+                if (td.on) {
+                    const int i = i0 + u;
+                    float m[1];
+                    tile_keep<1>(td, ph, (uint64_t)(i / n) * N + b * n + (i % n), kk, a, K1, A, m);
+                    g *= m[0];
+                }
+                acc += g * (1.f - th * th);
+                accw += g * th;
+            }
+        }
+        if (kk > 0) d_p_att[((size_t)b * K + kk - 1) * A + a] = w[a] * acc;
+        if (dw_part) dw_part[(size_t)blockIdx.x * A + a] = accw;
+        else atomicAdd(&d_w[a], accw);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int capmi_sentinel_attention_fwd(const float *fre, int fre_splits, int64_t fre_stride, const float *fre_bias, const float *hoe,
+                                 int hoe_splits, int64_t hoe_stride, const float *hoe_bias, float *fre_out, float *hoe_out,
+                                 const float *fr, const float *ho, const float *p_att, const float *att, const float *mask,
+                                 const float *w, const float *b, const capmi_tile_drop *drop, float *pi, float *ctx, int B,
+                                 int n, int K, int A, int R, void *stream) {
+    if (!fre || !hoe || !fr || !ho || !p_att || !att || !w || !pi || !ctx || B <= 0 || n <= 0 || K <= 0 || A <= 0 || R <= 0 ||
+        fre_splits < 0 || hoe_splits < 0)
+        return CAPMI_EINVAL;
+    if (drop && !drop->mask && (drop->p < 0.f || drop->p >= 1.f)) return CAPMI_EINVAL;
+    const TileDrop td = tile_drop(drop);
+    const int rpb = pick_rpb_fwd(B, n), chunks = (n + rpb - 1) / rpb;
+    const int vecA = A % 4 == 0 && aligned16(p_att, w, td.mask);
+    const int vecR = R % 4 == 0 && R <= 2048 && aligned16(att, fr, ho, ctx);
+    int G = 1;
+    if (vecR) {
+        G = rpb <= 2 ? 4 : 2;
+        if (G > ATT_THREADS / (R >> 2)) G = ATT_THREADS / (R >> 2);
+        if (G > K) G = K;
+        if (G < 1) G = 1;
+    }
+    const int R4 = (R + 3) & ~3, A4 = (A + 3) & ~3;
+    const size_t lds = ((size_t)rpb * (2 * A4 + (size_t)(G - 1) * R4 + K + 1)) * sizeof(float);
+    if (lds > 64 * 1024) return CAPMI_EINVAL;
+    hipLaunchKernelGGL(sentinel_fwd_kernel, dim3(grid_blocks(B, chunks)), dim3(ATT_THREADS), lds, (hipStream_t)stream, fre,
+                       fre_splits, (size_t)fre_stride, fre_bias, hoe, hoe_splits, (size_t)hoe_stride, hoe_bias, fre_out, hoe_out, fr,
+                       ho, p_att, att, mask, w, b, td, capmi::rng_epoch(), pi, ctx, B, n, rpb, chunks, K, A, R, G, vecA, vecR);
+    CAPMI_CHECK_LAUNCH();
+    return 0;
+}
+
+int capmi_sentinel_attention_bwd(const float *d_ctx, const float *fr, const float *fre, const float *hoe, const float *pi,
+                                 const float *p_att, const float *att, const float *w, const capmi_tile_drop *drop, float *d_e,
+                                 float *d_hoe, float *d_fre, float *d_fr, int T, int B, int n, int K, int A, int R,
+                                 void *stream) {
+    if (!d_ctx || !fr || !fre || !hoe || !pi || !p_att || !att || !w || !d_e || !d_hoe || !d_fre || !d_fr || T <= 0 ||
+        T > 65535 || B <= 0 || n <= 0 || K <= 0 || A <= 0 || R <= 0)
+        return CAPMI_EINVAL;
+    const TileDrop td = tile_drop(drop);
+    const int rpb = pick_rpb(B, n), chunks = (n + rpb - 1) / rpb;
+    const size_t lds = (size_t)rpb * (R + K + 1) * sizeof(float);
+    if (lds > 64 * 1024) return CAPMI_EINVAL;
+    hipLaunchKernelGGL(sentinel_bwd_kernel, dim3(grid_blocks(B, chunks), T), dim3(ATT_THREADS), lds, (hipStream_t)stream, d_ctx,
+                       fr, fre, hoe, pi, p_att, att, w, td, capmi::rng_epoch(), d_e, d_hoe, d_fre, d_fr, B, n, rpb, chunks, K,
+                       A, R, B * n);
+    CAPMI_CHECK_LAUNCH();
+    return 0;
+}
+
+int capmi_sentinel_attention_bwd_batched(const float *d_ctx, const float *fre, const float *hoe, const float *pi,
+                                         const float *d_e, const float *p_att, const float *w, const capmi_tile_drop *drop,
+                                         float *d_att, float *d_p_att, float *d_w, float *d_b, int T, int B, int n, int K,
+                                         int A, int R, float *dw_partial, void *stream) {
+    if (!d_ctx || !fre || !hoe || !pi || !d_e || !p_att || !w || !d_att || !d_p_att || !d_b || (!d_w && !dw_partial) ||
+        T <= 0 || B <= 0 || n <= 0 || K <= 0 || A <= 0 || R <= 0)
+        return CAPMI_EINVAL;
+    if ((size_t)T * n * KCH * sizeof(float) > 64 * 1024) return CAPMI_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const TileDrop td = tile_drop(drop);
+    const int N = B * n;
+    hipLaunchKernelGGL(sentinel_datt_kernel, dim3(B, (K + KCH - 1) / KCH, (R + DATT_T - 1) / DATT_T), dim3(DATT_T),
+                       (size_t)T * n * KCH * sizeof(float), st, d_ctx, pi, d_att, T, N, n, K, R);
+    CAPMI_CHECK_LAUNCH();
+    if (!dw_partial) {
+        hipError_t e = hipMemsetAsync(d_w, 0, (size_t)A * sizeof(float), st);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(sentinel_dpatt_kernel, dim3(B * (K + 1)), dim3(A >= 512 ? 512 : 256), 0, st, fre, hoe, d_e, p_att, w, td,
+                       capmi::rng_epoch(), d_p_att, d_w, dw_partial, T, N, n, K, A);
+    CAPMI_CHECK_LAUNCH();
+    hipLaunchKernelGGL(sum_all_kernel, dim3(1), dim3(1024), 0, st, d_e, (size_t)T * N * (K + 1), d_b);
+    CAPMI_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // extern "C"

@@ -13,6 +13,7 @@ The fast paths (one native call per rollout / per beam search) do not go through
   UpDownStepper   capmi_updown_decode_step  (UpDownCore.forward, AttModel.py:615-640, eval numerics)
   NewFCStepper    maxout LSTMCore.forward   (FCModel.py:13-42 via AttModel.py:904-945)
   Att2in2Stepper  capmi_att2in2_decode_step (Att2in2Core.forward, AttModel.py:750-790, eval numerics)
+  AdaAttStepper   capmi_adaatt_decode_step  (AdaAttCore.forward, AttModel.py:604-613, eval numerics)
   EnsembleStepper M member steppers + capmi_ensemble_logprobs (AttEnsemble.get_logprobs_state, AttEnsemble.py:45-53)
 """
 import ctypes as C
@@ -189,6 +190,47 @@ class Att2in2Stepper:
     def export_state(self, rows):
         s = self.state[self.cur]
         return (s[0, :rows].clone().unsqueeze(0), s[1, :rows].clone().unsqueeze(0))
+
+
+class AdaAttStepper(Att2in2Stepper):
+    """AdaAttModel / AdaAttMOModel (AttModel.py:843-852): BOS first, no image step; the state is (h, c) of the one layer (the
+    undropped h: AdaAtt_lstm returns it beside the copy that goes on to the attention).  Beam reorder, snapshot and the
+    reference's state layout are Att2in2Stepper's."""
+
+    def __init__(self, P, ap, rows_per_image_max):
+        from . import adaatt_engine
+        dev = ap.att.device
+        B, K, R = ap.att.shape
+        A = ap.p_att.shape[2]
+        V1, E = P['embed.0.weight'].shape
+        W = ap.fc_gates.shape[1]
+        self.P, self.pr = P, ap
+        self.B, self.R, self.V1, self.cap = B, R, V1, int(rows_per_image_max)
+        self.N = N = B * self.cap
+        z = lambda *s: torch.empty(*s, dtype=_f32, device=dev)       # noqa: E731
+        self.ws = ops.default_workspace(dev)
+        self.state = torch.zeros(2, 2, N, R, dtype=_f32, device=dev)   # ping-pong of (h, c)
+        self.cur = 0
+        self.bufs = dict(it=torch.zeros(N, dtype=torch.long, device=dev), xt=z(N, E), saved=z(N, W), h_drop=z(N, R),
+                         fake_drop=z(N, R), fr=z(N, E), ho_t=z(N, E), ho=z(N, E), fr_e=z(N, A), ho_e=z(N, A), pi=z(N, K + 1),
+                         ctx=z(N, R), out_t=z(N, R), out_drop=z(N, R), logits=z(N, V1))
+        s = _lib.AdaAttStep()
+        s.B, s.K, s.A, s.R, s.E, s.V1, s.maxout = B, K, A, R, E, V1, int(W == 6 * R)
+        s.fc_gates, s.att, s.p_att, s.att_mask = ptr(ap.fc_gates), ptr(ap.att), ptr(ap.p_att), ptr(ap.att_masks)
+        for k, t in self.bufs.items():
+            setattr(s, k, t.data_ptr())
+        s.partial, s.partial_capacity = self.ws.buf.data_ptr(), self.ws.capacity
+        self.s, self.w = s, adaatt_engine.weights_struct(P, ap.packs)
+
+    def step(self, t, it, rows_per_image):
+        rows = self.B * rows_per_image
+        assert it.shape[0] == rows and rows_per_image <= self.cap
+        self.bufs['it'][:rows].copy_(it)
+        src, dst = self.state[self.cur], self.state[1 - self.cur]
+        check(lib.capmi_adaatt_decode_step(C.byref(self.w), C.byref(self.s), rows, rows_per_image, ptr(src[0]), ptr(src[1]),
+                                           ptr(dst[0]), ptr(dst[1]), stream_ptr()), 'capmi_adaatt_decode_step')
+        self.cur = 1 - self.cur
+        return self.bufs['logits'][:rows]
 
 
 class EnsembleStepper:

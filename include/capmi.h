@@ -1038,6 +1038,131 @@ int capmi_att2in2_decode_step(const capmi_att2in2_weights *w, capmi_att2in2_step
                               const float *h_src, const float *c_src, float *h_dst, float *c_dst, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * AdaAtt decoder (caption_model adaatt / adaattmo): AdaAttModel / AdaAttMOModel (AttModel.py:843-852) over AdaAttCore
+ * (:604-613) = AdaAtt_lstm (:451-537, one layer) + AdaAtt_attention (:539-602).  Requires E == R == A (the views at
+ * :569-582).  G = 4R (adaatt, tanh candidate) or 5R (adaattmo, maxout of the last two R-blocks).  Per step:
+ *   sums [N, G+R] = (w2h | r_w2h)(x) + (h2h | r_h2h)(h_prev) + fc_gates[image]       fc_gates = (v2h | r_v2h)(fc) + all six biases
+ *   cell: c, h, sentinel fake = sigmoid(sums[:, G:]) * tanh(c); h_drop = h * drop_h (the STATE keeps h), fake_drop = fake * drop_fake
+ *   fr = relu(fr_linear(fake_drop)) * drop_fr;  ho = tanh(ho_linear(h_drop)) * drop_ho;  fr_e = fr_embed(fr);  ho_e = ho_embed(ho)
+ *   sentinel attention over [fr_e ; p_att] / [fr ; att] queried with ho_e (+ ho);  out = tanh(att2h(.)) * drop_out -> logit.
+ * ------------------------------------------------------------------------------------------- */
+/* dropout of the [rows, K+1, A] tanh tile of the sentinel attention (AttModel.py:585).  mask: pre-scaled keep mask of the
+ * launch's rows, or NULL with p > 0: keep = Philox4x32-10(seed)(element (row0 + row, score row, column)) >= p, value 1 / (1 - p);
+ * the backward entry points regenerate the same bits from the same (seed, row0).  NULL struct / NULL mask and p == 0: none. */
+typedef struct capmi_tile_drop {
+    const float *mask;
+    float p;
+    uint64_t seed;
+    int64_t row0;
+} capmi_tile_drop;
+/* AdaAtt_attention.forward (AttModel.py:579-598) for N = B * n image-major rows.  fre / hoe: fr_e / ho_e [N,A], finished
+ * (splits == 0) or as the K-slice slabs of their GEMMs (stride in floats) to which the bias is added here; fre_out / hoe_out
+ * (optional) receive the finished rows.  fr, ho [N,R]; p_att [B,K,A], att [B,K,R] are read once per workgroup; mask [B,K] or NULL:
+ * the sentinel takes the mask of region 0 (:592).  pi [N,K+1] (sentinel first), ctx [N,R] = pi . [fr ; att] + ho (:598). */
+int capmi_sentinel_attention_fwd(const float *fre, int fre_splits, int64_t fre_stride, const float *fre_bias, const float *hoe,
+                                 int hoe_splits, int64_t hoe_stride, const float *hoe_bias, float *fre_out, float *hoe_out,
+                                 const float *fr, const float *ho, const float *p_att, const float *att, const float *mask,
+                                 const float *w, const float *b, const capmi_tile_drop *drop, float *pi, float *ctx, int B,
+                                 int n, int K, int A, int R, void *stream);
+/* its backward for the rows of T steps at once ([T,N,.] buffers; the attention output of a step feeds only that step's logits):
+ * d_e [T,N,K+1], d_hoe [T,N,A] (the query gradient), d_fre [T,N,A], d_fr [T,N,R] = pi[:, 0] d_ctx.  The residual's gradient
+ * (d_ho += d_ctx) is the caller's.  drop: the forward's, with mask covering [T,N,K+1,A] and row0 = 0. */
+int capmi_sentinel_attention_bwd(const float *d_ctx, const float *fr, const float *fre, const float *hoe, const float *pi,
+                                 const float *p_att, const float *att, const float *w, const capmi_tile_drop *drop, float *d_e,
+                                 float *d_hoe, float *d_fre, float *d_fr, int T, int B, int n, int K, int A, int R,
+                                 void *stream);
+/* time-batched d_att [B,K,R], d_p_att [B,K,A], alpha_net gradients (d_w [A] by atomics, or dw_partial [B*(K+1), A] rows for the
+ * caller to column-sum; d_b [1]) as capmi_attention_bwd_batched_ws. */
+int capmi_sentinel_attention_bwd_batched(const float *d_ctx, const float *fre, const float *hoe, const float *pi,
+                                         const float *d_e, const float *p_att, const float *w, const capmi_tile_drop *drop,
+                                         float *d_att, float *d_p_att, float *d_w, float *d_b, int T, int B, int n, int K,
+                                         int A, int R, float *dw_partial, void *stream);
+/* AdaAtt_lstm.forward (AttModel.py:498-533), one launch: sums = sum_s partial[s] ([N,G+R] slabs) (+ addend [N,G+R])
+ * + fc_gates[row / n]; saved [N,G+R] = (sig(in), sig(f), sig(out), candidate (tanh value | the two maxout inputs), sig(sentinel)). */
+int capmi_adaatt_cell_fwd(const float *partial, int splits, const float *addend, const float *fc_gates, int n,
+                          const float *c_prev, float *h, float *c, float *saved, const float *drop_h, const float *drop_fake,
+                          float *h_drop, float *fake_drop, int N, int R, int maxout, void *stream);
+/* dh = dh_a (* dh_a_mask) + sum_s dh_b[s * b_stride + i]; dfake = d_fake (* d_fake_mask); writes d_sums [N,G+R], dc_prev. */
+int capmi_adaatt_cell_bwd(const float *dh_a, const float *dh_a_mask, const float *d_fake, const float *d_fake_mask,
+                          const float *dh_b, int b_splits, int64_t b_stride, const float *dc_next, const float *saved,
+                          const float *c_prev, const float *c_new, float *d_sums, float *dc_prev, int N, int R, int maxout,
+                          void *stream);
+
+typedef struct capmi_adaatt_weights {
+    const float *embed;                      /* [V1,E]  embed.0.weight */
+    const float *xw, *hw;                    /* [G+R,E], [G+R,R]: core.lstm (w2h | r_w2h) and (h2h.0 | r_h2h) weights stacked by rows */
+    const float *fr_w, *fr_b, *ho_w, *ho_b;          /* [E,R],[E]  core.attention.fr_linear.0 / ho_linear.0 */
+    const float *fre_w, *fre_b, *hoe_w, *hoe_b;      /* [A,E],[A]  core.attention.fr_embed / ho_embed */
+    const float *alpha_w, *alpha_b;          /* [A],[1]    core.attention.alpha_net */
+    const float *att2h_w, *att2h_b;          /* [R,R],[R]  core.attention.att2h */
+    const float *logit_w, *logit_b;          /* [V1,R],[V1] logit */
+} capmi_adaatt_weights;
+
+typedef struct capmi_adaatt_rollout {
+    int B, n, N, K, A, R, E, V1, T, L, maxout;
+    const float *fc_gates;                   /* [B,G+R] (v2h | r_v2h)(fc_embed(fc)) + the six gate biases: one product per rollout */
+    const float *att, *p_att, *att_mask;     /* [B,K,R], [B,K,A], [B,K] or NULL */
+    const float *drop_xt, *drop_h, *drop_fake, *drop_fr, *drop_ho, *drop_out;   /* [T,N,E|R|R|E|E|R] keep masks or NULL */
+    const float *drop_tile;                  /* [T,N,K+1,A] injected keep mask of the tanh tile, or NULL */
+    float tile_p; uint64_t tile_seed;        /* drop_tile NULL and tile_p > 0: the tile mask is drawn inside the kernels */
+    int mode; float temperature; const float *gumbel; uint64_t seed;
+    const int64_t *forced; int forced_ld; int teacher;
+    const uint8_t *ss_mode;                  /* as capmi_att2in2_rollout */
+    float *h, *c;                            /* [T+1,N,R]  slot 0 = zero state, slot t+1 after step t */
+    float *x;                                /* [T,N,E] */
+    int64_t *it_all;                         /* [T,N] */
+    float *xin;                              /* [T,N,G+R] teacher forcing: the xw product of all steps (one GEMM), or NULL */
+    float *saved;                            /* [T,N,G+R] */
+    float *h_drop, *fake_drop;               /* [T,N,R] */
+    float *fr, *ho_t, *ho;                   /* [T,N,E]: fr after ReLU and mask, ho before / after its mask */
+    float *fr_e, *ho_e;                      /* [T,N,A] */
+    float *pi, *ctx;                         /* [T,N,K+1], [T,N,R] (context + ho) */
+    float *out_t, *out_drop;                 /* [T,N,R] core output before / after its mask */
+    int64_t *seq; float *seq_logp; float *sel_logp; uint8_t *live;   /* [N,L], [N,L,V1], [N,L], [N,L] */
+    int64_t *it; uint8_t *unfinished;
+    float *partial; int64_t partial_capacity;
+} capmi_adaatt_rollout;
+
+typedef struct capmi_adaatt_grads {
+    float *embed, *w2h_w, *r_w2h_w, *h2h_w, *r_h2h_w;
+    float *gate_b;                           /* [G+R]: the gradient of each of the three biases behind a gate column */
+    float *d_fc_gates;                       /* [B,G+R]: for the v2h / r_v2h / fc_embed backward of the prefill */
+    float *fr_w, *fr_b, *ho_w, *ho_b, *fre_w, *fre_b, *hoe_w, *hoe_b, *alpha_w, *alpha_b, *att2h_w, *att2h_b, *logit_w, *logit_b;
+    float *d_att, *d_p_att;                  /* [B,K,R], [B,K,A] */
+} capmi_adaatt_grads;
+
+typedef struct capmi_adaatt_bwd_scratch {
+    float *dlogits;                          /* [T,N,V1] */
+    float *d_out, *d_ctx;                    /* [T,N,R] */
+    float *d_e;                              /* [T,N,K+1] */
+    float *d_hoe, *d_fre;                    /* [T,N,A] */
+    float *d_fr, *d_ho;                      /* [T,N,E] */
+    float *d_hdrop, *d_fakedrop;             /* [T,N,R] */
+    float *d_sums;                           /* [T,N,G+R] */
+    float *dc;                               /* [2][N,R] */
+    float *d_x;                              /* [T,N,E] */
+    float *partial; int64_t partial_capacity;
+    const capmi_sparse_logp_grad *sparse;    /* as in capmi_updown_bwd_scratch */
+} capmi_adaatt_bwd_scratch;
+
+/* AttModel._forward / _sample over AdaAttCore: one host call per rollout, no host sync (select modes, CAPMI_SELECT_RAW, injected
+ * Gumbel noise and ss_mode as capmi_att2in2_rollout_fwd), and the BPTT autograd would have recorded for it. */
+int capmi_adaatt_rollout_fwd(const capmi_adaatt_weights *w, capmi_adaatt_rollout *r, void *stream);
+int capmi_adaatt_rollout_bwd(const capmi_adaatt_weights *w, const capmi_adaatt_rollout *r, const float *g_seq_logp,
+                             capmi_adaatt_bwd_scratch *s, capmi_adaatt_grads *g, void *stream);
+
+/* one decode step in eval numerics (AttModel.get_logprobs_state up to the logits), as capmi_att2in2_decode_step */
+typedef struct capmi_adaatt_step {
+    int B, K, A, R, E, V1, maxout;
+    const float *fc_gates, *att, *p_att, *att_mask;   /* [B,G+R], [B,K,R], [B,K,A], [B,K] or NULL */
+    const int64_t *it;                       /* [rows] input tokens */
+    float *xt, *saved, *h_drop, *fake_drop, *fr, *ho_t, *ho, *fr_e, *ho_e, *pi, *ctx, *out_t, *out_drop, *logits;
+    float *partial; int64_t partial_capacity;
+} capmi_adaatt_step;
+int capmi_adaatt_decode_step(const capmi_adaatt_weights *w, capmi_adaatt_step *s, int rows, int rows_per_image,
+                             const float *h_src, const float *c_src, float *h_dst, float *c_dst, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Test-time ensemble: the mixture log-probability of M members (AttEnsemble.get_logprobs_state, AttEnsemble.py:45-53,
  *   logprobs = log( sum_i w_i * softmax(logit_i) / sum_i w_i ) ).  For every row r:
  *   lse_i     = logsumexp_v in_i[r, v]            (each member is normalised here: logits and log-probs give the same result)
