@@ -14,6 +14,7 @@ import torch  # noqa: F401  (must precede the CDLL: shared HIP runtime)
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CAPMI_LIB') or os.path.join(HERE, 'libcapmi.so')   # CAPMI_LIB: experiment builds only
 MAX_SEG = 4
+MAX_BCOL = 3
 EINVAL = -1
 
 c_f = C.c_void_p      # device pointers travel as integers (tensor.data_ptr())
@@ -29,7 +30,8 @@ class GemmDesc(C.Structure):
                 ('row_bias', c_f), ('row_bias_div', C.c_int), ('mul_mask', c_f), ('relu', C.c_int),
                 ('accumulate', C.c_int), ('partial', c_f), ('partial_capacity', C.c_int64), ('splits', C.c_int),
                 ('defer_reduce', C.c_int), ('splits_used', C.c_int), ('a_planes', c_f * MAX_SEG), ('addend', c_f),
-                ('allow_wide_deferred', C.c_int)]
+                ('allow_wide_deferred', C.c_int), ('n_bcol', C.c_int), ('bcol_B', c_f * MAX_BCOL), ('bcol_ldb', C.c_int * MAX_BCOL),
+                ('bcol_n', C.c_int * MAX_BCOL)]
 
 
 class NextEmbed(C.Structure):

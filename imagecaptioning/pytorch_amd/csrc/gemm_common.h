@@ -21,9 +21,20 @@ struct Seg {
     const unsigned char *Apl;   // the same activations pre-split as "A planes" (capmi_common.h), or null
 };
 
+// r7 (loader / consumer kernel, [K][N] weights, one K segment): B delivered as COLUMN segments that stay where they are -- output
+// columns [cbase, cbase + ncol) come from B[k * ldb + 0 .. ncol).  A column block never straddles two segments: the launch has
+// sum of ceil(ncol / 128) column blocks, segment i owns blocks [blk0, blk0 of segment i + 1).
+constexpr int MAX_BCOL = 3;
+struct BCol {
+    const float *B;
+    int ldb, ncol, blk0, cbase;
+};
+
 struct KArgs {
     Seg seg[CAPMI_MAX_SEG];
     int nseg;
+    int nbcol;           // 0: B is seg[].B with N columns
+    BCol bcol[MAX_BCOL];
     int M, N;
     float *C;
     int ldc;

@@ -446,9 +446,27 @@ extern "C" int capmi_gemm_f32(capmi_gemm_desc *d, void *stream) {
     if (d->a_layout < 0 || d->a_layout > 1 || d->b_layout < 0 || d->b_layout > 1) return CAPMI_EINVAL;
     KArgs a{};
     a.nseg = d->nseg;
+    // r7: B as column segments read in place (loader / consumer kernel only)
+    static_assert(CAPMI_MAX_BCOL == MAX_BCOL, "column segments of the descriptor and of the kernel arguments");
+    if (d->n_bcol < 0 || d->n_bcol > MAX_BCOL) return CAPMI_EINVAL;
+    if (d->n_bcol > 0) {
+        if (d->nseg != 1 || d->b_layout != 1) return CAPMI_EINVAL;
+        int ncol = 0, blk = 0;
+        for (int i = 0; i < d->n_bcol; ++i) {
+            if (!d->bcol_B[i] || d->bcol_n[i] <= 0 || d->bcol_n[i] % 4 || d->bcol_ldb[i] % 4 || d->bcol_ldb[i] < d->bcol_n[i] ||
+                !aligned16(d->bcol_B[i]))
+                return CAPMI_EINVAL;
+            a.bcol[i] = BCol{d->bcol_B[i], d->bcol_ldb[i], d->bcol_n[i], blk, ncol};
+            ncol += d->bcol_n[i];
+            blk += (d->bcol_n[i] + 127) / 128;
+        }
+        if (ncol != d->N) return CAPMI_EINVAL;
+        a.nbcol = d->n_bcol;
+    }
     int tiles = 0;
     for (int s = 0; s < d->nseg; ++s) {
-        const capmi_gemm_seg &g = d->seg[s];
+        capmi_gemm_seg g = d->seg[s];
+        if (a.nbcol) { g.B = a.bcol[0].B; g.ldb = a.bcol[0].ldb; }      // (the kernel takes B from the block's column segment)
         if (g.K <= 0) return CAPMI_EINVAL;
         if (!g.A || !g.B) return CAPMI_EINVAL;
         Seg &o = a.seg[s];
@@ -510,6 +528,8 @@ extern "C" int capmi_gemm_f32(capmi_gemm_desc *d, void *stream) {
             static const int env_opt = capmi::research("CAPMI_LC_OPT", 1);
             const int want = d->splits > 0 ? ((d->N + 127) / 128) * d->splits : env_ab;
             int splits = 0;
+            // (column segments: the plan is that of the packed matrix -- same K slices, same summation order -- and the grid has one
+            //  column block more per ragged segment end that a packed block would have straddled)
             a.sl = lc_plan(d->N, tiles, want, &splits);
             const bool partial = splits > 1 || d->defer_reduce;
             if (!partial || (d->partial && (int64_t)splits * d->M * d->N <= slab_cap)) {
@@ -527,6 +547,7 @@ extern "C" int capmi_gemm_f32(capmi_gemm_desc *d, void *stream) {
             }
         }
     }
+    if (a.nbcol) return CAPMI_EINVAL;   // column segments: no other kernel reads them
     if (env_path != 3 && ares_ok) {     // CAPMI_GEMM_PATH=3 forces the LDS-tiled kernel
         // ---- A-resident path (gemm_ares.hip): activations stay in LDS, weights stream straight to VGPRs ----
         static const int env_ab = capmi::research("CAPMI_ARES_BLOCKS", 256);

@@ -56,11 +56,17 @@ int lc_plan(int N, int tiles, int want_blocks, int *splits) {
     return sl;
 }
 
+// column blocks of a launch: per column segment when B comes as column segments
+static int lc_grid_x(const KArgs &a) {
+    if (a.nbcol <= 0) return (a.N + LC_BN - 1) / LC_BN;
+    return a.bcol[a.nbcol - 1].blk0 + (a.bcol[a.nbcol - 1].ncol + LC_BN - 1) / LC_BN;
+}
+
 template <bool BKC, int TM>
 static int launch_lc_t(const KArgs &a, hipStream_t st, int pcls, double bytes, double flops) {
     constexpr size_t lds = (size_t)LC_NS * LC_STAGE;
     static_assert(lds <= 160 * 1024, "ring does not fit the CU's LDS");
-    dim3 grid((a.N + LC_BN - 1) / LC_BN, a.splits);
+    dim3 grid(lc_grid_x(a), a.splits);
     hipEvent_t e0, e1;
     const bool prof = capmi_prof::take_events(pcls, &e0, &e1, bytes, flops);
     static const int abl = capmi::ablate_env("CAPMI_LC_ABLATE");
@@ -117,9 +123,10 @@ thread_local LcCapture *g_lc_capture = nullptr;
 int launch_lc(const KArgs &a, int b_layout, hipStream_t st, int pcls, double bytes, double flops) {
     if (a.sl < 1 || a.M > 64 || (long long)a.splits * a.sl < a.tiles_total || (long long)(a.splits - 1) * a.sl >= a.tiles_total)
         return CAPMI_EINVAL;
+    if (a.nbcol < 0 || a.nbcol > MAX_BCOL || (a.nbcol > 0 && (b_layout != 1 || a.nseg != 1))) return CAPMI_EINVAL;
     if (g_lc_capture) {                              // the caller launches the body itself (fused select + GEMM)
         LcCapture &c = *g_lc_capture;
-        c.a = a; c.b_layout = b_layout; c.grid_x = (a.N + LC_BN - 1) / LC_BN; c.grid_y = a.splits; c.tm = a.M <= 32 ? 1 : 2;
+        c.a = a; c.b_layout = b_layout; c.grid_x = lc_grid_x(a); c.grid_y = a.splits; c.tm = a.M <= 32 ? 1 : 2;
         c.filled = true;
         return 0;
     }

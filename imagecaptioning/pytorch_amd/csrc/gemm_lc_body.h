@@ -39,7 +39,21 @@ __device__ __forceinline__ void gemm_lc_body(const KArgs &a, const int blk_x, co
         z = p / grd_x;
         bx = p - z * grd_x;
     }
-    const int n0 = bx * LC_BN;
+    // [K][N] weights delivered as column segments (r7): the block's segment on the scalar unit; n0 / ncols are then columns OF THE
+    // SEGMENT, obase the segment's first output column.  Everywhere else: one segment of N columns at output column 0.
+    int n0 = bx * LC_BN, ncols = a.N, obase = 0;
+    const float *cB = nullptr;
+    int cL = 0;
+    if (!BKC && a.nbcol > 0) {
+        static_assert(MAX_BCOL == 3, "column-segment selects are written out for 3 segments");
+        const int j = (a.nbcol > 2 && bx >= a.bcol[2].blk0) ? 2 : (a.nbcol > 1 && bx >= a.bcol[1].blk0) ? 1 : 0;
+        const int b0 = j == 2 ? a.bcol[2].blk0 : j == 1 ? a.bcol[1].blk0 : 0;
+        n0 = (bx - b0) * LC_BN;
+        ncols = j == 2 ? a.bcol[2].ncol : j == 1 ? a.bcol[1].ncol : a.bcol[0].ncol;
+        obase = j == 2 ? a.bcol[2].cbase : j == 1 ? a.bcol[1].cbase : a.bcol[0].cbase;
+        cB = j == 2 ? a.bcol[2].B : j == 1 ? a.bcol[1].B : a.bcol[0].B;
+        cL = j == 2 ? a.bcol[2].ldb : j == 1 ? a.bcol[1].ldb : a.bcol[0].ldb;
+    }
     const int SL = a.sl;
     const int t0 = z * SL;
     const int nst = min(SL, a.tiles_total - t0);      // stages of this workgroup (>= 1: splits * sl covers the tiles exactly once)
@@ -66,8 +80,12 @@ __device__ __forceinline__ void gemm_lc_body(const KArgs &a, const int blk_x, co
         asm volatile("" : "+s"(sgP##i), "+s"(sgB##i), "+s"(sgL##i), "+s"(sgK##i), "+s"(sgT##i));
         CAPMI_PIN(0) CAPMI_PIN(1) CAPMI_PIN(2) CAPMI_PIN(3)
 #undef CAPMI_PIN
+        if (!BKC && cB) {                           // column segments come with ONE K segment: its B is the block's column segment
+            sgB0 = cB; sgL0 = cL;
+            asm volatile("" : "+s"(sgB0), "+s"(sgL0));
+        }
 #define CAPMI_SEL(F, tl) ((tl) >= sgT3 ? F##3 : (tl) >= sgT2 ? F##2 : (tl) >= sgT1 ? F##1 : F##0)
-        const int N = a.N;
+        const int N = ncols;
         // per-lane constants of the weight pieces this loader copies (pieces j, j + 4, j + 8, j + 12 of the 16 of a tile)
         // [N][K] weights: piece p = columns 8p .. 8p+7, lane l -> column 8p + (l >> 3), LDS slot l & 7 holds 16-byte piece
         //                 (l & 7) ^ ((column >> 1) & 7) of the column's 128 bytes
@@ -170,7 +188,7 @@ __device__ __forceinline__ void gemm_lc_body(const KArgs &a, const int blk_x, co
     const int cg = widu & 3, par = widu >> 2;
     const int l31 = lane & 31, half = lane >> 5;
     const int cl = 32 * cg + l31;                    // column within the workgroup's tile
-    const int col = n0 + cl;
+    const int col = n0 + cl;                        // column of the block's column segment (of C without segments)
     f32x16 acc0, acc1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = 0.f;
@@ -293,26 +311,56 @@ __device__ __forceinline__ void gemm_lc_body(const KArgs &a, const int blk_x, co
         if (TM == 2) acc1[r] += red[(32 + row) * RP + cl];
     }
     if (ABL & 16) { asm volatile("" ::"v"(acc0[15]), "v"(acc1[15])); CAPMI_LC_STAMP(2); }
-    if ((ABL & 8) || col >= a.N) {
+    if (ABL & 8) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) { asm volatile("" ::"v"(acc0[r])); asm volatile("" ::"v"(acc1[r])); }
         return;
     }
     // C/D map of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
     if (a.to_partial) {
-        float *out = a.partial + (size_t)z * a.M * a.N + col;
+        // K-slice slabs (r7): the finished tile goes back through `red` -- every lane overwrites exactly the words it has just read,
+        // and a wave's 32 columns are read back by that wave alone, so no barrier -- and leaves as 16-byte WRITE-THROUGH stores, a
+        // row's 128 bytes of this wave per 8 lanes: nothing stays dirty in L2 for the kernel boundary behind the launch to write
+        // back (MI355X_MICROARCH.md rows boundary / publish-large).  Same values in the same slab positions as the 4-byte stores.
+        float *slab = a.partial + (size_t)z * a.M * a.N + obase;
+        const int ldo = a.N;
+        const bool v16 = ((ldo | obase | ncols) & 3) == 0 && (reinterpret_cast<uintptr_t>(a.partial) & 15) == 0;
+        if (v16) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (row < a.M) out[(size_t)row * a.N] = acc0[r];
-            if (TM == 2 && row + 32 < a.M) out[(size_t)(row + 32) * a.N] = acc1[r];
+            for (int r = 0; r < 16; ++r) {
+                const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+                red[row * RP + cl] = acc0[r];
+                if (TM == 2) red[(32 + row) * RP + cl] = acc1[r];
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the wave's own LDS writes, read back by other lanes of it
+            __builtin_amdgcn_wave_barrier();
+            const int pc = n0 + 32 * cg + 4 * (lane & 7);           // first of this lane's 4 columns; ncols % 4 == 0: all in or all out
+            if (pc < ncols) {
+#pragma unroll
+                for (int it = 0; it < 8 * TM; ++it) {
+                    const int row = 8 * it + (lane >> 3);
+                    const f32x4 v = *reinterpret_cast<const f32x4 *>(red + row * RP + 32 * cg + 4 * (lane & 7));
+                    float *dst = slab + (size_t)row * ldo + pc;
+                    if (row < a.M) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
+                }
+            }
+        } else if (col < ncols) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+                if (row < a.M) __hip_atomic_store(slab + (size_t)row * ldo + col, acc0[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (TM == 2 && row + 32 < a.M)
+                    __hip_atomic_store(slab + (size_t)(row + 32) * ldo + col, acc1[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
         }
         if (ABL & 16) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); CAPMI_LC_STAMP(3); }
         return;
     }
+    if (col >= ncols) return;
+    const int oc = obase + col;                      // output column
     float cb = 0.f;
-    if (a.bias) cb += a.bias[col];
-    if (a.bias2) cb += a.bias2[col];
+    if (a.bias) cb += a.bias[oc];
+    if (a.bias2) cb += a.bias2[oc];
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -320,11 +368,11 @@ __device__ __forceinline__ void gemm_lc_body(const KArgs &a, const int blk_x, co
             const int row = 32 * i + (r & 3) + 8 * (r >> 2) + 4 * half;
             if (row >= a.M) continue;
             float v = (i == 0 ? acc0[r] : acc1[r]) + cb;
-            if (a.row_bias) v += a.row_bias[(size_t)(row / a.row_bias_div) * a.N + col];
+            if (a.row_bias) v += a.row_bias[(size_t)(row / a.row_bias_div) * a.N + oc];
             if (a.relu) v = fmaxf(v, 0.f);
-            if (a.mul_mask) v *= a.mul_mask[(size_t)row * a.N + col];
-            if (a.accumulate) v += a.addend[(size_t)row * a.ldc + col];
-            a.C[(size_t)row * a.ldc + col] = v;
+            if (a.mul_mask) v *= a.mul_mask[(size_t)row * a.N + oc];
+            if (a.accumulate) v += a.addend[(size_t)row * a.ldc + oc];
+            a.C[(size_t)row * a.ldc + oc] = v;
         }
     }
 #undef CAPMI_LC_STAMP

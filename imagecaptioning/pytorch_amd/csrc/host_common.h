@@ -43,10 +43,17 @@ struct SegSpec {
     const void *Apl;        // the same activations as A planes (capmi.h capmi_planes_from_f32), or null
 };
 
+// one column segment of a [K][N] B that is read in place (capmi_gemm_desc.n_bcol)
+struct BColSpec {
+    const float *B;
+    int ldb, ncol;
+};
+
 // C[M,N] = sum_s A_s op B_s ; thin wrapper filling capmi_gemm_desc.  The segments' A planes are used only with zero_planes.
 inline int gemm(void *stream, int a_layout, int b_layout, int M, int N, float *C, int ldc, const SegSpec *segs, int nseg,
                 float *partial, int64_t cap, int defer, int *splits_used, const float *bias = nullptr,
-                const float *bias2 = nullptr, int accumulate = 0, const void *zero_planes = nullptr, int splits_hint = 0) {
+                const float *bias2 = nullptr, int accumulate = 0, const void *zero_planes = nullptr, int splits_hint = 0,
+                const BColSpec *bcols = nullptr, int nbcol = 0) {
     capmi_gemm_desc d{};
     d.nseg = nseg;
     for (int i = 0; i < nseg; ++i) {
@@ -61,6 +68,8 @@ inline int gemm(void *stream, int a_layout, int b_layout, int M, int N, float *C
     d.accumulate = accumulate;
     d.partial = partial; d.partial_capacity = cap;
     d.splits = splits_hint; d.defer_reduce = defer;
+    d.n_bcol = nbcol;
+    for (int i = 0; i < nbcol && i < CAPMI_MAX_BCOL; ++i) { d.bcol_B[i] = bcols[i].B; d.bcol_ldb[i] = bcols[i].ldb; d.bcol_n[i] = bcols[i].ncol; }
     const int rc = capmi_gemm_f32(&d, stream);
     if (splits_used) *splits_used = d.splits_used;
     return rc;

@@ -36,6 +36,7 @@ __global__ void tn_to_nt_kernel(const float *__restrict__ src, float *__restrict
 
 // [lang W_ih | lang W_hh] -> w_lang_cat [4R,3R] and [att W_ih(:, 0:R) | att W_hh] -> w_att_cat [4R,2R] in one launch (were four
 // hipMemcpy2DAsync: 42 us + 4 kernel boundaries per BPTT).  R % 4 == 0 and 16-byte aligned operands (checked by the caller).
+// Since r7 only where the dX GEMMs cannot take the weights in place as column segments, or with CAPMI_BWD_PACK=1.
 __global__ void pack_recurrent_kernel(const float *__restrict__ lang_ih, const float *__restrict__ lang_hh,
                                       const float *__restrict__ att_ih, const float *__restrict__ att_hh,
                                       float *__restrict__ w_lang_cat, float *__restrict__ w_att_cat, int R, int ld_att_ih) {
@@ -560,12 +561,26 @@ int capmi_updown_rollout_bwd_phases(const capmi_updown_weights *w, const capmi_u
         RC(colsum(s->dlogits, TN, V1, g->logit_b, nullptr));
     }
 
-    // ---- pack the recurrent weight slices once: [W_ih | W_hh] side by side, so that each step needs ONE
-    //      dX GEMM per LSTM instead of two (+ their split-K reductions): 80 MB of copies per BPTT buys back
-    //      ~80 launches.
-    if (phases & CAPMI_BWD_RECURRENT) {
-        const bool al = R % 4 == 0 && ld_att_ih % 4 == 0 &&
-                        aligned16(w->lang_w_ih, w->lang_w_hh, w->att_w_ih, w->att_w_hh, s->w_lang_cat, s->w_att_cat);
+    // ---- BPTT over the recurrent part ----------------------------------------------------------
+    // Workspace carved in three: the d_x1 and dh_att(attention) GEMMs leave their K-slice slabs in regions of their own
+    // and the LSTM-cell kernels of the following launches finish those reductions (2 of the 3 split-K reduce launches
+    // per step disappear; d_x1 is never materialised).  d_x2 (read by three kernels and the batched pass) is finished and
+    // published by the attention Jacobian kernel, its first consumer.
+    const int64_t cap1 = (cap / 4) & ~(int64_t)1023, caph = (cap / 8) & ~(int64_t)1023, capm = cap - cap1 - caph;
+    float *P1 = P + capm, *Ph = P + capm + cap1;
+    // ---- one dX GEMM per LSTM and step over [W_ih | W_hh] side by side (instead of two + their split-K reductions).  r7: the loader /
+    //      consumer GEMM takes the two weights IN PLACE as column segments of its B; the packed copy (80 MB read + 80 MB written per
+    //      BPTT -- the weights change every step, so it can never be kept) is left for the shapes that kernel does not serve and
+    //      for CAPMI_BWD_PACK=1 (documented knob: the A/B and tests/test_gemm_lc_colseg_gpu.py).  Same d_x2 / d_x1 bit for bit.
+    static const int env_pack = capmi::knob("CAPMI_BWD_PACK", 0);
+    static const int env_lc = capmi::knob("CAPMI_LC", 1);
+    const bool w_al = R % 4 == 0 && ld_att_ih % 4 == 0 && aligned16(w->lang_w_ih, w->lang_w_hh, w->att_w_ih, w->att_w_hh);
+    const bool colseg = !env_pack && env_lc && w_al && N <= 64 && s->planes && s->planes_bytes >= capmi_updown_bwd_planes_bytes(R) &&
+                        (reinterpret_cast<uintptr_t>(s->planes) & 15) == 0 && aligned16(s->dg_lang, s->dg_att) &&
+                        // (the slabs of that kernel's plan fit their regions: <= 256 workgroups of 128 columns)
+                        (cap1 < capm ? cap1 : capm) - CAPMI_WS_COUNTER_FLOATS >= (int64_t)N * 256 * 128;
+    if ((phases & CAPMI_BWD_RECURRENT) && !colseg) {
+        const bool al = w_al && aligned16(s->w_lang_cat, s->w_att_cat);
         if (al) {
             const int total = 4 * R * 5 * R;
             hipLaunchKernelGGL(pack_recurrent_kernel, dim3((total / 4 + 255) / 256), dim3(256), 0, st, w->lang_w_ih, w->lang_w_hh,
@@ -581,13 +596,6 @@ int capmi_updown_rollout_bwd_phases(const capmi_updown_weights *w, const capmi_u
         }
     }
 
-    // ---- BPTT over the recurrent part ----------------------------------------------------------
-    // Workspace carved in three: the d_x1 and dh_att(attention) GEMMs leave their K-slice slabs in regions of their own
-    // and the LSTM-cell kernels of the following launches finish those reductions (2 of the 3 split-K reduce launches
-    // per step disappear; d_x1 is never materialised).  d_x2 (read by three kernels and the batched pass) is finished and
-    // published by the attention Jacobian kernel, its first consumer.
-    const int64_t cap1 = (cap / 4) & ~(int64_t)1023, caph = (cap / 8) & ~(int64_t)1023, capm = cap - cap1 - caph;
-    float *P1 = P + capm, *Ph = P + capm + cap1;
     if (phases & CAPMI_BWD_RECURRENT) {
     if (capm <= CAPMI_WS_COUNTER_FLOATS || cap1 <= CAPMI_WS_COUNTER_FLOATS || caph <= CAPMI_WS_COUNTER_FLOATS) return CAPMI_EINVAL;
     static const bool self_reduce = capmi::research("CAPMI_GEMM_SELF_REDUCE", 0) != 0;
@@ -627,7 +635,8 @@ int capmi_updown_rollout_bwd_phases(const capmi_updown_weights *w, const capmi_u
         int x2_splits = 1;
         {
             SegSpec a{dg_lang, 4 * R, s->w_lang_cat, 3 * R, 4 * R, 1, pl_dg_lang};
-            RC(gemm(stream, 0, 1, N, 3 * R, P, 3 * R, &a, 1, P, capm, 1, &x2_splits, nullptr, nullptr, 0, pl_zero));
+            const BColSpec bc[2] = {{w->lang_w_ih, 2 * R, 2 * R}, {w->lang_w_hh, R, R}};
+            RC(gemm(stream, 0, 1, N, 3 * R, P, 3 * R, &a, 1, P, capm, 1, &x2_splits, nullptr, nullptr, 0, pl_zero, 0, bc, colseg ? 2 : 0));
         }
         RC(capmi_attention_bwd_partial(P + CAPMI_WS_COUNTER_FLOATS, x2_splits, (int64_t)N * 3 * R, 3 * R, d_x2,
                                        r->att_h + (size_t)t * Nf * A, r->alpha + (size_t)t * Nf * K, r->p_att, r->att,
@@ -647,7 +656,8 @@ int capmi_updown_rollout_bwd_phases(const capmi_updown_weights *w, const capmi_u
         // d_x1 = dg_att [W_ih(:, 0:R) | W_hh] -> (dh_lang_prev | dh_att_prev) as slabs for step t-1; not needed at t = 0
         if (t > 0) {
             SegSpec a{dg_att, 4 * R, s->w_att_cat, 2 * R, 4 * R, 1, pl_dg_att};
-            RC(gemm(stream, 0, 1, N, 2 * R, P1, 2 * R, &a, 1, P1, cap1, 1, &x1_splits, nullptr, nullptr, 0, pl_zero));
+            const BColSpec bc[2] = {{w->att_w_ih, ld_att_ih, R}, {w->att_w_hh, R, R}};
+            RC(gemm(stream, 0, 1, N, 2 * R, P1, 2 * R, &a, 1, P1, cap1, 1, &x1_splits, nullptr, nullptr, 0, pl_zero, 0, bc, colseg ? 2 : 0));
         }
         // chunk boundaries at t = c * T / side_chunks, c = side_chunks - 1 .. 1: steps [t, dw_done_from) are complete
         if (side_chunks > 1 && t > 0 && t < dw_done_from && chunk_boundary(t)) {

@@ -52,8 +52,10 @@ def default_workspace(device):
 
 def gemm(segs, M, N, out, ldc=None, a_layout=0, b_layout=0, bias=None, bias2=None, row_bias=None, row_bias_div=1,
          mul_mask=None, relu=False, accumulate=False, ws=None, splits=0, defer_reduce=False, a_planes=None, addend=None, stream=None,
-         allow_wide=False):
+         allow_wide=False, b_cols=None):
     """segs: list of (A, lda, B, ldb, K, a_row_div) with tensors (or (tensor, element_offset) pairs).
+    b_cols: optional list of up to 3 (B, ldb, ncol) column segments of a [K][N] B that stay where they are (capmi_gemm_desc.n_bcol;
+    one K segment with A planes, M <= 64); the segment's own B may then be None.
     a_planes: optional list (one uint8 tensor per segment, see planes_from_f32) -- the activations also delivered pre-split,
     staged by LDS-DMA in the M <= 64 decode kernel.
     addend: out = addend + epilogue(...) (a residual stream added without copying it into `out` first; row pitch ldc).
@@ -81,6 +83,10 @@ def gemm(segs, M, N, out, ldc=None, a_layout=0, b_layout=0, bias=None, bias2=Non
     d.partial, d.partial_capacity = ws.buf.data_ptr(), ws.capacity
     d.splits, d.defer_reduce = splits, int(defer_reduce)
     d.allow_wide_deferred = int(allow_wide)      # (deferred GEMMs: nothing runs beside this one on another stream)
+    if b_cols:
+        d.n_bcol = len(b_cols)
+        for i, (B, ldb, ncol) in enumerate(b_cols):
+            d.bcol_B[i], d.bcol_ldb[i], d.bcol_n[i] = _addr(B), ldb, ncol
     check(lib.capmi_gemm_f32(C.byref(d), stream_ptr() if stream is None else stream), 'capmi_gemm_f32')
     return d.splits_used
 

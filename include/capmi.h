@@ -26,6 +26,7 @@ extern "C" {
 
 #define CAPMI_EINVAL (-1)
 #define CAPMI_MAX_SEG 4
+#define CAPMI_MAX_BCOL 3
 /* GEMM workspace layout: the first CAPMI_WS_COUNTER_FLOATS 4-byte words are per-tile arrival tickets for
  * the in-launch split-K reduction (must be ZERO when a workspace is first used; kernels re-arm them),
  * K-slice slabs follow.  A fused consumer of deferred slices reads them at partial + this offset. */
@@ -97,6 +98,16 @@ typedef struct capmi_gemm_desc {
      * it 256 x 128 tiles (a wide workgroup owns its CU; see capmi_gemm_set_policy, whose process-wide flag this replaces for callers
      * that know -- ops.DeferredGrads without its side stream).  0: the process-wide policy decides. */
     int allow_wide_deferred;
+    /* r7 (b_layout 1, nseg 1, M <= 64 with A planes: the dX GEMMs of a BPTT step): B delivered as n_bcol column segments that stay
+     * where they are -- output columns [sum of bcol_n[0..i), + bcol_n[i]) are A [K][bcol_B[i] with row stride bcol_ldb[i]] -- instead
+     * of one matrix packed side by side (dX = dG [W_ih | W_hh] with the two weights read in place).  N = sum of bcol_n; every
+     * bcol_n[i] % 4 == 0, 16-byte aligned; seg[0].B / ldb are ignored.  Each output element is the same sum in the same order as
+     * with a packed B: bit-identical.  Served by the loader / consumer kernel only (CAPMI_EINVAL where that kernel cannot run).
+     * 0: B is seg[].B. */
+    int n_bcol;
+    const float *bcol_B[CAPMI_MAX_BCOL];
+    int bcol_ldb[CAPMI_MAX_BCOL];
+    int bcol_n[CAPMI_MAX_BCOL];
 } capmi_gemm_desc;
 
 int capmi_gemm_f32(capmi_gemm_desc *d, void *stream);
