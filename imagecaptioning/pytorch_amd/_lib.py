@@ -110,6 +110,11 @@ class UpDownBeam(C.Structure):
                 [('partial_capacity', C.c_int64)])
 
 
+class UpDownBeamTrain(C.Structure):
+    """capmi_updown_beam_train: the search struct + the per-step keep masks by search row"""
+    _fields_ = [('b', UpDownBeam), ('drop_xt', c_f), ('drop_out', c_f), ('h_drop', c_f)]
+
+
 class NewFCWeights(C.Structure):
     _fields_ = [(k, c_f) for k in ('embed', 'i2h_w', 'i2h_b', 'h2h_w', 'h2h_b', 'logit_w', 'logit_b')]
 
@@ -291,6 +296,9 @@ SIGNATURES = {
     'capmi_beam_logsoftmax': [_P, _P, _I, _I, _F, _I, _P],
     'capmi_updown_beam_search': [C.POINTER(UpDownWeights), C.POINTER(UpDownBeam), _P],
     'capmi_updown_decode_step': [C.POINTER(UpDownWeights), C.POINTER(UpDownBeam), _I, _I, _P, _P, _I, _P],
+    'capmi_updown_beam_search_train': [C.POINTER(UpDownWeights), C.POINTER(UpDownBeamTrain), _P],
+    'capmi_beam_finalize': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    'capmi_lineage_gather': [_P, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P],
     'capmi_decode_constrain': [_P, _I, _I, _P, _I, _I, _P, _I, _P, _I, _I, _I, _P],
     'capmi_beam_diversity': [_P, _P, _I, _I, _I, _P, _I, _I, _F, _P],
     'capmi_column_penalty': [_P, _I, _I, _P, _I, _I, _F, _P],

@@ -42,10 +42,21 @@ def sample_beam(model, fc_feats, att_feats, att_masks, opt):
         from .step import UpDownStepper
         return beam_search_steps(model, lambda rows: UpDownStepper(P, pr, rows), pr.att.shape[0], P['embed.0.weight'].shape[0],
                                  model.seq_length, opt, dev)
+    B, V1 = pr.att.shape[0], P['embed.0.weight'].shape[0]
+    L, bd = model.seq_length, beam_size
+    bufs = _native_search(model, P, pr, bd, L, opt)
+    return assemble_done_beams(model, bufs['parent'], bufs['token'], bufs['score'], bufs['ended'], bufs['logp_rows'], B, bd, L, V1,
+                               sample_n, beam_size, opt)
+
+
+def _native_search(model, P, pr, bd, L, opt, drop_xt=None, drop_out=None, train=False):
+    """All L steps of the UpDown search in one native call; returns the buffers (tables parent / token / score / ended [L,B,bd],
+    logp_rows [L,B*bd,V1]).  train: capmi_updown_beam_search_train, `pr` holds the dropped features and drop_xt [L,B*bd,E] /
+    drop_out [L,B*bd,R] are the keep masks by search row (None: no dropout there)."""
+    dev = pr.att.device
     B, K, R = pr.att.shape
     A = pr.p_att.shape[2]
     V1, E = P['embed.0.weight'].shape
-    L, bd = model.seq_length, beam_size
     assert bd <= V1
     N = B * bd
     ws = ops.default_workspace(dev)
@@ -55,7 +66,8 @@ def sample_beam(model, fc_feats, att_feats, att_masks, opt):
                 logp_rows=z(L, N, V1), parent=torch.empty(L, B, bd, dtype=torch.int32, device=dev),
                 token=torch.empty(L, B, bd, dtype=torch.long, device=dev), score=z(L, B, bd),
                 ended=torch.empty(L, B, bd, dtype=torch.uint8, device=dev))
-    b = _lib.UpDownBeam()
+    bt = _lib.UpDownBeamTrain() if train else None
+    b = bt.b if train else _lib.UpDownBeam()
     b.B, b.bd, b.K, b.A, b.R, b.E, b.V1, b.L = B, bd, K, A, R, E, V1, L
     b.fc, b.att, b.p_att, b.att_mask = ptr(pr.fc), ptr(pr.att), ptr(pr.p_att), ptr(pr.att_masks)
     b.temperature = float(opt.get('temperature', 1))
@@ -69,10 +81,171 @@ def sample_beam(model, fc_feats, att_feats, att_masks, opt):
         setattr(b, k, t.data_ptr())
     b.partial, b.partial_capacity = ws.buf.data_ptr(), ws.capacity
     w = engine.weights_struct(P)
-    check(lib.capmi_updown_beam_search(C.byref(w), C.byref(b), stream_ptr()), 'capmi_updown_beam_search')
+    if train:
+        for m, c in ((drop_xt, E), (drop_out, R)):
+            assert m is None or (m.shape == (L, N, c) and m.is_contiguous() and m.dtype == _f32)
+        bufs['h_drop'] = z(N, R)
+        bt.drop_xt, bt.drop_out, bt.h_drop = ptr(drop_xt), ptr(drop_out), ptr(bufs['h_drop'])
+        check(lib.capmi_updown_beam_search_train(C.byref(w), C.byref(bt), stream_ptr()), 'capmi_updown_beam_search_train')
+    else:
+        check(lib.capmi_updown_beam_search(C.byref(w), C.byref(b), stream_ptr()), 'capmi_updown_beam_search')
+    return bufs
 
-    return assemble_done_beams(model, bufs['parent'], bufs['token'], bufs['score'], bufs['ended'], bufs['logp_rows'], B, bd, L, V1,
-                               sample_n, beam_size, opt)
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Beam search as a training rollout (reference ADVANCED.md "SCST in Topdown Bottomup paper": train_sample_method greedy,
+# train_beam_size > 1): search with training numerics -> capmi_beam_finalize -> forced replay of the surviving beams with the
+# dropout masks their ancestors saw.  Nothing here reads the device.
+# ---------------------------------------------------------------------------------------------------------------------------
+_len_div_cache = {}
+marks = None        # a list: the phases of a training beam search append (name, recorded event) -- scripts/tools_beam_scst_bench.py
+
+
+def _mark(name):
+    if marks is not None:
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        marks.append((name, e))
+
+
+def length_divisors(cfg, L, dev):
+    """[L] float64 on the device: what the length penalty `cfg` divides the joint log-prob of a (t+1)-word beam by, computed
+    with the host arithmetic of _penalty (so that device keys order exactly like the host's); None for ''.  Cached."""
+    if cfg == '':
+        return None
+    key = (cfg, L, str(dev))
+    t = _len_div_cache.get(key)
+    if t is None:
+        kind, alpha = cfg.split('_')
+        alpha = float(alpha)
+        if kind == 'wu':
+            div = [((5 + n) ** alpha) / ((5 + 1) ** alpha) for n in range(1, L + 1)]
+        elif kind == 'avg':
+            div = [float(n) for n in range(1, L + 1)]
+        else:
+            raise ValueError(cfg)
+        t = _len_div_cache[key] = torch.tensor(div, dtype=torch.float64).to(dev)
+    return t
+
+
+def finalize(parent, token, score, ended, sample_n, length_penalty=''):
+    """capmi_beam_finalize: tables [L,B,bd] -> (seq [B*sample_n,L] int64, lineage [L,B*sample_n] int32, length [B*sample_n] int32,
+    p [B*sample_n] fp32), all on the device (CaptionModel.py:183-208)."""
+    L, B, bd = parent.shape
+    dev = parent.device
+    rows = B * sample_n
+    seq = torch.empty(rows, L, dtype=torch.long, device=dev)
+    lineage = torch.empty(L, rows, dtype=torch.int32, device=dev)
+    length = torch.empty(rows, dtype=torch.int32, device=dev)
+    p = torch.empty(rows, dtype=_f32, device=dev)
+    div = length_divisors(length_penalty, L, dev)
+    check(lib.capmi_beam_finalize(ptr(parent), ptr(token), ptr(score), ptr(ended), ptr(div), B, bd, L, sample_n, ptr(seq),
+                                  ptr(lineage), ptr(length), ptr(p), stream_ptr()), 'capmi_beam_finalize')
+    return seq, lineage, length, p
+
+
+def lineage_gather(lineage, rows_src, src_a, src_b=None):
+    """mask_replay[t, i, :] = mask_search[t, lineage[t, i], :] for one or two [L, rows_src, C] arrays in one launch."""
+    L, rows = lineage.shape
+    out = [None if s is None else torch.empty(L, rows, s.shape[2], dtype=_f32, device=s.device) for s in (src_a, src_b)]
+    if src_a is None and src_b is None:
+        return out
+    check(lib.capmi_lineage_gather(ptr(lineage), L, rows_src, rows, ptr(src_a), ptr(out[0]), 0 if src_a is None else src_a.shape[2],
+                                   ptr(src_b), ptr(out[1]), 0 if src_b is None else src_b.shape[2], stream_ptr()),
+          'capmi_lineage_gather')
+    return out
+
+
+def wants_train_beam(model, opt):
+    """The dispatch rule of the training beam search: beam_size > 1, greedy / beam_search, train mode, gradients enabled."""
+    return (opt.get('beam_size', 1) > 1 and opt.get('sample_method', 'greedy') in ('greedy', 'beam_search') and model.training
+            and torch.is_grad_enabled())
+
+
+def refuse_train_beam(model, opt):
+    """Families without a training beam search: refuse instead of returning log-probs that carry no gradient."""
+    if wants_train_beam(model, opt):
+        raise NotImplementedError('train_beam_size > 1 (beam search in train mode with gradients) is implemented for updown / '
+                                  'topdown and newfc, not for %s; its eval / no_grad beam search is unchanged' % type(model).__name__)
+
+
+def check_train_beam_options(opt):
+    """Options the replay cannot reproduce (none is reachable from LossWrapper's training calls except the last two)."""
+    for name, bad in (('group_size', int(opt.get('group_size', 1)) != 1), ('decoding_constraint', opt.get('decoding_constraint', 0)),
+                      ('remove_bad_endings', opt.get('remove_bad_endings', 0)), ('temperature', float(opt.get('temperature', 1)) != 1.0),
+                      ('output_logsoftmax', not opt.get('output_logsoftmax', 1)), ('use_ppo', opt.get('use_ppo', 0))):
+        if bad:
+            raise NotImplementedError('the training beam search (train_beam_size > 1) does not support %s=%r'
+                                      % (name, opt.get(name)))
+    beam_size, sample_n = opt.get('beam_size', 10), opt.get('sample_n', 10)
+    assert sample_n == 1 or sample_n == beam_size, 'when beam search, sample_n == 1 or beam search'
+
+
+def updown_beam_train(model, fc_feats, att_feats, att_masks, opt):
+    """AttModel._sample_beam called in train() mode with gradients (loss_wrapper.py with train_beam_size > 1): returns
+    (seq [B*sample_n, L], seqLogprobs [B*sample_n, L, V1] attached to the forced rollout's autograd function)."""
+    check_train_beam_options(opt)
+    bd, sample_n = opt.get('beam_size', 10), opt.get('sample_n', 10)
+    fc_feats, att_feats = fc_feats.float().contiguous(), att_feats.float().contiguous()
+    att_masks = None if att_masks is None else att_masks.float().contiguous()
+    B, L, dev = fc_feats.shape[0], model.seq_length, fc_feats.device
+    K = ops.clip_len(att_masks, att_feats.shape[1])
+    masks = opt.get('_beam_masks')              # test hook: injected keep masks (drop_fc, drop_att, drop_xt, drop_out by search row)
+    if masks is None:
+        masks = model._dropout_masks(B, K, B * bd, L, dev)
+    _mark('start')
+    with torch.no_grad():
+        P = {k: v.detach() for k, v in model._named_param_list()}
+        pr = engine.prepare(P, fc_feats, att_feats, att_masks, masks.get('drop_fc'), masks.get('drop_att'))
+        bufs = _native_search(model, P, pr, bd, L, opt, masks.get('drop_xt'), masks.get('drop_out'), train=True)
+        _mark('search')
+        seq, lineage, length, p = finalize(bufs['parent'], bufs['token'], bufs['score'], bufs['ended'], sample_n,
+                                           opt.get('length_penalty', ''))
+        r_xt, r_out = lineage_gather(lineage, B * bd, masks.get('drop_xt'), masks.get('drop_out'))
+        _mark('finalize')
+    cfg = dict(n=sample_n, T=L, L=L, mode='forced', forced=seq, temperature=1.0)
+    for k, v in (('drop_fc', masks.get('drop_fc')), ('drop_att', masks.get('drop_att')), ('drop_xt', r_xt), ('drop_out', r_out)):
+        if v is not None:
+            cfg[k] = v
+    model.done_beams = None                      # not assembled on the host in this path
+    model._last_beam = dict(score=bufs['score'], parent=bufs['parent'], token=bufs['token'], ended=bufs['ended'], lineage=lineage,
+                            length=length, p=p)
+    out = model._run(cfg, fc_feats, att_feats, att_masks)
+    _mark('replay')
+    return out
+
+
+def newfc_beam_train(model, fc_feats, opt):
+    """The same for NewFCModel: the search is host-stepped over NewFCStepper (L iterations, no synchronisation), the only
+    dropout is the LSTMCore output's ([L, B*bd, R] by search row; the image step's output is discarded)."""
+    from .step import NewFCStepper
+    check_train_beam_options(opt)
+    bd, sample_n = opt.get('beam_size', 10), opt.get('sample_n', 10)
+    fc_feats = fc_feats.float().contiguous()
+    B, L, dev = fc_feats.shape[0], model.seq_length, fc_feats.device
+    masks = opt.get('_beam_masks')
+    if masks is None:
+        masks = {}
+        if model.drop_prob_lm > 0:
+            masks['drop_out'] = ops.dropout_mask((L, B * bd, model.rnn_size), model.drop_prob_lm, model._next_seed(), 0, dev)
+    drop = masks.get('drop_out')
+    _mark('start')
+    with torch.no_grad():
+        P = dict(zip(model._param_names, [q.detach() for q in model._param_list()]))
+        parent, token, score, ended, _ = beam_search_steps(model, lambda rows: NewFCStepper(P, fc_feats, rows, drop_out=drop), B,
+                                                           P['embed.weight'].shape[0], L, opt, dev, tables_only=True)
+        _mark('search')
+        seq, lineage, length, p = finalize(parent, token, score, ended, sample_n, opt.get('length_penalty', ''))
+        r_out, _ = lineage_gather(lineage, B * bd, drop)
+        _mark('finalize')
+    cfg = dict(n=sample_n, T=L, L=L, mode='forced', forced=seq, temperature=1.0)
+    if r_out is not None:
+        cfg['drop_out'] = r_out
+    model.done_beams = None
+    model._last_beam = dict(score=score, parent=parent, token=token, ended=ended, lineage=lineage, length=length, p=p)
+    out = model._run(cfg, fc_feats)
+    _mark('replay')
+    return out
 
 
 def assemble_done_beams(model, parent, token, score, ended, logp_rows, B, bd, L, V1, sample_n, beam_size, opt, groups=1):
@@ -153,7 +326,7 @@ def _decode_flags(model, opt, dev):
     return flags, bad
 
 
-def beam_search_steps(model, make_decoder, B, V1, L, opt, dev):
+def beam_search_steps(model, make_decoder, B, V1, L, opt, dev, tables_only=False):
     """CaptionModel.beam_search (CaptionModel.py:35-209) for any decoder given as a single-step object (step.py
     protocol): the selection / reordering / normalisation / constraint / diversity kernels are native, only the decoder
     step is a callback.  Covers decoding_constraint, remove_bad_endings, suppress_UNK, temperature, length_penalty and
@@ -200,6 +373,8 @@ def beam_search_steps(model, make_decoder, B, V1, L, opt, dev):
             check(lib.capmi_decode_constrain(ptr(logp_rows[t + 1]), N, V1, ptr(token[t]), 1, flags, ptr(bad), bad.numel(), None, 0,
                                              t + 1, 0, st), 'decode_constrain')
         cur = bd
+    if tables_only:                                                         # the training search finalises on the device
+        return parent, token, score, ended, logp_rows
     return assemble_done_beams(model, parent, token, score, ended, logp_rows, B, bd, L, V1, sample_n, beam_size, opt)
 
 

@@ -194,6 +194,8 @@ class AoAModel(CaptionModel):
         if opt.get('beam_size', 1) > 1 and method in ('greedy', 'beam_search'):
             if not att_feats.is_cuda:
                 raise CapmiError('the capmi backend runs on a HIP device only; there is no CPU path')
+            from imagecaptioning.pytorch_amd import beam
+            beam.refuse_train_beam(self, opt)       # train_beam_size > 1: no log-probs without a graph
             if att_masks is not None:
                 ml = clip_len(att_masks)
                 att_feats, att_masks = att_feats[:, :ml], att_masks[:, :ml].float().contiguous()

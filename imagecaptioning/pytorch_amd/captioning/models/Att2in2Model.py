@@ -182,6 +182,7 @@ class Att2in2Model(CaptionModel):
         """Greedy / sampling rollout (AttModel.py:258-352); beam search and the decode-time options on the stepper."""
         from imagecaptioning.pytorch_amd import decode, beam
         self._device_check(att_feats)
+        beam.refuse_train_beam(self, opt)           # train_beam_size > 1: no log-probs without a graph
         method = opt.get('sample_method', 'greedy')
         raw = not opt.get('output_logsoftmax', 1)
         is_beam = opt.get('beam_size', 1) > 1 and method in ('greedy', 'beam_search')

@@ -93,8 +93,9 @@ class AttEnsemble(CaptionModel):
 
     def _sample(self, fc_feats, att_feats, att_masks=None, opt={}):
         """AttModel._sample / _sample_beam (AttModel.py:218-352) on the mixture, host-stepped on an EnsembleStepper."""
-        self._eval_only()
         from imagecaptioning.pytorch_amd import beam
+        beam.refuse_train_beam(self, opt)           # train_beam_size > 1: named, before the general "evaluation only"
+        self._eval_only()
         if not opt.get('output_logsoftmax', 1):
             raise NotImplementedError('output_logsoftmax=0 is only used by margin structure losses; AttEnsemble returns the '
                                       'mixture log-probabilities')

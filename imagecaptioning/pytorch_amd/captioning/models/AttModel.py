@@ -273,6 +273,10 @@ class AttModel(CaptionModel):
         sample_n = int(opt.get('sample_n', 1))
         group_size = opt.get('group_size', 1)
         if beam_size > 1 and sample_method in ('greedy', 'beam_search'):
+            from imagecaptioning.pytorch_amd import beam
+            if beam.wants_train_beam(self, opt):
+                # train mode with gradients (loss_wrapper.py, train_beam_size > 1): search, finalise on the device, forced replay
+                return beam.updown_beam_train(self, fc_feats, att_feats, att_masks, opt)
             return self._sample_beam(fc_feats, att_feats, att_masks, opt)
         from imagecaptioning.pytorch_amd import decode
         if decode.wants_options(opt):

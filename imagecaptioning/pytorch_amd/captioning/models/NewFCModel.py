@@ -86,7 +86,9 @@ class NewFCModel(CaptionModel):
         if not fc_feats.is_cuda:
             raise CapmiError('the capmi backend runs on a HIP device only; there is no CPU path')
         N, T = fc_feats.shape[0] * cfg['n'], cfg['T']
-        if self.training and self.drop_prob_lm > 0:
+        if 'drop_out' in cfg:
+            pass                                  # the training beam search replays with the masks of its search
+        elif self.training and self.drop_prob_lm > 0:
             cfg['drop_out'] = ops.dropout_mask((T, N, self.rnn_size), self.drop_prob_lm, self._next_seed(), 0,
                                                fc_feats.device)
         params = self._param_list()
@@ -139,6 +141,9 @@ class NewFCModel(CaptionModel):
                                       'decode-time options of %s return log-probabilities' % type(self).__name__)
         if not fc_feats.is_cuda:
             raise CapmiError('the capmi backend runs on a HIP device only; there is no CPU path')
+        if is_beam and beam.wants_train_beam(self, opt):
+            # train mode with gradients (loss_wrapper.py, train_beam_size > 1): search, finalise on the device, forced replay
+            return beam.newfc_beam_train(self, fc_feats, opt)
         P = dict(zip(self._param_names, [p.detach() for p in self._param_list()]))
         if is_beam:
             # AttModel._sample_beam on the single-step decoder (the image step is taken once per image, AttModel.py:925-927)

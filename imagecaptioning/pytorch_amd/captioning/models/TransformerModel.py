@@ -262,6 +262,8 @@ class TransformerModel(CaptionModel):
                                       'decode-time options of %s return log-probabilities' % type(self).__name__)
         if not att_feats.is_cuda:
             raise CapmiError('the capmi backend runs on a HIP device only; there is no CPU path')
+        from imagecaptioning.pytorch_amd import beam
+        beam.refuse_train_beam(self, opt)           # train_beam_size > 1: no log-probs without a graph
         if opt.get('beam_size', 1) > 1 and method in ('greedy', 'beam_search'):
             att_feats, att_masks = self._clip(att_feats, att_masks)
             with torch.no_grad():

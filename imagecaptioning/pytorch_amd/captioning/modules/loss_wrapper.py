@@ -32,6 +32,9 @@ class LossWrapper(torch.nn.Module):
                 raise NotImplementedError('use_ppo reads the rollout output; with structure_loss_type %r (max_margin, multi_margin, '
                                           'real_softmax_margin) and no struc_use_logsoftmax that is raw logits, which is not '
                                           'supported' % opt.structure_loss_type)
+            if use_ppo and opt.train_beam_size > 1 and opt.train_sample_method in ('greedy', 'beam_search'):
+                raise NotImplementedError('use_ppo with train_beam_size > 1: the PPO reference pass re-runs a sampled rollout, not a '
+                                          'beam search')
             w = opt.structure_loss_weight
             if w < 1:
                 lm_loss = self.crit(self.model(fc_feats, att_feats, labels[..., :-1], att_masks), labels[..., 1:],

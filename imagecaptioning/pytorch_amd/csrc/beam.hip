@@ -129,9 +129,11 @@ __global__ __launch_bounds__(SEL_T) void beam_logsoftmax_kernel(const float *__r
     }
 }
 
-// one decoder step on `rows` rows, `n` rows per image (get_logprobs_state, AttModel.py:166-176)
+// one decoder step on `rows` rows, `n` rows per image (get_logprobs_state, AttModel.py:166-176).  Train mode: xt_mask [rows,E] /
+// out_mask [rows,R] are the step's keep masks (AttModel.py:74-76, 637), h_drop [rows,R] the dropped output the logit reads.
 int decode_step(const capmi_updown_weights *w, capmi_updown_beam *b, int rows, int n, const float *st_in, float *st_out,
-                float *logp_out, float temperature, void *stream) {
+                float *logp_out, float temperature, void *stream, const float *xt_mask = nullptr,
+                const float *out_mask = nullptr, float *h_drop = nullptr) {
     const int B = b->B, K = b->K, A = b->A, R = b->R, E = b->E, V1 = b->V1;
     const size_t per = (size_t)B * b->bd * R;
     const float *h_att_p = st_in, *c_att_p = st_in + per, *h_lang_p = st_in + 2 * per, *c_lang_p = st_in + 3 * per;
@@ -139,7 +141,7 @@ int decode_step(const capmi_updown_weights *w, capmi_updown_beam *b, int rows, i
     const int ld_att_ih = 2 * R + E;
     float *slabs = b->partial + CAPMI_WS_COUNTER_FLOATS;
     int splits = 1;
-    RC(capmi_embed_fwd(b->it, 1, nullptr, w->embed, nullptr, b->xt, rows, E, 1, stream));
+    RC(capmi_embed_fwd(b->it, 1, nullptr, w->embed, xt_mask, b->xt, rows, E, 1, stream));
     {
         SegSpec s[3] = {{h_lang_p, R, w->att_w_ih, ld_att_ih, R, 1}, {b->xt, E, w->att_w_ih + 2 * R, ld_att_ih, E, 1},
                         {h_att_p, R, w->att_w_hh, R, R, 1}};
@@ -158,14 +160,137 @@ int decode_step(const capmi_updown_weights *w, capmi_updown_beam *b, int rows, i
                         {h_lang_p, R, w->lang_w_hh, R, R, 1}};
         RC(gemm(stream, 0, 0, rows, 4 * R, b->partial, 4 * R, s, 3, b->partial, b->partial_capacity, 1, &splits));
         RC(capmi_lstm_cell_fwd(slabs, splits, w->lang_b_ih, w->lang_b_hh, nullptr, 1, nullptr, c_lang_p, h_lang, c_lang,
-                               b->gates, nullptr, nullptr, rows, R, stream));
+                               b->gates, out_mask, out_mask ? h_drop : nullptr, rows, R, stream));
     }
     {
-        SegSpec s{h_lang, R, w->logit_w, R, R, 1};     // eval mode: no dropout on the output
+        SegSpec s{out_mask ? h_drop : h_lang, R, w->logit_w, R, R, 1};     // eval mode: no dropout on the output
         RC(gemm(stream, 0, 0, rows, V1, b->logits, V1, &s, 1, b->partial, b->partial_capacity, 0, nullptr, w->logit_b));
     }
     if (!logp_out) return 0;      // raw logits wanted (capmi_updown_decode_step)
     return capmi_beam_logsoftmax(b->logits, logp_out, rows, V1, temperature, b->unk_col, stream);
+}
+
+// all L steps of the search; the train variant hands in the per-step keep masks by search row
+int beam_search_run(const capmi_updown_weights *w, capmi_updown_beam *b, const float *drop_xt, const float *drop_out,
+                    float *h_drop, void *stream) {
+    const int B = b->B, bd = b->bd, R = b->R, E = b->E, V1 = b->V1, L = b->L;
+    const int N = B * bd;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t per = (size_t)N * R, st_sz = 4 * per;
+    HIP_RC(hipMemsetAsync(b->state, 0, 2 * st_sz * sizeof(float), st));
+    HIP_RC(hipMemsetAsync(b->it, 0, (size_t)N * sizeof(int64_t), st));   // BOS
+    HIP_RC(hipMemsetAsync(b->sums, 0, (size_t)2 * N * sizeof(float), st));
+    {   // fc term of the attention LSTM
+        SegSpec s{b->fc, R, w->att_w_ih + R, 2 * R + E, R, 1};
+        RC(gemm(stream, 0, 0, B, 4 * R, b->fc_gates, 4 * R, &s, 1, b->partial, b->partial_capacity, 0, nullptr));
+    }
+    // first step from BOS on B rows (AttModel.py:235-239): rows b of the [B*bd]-row arrays, one row per image
+    float *st_a = b->state, *st_b = b->state + st_sz;
+    // the first distribution is the model's own log_softmax: the temperature only enters at CaptionModel.py:203-204
+    RC(decode_step(w, b, B, 1, st_a, st_b, b->logp_rows, 1.f, stream, drop_xt, drop_out, h_drop));
+    // NOTE: after this call the B live rows of st_b / logp_rows[0] are rows 0..B-1 (cur = 1 per image)
+    float *cur_state = st_b, *nxt_state = st_a;
+    int cur = 1;
+    for (int t = 0; t < L; ++t) {
+        const size_t o = (size_t)t * N;
+        float *sums_in = b->sums + (size_t)(t & 1) * N, *sums_out = b->sums + (size_t)((t + 1) & 1) * N;
+        RC(capmi_beam_select(b->logp_rows + (size_t)t * N * V1, sums_in, B, cur, bd, V1, t == L - 1 ? 1 : 0, b->parent + o,
+                             b->token + o, b->score + o, sums_out, b->ended + o, stream));
+        if (t == L - 1) break;
+        RC(capmi_beam_reorder(cur_state, nxt_state, b->parent + o, 4, B, cur, bd, R, stream));
+        HIP_RC(hipMemcpyAsync(b->it, b->token + o, (size_t)N * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        // step on B*bd rows, bd rows per image; writes the next state in place of the consumed one
+        RC(decode_step(w, b, N, bd, nxt_state, cur_state, b->logp_rows + (size_t)(t + 1) * N * V1, b->temperature, stream,
+                       drop_xt ? drop_xt + (size_t)(t + 1) * N * E : nullptr,
+                       drop_out ? drop_out + (size_t)(t + 1) * N * R : nullptr, h_drop));
+        cur = bd;
+        // cur_state now holds the new state; nxt_state is free
+    }
+    return 0;
+}
+
+constexpr int FIN_T = 256;
+constexpr int FIN_MAX = 1024;
+
+// one workgroup per image: keys of the <= L*bd finished candidates in LDS, every candidate counts the candidates that sort in
+// front of it (larger key; equal key -> earlier (t, j): the stable order of the host's sorted()), the sample_n first write their
+// flat index to s_out, then one lane per output beam walks the parent pointers back.
+__global__ __launch_bounds__(FIN_T) void beam_finalize_kernel(const int32_t *__restrict__ parent, const int64_t *__restrict__ token,
+                                                             const float *__restrict__ score, const uint8_t *__restrict__ ended,
+                                                             const double *__restrict__ len_div, int B, int bd, int L,
+                                                             int sample_n, int64_t *__restrict__ seq, int32_t *__restrict__ lineage,
+                                                             int32_t *__restrict__ length, float *__restrict__ p) {
+    __shared__ double s_key[FIN_MAX];
+    __shared__ uint8_t s_end[FIN_MAX];
+    __shared__ int s_out[BD_MAX];
+    const int b = blockIdx.x, n = L * bd, tid = threadIdx.x;
+    for (int c = tid; c < n; c += FIN_T) {
+        const int t = c / bd, j = c - t * bd;
+        const size_t o = ((size_t)t * B + b) * bd + j;
+        const double s = (double)score[o];
+        s_key[c] = len_div ? s / len_div[t] : s;
+        s_end[c] = ended[o];
+    }
+    if (tid < BD_MAX) s_out[tid] = -1;
+    __syncthreads();
+    for (int c = tid; c < n; c += FIN_T) {
+        if (!s_end[c]) continue;
+        const double k = s_key[c];
+        int rank = 0;
+        for (int c2 = 0; c2 < n; ++c2) {
+            const double k2 = s_key[c2];
+            rank += (s_end[c2] && (k2 > k || (k2 == k && c2 < c))) ? 1 : 0;
+        }
+        if (rank < sample_n) s_out[rank] = c;
+    }
+    __syncthreads();
+    if (tid < sample_n) {
+        const int rows = B * sample_n, row = b * sample_n + tid;
+        const int c = s_out[tid];
+        int len = 0;
+        float pv = 0.f;
+        if (c >= 0) {
+            const int t = c / bd;
+            int jj = c - t * bd;
+            len = t + 1;
+            pv = (float)s_key[c];
+            for (int s = t; s >= 0; --s) {
+                const size_t o = ((size_t)s * B + b) * bd + jj;
+                seq[(size_t)row * L + s] = token[o];
+                int par = parent[o];
+                par = par < 0 ? 0 : (par >= bd ? bd - 1 : par);
+                lineage[(size_t)s * rows + row] = s == 0 ? b : b * bd + par;
+                jj = par;
+            }
+        }
+        for (int s = len; s < L; ++s) {
+            seq[(size_t)row * L + s] = 0;
+            lineage[(size_t)s * rows + row] = -1;
+        }
+        length[row] = len;
+        p[row] = pv;
+    }
+}
+
+// the replay's keep masks: row i of step t takes the mask of the search row its ancestor occupied (both masks of a step in one
+// launch, float4 moves)
+__global__ void lineage_gather_kernel(const int32_t *__restrict__ lineage, int L, int rows_src, int rows_dst,
+                                      const float4 *__restrict__ src_a, float4 *__restrict__ dst_a, int C4a,
+                                      const float4 *__restrict__ src_b, float4 *__restrict__ dst_b, int C4b) {
+    const size_t na = src_a ? (size_t)L * rows_dst * C4a : 0, nb = src_b ? (size_t)L * rows_dst * C4b : 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < na + nb; i += (size_t)gridDim.x * blockDim.x) {
+        const bool second = i >= na;
+        const size_t k = second ? i - na : i;
+        const int C4 = second ? C4b : C4a;
+        const size_t tr = k / C4;
+        const int c = (int)(k - tr * C4);
+        const int t = (int)(tr / rows_dst);
+        int r = lineage[tr];
+        r = r < 0 ? 0 : (r >= rows_src ? rows_src - 1 : r);
+        const float4 *src = second ? src_b : src_a;
+        float4 *dst = second ? dst_b : dst_a;
+        dst[k] = src[((size_t)t * rows_src + r) * C4 + c];
+    }
 }
 
 }  // namespace
@@ -222,37 +347,38 @@ int capmi_updown_decode_step(const capmi_updown_weights *w, capmi_updown_beam *b
 
 int capmi_updown_beam_search(const capmi_updown_weights *w, capmi_updown_beam *b, void *stream) {
     if (!w || !b || b->B <= 0 || b->bd <= 0 || b->bd > BD_MAX || b->L <= 0 || !b->partial) return CAPMI_EINVAL;
-    const int B = b->B, bd = b->bd, R = b->R, E = b->E, V1 = b->V1, L = b->L;
-    const int N = B * bd;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t per = (size_t)N * R, st_sz = 4 * per;
-    HIP_RC(hipMemsetAsync(b->state, 0, 2 * st_sz * sizeof(float), st));
-    HIP_RC(hipMemsetAsync(b->it, 0, (size_t)N * sizeof(int64_t), st));   // BOS
-    HIP_RC(hipMemsetAsync(b->sums, 0, (size_t)2 * N * sizeof(float), st));
-    {   // fc term of the attention LSTM
-        SegSpec s{b->fc, R, w->att_w_ih + R, 2 * R + E, R, 1};
-        RC(gemm(stream, 0, 0, B, 4 * R, b->fc_gates, 4 * R, &s, 1, b->partial, b->partial_capacity, 0, nullptr));
-    }
-    // first step from BOS on B rows (AttModel.py:235-239): rows b of the [B*bd]-row arrays, one row per image
-    float *st_a = b->state, *st_b = b->state + st_sz;
-    // the first distribution is the model's own log_softmax: the temperature only enters at CaptionModel.py:203-204
-    RC(decode_step(w, b, B, 1, st_a, st_b, b->logp_rows, 1.f, stream));
-    // NOTE: after this call the B live rows of st_b / logp_rows[0] are rows 0..B-1 (cur = 1 per image)
-    float *cur_state = st_b, *nxt_state = st_a;
-    int cur = 1;
-    for (int t = 0; t < L; ++t) {
-        const size_t o = (size_t)t * N;
-        float *sums_in = b->sums + (size_t)(t & 1) * N, *sums_out = b->sums + (size_t)((t + 1) & 1) * N;
-        RC(capmi_beam_select(b->logp_rows + (size_t)t * N * V1, sums_in, B, cur, bd, V1, t == L - 1 ? 1 : 0, b->parent + o,
-                             b->token + o, b->score + o, sums_out, b->ended + o, stream));
-        if (t == L - 1) break;
-        RC(capmi_beam_reorder(cur_state, nxt_state, b->parent + o, 4, B, cur, bd, R, stream));
-        HIP_RC(hipMemcpyAsync(b->it, b->token + o, (size_t)N * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-        // step on B*bd rows, bd rows per image; writes the next state in place of the consumed one
-        RC(decode_step(w, b, N, bd, nxt_state, cur_state, b->logp_rows + (size_t)(t + 1) * N * V1, b->temperature, stream));
-        cur = bd;
-        // cur_state now holds the new state; nxt_state is free
-    }
+    return beam_search_run(w, b, nullptr, nullptr, nullptr, stream);
+}
+
+int capmi_updown_beam_search_train(const capmi_updown_weights *w, capmi_updown_beam_train *bt, void *stream) {
+    if (!w || !bt) return CAPMI_EINVAL;
+    capmi_updown_beam *b = &bt->b;
+    if (b->B <= 0 || b->bd <= 0 || b->bd > BD_MAX || b->L <= 0 || !b->partial || (bt->drop_out && !bt->h_drop)) return CAPMI_EINVAL;
+    return beam_search_run(w, b, bt->drop_xt, bt->drop_out, bt->h_drop, stream);
+}
+
+int capmi_beam_finalize(const int32_t *parent, const int64_t *token, const float *score, const uint8_t *ended,
+                        const double *len_div, int B, int bd, int L, int sample_n, int64_t *seq, int32_t *lineage,
+                        int32_t *length, float *p, void *stream) {
+    if (!parent || !token || !score || !ended || !seq || !lineage || !length || !p) return CAPMI_EINVAL;
+    if (B <= 0 || bd <= 0 || bd > BD_MAX || L <= 0 || (long long)L * bd > FIN_MAX || sample_n <= 0 || sample_n > bd)
+        return CAPMI_EINVAL;
+    hipLaunchKernelGGL(beam_finalize_kernel, dim3(B), dim3(FIN_T), 0, (hipStream_t)stream, parent, token, score, ended, len_div,
+                       B, bd, L, sample_n, seq, lineage, length, p);
+    CAPMI_CHECK_LAUNCH();
+    return 0;
+}
+
+int capmi_lineage_gather(const int32_t *lineage, int L, int rows_src, int rows_dst, const float *src_a, float *dst_a, int C_a,
+                         const float *src_b, float *dst_b, int C_b, void *stream) {
+    if (!lineage || L <= 0 || rows_src <= 0 || rows_dst <= 0 || (!src_a && !src_b)) return CAPMI_EINVAL;
+    if ((src_a && (!dst_a || C_a <= 0 || C_a % 4)) || (src_b && (!dst_b || C_b <= 0 || C_b % 4)) ||
+        !aligned16(src_a, dst_a, src_b, dst_b))
+        return CAPMI_EINVAL;
+    const size_t work = (size_t)L * rows_dst * ((src_a ? C_a / 4 : 0) + (src_b ? C_b / 4 : 0));
+    hipLaunchKernelGGL(lineage_gather_kernel, dim3(grid_for(work)), dim3(256), 0, (hipStream_t)stream, lineage, L, rows_src,
+                       rows_dst, (const float4 *)src_a, (float4 *)dst_a, C_a / 4, (const float4 *)src_b, (float4 *)dst_b, C_b / 4);
+    CAPMI_CHECK_LAUNCH();
     return 0;
 }
 

@@ -145,6 +145,8 @@ class TrainStep:
         graphable = self.graph and not force_stepped and self.failed is None and not drop_worst_flag and getattr(self.model, 'ss_prob', 0.0) == 0.0 \
             and self.flat.on_grads_ready is None \
             and not (struc_flag and getattr(o, 'use_ppo', 0))    # the old model's teacher-forced forward picks its length on the host
+        if (sc_flag or struc_flag) and getattr(o, 'train_beam_size', 1) > 1:
+            graphable = False                                     # beam-search SCST runs launch by launch
         ent = None
         if graphable:
             sig = self._signature(data, sc_flag, struc_flag)

@@ -83,9 +83,12 @@ class NewFCStepper:
     """AttModel.py:925-936: the first call feeds the image (state all zero), then words.  The image step is taken in the
     constructor so that step(0, BOS) is the first WORD step like for every other family."""
 
-    def __init__(self, P, fc_feats, rows_per_image_max):
+    def __init__(self, P, fc_feats, rows_per_image_max, drop_out=None):
+        # drop_out [steps, B*rows_per_image_max, R] (train-mode beam search): step t multiplies the LSTMCore output of row r
+        # by drop_out[t, r] before the logit (FCModel.py:40); the image step's output is discarded, so it has no mask
         dev = fc_feats.device
         self.P = P
+        self.drop_out = drop_out
         self.B = B = fc_feats.shape[0]
         self.V1, self.E = P['embed.weight'].shape
         self.R = R = P['_core.h2h.weight'].shape[1]
@@ -96,17 +99,18 @@ class NewFCStepper:
         self.cur = 0
         self.saved = torch.empty(N, 5 * R, dtype=_f32, device=dev)
         self.logits = torch.empty(N, self.V1, dtype=_f32, device=dev)
+        self.h_drop = None if drop_out is None else torch.empty(N, R, dtype=_f32, device=dev)
         fc_emb = ops.linear(fc_feats.float().contiguous(), P['fc_embed.weight'], P['fc_embed.bias'], ws=self.ws)
         self._cell(fc_emb, B)                                           # one row per image, cur = 1 afterwards
 
-    def _cell(self, x, rows):
+    def _cell(self, x, rows, out_mask=None):
         P, R, E = self.P, self.R, self.E
         src, dst = self.state[self.cur], self.state[1 - self.cur]
         splits = ops.gemm([(x, E, P['_core.i2h.weight'], E, E, 1), (src[0, :rows], R, P['_core.h2h.weight'], R, R, 1)], rows,
                           5 * R, self.ws.buf, ws=self.ws, defer_reduce=True)
         check(lib.capmi_maxout_cell_fwd(self.ws.slabs.data_ptr(), splits, ptr(P['_core.i2h.bias']), ptr(P['_core.h2h.bias']),
-                                        ptr(src[1]), ptr(dst[0]), ptr(dst[1]), ptr(self.saved), None, None, rows, R,
-                                        stream_ptr()), 'capmi_maxout_cell_fwd')
+                                        ptr(src[1]), ptr(dst[0]), ptr(dst[1]), ptr(self.saved), ptr(out_mask),
+                                        None if out_mask is None else ptr(self.h_drop), rows, R, stream_ptr()), 'capmi_maxout_cell_fwd')
         self.cur = 1 - self.cur
         self._keep = x
 
@@ -119,8 +123,9 @@ class NewFCStepper:
             s = self.state[self.cur]
             s[:, :rows] = s[:, :self.B][:, idx]
         x = ops.embed_fwd(it, self.P['embed.weight'], relu=False)      # plain Embedding (AttModel.py:908)
-        self._cell(x, rows)
-        h = self.state[self.cur][0, :rows]
+        mask = None if self.drop_out is None else self.drop_out[t, :rows]
+        self._cell(x, rows, mask)
+        h = self.state[self.cur][0, :rows] if mask is None else self.h_drop[:rows]
         logits = self.logits[:rows]
         ops.gemm([(h, self.R, self.P['logit.weight'], self.R, self.R, 1)], rows, self.V1, logits, bias=self.P['logit.bias'],
                  ws=self.ws)

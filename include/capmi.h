@@ -757,6 +757,43 @@ int capmi_updown_decode_step(const capmi_updown_weights *w, capmi_updown_beam *b
                              const float *state_in, float *state_out, int first, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Beam search as a TRAINING rollout ("SCST in Topdown Bottomup paper", reference ADVANCED.md; loss_wrapper.py with
+ * train_sample_method greedy / train_beam_size > 1): search with the model's training numerics, finalise on the device, replay
+ * the surviving beams through the forced rollout (capmi_updown_rollout_fwd / capmi_newfc_rollout_fwd) with the dropout masks
+ * their ancestors saw.  A beam's log-probs are the decoder run along its own ancestry, so the replay's BPTT is the search's.
+ * ------------------------------------------------------------------------------------------- */
+/* capmi_updown_beam_search in train mode: `fc/att/p_att` of `b` are the DROPPED prepared features; the decoder call that
+ * produces logp_rows[t] multiplies the word embedding of search row r by drop_xt[t][r][:] and the language LSTM output by
+ * drop_out[t][r][:] (pre-scaled keep masks, [L][B*bd][E] and [L][B*bd][R]; call 0 runs on rows 0..B-1, one per image).
+ * h_drop: [B*bd,R] scratch.  Either mask may be NULL (no dropout there). */
+typedef struct capmi_updown_beam_train {
+    capmi_updown_beam b;
+    const float *drop_xt;
+    const float *drop_out;
+    float *h_drop;
+} capmi_updown_beam_train;
+
+int capmi_updown_beam_search_train(const capmi_updown_weights *w, capmi_updown_beam_train *bt, void *stream);
+
+/* CaptionModel.py:183-208 on the device: from the [L][B,bd] tables of a finished search to the returned beams.  Per image
+ * the candidates are the (t, j) with ended[t,b,j], in order of t then j; key p = (double)score / len_div[t] (len_div [L]
+ * doubles on the device: the length penalty's divisor for a beam of t + 1 words, tabulated by the host so that the keys order
+ * exactly as its own arithmetic does; NULL: p = score); stable descending sort; the best sample_n (1 <= sample_n <= bd) are
+ * written to rows b*sample_n + i:
+ *   seq [B*sample_n, L] int64 zero padded, length [B*sample_n] int32, p [B*sample_n] float,
+ *   lineage [L][B*sample_n] int32: the search row (of logp_rows[t]) the beam's ancestor occupied at step t -- b at step 0
+ *   (one row per image), b*bd + parent afterwards; -1 at and behind the beam's end.
+ * One workgroup per image; L*bd <= 1024, bd <= 16.  The last step of a search ends every beam, so bd candidates always exist. */
+int capmi_beam_finalize(const int32_t *parent, const int64_t *token, const float *score, const uint8_t *ended,
+                        const double *len_div, int B, int bd, int L, int sample_n, int64_t *seq, int32_t *lineage,
+                        int32_t *length, float *p, void *stream);
+
+/* dst[t][i][:] = src[t][max(lineage[t][i], 0)][:] for up to two mask arrays in one launch (16-byte moves; C_a, C_b % 4 == 0,
+ * 16-byte aligned; either pair may be NULL).  src [L][rows_src][C], dst [L][rows_dst][C], lineage [L][rows_dst]. */
+int capmi_lineage_gather(const int32_t *lineage, int L, int rows_src, int rows_dst, const float *src_a, float *dst_a, int C_a,
+                         const float *src_b, float *dst_b, int C_b, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Decode-time options (eval): the reference edits the [rows,V1] log-probabilities of a step on the host side
  * (AttModel.py:293-330, 391-432; CaptionModel.py:38-57, 152-157).  Here they are in-place device edits.
  * ------------------------------------------------------------------------------------------- */
