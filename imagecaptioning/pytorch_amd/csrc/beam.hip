@@ -273,23 +273,25 @@ __global__ __launch_bounds__(FIN_T) void beam_finalize_kernel(const int32_t *__r
 }
 
 // the replay's keep masks: row i of step t takes the mask of the search row its ancestor occupied (both masks of a step in one
-// launch, float4 moves)
+// launch).  V = float4: 16-byte moves, widths in units of 4 floats; V = float: the scalar route for widths that are no multiple
+// of 4 or pointers off a 16-byte boundary (what pointwise.hip / attention.hip / gemm_f32.hip do at such sizes)
+template <typename V>
 __global__ void lineage_gather_kernel(const int32_t *__restrict__ lineage, int L, int rows_src, int rows_dst,
-                                      const float4 *__restrict__ src_a, float4 *__restrict__ dst_a, int C4a,
-                                      const float4 *__restrict__ src_b, float4 *__restrict__ dst_b, int C4b) {
-    const size_t na = src_a ? (size_t)L * rows_dst * C4a : 0, nb = src_b ? (size_t)L * rows_dst * C4b : 0;
+                                      const V *__restrict__ src_a, V *__restrict__ dst_a, int Ca,
+                                      const V *__restrict__ src_b, V *__restrict__ dst_b, int Cb) {
+    const size_t na = src_a ? (size_t)L * rows_dst * Ca : 0, nb = src_b ? (size_t)L * rows_dst * Cb : 0;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < na + nb; i += (size_t)gridDim.x * blockDim.x) {
         const bool second = i >= na;
         const size_t k = second ? i - na : i;
-        const int C4 = second ? C4b : C4a;
-        const size_t tr = k / C4;
-        const int c = (int)(k - tr * C4);
+        const int Cw = second ? Cb : Ca;
+        const size_t tr = k / Cw;
+        const int c = (int)(k - tr * Cw);
         const int t = (int)(tr / rows_dst);
         int r = lineage[tr];
         r = r < 0 ? 0 : (r >= rows_src ? rows_src - 1 : r);
-        const float4 *src = second ? src_b : src_a;
-        float4 *dst = second ? dst_b : dst_a;
-        dst[k] = src[((size_t)t * rows_src + r) * C4 + c];
+        const V *src = second ? src_b : src_a;
+        V *dst = second ? dst_b : dst_a;
+        dst[k] = src[((size_t)t * rows_src + r) * Cw + c];
     }
 }
 
@@ -372,12 +374,19 @@ int capmi_beam_finalize(const int32_t *parent, const int64_t *token, const float
 int capmi_lineage_gather(const int32_t *lineage, int L, int rows_src, int rows_dst, const float *src_a, float *dst_a, int C_a,
                          const float *src_b, float *dst_b, int C_b, void *stream) {
     if (!lineage || L <= 0 || rows_src <= 0 || rows_dst <= 0 || (!src_a && !src_b)) return CAPMI_EINVAL;
-    if ((src_a && (!dst_a || C_a <= 0 || C_a % 4)) || (src_b && (!dst_b || C_b <= 0 || C_b % 4)) ||
-        !aligned16(src_a, dst_a, src_b, dst_b))
-        return CAPMI_EINVAL;
-    const size_t work = (size_t)L * rows_dst * ((src_a ? C_a / 4 : 0) + (src_b ? C_b / 4 : 0));
-    hipLaunchKernelGGL(lineage_gather_kernel, dim3(grid_for(work)), dim3(256), 0, (hipStream_t)stream, lineage, L, rows_src,
-                       rows_dst, (const float4 *)src_a, (float4 *)dst_a, C_a / 4, (const float4 *)src_b, (float4 *)dst_b, C_b / 4);
+    if ((src_a && (!dst_a || C_a <= 0)) || (src_b && (!dst_b || C_b <= 0))) return CAPMI_EINVAL;
+    if (!src_a) C_a = 0;
+    if (!src_b) C_b = 0;
+    if (C_a % 4 == 0 && C_b % 4 == 0 && aligned16(src_a, dst_a, src_b, dst_b)) {
+        const size_t work = (size_t)L * rows_dst * (C_a / 4 + C_b / 4);
+        hipLaunchKernelGGL(lineage_gather_kernel<float4>, dim3(grid_for(work)), dim3(256), 0, (hipStream_t)stream, lineage, L,
+                           rows_src, rows_dst, (const float4 *)src_a, (float4 *)dst_a, C_a / 4, (const float4 *)src_b,
+                           (float4 *)dst_b, C_b / 4);
+    } else {
+        const size_t work = (size_t)L * rows_dst * ((size_t)C_a + C_b);
+        hipLaunchKernelGGL(lineage_gather_kernel<float>, dim3(grid_for(work)), dim3(256), 0, (hipStream_t)stream, lineage, L,
+                           rows_src, rows_dst, src_a, dst_a, C_a, src_b, dst_b, C_b);
+    }
     CAPMI_CHECK_LAUNCH();
     return 0;
 }

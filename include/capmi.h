@@ -788,8 +788,9 @@ int capmi_beam_finalize(const int32_t *parent, const int64_t *token, const float
                         const double *len_div, int B, int bd, int L, int sample_n, int64_t *seq, int32_t *lineage,
                         int32_t *length, float *p, void *stream);
 
-/* dst[t][i][:] = src[t][max(lineage[t][i], 0)][:] for up to two mask arrays in one launch (16-byte moves; C_a, C_b % 4 == 0,
- * 16-byte aligned; either pair may be NULL).  src [L][rows_src][C], dst [L][rows_dst][C], lineage [L][rows_dst]. */
+/* dst[t][i][:] = src[t][clamp(lineage[t][i], 0, rows_src - 1)][:] for up to two mask arrays in one launch (16-byte moves when
+ * C_a, C_b % 4 == 0 and every pointer is 16-byte aligned, scalar moves otherwise; either pair may be NULL).
+ * src [L][rows_src][C], dst [L][rows_dst][C], lineage [L][rows_dst]. */
 int capmi_lineage_gather(const int32_t *lineage, int L, int rows_src, int rows_dst, const float *src_a, float *dst_a, int C_a,
                          const float *src_b, float *dst_b, int C_b, void *stream);
 

@@ -164,19 +164,43 @@ def replay(family, P, fc_feats, att_feats, att_masks, seq, lineage, sample_n, ma
     return torch.stack(out, 1)
 
 
+def replay_loss_grads(family, P, fc_feats, att_feats, att_masks, seq, lineage, sample_n, masks, reward, dtype=D):
+    """The forced replay, its RewardCriterion loss and every parameter gradient in `dtype`: float64 is the yardstick; float32 is
+    the SAME restatement at the kernels' precision -- its distance from the float64 run is what fp32 arithmetic alone costs a
+    gradient, the measure a config-size test falls back on where 1e-3 is too tight.  Returns (logp, loss, grads)."""
+    global D
+    keep, D = D, dtype
+    try:
+        Pg = {k: torch.as_tensor(v).to(D).clone().requires_grad_(True) for k, v in P.items()}
+        logp = replay(family, Pg, fc_feats, att_feats, att_masks, seq, lineage, sample_n, masks)
+        loss = O.reward_criterion(logp, torch.as_tensor(seq), torch.as_tensor(reward).to(D))
+        loss.backward()
+        grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)).detach() for k, v in Pg.items()}
+        return logp.detach(), float(loss.detach()), grads
+    finally:
+        D = keep
+
+
 def run(family, P, fc_feats, att_feats, att_masks, bd, sample_n, L, length_penalty='', masks=None, reward=None):
     """search -> finalize -> replay; with `reward` [rows, L] also the RewardCriterion loss and every parameter gradient."""
     s = search(family, P, fc_feats, att_feats, att_masks, bd, L, masks)
     seq, lineage, length, p, p_gap = finalize(s['parent'], s['token'], s['score'], s['ended'], sample_n, length_penalty)
-    Pg = {k: torch.as_tensor(v).to(D).clone().requires_grad_(True) for k, v in P.items()}
-    logp = replay(family, Pg, fc_feats, att_feats, att_masks, seq, lineage, sample_n, masks)
-    res = dict(s, seq=seq, lineage=lineage, length=length, p=p, p_gap=p_gap, logp=logp.detach())
+    res = dict(s, seq=seq, lineage=lineage, length=length, p=p, p_gap=p_gap)
     if reward is not None:
-        loss = O.reward_criterion(logp, torch.as_tensor(seq), torch.as_tensor(reward).to(D))
-        loss.backward()
-        res['loss'] = float(loss.detach())
-        res['grads'] = {k: (v.grad if v.grad is not None else torch.zeros_like(v)).detach() for k, v in Pg.items()}
+        res['logp'], res['loss'], res['grads'] = replay_loss_grads(family, P, fc_feats, att_feats, att_masks, seq, lineage, sample_n,
+                                                                   masks, reward)
+    else:
+        with torch.no_grad():
+            res['logp'] = replay(family, _p64(P), fc_feats, att_feats, att_masks, seq, lineage, sample_n, masks)
     return res
+
+
+def mask_dict(family, drops):
+    """oracle.att_lstm.make_drops(p, B, K, B*bd, L, E, R, g) -> the masks by search row as this module and opt['_beam_masks'] take
+    them (NewFC drops the LSTM output only)."""
+    if family == 'updown':
+        return dict(drop_fc=drops.fc, drop_att=drops.att, drop_xt=drops.xt, drop_out=drops.out)
+    return dict(drop_out=drops.out)
 
 
 # ------------------------------------------------------------------------------------------------------ fixture plumbing

@@ -199,3 +199,18 @@ def mid_state(name, state_shapes, seed, w00=None, b0=None, rate=None):
     st[lw][0, clock] = w00 * BEAM5_LOGIT_SCALE
     st[lb][0] = b0
     return st
+
+
+# ---- the training beam search at config size (tests/test_beam_train_full_gpu.py).  (weights / features seed, keep-mask seed),
+# picked on the CPU with tests/beam_train_ref64.py alone so that the smallest kept / dropped candidate gap and the smallest
+# finalise-key gap of the float64 run are >= 1e-4 (measured: gap / key gap / lengths of the returned beams)
+BEAM_TRAIN_NEWFC_EOS_BIAS = 4.5
+BEAM_TRAIN_ODD_LOGIT_SCALE, BEAM_TRAIN_ODD_EOS_BIAS = 30.0, 0.5
+BEAM_TRAIN_SEED = {'mid': (47, 605),               # 1.4e-3 / 1.2e-2 / {5,6,7,8,9}; smallest score -123
+                   'mid_wu': (48, 601),            # 4.8e-3 / 1.1e-2 / {5,6,7,8,9,11}; smallest score -137
+                   'sharp_n1': (43, 604),          # 1.4e-3 / 1.7e-2 / {1,20} over the five beams of an image
+                   'rows80': (48, 548),            # 4.8e-3 / 3.9e-3 / {5,6,7,8}
+                   'newfc_n5': (63, 563),          # 3.8e-4 / 5.2e-3 / {2..9, 12..20}
+                   'newfc_n1': (63, 563),          # 3.8e-4 / 5.2e-3 / {2,3,4,6,8,13,20}
+                   'odd_updown': (73, 573),        # 3.8e-3 / 4.0e-2 / {1,4,5,7}
+                   'odd_newfc': (77, 577)}         # 3.2e-3 / 2.7e-2 / {1,2,5,7}

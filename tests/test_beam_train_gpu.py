@@ -178,47 +178,55 @@ def test_without_dropout_the_new_path_equals_the_eval_mode_beam_search_config_si
 
 
 # ------------------------------------------------------------------------------------------------------- Philox masks
-@pytest.mark.parametrize('family', ['updown', 'newfc'])
-def test_philox_masks_are_shared_by_search_and_replay(family):
+def philox_search_and_replay_agree(model, fc, att, am, bd, tol):
     """Two calls at the same _rng_calls position agree bit for bit, and the replayed log-prob of every beam token equals the
-    search's own score difference along the beam's lineage: search and replay saw the same masks."""
-    zz, P, model = golden_model(family, 0.5)
-    fc, att, am = inputs(zz)
+    search's own score difference along the beam's lineage (within `tol`): search and replay saw the same masks.  Inputs on the
+    device; shared with the config-size test (tests/test_beam_train_full_gpu.py)."""
     model.train()
     outs = []
     for _ in range(2):
         torch.manual_seed(9)
         model._rng_calls = 0
-        seq, slp = model(d(fc), d(att), d(am), opt=dict(sample_method='greedy', beam_size=BEAM, sample_n=BEAM), mode='sample')
+        seq, slp = model(fc, att, am, opt=dict(sample_method='greedy', beam_size=bd, sample_n=bd), mode='sample')
         outs.append((seq.clone(), slp.detach().clone(), {k: v.clone() for k, v in model._last_beam.items()}))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     seq, slp, t = outs[0]
     sel = slp.gather(2, seq.unsqueeze(2)).squeeze(2).cpu().double()                 # [rows, L]
+    seq = seq.cpu()
     score, lineage, length = t['score'].cpu().double(), t['lineage'].cpu().long(), t['length'].cpu()
     B = fc.shape[0]
     checked = 0
     # the beam's own slot after the selection of step t: the row its successor came from (lineage[t + 1] - b * bd); the last
     # step's slot is found by the token / parent match below
     parent, token = t['parent'].cpu(), t['token'].cpu()
-    for row in range(B * BEAM):
-        b, n = row // BEAM, int(length[row])
+    for row in range(B * bd):
+        b, n = row // bd, int(length[row])
         prev = 0.0
         for s in range(n):
             if s + 1 < n:
-                slot = int(lineage[s + 1, row]) - b * BEAM
+                slot = int(lineage[s + 1, row]) - b * bd
             else:
-                src = 0 if s == 0 else int(lineage[s, row]) - b * BEAM
-                cand = [j for j in range(BEAM) if int(token[s, b, j]) == int(seq[row, s]) and int(parent[s, b, j]) == src]
+                src = 0 if s == 0 else int(lineage[s, row]) - b * bd
+                cand = [j for j in range(bd) if int(token[s, b, j]) == int(seq[row, s]) and int(parent[s, b, j]) == src]
                 assert len(cand) == 1
                 slot = cand[0]
             sc = float(score[s, b, slot])
-            np.testing.assert_allclose(float(sel[row, s]), sc - prev, rtol=2e-5, atol=2e-5)
+            np.testing.assert_allclose(float(sel[row, s]), sc - prev, **tol)
             prev = sc
             checked += 1
-    assert checked > B * BEAM
+    assert checked > B * bd
     # a different stream position gives different masks
-    seq2, slp2 = model(d(fc), d(att), d(am), opt=dict(sample_method='greedy', beam_size=BEAM, sample_n=BEAM), mode='sample')
+    seq2, slp2 = model(fc, att, am, opt=dict(sample_method='greedy', beam_size=bd, sample_n=bd), mode='sample')
     assert not torch.equal(slp2.detach(), slp)
+
+
+@pytest.mark.parametrize('family', ['updown', 'newfc'])
+def test_philox_masks_are_shared_by_search_and_replay(family):
+    """Two calls at the same _rng_calls position agree bit for bit, and the replayed log-prob of every beam token equals the
+    search's own score difference along the beam's lineage: search and replay saw the same masks."""
+    zz, P, model = golden_model(family, 0.5)
+    fc, att, am = inputs(zz)
+    philox_search_and_replay_agree(model, d(fc), d(att), d(am), BEAM, dict(rtol=2e-5, atol=2e-5))
 
 
 # ------------------------------------------------------------------------------------------------- LossWrapper / train
