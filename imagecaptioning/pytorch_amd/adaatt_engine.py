@@ -6,12 +6,11 @@
   Rollout.backward()   the BPTT torch would have recorded for them
   prepare_backward()   v2h / r_v2h / gate-bias / fc_embed / att_embed / ctx2att gradients
 """
-import ctypes as C
-
 import torch
 
 from . import _lib, ops, updown_engine
-from ._lib import lib, ptr, check, stream_ptr
+from ._lib import ptr
+from .engine_common import RolloutBase, fill_struct
 
 _f32 = torch.float32
 _L, _A = 'core.lstm.', 'core.attention.'
@@ -42,12 +41,7 @@ def packed(P):
 
 
 def weights_struct(P, packs=None):
-    w = _lib.AdaAttWeights()
-    for f, k in _W:
-        t = P[k]
-        if not (t.is_cuda and t.is_contiguous() and t.dtype == _f32):
-            raise _lib.CapmiError('parameter %s must be a contiguous fp32 device tensor' % k)
-        setattr(w, f, t.data_ptr())
+    w = fill_struct(_lib.AdaAttWeights(), _W, P)
     xw, hw, _, _ = packs or packed(P)
     w.xw, w.hw = xw.data_ptr(), hw.data_ptr()
     w._keep = (xw, hw)
@@ -91,49 +85,30 @@ def prepare_backward(P, ap, d_fc_gates, gate_b, d_att, d_p_att, grads, ws=None):
     return dvw, d_fc
 
 
-class Rollout:
+class Rollout(RolloutBase):
     """Device buffers + one native call for a T-step rollout of N = B*n caption rows."""
 
+    SCRATCH, GRADS, G_FIELDS = _lib.AdaAttBwdScratch, _lib.AdaAttGrads, _G
+    FWD, BWD = 'capmi_adaatt_rollout_fwd', 'capmi_adaatt_rollout_bwd'
     DROPS = ('drop_xt', 'drop_h', 'drop_fake', 'drop_fr', 'drop_ho', 'drop_out', 'drop_tile')
 
     def __init__(self, P, ap, n, T, L=None, mode='greedy', temperature=1.0, gumbel=None, seed=0, forced=None, teacher=False,
                  ss_mode=None, raw=False, tile_p=0.0, tile_seed=0, ws=None, **drops):
         """drops: keep masks by capmi_adaatt_rollout field name (drop_xt [T,N,E] ... drop_tile [T,N,K+1,A]); without drop_tile,
         tile_p > 0 draws the tanh-tile mask inside the kernels from (tile_seed, step, row, score row, column).
-        ss_mode / raw: as att2in2_engine.Rollout."""
+        ss_mode, raw: RolloutBase._bind."""
         dev = ap.att.device
         B, K, R = ap.att.shape
         A = ap.p_att.shape[2]
         V1, E = P['embed.0.weight'].shape
         W = P[_L + 'w2h.weight'].shape[0] + R
-        maxout = int(W == 6 * R)
         N = B * n
         L = T if L is None else L
         assert set(drops) <= set(self.DROPS), sorted(drops)
-        self.P, self.ap, self.dims = P, ap, (B, n, N, K, A, R, E, V1, T, L, W)
-        self.ws = ws or ops.default_workspace(dev)
+        self.P, self.ap, self.dims, self.drops = P, ap, (B, n, N, K, A, R, E, V1, T, L, W), drops
         z = lambda *s: torch.empty(*s, dtype=_f32, device=dev)          # noqa: E731
-        self.h, self.c = z(T + 1, N, R), z(T + 1, N, R)
-        self.x, self.saved = z(T, N, E), z(T, N, W)
-        self.h_drop, self.fake_drop, self.ctx, self.out_t, self.out_drop = (z(T, N, R) for _ in range(5))
-        self.fr, self.ho_t, self.ho = z(T, N, E), z(T, N, E), z(T, N, E)
-        self.fr_e, self.ho_e, self.pi = z(T, N, A), z(T, N, A), z(T, N, K + 1)
-        self.xin = z(T, N, W) if (teacher and ss_mode is None) else None
-        self.it_all = torch.empty(T, N, dtype=torch.long, device=dev)
-        zl = torch.empty if T == L else torch.zeros      # the select writes every (row, step < T) slot
-        self.seq = zl(N, L, dtype=torch.long, device=dev)
-        self.seq_logp = zl(N, L, V1, dtype=_f32, device=dev)
-        self.sel_logp = zl(N, L, dtype=_f32, device=dev)
-        self.live = zl(N, L, dtype=torch.uint8, device=dev)
-        self.it = torch.empty(N, dtype=torch.long, device=dev)
-        self.unfinished = torch.empty(N, dtype=torch.uint8, device=dev)
-        self.gumbel, self.forced, self.ss_mode, self.drops = gumbel, forced, ss_mode, drops
-        if ss_mode is not None:
-            assert teacher and ss_mode.dtype == torch.uint8 and ss_mode.shape == (T, N) and ss_mode.is_contiguous()
-        if forced is not None:
-            assert forced.dtype == torch.long and forced.is_contiguous()
         r = _lib.AdaAttRollout()
-        r.B, r.n, r.N, r.K, r.A, r.R, r.E, r.V1, r.T, r.L, r.maxout = B, n, N, K, A, R, E, V1, T, L, maxout
+        r.B, r.n, r.N, r.K, r.A, r.R, r.E, r.V1, r.T, r.L, r.maxout = B, n, N, K, A, R, E, V1, T, L, int(W == 6 * R)
         r.fc_gates, r.att, r.p_att, r.att_mask = ptr(ap.fc_gates), ptr(ap.att), ptr(ap.p_att), ptr(ap.att_masks)
         shapes = dict(drop_xt=(T, N, E), drop_h=(T, N, R), drop_fake=(T, N, R), drop_fr=(T, N, E), drop_ho=(T, N, E),
                       drop_out=(T, N, R), drop_tile=(T, N, K + 1, A))
@@ -142,43 +117,21 @@ class Rollout:
                 assert m.shape == shapes[k] and m.is_contiguous() and m.dtype == _f32, (k, tuple(m.shape), shapes[k])
             setattr(r, k, ptr(m))
         r.tile_p, r.tile_seed = (0.0 if drops.get('drop_tile') is not None else float(tile_p)), int(tile_seed) & 0xFFFFFFFFFFFFFFFF
-        r.mode = {'greedy': 0, 'sample': 1, 'forced': 2}[mode] | (_lib.SELECT_RAW if (raw and not teacher) else 0)
-        r.temperature, r.gumbel, r.seed = float(temperature), ptr(gumbel), int(seed) & 0xFFFFFFFFFFFFFFFF
-        if forced is not None:
-            r.forced, r.forced_ld = ptr(forced), forced.shape[1]
-        r.teacher, r.ss_mode = int(teacher), ptr(ss_mode)
-        for k in ('h', 'c', 'x', 'it_all', 'xin', 'saved', 'h_drop', 'fake_drop', 'fr', 'ho_t', 'ho', 'fr_e', 'ho_e', 'pi', 'ctx',
-                  'out_t', 'out_drop', 'seq', 'seq_logp', 'sel_logp', 'live', 'it', 'unfinished'):
-            setattr(r, k, ptr(getattr(self, k)))
-        r.partial, r.partial_capacity = self.ws.buf.data_ptr(), self.ws.capacity
-        self.r, self.w = r, weights_struct(P, ap.packs)
-
-    def run(self):
-        check(lib.capmi_adaatt_rollout_fwd(C.byref(self.w), C.byref(self.r), stream_ptr()), 'capmi_adaatt_rollout_fwd')
-        return self.seq, self.seq_logp
+        acts = dict(h=z(T + 1, N, R), c=z(T + 1, N, R), x=z(T, N, E), saved=z(T, N, W), h_drop=z(T, N, R), fake_drop=z(T, N, R),
+                    ctx=z(T, N, R), out_t=z(T, N, R), out_drop=z(T, N, R), fr=z(T, N, E), ho_t=z(T, N, E), ho=z(T, N, E),
+                    fr_e=z(T, N, A), ho_e=z(T, N, A), pi=z(T, N, K + 1), xin=z(T, N, W) if (teacher and ss_mode is None) else None)
+        self._bind(r, acts, dev, N, T, L, V1, mode, temperature, gumbel, seed, forced, teacher, ss_mode, raw, ws)
+        self.w = weights_struct(P, ap.packs)
 
     def backward(self, g_seq_logp, grads, sparse=None):
-        """g_seq_logp [N,L,V1] (None when `sparse` carries the loss gradient); grads: name -> preallocated fp32 tensor (overwritten)
-        for every parameter, the prefill's included."""
+        """g_seq_logp, grads, sparse: RolloutBase._bwd_structs; grads includes the prefill's parameters."""
         B, n, N, K, A, R, E, V1, T, L, W = self.dims
         dev = self.seq.device
         z = lambda *s: torch.empty(*s, dtype=_f32, device=dev)          # noqa: E731
         keep = dict(dlogits=z(T, N, V1), d_out=z(T, N, R), d_ctx=z(T, N, R), d_e=z(T, N, K + 1), d_hoe=z(T, N, A), d_fre=z(T, N, A),
                     d_fr=z(T, N, E), d_ho=z(T, N, E), d_hdrop=z(T, N, R), d_fakedrop=z(T, N, R), d_sums=z(T, N, W), dc=z(2, N, R),
                     d_x=z(T, N, E))
-        s = _lib.AdaAttBwdScratch()
-        for k, t in keep.items():
-            setattr(s, k, t.data_ptr())
-        s.partial, s.partial_capacity = self.ws.buf.data_ptr(), self.ws.capacity
-        if sparse is not None:
-            s.sparse = C.pointer(sparse)
-        g = _lib.AdaAttGrads()
-        for f, k in _G:
-            setattr(g, f, grads[k].data_ptr())
-        gate_b, d_fc_gates, d_att, d_p_att = z(W), z(B, W), z(B, K, R), z(B, K, A)
-        g.gate_b, g.d_fc_gates, g.d_att, g.d_p_att = gate_b.data_ptr(), d_fc_gates.data_ptr(), d_att.data_ptr(), d_p_att.data_ptr()
-        g_seq_logp = None if g_seq_logp is None else g_seq_logp.contiguous()
-        check(lib.capmi_adaatt_rollout_bwd(C.byref(self.w), C.byref(self.r), ptr(g_seq_logp), C.byref(s), C.byref(g),
-                                           stream_ptr()), 'capmi_adaatt_rollout_bwd')
-        kp = prepare_backward(self.P, self.ap, d_fc_gates, gate_b, d_att, d_p_att, grads, ws=self.ws)
-        self._keep = (keep, gate_b, d_fc_gates, d_att, d_p_att, g_seq_logp, kp)     # scratch alive until the stream has consumed it
+        o = dict(gate_b=z(W), d_fc_gates=z(B, W), d_att=z(B, K, R), d_p_att=z(B, K, A))
+        kept = self._bwd(keep, o, grads, g_seq_logp, sparse)
+        kp = prepare_backward(self.P, self.ap, o['d_fc_gates'], o['gate_b'], o['d_att'], o['d_p_att'], grads, ws=self.ws)
+        self._keep = (kept, kp)     # scratch alive until the stream has consumed it

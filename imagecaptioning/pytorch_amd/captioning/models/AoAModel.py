@@ -109,27 +109,12 @@ class AoAModel(CaptionModel):
         self.ctx2att = nn.Linear(R, 2 * R)
         self.refiner = _Refiner(R)
         self.core = _Core(opt)
-        self._flat = None
-        self._rng_calls = 0
-
-    @property
-    def _param_names(self):
-        return self._param_name_list()
 
     def _flat_groups(self):
         """Wq | Wk | Wv (and biases) of every refiner layer back to back in the flat buffers: one fused projection GEMM each"""
         names = [n for n, _ in self.named_parameters()]
         blocks = sorted({n[:n.index('.self_attn.') + len('.self_attn')] for n in names if n.startswith('refiner.') and '.self_attn.linears.' in n})
         return [['%s.linears.%d.%s' % (b, i, kind) for i in range(3)] for b in blocks for kind in ('weight', 'bias')]
-
-    def flatten_parameters_(self):
-        from imagecaptioning.pytorch_amd.flat import FlatParams
-        self._flat = FlatParams(self)
-        return self._flat
-
-    def _next_seed(self):
-        self._rng_calls += 1
-        return (torch.initial_seed() * 0x9E3779B97F4A7C15 + self._rng_calls * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
 
     def _run(self, cfg, att_feats, att_masks, clipped=False):
         if not att_feats.is_cuda:

@@ -62,6 +62,32 @@ class CaptionModel(nn.Module):
             self.__dict__.pop('_pcache', None)
         super().__setattr__(name, value)
 
+    # ---- what every family's autograd.Function and trainer ask of the model
+    _flat = None            # the FlatParams of flatten_parameters_()
+    _rng_calls = 0
+
+    @property
+    def _param_names(self):
+        return self._param_name_list()
+
+    def _params(self):
+        return {k: v.detach() for k, v in self._named_param_list()}
+
+    def flatten_parameters_(self):
+        """Move all parameters into one flat buffer (+ flat grads, Adam state).  Call after .cuda()."""
+        from imagecaptioning.pytorch_amd.flat import FlatParams
+        self._flat = FlatParams(self)
+        return self._flat
+
+    def _grad_targets(self, P):
+        if self._flat is not None:
+            return self._flat.grad_views
+        return {k: torch.empty_like(v) for k, v in P.items()}
+
+    def _next_seed(self):
+        self._rng_calls += 1
+        return (torch.initial_seed() * 0x9E3779B97F4A7C15 + self._rng_calls * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
+
     @property
     def bad_endings_ix(self):
         """AttModel.py:96-97 (every family derives from AttModel there); assignable for tests."""

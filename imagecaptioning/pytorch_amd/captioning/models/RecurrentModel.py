@@ -1,0 +1,190 @@
+"""RecurrentModel: the host side the LSTM families (UpDown, NewFC, Att2in2, AdaAtt) share -- one autograd.Function around a
+family's one-call rollout, the teacher-forced _forward and the free-running _sample -- and StepAPI, the reference's single-step
+API (init_hidden, get_logprobs_state) for the attention families: NewFC has neither, and callers probe for them with hasattr.
+
+A family holds its parameters (nn.Module tree with the reference's names) and states, by overriding:
+
+    _feeds(fc_feats, att_feats, att_masks)    which of the three its rollout reads, as a tuple (default: all)
+    _make_rollout(P, cfg, *feeds)             cfg -> (engine Rollout, whatever its _rollout_backward wants back)
+    _dropout_masks(B, K, N, T, dev)           the keep masks of its dropout sites as Rollout keywords ({} in eval mode)
+    _rollout_masks(B, N, T, att_feats, att_masks, dev)
+                                              only a family without region features (NewFC): the default derives K from them
+                                              and calls _dropout_masks
+    _stepper(*feeds)                          rows_per_image -> single-step decoder on features prepared once
+    _row_stepper(P, pr, fc_feats)             the same for one row per already embedded feature (StepAPI.get_logprobs_state)
+
+and, where it differs, _rollout_backward / _publish_rollout / _sample ("Adding a recurrent family").
+"""
+import torch
+
+from .CaptionModel import CaptionModel
+from .utils import parse_sample_method, clip_len
+from imagecaptioning.pytorch_amd import _lib, sparse_logp
+from imagecaptioning.pytorch_amd.engine_common import Prepared
+
+
+class _RolloutFn(torch.autograd.Function):
+    """(feeds..., params...) -> (seq, dense seqLogprobs); backward = hand-written BPTT + prefill backward.
+    Gradients are written into the model's flat gradient views when it has them."""
+
+    @staticmethod
+    def forward(ctx, model, cfg, *args):
+        names = model._param_names
+        k = len(args) - len(names)                                  # the family's feeds come first
+        P = dict(zip(names, [p.detach() for p in args[k:]]))
+        ctx.sink = cfg.pop('_sink', None)
+        ctx.set_materialize_grads(False)        # the dense log-prob gradient may be undefined (sparse route)
+        ro, ctx.kept = model._make_rollout(P, cfg, *args[:k])
+        seq, logp = ro.run()
+        ctx.model, ctx.ro, ctx.P, ctx.lead = model, ro, P, 2 + k
+        model._publish_rollout(ro, ctx.sink)
+        ctx.mark_non_differentiable(seq)
+        # (an ALIAS of the engine's tensor is returned: autograd hangs this Function on the returned object, and returning the very
+        #  tensor the saved engine holds would close a reference cycle ctx -> engine -> tensor -> grad_fn -> ctx -- every activation
+        #  of the step then lives until the interpreter's cyclic collector happens to run, not until the step's graph is dropped)
+        return seq, logp.detach()
+
+    @staticmethod
+    def backward(ctx, _g_seq, g_logp):
+        model, ro, P = ctx.model, ctx.ro, ctx.P
+        flat = model._flat
+        stash = flat.begin_backward() if flat is not None else None
+        grads = model._grad_targets(P)
+        g_logp, sparse, keep = sparse_logp.split_grad(g_logp, ctx.sink, ro.seq_logp)       # the criteria hand their gradient over sparse
+        ro._sparse_keep = keep
+        model._rollout_backward(ro, ctx.kept, P, g_logp, grads, sparse, flat, stash)
+        if flat is not None:
+            flat.end_backward(stash)
+            return (None,) * (ctx.lead + len(P))
+        return (None,) * ctx.lead + tuple(grads[k] for k in model._param_names)
+
+
+class RecurrentModel(CaptionModel):
+    ss_prob = 0.0
+
+    @staticmethod
+    def _check_supported_opt(opt):
+        if (getattr(opt, 'bos_idx', 0), getattr(opt, 'eos_idx', 0), getattr(opt, 'pad_idx', 0)) != (0, 0, 0):
+            raise NotImplementedError('capmi kernels assume bos=eos=pad=0 (the reference default, AttModel.py:65-67)')
+        if getattr(opt, 'use_bn', 0):
+            raise NotImplementedError('use_bn is outside the shipped configs')
+        if getattr(opt, 'logit_layers', 1) != 1:
+            raise NotImplementedError('logit_layers > 1 is broken in the reference itself (AttModel.py:92)')
+
+    def _device_check(self, t):
+        if not t.is_cuda:
+            raise _lib.CapmiError('the capmi backend runs on a HIP device only (got a %s tensor); there is no CPU path'
+                                  % t.device.type)
+
+    # ------------------------------------------------------------------ the family's hooks
+    def _feeds(self, fc_feats, att_feats, att_masks):
+        return fc_feats, att_feats, att_masks
+
+    def _dropout_masks(self, B, K, N, T, dev):
+        return {}
+
+    def _rollout_masks(self, B, N, T, att_feats, att_masks, dev):
+        self._device_check(att_feats)             # the masks are the first launches of a rollout
+        return self._dropout_masks(B, clip_len(att_masks, att_feats.shape[1]), N, T, dev)
+
+    def _rollout_backward(self, ro, kept, P, g_logp, grads, sparse, flat, stash):
+        ro.backward(g_logp, grads, sparse=sparse)
+
+    def _publish_rollout(self, ro, sink):
+        pass
+
+    # ------------------------------------------------------------------ rollouts
+    def _run(self, cfg, *feeds):
+        """one rollout of the family's feeds (in _feeds order) -> (seq, seqLogprobs attached to the autograd graph)"""
+        self._device_check(feeds[0])
+        feeds = [None if t is None else t.float().contiguous() for t in feeds]
+        cfg['_sink'] = sink = sparse_logp.LogpSink()
+        seq, logp = _RolloutFn.apply(self, cfg, *feeds, *self._param_list())
+        return seq, sparse_logp.attach(logp, sink)
+
+    def _forward(self, fc_feats, att_feats, seq, att_masks=None):
+        """Teacher-forced log-probs [N,T,V1] (AttModel.py:126-164), scheduled sampling included."""
+        feeds = self._feeds(fc_feats, att_feats, att_masks)
+        B, dev = feeds[0].size(0), feeds[0].device
+        if seq.ndim == 3:
+            seq = seq.reshape(-1, seq.shape[2])
+        seq = seq.long().contiguous()
+        N, T = seq.shape
+        # AttModel.py:158-159: stop at the first all-pad column.  The labels are an INPUT, so this is one
+        # host decision per batch made before anything is enqueued, not a per-step sync.
+        zero_cols = (seq[:, 1:].sum(0) == 0).nonzero()
+        T_eff = int(zero_cols[0]) + 1 if zero_cols.numel() else T
+        cfg = dict(n=N // B, T=T_eff, L=T, mode='forced', forced=seq, teacher=True)
+        cfg.update(self._rollout_masks(B, N, T_eff, att_feats, att_masks, dev))
+        if self.training and self.ss_prob > 0.0:
+            # scheduled sampling (AttModel.py:145-154): from step 1 on each row feeds, with probability ss_prob, a draw from
+            # the model's previous distribution instead of the ground-truth word.  The coin flips are made here for all
+            # steps at once (they do not depend on the model), the draws happen inside the rollout.
+            coin = self._ss_coin if getattr(self, '_ss_coin', None) is not None else \
+                torch.rand(T_eff, N, device=dev) < self.ss_prob            # _ss_coin / _ss_gumbel: test hooks
+            cfg['ss_mode'] = torch.where(coin, 1, 2).to(torch.uint8).contiguous()
+            cfg['seed'] = self._next_seed()
+            if getattr(self, '_ss_gumbel', None) is not None:
+                cfg['gumbel'] = self._ss_gumbel
+        _, logp = self._run(cfg, *feeds)
+        return logp
+
+    def _sample(self, fc_feats, att_feats, att_masks=None, opt={}):
+        """Greedy / sampling rollout (AttModel.py:258-352); beam search and the decode-time options on the stepper."""
+        from imagecaptioning.pytorch_amd import decode, beam
+        self._device_check(att_feats)
+        beam.refuse_train_beam(self, opt)           # train_beam_size > 1: no log-probs without a graph
+        method = opt.get('sample_method', 'greedy')
+        raw = not opt.get('output_logsoftmax', 1)
+        is_beam = opt.get('beam_size', 1) > 1 and method in ('greedy', 'beam_search')
+        mode, temperature, top_k, top_p = (None, 1.0, 0, 0.0) if is_beam else parse_sample_method(method, opt.get('temperature', 1.0))
+        if raw and (is_beam or decode.wants_options(opt) or top_k or top_p):
+            raise NotImplementedError('output_logsoftmax=0 is implemented for the sampled / greedy rollout; beam search and the '
+                                      'decode-time options of %s return log-probabilities' % type(self).__name__)
+        B, feeds = att_feats.size(0), self._feeds(fc_feats, att_feats, att_masks)
+        if is_beam:
+            with torch.no_grad():
+                return beam.beam_search_steps(self, self._stepper(*feeds), B, self.vocab_size + 1, self.seq_length, opt,
+                                              att_feats.device)
+        if decode.wants_options(opt) or top_k or top_p:
+            return self._sample_with_options(self._stepper(*feeds), B, opt)
+        n, L = int(opt.get('sample_n', 1)), self.seq_length
+        cfg = dict(n=n, T=L, L=L, mode=mode, temperature=temperature, seed=self._next_seed(), raw=raw)
+        cfg.update(self._rollout_masks(B, B * n, L, att_feats, att_masks, att_feats.device))
+        if opt.get('_gumbel') is not None:         # test hook: injected noise [L, N, V1]
+            cfg['gumbel'] = opt['_gumbel']
+        return self._run(cfg, *feeds)
+
+    # ------------------------------------------------------------------ single steps
+    def _decode_stepper(self, fc_feats, att_feats, att_masks, L):
+        """make(rows_per_image) -> the family's stepper (= _stepper).  Used by AttEnsemble; L is the caller's decode length (the
+        stepper has none)."""
+        feeds = self._feeds(fc_feats, att_feats, att_masks)
+        self._device_check(feeds[0])
+        return self._stepper(*feeds)
+
+
+class StepAPI:
+    """init_hidden / get_logprobs_state (AttModel.py:166-176) of UpDown, Att2in2 and AdaAtt, mixed in before RecurrentModel"""
+
+    def init_hidden(self, bsz):
+        w = self.logit.weight
+        return (w.new_zeros(self.num_layers, bsz, self.rnn_size), w.new_zeros(self.num_layers, bsz, self.rnn_size))
+
+    def get_logprobs_state(self, it, fc_feats, att_feats, p_att_feats, att_masks, state, output_logsoftmax=1):
+        """One decoder step on prepared features (AttModel.py:166-176) for callers that drive the decoder themselves (ensembles,
+        custom searches): features are per ROW (already repeated by the caller, as in the reference), state is the reference's
+        (h [layers,N,R], c [layers,N,R]).  Eval numerics; returns (logprobs [N,V1], new state)."""
+        self._device_check(att_feats)
+        pr = Prepared.of_features(att_feats, p_att_feats, att_masks)
+        N = pr.att.shape[0]
+        st = self._row_stepper(self._params(), pr, fc_feats)
+        st.load_state(state, N)
+        logits = st.step(0, it.long().contiguous(), 1)
+        new_state = st.export_state(N)
+        if not output_logsoftmax:
+            return logits.clone(), new_state
+        logp = torch.empty_like(logits)
+        _lib.check(_lib.lib.capmi_log_softmax_rows(_lib.ptr(logits), _lib.ptr(logp), N, st.V1, _lib.stream_ptr()),
+                   'capmi_log_softmax_rows')
+        return logp, new_state

@@ -165,20 +165,15 @@ class TransformerModel(CaptionModel):
         # on -- the n caption rows of an image then share their encoder dropout masks (same expected gradient, correlated noise)
         import os
         self.tie_encoder_dropout = bool(getattr(opt, 'tie_encoder_dropout', 0)) or os.environ.get('CAPMI_TIE_ENC') == '1'
-        self._flat = None
-        self._rng_calls = 0
 
     # ---- plumbing
-    @property
-    def _param_names(self):
-        return self._param_name_list()
-
     def _pdict(self, params):
         P = dict(zip(self._param_names, [p.detach() for p in params]))
         P['model.tgt_embed.1.pe'] = self.model.tgt_embed[1].pe[0].contiguous()      # [max_len, D]
         return P
 
     def _grad_targets(self, P):
+        # (not CaptionModel's: P carries the positional table beside the parameters, and it has no gradient)
         if self._flat is not None:
             return self._flat.grad_views
         return {k: torch.empty_like(v) for k, v in P.items() if k != 'model.tgt_embed.1.pe'}
@@ -196,15 +191,6 @@ class TransformerModel(CaptionModel):
         for kind in ('weight', 'bias'):
             groups.append(['model.decoder.layers.%d.src_attn.linears.%d.%s' % (i, j, kind) for i in range(n_dec) for j in (1, 2)])
         return groups
-
-    def flatten_parameters_(self):
-        from imagecaptioning.pytorch_amd.flat import FlatParams
-        self._flat = FlatParams(self)
-        return self._flat
-
-    def _next_seed(self):
-        self._rng_calls += 1
-        return (torch.initial_seed() * 0x9E3779B97F4A7C15 + self._rng_calls * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
 
     def logit(self, x):
         return torch.nn.functional.linear(x, self.model.generator.proj.weight, self.model.generator.proj.bias)

@@ -20,53 +20,102 @@ import ctypes as C
 
 import torch
 
-from . import _lib, ops, updown_engine as engine
+from . import _lib, ops
 from ._lib import lib, ptr, check, stream_ptr
 
 _f32 = torch.float32
 
 
-class UpDownStepper:
-    def __init__(self, P, pr, rows_per_image_max):
-        self.P, self.pr = P, pr
-        dev = pr.att.device
-        B, K, R = pr.att.shape
-        A = pr.p_att.shape[2]
-        V1, E = P['embed.0.weight'].shape
-        self.B, self.R, self.V1, self.cap = B, R, V1, int(rows_per_image_max)
-        self.N = N = B * self.cap
-        z = lambda *s: torch.empty(*s, dtype=_f32, device=dev)       # noqa: E731
-        self.ws = ops.default_workspace(dev)
-        self.state = torch.zeros(2, 4, N, R, dtype=_f32, device=dev)   # ping-pong of (h_att, c_att, h_lang, c_lang)
-        self.cur = 0
-        self.bufs = dict(xt=z(N, E), gates=z(N, 4 * R), att_h=z(N, A), alpha=z(N, K), ctx=z(N, R), fc_gates=z(B, 4 * R),
-                         logits=z(N, V1), it=torch.zeros(N, dtype=torch.long, device=dev))
-        b = _lib.UpDownBeam()
-        b.B, b.bd, b.K, b.A, b.R, b.E, b.V1, b.L = B, self.cap, K, A, R, E, V1, 0
-        b.fc, b.att, b.p_att, b.att_mask = ptr(pr.fc), ptr(pr.att), ptr(pr.p_att), ptr(pr.att_masks)
-        b.temperature, b.unk_col = 1.0, -1
-        for k, t in self.bufs.items():
-            setattr(b, k, t.data_ptr())
-        b.partial, b.partial_capacity = self.ws.buf.data_ptr(), self.ws.capacity
-        self.b, self.w = b, engine.weights_struct(P)
-        self._first = True
+class _Stepper:
+    """The recurrent state of B * cap hypotheses as a ping-pong pair [2, S, N, R] (a step and a beam reorder read one half and
+    write the other), the workspace, and the beam reorder."""
 
-    def step(self, t, it, rows_per_image):
-        rows = self.B * rows_per_image
-        assert it.shape[0] == rows and rows_per_image <= self.cap
-        self.bufs['it'][:rows].copy_(it)
-        src, dst = self.state[self.cur], self.state[1 - self.cur]
-        check(lib.capmi_updown_decode_step(C.byref(self.w), C.byref(self.b), rows, rows_per_image, ptr(src), ptr(dst),
-                                           1 if self._first else 0, stream_ptr()), 'capmi_updown_decode_step')
-        self._first = False
-        self.cur = 1 - self.cur
-        return self.bufs['logits'][:rows]
+    def _init_state(self, B, R, V1, rows_per_image_max, S, dev):
+        self.B, self.R, self.V1, self.cap = B, R, V1, int(rows_per_image_max)
+        self.N = B * self.cap
+        self.ws = ops.default_workspace(dev)
+        self.state = torch.zeros(2, S, self.N, R, dtype=_f32, device=dev)
+        self.cur = 0
 
     def reorder(self, parent, cur):
         from . import beam
         src, dst = self.state[self.cur], self.state[1 - self.cur]
         beam.reorder_rows(src, dst, parent, self.B, cur, parent.shape[1])
         self.cur = 1 - self.cur
+
+
+class _StructStepper(_Stepper):
+    """A stepper whose step is ONE native call on a capmi.h struct.  The family fills the struct's dims and features and states
+    its buffers (by field name; `it` and `logits` are added here) and its entry point."""
+
+    STEP = None                       # native entry point, by name
+
+    def _bind(self, s, bufs, dev):
+        logits = torch.empty(self.N, self.V1, dtype=_f32, device=dev)
+        self.bufs = dict(bufs, logits=logits, it=torch.zeros(self.N, dtype=torch.long, device=dev))
+        for k, t in self.bufs.items():
+            setattr(s, k, t.data_ptr())
+        s.partial, s.partial_capacity = self.ws.buf.data_ptr(), self.ws.capacity
+        self.s = s
+
+    def _native(self, rows, rows_per_image, src, dst):
+        return getattr(lib, self.STEP)(C.byref(self.w), C.byref(self.s), rows, rows_per_image, ptr(src[0]), ptr(src[1]),
+                                       ptr(dst[0]), ptr(dst[1]), stream_ptr())
+
+    def step(self, t, it, rows_per_image):
+        rows = self.B * rows_per_image
+        assert it.shape[0] == rows and rows_per_image <= self.cap
+        self.bufs['it'][:rows].copy_(it)
+        check(self._native(rows, rows_per_image, self.state[self.cur], self.state[1 - self.cur]), self.STEP)
+        self.cur = 1 - self.cur
+        return self.bufs['logits'][:rows]
+
+
+class _OneLayerState:
+    """snapshot / restore, and the reference layout of the recurrent state (h [layers,N,R], c [layers,N,R]) for a core that
+    reads the last layer and returns one; the stepper's state is (h, c)"""
+
+    def snapshot(self):
+        return self.state[self.cur].clone()
+
+    def restore(self, snap):
+        self.state[self.cur].copy_(snap)
+
+    def load_state(self, state, rows):
+        h, c = state
+        s = self.state[self.cur]
+        s[0, :rows], s[1, :rows] = h[-1], c[-1]
+
+    def export_state(self, rows):
+        s = self.state[self.cur]
+        return (s[0, :rows].clone().unsqueeze(0), s[1, :rows].clone().unsqueeze(0))
+
+
+class UpDownStepper(_StructStepper):
+    STEP = 'capmi_updown_decode_step'
+
+    def __init__(self, P, pr, rows_per_image_max):
+        from . import updown_engine
+        self.P, self.pr = P, pr
+        dev = pr.att.device
+        B, K, R = pr.att.shape
+        A = pr.p_att.shape[2]
+        V1, E = P['embed.0.weight'].shape
+        self._init_state(B, R, V1, rows_per_image_max, 4, dev)      # (h_att, c_att, h_lang, c_lang)
+        N = self.N
+        z = lambda *s: torch.empty(*s, dtype=_f32, device=dev)       # noqa: E731
+        b = _lib.UpDownBeam()
+        b.B, b.bd, b.K, b.A, b.R, b.E, b.V1, b.L = B, self.cap, K, A, R, E, V1, 0
+        b.fc, b.att, b.p_att, b.att_mask = ptr(pr.fc), ptr(pr.att), ptr(pr.p_att), ptr(pr.att_masks)
+        b.temperature, b.unk_col = 1.0, -1
+        self._bind(b, dict(xt=z(N, E), gates=z(N, 4 * R), att_h=z(N, A), alpha=z(N, K), ctx=z(N, R), fc_gates=z(B, 4 * R)), dev)
+        self.w = updown_engine.weights_struct(P)
+        self._first = True
+
+    def _native(self, rows, rows_per_image, src, dst):
+        first, self._first = self._first, False
+        return lib.capmi_updown_decode_step(C.byref(self.w), C.byref(self.s), rows, rows_per_image, ptr(src), ptr(dst),
+                                            1 if first else 0, stream_ptr())
 
     # reference layout of the recurrent state: (h [2,N,R], c [2,N,R]) with index 0 = att_lstm, 1 = lang_lstm
     def load_state(self, state, rows):
@@ -79,7 +128,7 @@ class UpDownStepper:
         return (torch.stack([s[0, :rows], s[2, :rows]]), torch.stack([s[1, :rows], s[3, :rows]]))
 
 
-class NewFCStepper:
+class NewFCStepper(_Stepper):
     """AttModel.py:925-936: the first call feeds the image (state all zero), then words.  The image step is taken in the
     constructor so that step(0, BOS) is the first WORD step like for every other family."""
 
@@ -89,14 +138,11 @@ class NewFCStepper:
         dev = fc_feats.device
         self.P = P
         self.drop_out = drop_out
-        self.B = B = fc_feats.shape[0]
-        self.V1, self.E = P['embed.weight'].shape
-        self.R = R = P['_core.h2h.weight'].shape[1]
-        self.cap = int(rows_per_image_max)
-        self.N = N = B * self.cap
-        self.ws = ops.default_workspace(dev)
-        self.state = torch.zeros(2, 2, N, R, dtype=_f32, device=dev)   # ping-pong of (h, c)
-        self.cur = 0
+        B = fc_feats.shape[0]
+        V1, self.E = P['embed.weight'].shape
+        R = P['_core.h2h.weight'].shape[1]
+        self._init_state(B, R, V1, rows_per_image_max, 2, dev)      # (h, c)
+        N = self.N
         self.saved = torch.empty(N, 5 * R, dtype=_f32, device=dev)
         self.logits = torch.empty(N, self.V1, dtype=_f32, device=dev)
         self.h_drop = None if drop_out is None else torch.empty(N, R, dtype=_f32, device=dev)
@@ -131,15 +177,11 @@ class NewFCStepper:
                  ws=self.ws)
         return logits
 
-    def reorder(self, parent, cur):
-        from . import beam
-        src, dst = self.state[self.cur], self.state[1 - self.cur]
-        beam.reorder_rows(src, dst, parent, self.B, cur, parent.shape[1])
-        self.cur = 1 - self.cur
 
-
-class Att2in2Stepper:
+class Att2in2Stepper(_OneLayerState, _StructStepper):
     """Att2in2Model (AttModel.py:854-859): BOS first, no image step; the state is (h, c) of the one cell."""
+
+    STEP = 'capmi_att2in2_decode_step'
 
     def __init__(self, P, pr, rows_per_image_max):
         from . import att2in2_engine
@@ -148,59 +190,21 @@ class Att2in2Stepper:
         A = pr.p_att.shape[2]
         V1, E = P['embed.0.weight'].shape
         self.P, self.pr = P, pr
-        self.B, self.R, self.V1, self.cap = B, R, V1, int(rows_per_image_max)
-        self.N = N = B * self.cap
+        self._init_state(B, R, V1, rows_per_image_max, 2, dev)
+        N = self.N
         z = lambda *s: torch.empty(*s, dtype=_f32, device=dev)       # noqa: E731
-        self.ws = ops.default_workspace(dev)
-        self.state = torch.zeros(2, 2, N, R, dtype=_f32, device=dev)   # ping-pong of (h, c)
-        self.cur = 0
-        self.bufs = dict(it=torch.zeros(N, dtype=torch.long, device=dev), xt=z(N, E), att_h=z(N, A), alpha=z(N, K), ctx=z(N, R),
-                         saved=z(N, 5 * R), logits=z(N, V1))
         s = _lib.Att2in2Step()
         s.B, s.K, s.A, s.R, s.E, s.V1 = B, K, A, R, E, V1
         s.att, s.p_att, s.att_mask = ptr(pr.att), ptr(pr.p_att), ptr(pr.att_masks)
-        for k, t in self.bufs.items():
-            setattr(s, k, t.data_ptr())
-        s.partial, s.partial_capacity = self.ws.buf.data_ptr(), self.ws.capacity
-        self.s, self.w = s, att2in2_engine.weights_struct(P)
-
-    def step(self, t, it, rows_per_image):
-        rows = self.B * rows_per_image
-        assert it.shape[0] == rows and rows_per_image <= self.cap
-        self.bufs['it'][:rows].copy_(it)
-        src, dst = self.state[self.cur], self.state[1 - self.cur]
-        check(lib.capmi_att2in2_decode_step(C.byref(self.w), C.byref(self.s), rows, rows_per_image, ptr(src[0]), ptr(src[1]),
-                                            ptr(dst[0]), ptr(dst[1]), stream_ptr()), 'capmi_att2in2_decode_step')
-        self.cur = 1 - self.cur
-        return self.bufs['logits'][:rows]
-
-    def reorder(self, parent, cur):
-        from . import beam
-        src, dst = self.state[self.cur], self.state[1 - self.cur]
-        beam.reorder_rows(src, dst, parent, self.B, cur, parent.shape[1])
-        self.cur = 1 - self.cur
-
-    def snapshot(self):
-        return self.state[self.cur].clone()
-
-    def restore(self, snap):
-        self.state[self.cur].copy_(snap)
-
-    # reference layout of the recurrent state: (h [layers,N,R], c [layers,N,R]); the core reads the last layer and returns one
-    def load_state(self, state, rows):
-        h, c = state
-        s = self.state[self.cur]
-        s[0, :rows], s[1, :rows] = h[-1], c[-1]
-
-    def export_state(self, rows):
-        s = self.state[self.cur]
-        return (s[0, :rows].clone().unsqueeze(0), s[1, :rows].clone().unsqueeze(0))
+        self._bind(s, dict(xt=z(N, E), att_h=z(N, A), alpha=z(N, K), ctx=z(N, R), saved=z(N, 5 * R)), dev)
+        self.w = att2in2_engine.weights_struct(P)
 
 
-class AdaAttStepper(Att2in2Stepper):
+class AdaAttStepper(_OneLayerState, _StructStepper):
     """AdaAttModel / AdaAttMOModel (AttModel.py:843-852): BOS first, no image step; the state is (h, c) of the one layer (the
-    undropped h: AdaAtt_lstm returns it beside the copy that goes on to the attention).  Beam reorder, snapshot and the
-    reference's state layout are Att2in2Stepper's."""
+    undropped h: AdaAtt_lstm returns it beside the copy that goes on to the attention)."""
+
+    STEP = 'capmi_adaatt_decode_step'
 
     def __init__(self, P, ap, rows_per_image_max):
         from . import adaatt_engine
@@ -210,32 +214,15 @@ class AdaAttStepper(Att2in2Stepper):
         V1, E = P['embed.0.weight'].shape
         W = ap.fc_gates.shape[1]
         self.P, self.pr = P, ap
-        self.B, self.R, self.V1, self.cap = B, R, V1, int(rows_per_image_max)
-        self.N = N = B * self.cap
+        self._init_state(B, R, V1, rows_per_image_max, 2, dev)
+        N = self.N
         z = lambda *s: torch.empty(*s, dtype=_f32, device=dev)       # noqa: E731
-        self.ws = ops.default_workspace(dev)
-        self.state = torch.zeros(2, 2, N, R, dtype=_f32, device=dev)   # ping-pong of (h, c)
-        self.cur = 0
-        self.bufs = dict(it=torch.zeros(N, dtype=torch.long, device=dev), xt=z(N, E), saved=z(N, W), h_drop=z(N, R),
-                         fake_drop=z(N, R), fr=z(N, E), ho_t=z(N, E), ho=z(N, E), fr_e=z(N, A), ho_e=z(N, A), pi=z(N, K + 1),
-                         ctx=z(N, R), out_t=z(N, R), out_drop=z(N, R), logits=z(N, V1))
         s = _lib.AdaAttStep()
         s.B, s.K, s.A, s.R, s.E, s.V1, s.maxout = B, K, A, R, E, V1, int(W == 6 * R)
         s.fc_gates, s.att, s.p_att, s.att_mask = ptr(ap.fc_gates), ptr(ap.att), ptr(ap.p_att), ptr(ap.att_masks)
-        for k, t in self.bufs.items():
-            setattr(s, k, t.data_ptr())
-        s.partial, s.partial_capacity = self.ws.buf.data_ptr(), self.ws.capacity
-        self.s, self.w = s, adaatt_engine.weights_struct(P, ap.packs)
-
-    def step(self, t, it, rows_per_image):
-        rows = self.B * rows_per_image
-        assert it.shape[0] == rows and rows_per_image <= self.cap
-        self.bufs['it'][:rows].copy_(it)
-        src, dst = self.state[self.cur], self.state[1 - self.cur]
-        check(lib.capmi_adaatt_decode_step(C.byref(self.w), C.byref(self.s), rows, rows_per_image, ptr(src[0]), ptr(src[1]),
-                                           ptr(dst[0]), ptr(dst[1]), stream_ptr()), 'capmi_adaatt_decode_step')
-        self.cur = 1 - self.cur
-        return self.bufs['logits'][:rows]
+        self._bind(s, dict(xt=z(N, E), saved=z(N, W), h_drop=z(N, R), fake_drop=z(N, R), fr=z(N, E), ho_t=z(N, E), ho=z(N, E),
+                           fr_e=z(N, A), ho_e=z(N, A), pi=z(N, K + 1), ctx=z(N, R), out_t=z(N, R), out_drop=z(N, R)), dev)
+        self.w = adaatt_engine.weights_struct(P, ap.packs)
 
 
 class EnsembleStepper:
@@ -273,24 +260,3 @@ class EnsembleStepper:
     def _restore(self, snap):
         for m, s in zip(self.members, snap):
             m.restore(s)
-
-
-def updown_step(model, it, fc_feats, att_feats, p_att_feats, att_masks, state, output_logsoftmax=1):
-    """AttModel.get_logprobs_state (AttModel.py:166-176) for callers that drive the decoder themselves (ensembles, custom
-    searches): features are per ROW (already repeated by the caller, as in the reference), state = (h [2,N,R], c [2,N,R]).
-    Eval numerics; returns (logprobs [N,V1], new state)."""
-    model._device_check(fc_feats)
-    P = {k: v.detach() for k, v in model.named_parameters()}
-    pr = engine.Prepared()
-    pr.fc, pr.att, pr.p_att = fc_feats.float().contiguous(), att_feats.float().contiguous(), p_att_feats.float().contiguous()
-    pr.att_masks = None if att_masks is None else att_masks.float().contiguous()
-    N = pr.fc.shape[0]
-    st = UpDownStepper(P, pr, 1)
-    st.load_state(state, N)
-    logits = st.step(0, it.long().contiguous(), 1)
-    new_state = st.export_state(N)
-    if not output_logsoftmax:
-        return logits.clone(), new_state
-    logp = torch.empty_like(logits)
-    check(lib.capmi_log_softmax_rows(ptr(logits), ptr(logp), N, st.V1, stream_ptr()), 'capmi_log_softmax_rows')
-    return logp, new_state
