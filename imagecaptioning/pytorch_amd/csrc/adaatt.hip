@@ -1,8 +1,8 @@
 // AdaAtt decoder on gfx950 ("Knowing when to look"): the visual-sentinel LSTM cell, whole-rollout drivers (forward and BPTT) and
 // a single decode step.  Replaces AdaAttCore.forward (AttModel.py:604-613) = AdaAtt_lstm (:451-537, one layer) + AdaAtt_attention
 // (:539-602) under AdaAttModel / AdaAttMOModel (:843-852) and the time loops of AttModel._forward / _sample for them.  The
-// sentinel attention kernels live beside the additive attention they extend (attention.hip).  Same structure as the Att2in2
-// driver: one host call per rollout, no host sync, time-batched weight gradients as one grouped launch.
+// sentinel attention kernels live beside the additive attention they extend (attention.hip).  One host call per rollout, no
+// host sync, time-batched weight gradients as one grouped launch; the driver plumbing around the step is rollout_common.h's.
 //
 // What the structure of this model gives the driver:
 //  * v2h(fc) and r_v2h(fc) do not depend on the step: the caller hands them in as fc_gates [B, G+R] (with all six gate biases
@@ -12,7 +12,7 @@
 //  * the recurrence runs through (h, c) only: the attention output of a step feeds that step's logits and nothing else.  The
 //    backward therefore runs logit -> att2h -> sentinel attention -> ho / fr projections for ALL T steps as time-batched launches
 //    and only the cell (one launch + one dX GEMM per step) walks back through time.
-#include "host_common.h"
+#include "rollout_common.h"
 
 using namespace capmi;
 
@@ -160,18 +160,6 @@ int act_bwd(const ActBwdSeg &s0, const ActBwdSeg *s1, size_t per, void *stream) 
     return 0;
 }
 
-// The split-K workspace in two regions, so that two independent GEMMs of a pair (fr / ho) can both stay as slabs.
-struct Carve {
-    float *p1; int64_t cap1;
-    float *p2; int64_t cap2;
-};
-inline bool carve(float *partial, int64_t cap, Carve *o) {
-    const int64_t cap2 = (cap / 4) & ~(int64_t)1023;
-    o->p1 = partial; o->cap1 = cap - cap2;
-    o->p2 = partial + o->cap1; o->cap2 = cap2;
-    return o->cap1 > CAPMI_WS_COUNTER_FLOATS && o->cap2 > CAPMI_WS_COUNTER_FLOATS;
-}
-
 struct StepBufs {
     const float *x, *xin, *h_prev, *c_prev;
     float *h, *c, *saved, *h_drop, *fake_drop, *fr, *ho_t, *ho, *fr_e, *ho_e, *pi, *ctx, *out_t, *out_drop;
@@ -258,34 +246,21 @@ int capmi_adaatt_cell_bwd(const float *dh_a, const float *dh_a_mask, const float
 
 int capmi_adaatt_rollout_fwd(const capmi_adaatt_weights *w, capmi_adaatt_rollout *r, void *stream) {
     if (!w || !r) return CAPMI_EINVAL;
-    const int B = r->B, n = r->n, N = r->N, K = r->K, A = r->A, R = r->R, E = r->E, V1 = r->V1, T = r->T, L = r->L;
-    if (B <= 0 || n <= 0 || N != B * n || K <= 0 || A <= 0 || T <= 0 || L < T || !r->partial || !r->att || !r->p_att ||
-        !r->fc_gates || E != R || A != R)
+    const int B = r->B, n = r->n, N = r->N, K = r->K, A = r->A, R = r->R, E = r->E, V1 = r->V1, T = r->T;
+    if (B <= 0 || n <= 0 || N != B * n || K <= 0 || A <= 0 || !r->partial || !r->att || !r->p_att || !r->fc_gates || E != R || A != R)
         return CAPMI_EINVAL;
-    if (((r->mode & 255) == 2 || r->teacher) && !r->forced) return CAPMI_EINVAL;
-    if (r->ss_mode && !r->teacher) return CAPMI_EINVAL;
+    const SelectIO io = select_io(r);
+    RC(check_rollout_io(io));
     if (!r->drop_tile && (r->tile_p < 0.f || r->tile_p >= 1.f)) return CAPMI_EINVAL;
     Carve ws;
     if (!carve(r->partial, r->partial_capacity, &ws)) return CAPMI_EINVAL;
     const int W = (r->maxout ? 6 : 5) * R;
     const size_t NR = (size_t)N * R, NE = (size_t)N * E, NA = (size_t)N * A, NW = (size_t)N * W, NK1 = (size_t)N * (K + 1);
-    const bool sched = r->teacher && r->ss_mode;
     // teacher forcing knows every input token up front: the (w2h | r_w2h) half of all T steps is ONE GEMM over T*N rows
-    const bool batched_x = r->teacher && !sched && r->xin;
+    const bool batched_x = r->teacher && !scheduled(io) && r->xin;
+    const EmbedSpec emb{w->embed, E, 1, r->drop_xt, r->x, true};
     RC(capmi_rollout_init(r->h, r->c, nullptr, nullptr, (int64_t)NR, r->it, r->unfinished, N, stream));    // state 0, BOS
-    if (r->teacher && !sched) {
-        for (int t = 0; t < T; ++t)
-            RC(capmi_embed_fwd(r->forced + t, r->forced_ld, r->it_all + (size_t)t * N, w->embed,
-                               r->drop_xt ? r->drop_xt + t * NE : nullptr, r->x + t * NE, N, E, 1, stream));
-        if (batched_x) {
-            SegSpec s{r->x, E, w->xw, E, E};
-            RC(gemm(stream, 0, 0, T * N, W, r->xin, W, &s, 1, ws.p1, ws.cap1, 0, nullptr));
-        }
-    } else {
-        // step 0's input: BOS (free-running) or forced[:, 0] (scheduled sampling); later inputs come from the select's tail
-        RC(capmi_embed_fwd(r->teacher ? r->forced : r->it, r->teacher ? r->forced_ld : 1, r->it_all, w->embed, r->drop_xt, r->x,
-                           N, E, 1, stream));
-    }
+    RC(teacher_inputs(io, emb, w->xw, W, batched_x ? r->xin : nullptr, ws.p1, ws.cap1, stream));
     for (int t = 0; t < T; ++t) {
         capmi_tile_drop tile{};
         tile.mask = r->drop_tile ? r->drop_tile + t * NK1 * A : nullptr;
@@ -304,32 +279,8 @@ int capmi_adaatt_rollout_fwd(const capmi_adaatt_weights *w, capmi_adaatt_rollout
         b.tile = (tile.mask || tile.p > 0.f) ? &tile : nullptr;
         RC(core_step(w, ws, B, n, N, K, A, R, E, r->maxout, r->fc_gates, r->att, r->p_att, r->att_mask, b, stream));
         int splits = 1;
-        {
-            SegSpec s{b.out_drop, R, w->logit_w, R, R};
-            RC(gemm(stream, 0, 0, N, V1, ws.p1, V1, &s, 1, ws.p1, ws.cap1, 1, &splits));
-        }
-        const float *slabs = ws.p1 + CAPMI_WS_COUNTER_FLOATS;
-        const float *gum = r->gumbel ? r->gumbel + (size_t)t * N * V1 : nullptr;
-        capmi_next_embed ne{};
-        if ((!r->teacher || sched) && t + 1 < T) {
-            ne.E = w->embed; ne.Edim = E; ne.relu = 1;
-            ne.mask = r->drop_xt ? r->drop_xt + (t + 1) * NE : nullptr;
-            ne.x = r->x + (t + 1) * NE;
-            ne.it_save = r->it_all + (size_t)(t + 1) * N;
-        }
-        if (sched && t + 1 < T) {
-            // AttModel.py:145-154: the token chosen here is the INPUT of step t+1 -- forced[:, t+1] (ss_mode 2 rows) or a
-            // categorical draw from this step's log-probs (ss_mode 1 rows); the same launch embeds it
-            RC(capmi_logsoftmax_select_partial(slabs, splits, (int64_t)N * V1, w->logit_b, N, V1, t, L, 2,
-                                               r->ss_mode + (size_t)(t + 1) * N, 1.f, gum, r->seed, r->forced + 1, r->forced_ld, 1,
-                                               r->seq, L, r->it, r->unfinished, r->seq_logp, r->sel_logp, r->live, &ne, nullptr,
-                                               stream));
-            continue;
-        }
-        RC(capmi_logsoftmax_select_partial(slabs, splits, (int64_t)N * V1, w->logit_b, N, V1, t, L, r->teacher ? 2 : r->mode, nullptr,
-                                           r->temperature, gum, r->seed, r->forced, r->forced_ld, r->teacher ? 1 : 0, r->seq, L,
-                                           r->it, r->unfinished, r->seq_logp, r->sel_logp, r->live, ne.x ? &ne : nullptr, nullptr,
-                                           stream));
+        RC(logit_slabs(stream, b.out_drop, w->logit_w, N, V1, R, ws.p1, ws.cap1, &splits));
+        RC(select_step(io, t, ws.p1 + CAPMI_WS_COUNTER_FLOATS, splits, w->logit_b, emb, stream));
     }
     return 0;
 }
@@ -337,7 +288,7 @@ int capmi_adaatt_rollout_fwd(const capmi_adaatt_weights *w, capmi_adaatt_rollout
 int capmi_adaatt_rollout_bwd(const capmi_adaatt_weights *w, const capmi_adaatt_rollout *r, const float *g_seq_logp,
                              capmi_adaatt_bwd_scratch *s, capmi_adaatt_grads *g, void *stream) {
     if (!w || !r || (!g_seq_logp && !(s && s->sparse)) || !s || !g) return CAPMI_EINVAL;
-    const int B = r->B, n = r->n, N = r->N, K = r->K, A = r->A, R = r->R, E = r->E, V1 = r->V1, T = r->T, L = r->L;
+    const int B = r->B, n = r->n, N = r->N, K = r->K, A = r->A, R = r->R, E = r->E, V1 = r->V1, T = r->T;
     if (!s->partial || s->partial_capacity <= CAPMI_WS_COUNTER_FLOATS || E != R || A != R) return CAPMI_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int G = (r->maxout ? 5 : 4) * R, W = G + R;
@@ -352,11 +303,8 @@ int capmi_adaatt_rollout_bwd(const capmi_adaatt_weights *w, const capmi_adaatt_r
     tile.seed = r->tile_seed;
     const capmi_tile_drop *td = (tile.mask || tile.p > 0.f) ? &tile : nullptr;
     // ---- everything behind the cell, for all T steps at once ----------------------------------------------------------------
-    RC(dlogits_bwd((r->mode & CAPMI_SELECT_RAW) && !r->teacher, s->sparse, g_seq_logp, r->seq_logp, r->live, s->dlogits, N, L, T,
-                   V1, stream));
+    RC(logit_bwd_head(select_io(r), s->sparse, g_seq_logp, s->dlogits, w->logit_w, R, s->d_out, P, cap, stream));   // d_out_drop
     {
-        SegSpec a{s->dlogits, V1, w->logit_w, R, V1};                 // d_out_drop = dlogits W_logit   [TN,R]
-        RC(gemm(stream, 0, 1, TN, R, s->d_out, R, &a, 1, P, cap, 0, nullptr));
         const ActBwdSeg ab{s->d_out, r->drop_out, r->out_t, 1};         // through the output dropout and att2h's tanh, in place
         RC(act_bwd(ab, nullptr, (size_t)TN * R, stream));
         SegSpec c{s->d_out, R, w->att2h_w, R, R};                      // d_ctx = d_out W_att2h
@@ -381,11 +329,10 @@ int capmi_adaatt_rollout_bwd(const capmi_adaatt_weights *w, const capmi_adaatt_r
     for (int t = T - 1; t >= 0; --t) {
         const bool last = (t == T - 1);
         float *d_sums = s->d_sums + t * NW;
-        float *dc_in = s->dc + (size_t)((t + 1) & 1) * NR, *dc_out = s->dc + (size_t)(t & 1) * NR;
         RC(capmi_adaatt_cell_bwd(s->d_hdrop + t * NR, r->drop_h ? r->drop_h + t * NR : nullptr, s->d_fakedrop + t * NR,
                                  r->drop_fake ? r->drop_fake + t * NR : nullptr, last ? nullptr : slabs, dh_splits, (int64_t)NR,
-                                 last ? nullptr : dc_in, r->saved + t * NW, r->c + t * NR, r->c + (t + 1) * NR, d_sums, dc_out, N, R,
-                                 r->maxout, stream));
+                                 pp_in(s->dc, t, T, NR), r->saved + t * NW, r->c + t * NR, r->c + (t + 1) * NR, d_sums,
+                                 pp_out(s->dc, t, NR), N, R, r->maxout, stream));
         if (t > 0) {       // the state before step 0 is the constant zero
             SegSpec a{d_sums, W, w->hw, R, W};
             RC(gemm(stream, 0, 1, N, R, P, R, &a, 1, P, cap, 1, &dh_splits));
@@ -393,17 +340,12 @@ int capmi_adaatt_rollout_bwd(const capmi_adaatt_weights *w, const capmi_adaatt_r
     }
     // ---- time-batched parameter / feature gradients ------------------------------------------------------------------------------
     const int64_t dw_floats = (int64_t)B * (K + 1) * A;
-    const bool dw_ws = cap >= CAPMI_WS_COUNTER_FLOATS + dw_floats;
-    float *dw_part = dw_ws ? slabs : nullptr;
+    float *dw_part = alpha_dw_part(P, cap, dw_floats);
     RC(capmi_sentinel_attention_bwd_batched(s->d_ctx, r->fr_e, r->ho_e, r->pi, s->d_e, r->p_att, w->alpha_w, td, g->d_att,
-                                            g->d_p_att, dw_ws ? nullptr : g->alpha_w, g->alpha_b, T, B, n, K, A, R, dw_part, stream));
+                                            g->d_p_att, dw_part ? nullptr : g->alpha_w, g->alpha_b, T, B, n, K, A, R, dw_part, stream));
     if (dw_part) RC(capmi_colsum(dw_part, B * (K + 1), A, A, g->alpha_w, 0, stream));
-    {
-        SegSpec a{s->d_sums, W, w->xw, E, W};                          // token embeddings: d_x = d_sums (w2h | r_w2h)
-        RC(gemm(stream, 0, 1, TN, E, s->d_x, E, &a, 1, P, cap, 0, nullptr));
-        HIP_RC(hipMemsetAsync(g->embed, 0, (size_t)V1 * E * sizeof(float), st));
-        RC(capmi_embed_bwd(r->it_all, s->d_x, r->x, r->drop_xt, g->embed, TN, E, 1, stream));
-    }
+    // token embeddings: d_x = d_sums (w2h | r_w2h)
+    RC(embed_grad(stream, SegSpec{s->d_sums, W, w->xw, E, W}, TN, E, s->d_x, r->it_all, r->x, r->drop_xt, 1, g->embed, V1, P, cap));
     RC(capmi_colsum(s->d_sums, TN, W, W, g->gate_b, 0, stream));
     RC(capmi_group_rowsum(s->d_sums, T, (int64_t)NW, B, n, W, g->d_fc_gates, stream));
     // the ten time-batched weight gradients (K = T*N rows) with their bias column sums as ONE grouped launch; h_prev of step t is
@@ -419,17 +361,10 @@ int capmi_adaatt_rollout_bwd(const capmi_adaatt_weights *w, const capmi_adaatt_r
         {s->d_sums + G, r->x, g->r_w2h_w, W, E, E, TN, R, E, 0, 0, nullptr},
         {s->d_sums, r->h, g->h2h_w, W, R, R, TN, G, R, 0, 0, nullptr},
         {s->d_sums + G, r->h, g->r_h2h_w, W, R, R, TN, R, R, 0, 0, nullptr}};
-    struct { float *out; const float *in; int ld, cols; } bias[6] = {
+    const BiasCol bias[6] = {
         {g->logit_b, s->dlogits, V1, V1}, {g->att2h_b, s->d_out, R, R}, {g->fre_b, s->d_fre, A, A}, {g->hoe_b, s->d_hoe, A, A},
         {g->fr_b, s->d_fr, E, E}, {g->ho_b, s->d_ho, E, E}};
-    for (int i = 0; i < 6; ++i) {
-        if (aligned16(bias[i].out)) grp[i].colsum = bias[i].out;
-        else RC(capmi_colsum(bias[i].in, TN, bias[i].cols, bias[i].ld, bias[i].out, 0, stream));
-    }
-    // (the K-slice pieces go behind alpha_net's partial rows: the column sum above is enqueued before, but keep them apart anyway)
-    const int64_t skip = CAPMI_WS_COUNTER_FLOATS + ((dw_floats + 1023) & ~(int64_t)1023);
-    RC(capmi_gemm_group_tn(grp, 10, cap > skip ? P + skip : nullptr, cap > skip ? cap - skip : 0, stream));
-    return 0;
+    return grouped_dw_with_bias(grp, 10, bias, 6, dw_floats, P, cap, stream);
 }
 
 int capmi_adaatt_decode_step(const capmi_adaatt_weights *w, capmi_adaatt_step *s, int rows, int rows_per_image,
@@ -446,8 +381,7 @@ int capmi_adaatt_decode_step(const capmi_adaatt_weights *w, capmi_adaatt_step *s
     b.saved = s->saved; b.h_drop = s->h_drop; b.fake_drop = s->fake_drop; b.fr = s->fr; b.ho_t = s->ho_t; b.ho = s->ho;
     b.fr_e = s->fr_e; b.ho_e = s->ho_e; b.pi = s->pi; b.ctx = s->ctx; b.out_t = s->out_t; b.out_drop = s->out_drop;
     RC(core_step(w, ws, B, rows_per_image, rows, K, A, R, E, s->maxout, s->fc_gates, s->att, s->p_att, s->att_mask, b, stream));
-    SegSpec l{s->out_drop, R, w->logit_w, R, R};
-    return gemm(stream, 0, 0, rows, V1, s->logits, V1, &l, 1, ws.p1, ws.cap1, 0, nullptr, w->logit_b);
+    return decode_logits(stream, s->out_drop, w->logit_w, w->logit_b, rows, V1, R, s->logits, ws.p1, ws.cap1);
 }
 
 }  // extern "C"

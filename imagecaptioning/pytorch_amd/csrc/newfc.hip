@@ -1,10 +1,10 @@
 // NewFC decoder on gfx950: maxout-LSTM cell kernels + whole-rollout drivers (forward and BPTT).
 // Replaces NewFCModel.core / _prepare_feature (AttModel.py:904-945) over LSTMCore (FCModel.py:13-42)
-// and the time loops of AttModel._forward / _sample for that model.  Same structure as the UpDown
-// drivers (rollout.hip): one host call per rollout, no host sync, time-batched weight gradients.
+// and the time loops of AttModel._forward / _sample for that model.  One host call per rollout, no host
+// sync, time-batched weight gradients; the driver plumbing around the step is rollout_common.h's.
 // The cell kernels also serve Att2in2 (att2in2.hip), whose cell is this one with an a2c term on the candidate half:
 // capmi_att2in2_cell_fwd / _bwd are defined here beside capmi_maxout_cell_fwd / _bwd.
-#include "host_common.h"
+#include "rollout_common.h"
 
 using namespace capmi;
 
@@ -135,17 +135,20 @@ int capmi_maxout_cell_bwd(const float *dh_a, const float *dh_a_mask, const float
 
 int capmi_newfc_rollout_fwd(const capmi_newfc_weights *w, capmi_newfc_rollout *r, void *stream) {
     if (!w || !r) return CAPMI_EINVAL;
-    const int B = r->B, n = r->n, N = r->N, R = r->R, E = r->E, V1 = r->V1, T = r->T, L = r->L;
-    if (B <= 0 || n <= 0 || N != B * n || T <= 0 || L < T || !r->partial) return CAPMI_EINVAL;
+    const int B = r->B, n = r->n, N = r->N, R = r->R, E = r->E, V1 = r->V1, T = r->T;
+    if (B <= 0 || n <= 0 || N != B * n || !r->partial) return CAPMI_EINVAL;
     // (r5: mode may carry CAPMI_SELECT_RAW -- a free-running rollout that stores the LOGITS, AttModel._sample(output_logsoftmax=0))
-    if (((r->mode & 255) == 2 || r->teacher) && !r->forced) return CAPMI_EINVAL;
-    if (r->ss_mode && !r->teacher) return CAPMI_EINVAL;
+    const SelectIO io = select_io(r);
+    RC(check_rollout_io(io));
     const size_t NR = (size_t)N * R;
-    const bool sched = r->teacher && r->ss_mode;
+    const bool sched = scheduled(io);
+    // plain Embedding: no ReLU, no mask; only scheduled sampling folds it into the select (free-running steps embed below)
+    const EmbedSpec emb{w->embed, E, 0, nullptr, r->x, false};
     float *slabs = r->partial + CAPMI_WS_COUNTER_FLOATS;
     RC(capmi_rollout_init(r->h, r->c, nullptr, nullptr, (int64_t)NR, r->it, r->unfinished, N, stream));    // state 0, BOS
     int splits = 1;
-    // step "-1": the image (AttModel.py:925-927); h = c = 0 so only the i2h term matters but keep the general form
+    // step "-1": the image (AttModel.py:925-927); h = c = 0 so only the i2h term matters but keep the general form.  (Its own, like
+    // the per-step embed below: no select and a row divisor; teacher_inputs would embed all steps first and reorder the launches.)
     {
         SegSpec s[2] = {{r->fc_emb, E, w->i2h_w, E, E, n}, {r->h, R, w->h2h_w, R, R, 1}};
         RC(gemm(stream, 0, 0, N, 5 * R, r->partial, 5 * R, s, 2, r->partial, r->partial_capacity, 1, &splits));
@@ -167,26 +170,8 @@ int capmi_newfc_rollout_fwd(const capmi_newfc_weights *w, capmi_newfc_rollout *r
         RC(gemm(stream, 0, 0, N, 5 * R, r->partial, 5 * R, s, 2, r->partial, r->partial_capacity, 1, &splits));
         RC(capmi_maxout_cell_fwd(slabs, splits, w->i2h_b, w->h2h_b, c_prev, h, c, r->saved + (size_t)(t + 1) * N * 5 * R,
                                  r->drop_out ? r->drop_out + (size_t)t * NR : nullptr, h_drop, N, R, stream));
-        SegSpec sl{h_drop, R, w->logit_w, R, R, 1};
-        RC(gemm(stream, 0, 0, N, V1, r->partial, V1, &sl, 1, r->partial, r->partial_capacity, 1, &splits));
-        const float *gum = r->gumbel ? r->gumbel + (size_t)t * N * V1 : nullptr;
-        if (sched && t + 1 < T) {
-            // AttModel.py:145-154: the token chosen here is the INPUT of step t+1 -- forced[:, t+1] (ss_mode 2 rows) or a categorical
-            // draw from this step's log-probs (ss_mode 1 rows); the same launch embeds it (plain Embedding: no ReLU, no mask).  A
-            // drawn 0 does not end the row: the labels decide that (no_finish_mask).
-            capmi_next_embed ne{};
-            ne.E = w->embed; ne.Edim = E; ne.relu = 0;
-            ne.x = r->x + (size_t)(t + 1) * N * E;
-            ne.it_save = r->it_all + (size_t)(t + 1) * N;
-            RC(capmi_logsoftmax_select_partial(slabs, splits, (int64_t)N * V1, w->logit_b, N, V1, t, L, 2,
-                                               r->ss_mode + (size_t)(t + 1) * N, 1.f, gum, r->seed, r->forced + 1, r->forced_ld, 1,
-                                               r->seq, L, r->it, r->unfinished, r->seq_logp, r->sel_logp, r->live, &ne, nullptr,
-                                               stream));
-            continue;
-        }
-        RC(capmi_logsoftmax_select_partial(slabs, splits, (int64_t)N * V1, w->logit_b, N, V1, t, L, r->teacher ? 2 : r->mode,
-                                           nullptr, r->temperature, gum, r->seed, r->forced, r->forced_ld, r->teacher ? 1 : 0, r->seq,
-                                           L, r->it, r->unfinished, r->seq_logp, r->sel_logp, r->live, nullptr, nullptr, stream));
+        RC(logit_slabs(stream, h_drop, w->logit_w, N, V1, R, r->partial, r->partial_capacity, &splits));
+        RC(select_step(io, t, slabs, splits, w->logit_b, emb, stream));
     }
     return 0;
 }
@@ -194,24 +179,22 @@ int capmi_newfc_rollout_fwd(const capmi_newfc_weights *w, capmi_newfc_rollout *r
 int capmi_newfc_rollout_bwd(const capmi_newfc_weights *w, const capmi_newfc_rollout *r, const float *g_seq_logp,
                             capmi_newfc_bwd_scratch *s, capmi_newfc_grads *g, void *stream) {
     if (!w || !r || (!g_seq_logp && !(s && s->sparse)) || !s || !g) return CAPMI_EINVAL;
-    const int B = r->B, n = r->n, N = r->N, R = r->R, E = r->E, V1 = r->V1, T = r->T, L = r->L;
+    const int B = r->B, n = r->n, N = r->N, R = r->R, E = r->E, V1 = r->V1, T = r->T;
     hipStream_t st = (hipStream_t)stream;
     const size_t NR = (size_t)N * R;
     const int TN = T * N;
     float *P = s->partial;
     const int64_t cap = s->partial_capacity;
-    RC(dlogits_bwd((r->mode & CAPMI_SELECT_RAW) && !r->teacher, s->sparse, g_seq_logp, r->seq_logp, r->live, s->dlogits, N, L, T,
-                   V1, stream));
+    RC(logit_bwd_head(select_io(r), s->sparse, g_seq_logp, s->dlogits, w->logit_w, R, s->d_hdrop, P, cap, stream));
     static const int env_group = capmi::knob("CAPMI_GEMM_GROUP", 1);
     const bool grouped = env_group != 0;
     capmi_group_gemm grp[3];
     int n_grp = 0;
     {
-        SegSpec a{s->dlogits, V1, w->logit_w, R, V1, 1};
-        RC(gemm(stream, 0, 1, TN, R, s->d_hdrop, R, &a, 1, P, cap, 0, nullptr));
         // r6: the three time-batched weight gradients (logit, i2h, h2h: K = T * N rows -- 1 050 at bs10 x 5, not a multiple of 4, which
         // sent them to the exact-fp32 tile kernel: 263 us of a 1.9-ms step) are listed and go out as ONE grouped launch at the end;
-        // the logit bias gradient rides in it.  CAPMI_GEMM_GROUP=0: one launch each, as before.
+        // the logit bias gradient rides in it.  CAPMI_GEMM_GROUP=0: one launch each, as before.  (Not grouped_dw_with_bias: the
+        // bias's own column sum goes out HERE, before BPTT, and the listing is interleaved with that route.)
         if (grouped) {
             grp[n_grp++] = capmi_group_gemm{s->dlogits, r->h_drop, g->logit_w, V1, R, R, TN, V1, R, 0, 0,
                                             aligned16(g->logit_b) ? g->logit_b : nullptr};
@@ -223,20 +206,15 @@ int capmi_newfc_rollout_bwd(const capmi_newfc_weights *w, const capmi_newfc_roll
         }
     }
     for (int t = T - 1; t >= -1; --t) {
-        const bool last = (t == T - 1);
         const int slot = t + 1;                       // saved / d_sums slot (0 = image step)
         float *d_sums = s->d_sums + (size_t)slot * N * 5 * R;
-        const float *dh_next = last ? nullptr : s->dh_prev + (size_t)((t + 1) & 1) * NR;
-        float *dh_out = s->dh_prev + (size_t)(t & 1) * NR;
-        const float *dc_in = last ? nullptr : s->dc + (size_t)((t + 1) & 1) * NR;
-        float *dc_out = s->dc + (size_t)(t & 1) * NR;
         RC(capmi_maxout_cell_bwd(t >= 0 ? s->d_hdrop + (size_t)t * NR : nullptr,
-                                 (t >= 0 && r->drop_out) ? r->drop_out + (size_t)t * NR : nullptr, dh_next, dc_in,
-                                 r->saved + (size_t)slot * N * 5 * R, r->c + (size_t)slot * NR, r->c + (size_t)(slot + 1) * NR,
-                                 d_sums, dc_out, N, R, stream));
+                                 (t >= 0 && r->drop_out) ? r->drop_out + (size_t)t * NR : nullptr, pp_in(s->dh_prev, t, T, NR),
+                                 pp_in(s->dc, t, T, NR), r->saved + (size_t)slot * N * 5 * R, r->c + (size_t)slot * NR,
+                                 r->c + (size_t)(slot + 1) * NR, d_sums, pp_out(s->dc, t, NR), N, R, stream));
         if (t >= 0) {   // dh_prev = d_sums W_h2h (the image step's predecessor state is the constant zero)
             SegSpec a{d_sums, 5 * R, w->h2h_w, R, 5 * R, 1};
-            RC(gemm(stream, 0, 1, N, R, dh_out, R, &a, 1, P, cap, 0, nullptr));
+            RC(gemm(stream, 0, 1, N, R, pp_out(s->dh_prev, t, NR), R, &a, 1, P, cap, 0, nullptr));
         }
     }
     // time-batched gradients.  d_sums slots 1..T belong to the word steps, slot 0 to the image step.
@@ -265,10 +243,8 @@ int capmi_newfc_rollout_bwd(const capmi_newfc_weights *w, const capmi_newfc_roll
             grp[n_grp++] = capmi_group_gemm{ds_words, r->h + NR, g->h2h_w, 5 * R, R, R, TN, 5 * R, R, 0, 0, nullptr};
         } else RC(gemm(stream, 1, 1, 5 * R, R, g->h2h_w, R, &c, 1, P, cap, 0, nullptr));
         // word embeddings (plain Embedding: no ReLU, no dropout)
-        SegSpec x{ds_words, 5 * R, w->i2h_w, E, 5 * R, 1};
-        RC(gemm(stream, 0, 1, TN, E, s->d_x_all, E, &x, 1, P, cap, 0, nullptr));
-        HIP_RC(hipMemsetAsync(g->embed, 0, (size_t)V1 * E * sizeof(float), st));
-        RC(capmi_embed_bwd(r->it_all, s->d_x_all, nullptr, nullptr, g->embed, TN, E, 0, stream));
+        RC(embed_grad(stream, SegSpec{ds_words, 5 * R, w->i2h_w, E, 5 * R, 1}, TN, E, s->d_x_all, r->it_all, nullptr, nullptr, 0,
+                      g->embed, V1, P, cap));
     }
     if (n_grp) RC(capmi_gemm_group_tn(grp, n_grp, cap > CAPMI_WS_COUNTER_FLOATS ? P + CAPMI_WS_COUNTER_FLOATS : nullptr,
                                       cap > CAPMI_WS_COUNTER_FLOATS ? cap - CAPMI_WS_COUNTER_FLOATS : 0, stream));

@@ -14,7 +14,7 @@
 //    only the 4 skinny "dX" GEMMs + the pointwise cells + the attention Jacobian stay in the loop.
 #include <chrono>
 #include <cstdlib>
-#include "host_common.h"
+#include "rollout_common.h"
 
 namespace {
 
@@ -139,17 +139,19 @@ int capmi_updown_rollout_fwd(const capmi_updown_weights *w, capmi_updown_rollout
     if (!w || !r) return CAPMI_EINVAL;
     const int B = r->B, n = r->n, N = r->N, K = r->K, A = r->A, R = r->R, E = r->E, V1 = r->V1, T = r->T, L = r->L;
     const int B_feat = r->B_feat > 0 ? r->B_feat : B;
-    if (B <= 0 || n <= 0 || N <= 0 || T <= 0 || L < T || !r->partial || B_feat < B) return CAPMI_EINVAL;
+    if (B <= 0 || n <= 0 || !r->partial || B_feat < B) return CAPMI_EINVAL;
     if (!r->row_img && (N != B * n || B_feat != B)) return CAPMI_EINVAL;
     if (r->row_img && N < B * n) return CAPMI_EINVAL;
-    if ((r->mode == 2 || r->teacher) && !r->forced) return CAPMI_EINVAL;
+    SelectIO io = select_io(r);
+    if (!r->teacher) io.ss_mode = nullptr;            // this driver has always ignored ss_mode without teacher forcing
+    RC(check_rollout_io(io));
     hipStream_t st = (hipStream_t)stream;
     const size_t NR = (size_t)N * R;
     const int ld_att_ih = 2 * R + E;
     // teacher forcing knows every input token up front: the vocabulary projection + log-softmax of all T steps run as ONE
     // fat GEMM over T*N rows after the loop (20 launches of a 320-row GEMM + 20 select launches otherwise)
     // scheduled sampling: the next input may be a draw from this step's distribution, so the steps stay sequential
-    const bool sched = r->teacher && r->ss_mode;
+    const bool sched = scheduled(io);
     const bool batched_logit = r->teacher && !sched && T == L && r->seq_logp &&
                                (int64_t)N * T * R <= r->partial_capacity - CAPMI_WS_COUNTER_FLOATS;
 
@@ -203,6 +205,10 @@ int capmi_updown_rollout_fwd(const capmi_updown_weights *w, capmi_updown_rollout
     }
     if (ee) for (int t = 0; t < L; ++t) r->alive_host[t] = 0;
     int ee_pending = -1, ee_slot = 0, steps_run = T;
+    // the select's side: UpDown's extras, and the embedding (ReLU + dropout) every select launch folds in for the step after it
+    io.row_mode = r->row_mode; io.filter = capmi_sample_filter{r->top_k, r->top_p}; io.raw_flag = raw_flag;
+    io.x_planes = pl_xt; io.alive = ee ? r->alive_host : nullptr;
+    const EmbedSpec emb{w->embed, E, 1, r->drop_xt, r->xt, true};
     const int ee_from = r->early_exit_from > 0 ? r->early_exit_from : 0;
 
     // r5: teacher forcing knows every INPUT token up front too (AttModel.py:140-164): the token-embedding third of the attention-LSTM
@@ -310,31 +316,7 @@ int capmi_updown_rollout_fwd(const capmi_updown_weights *w, capmi_updown_rollout
         if (batched_logit) continue;
         // 8-9. vocabulary projection left as K-slice slabs; log-softmax + choice + bookkeeping assemble the row
         //      (slabs + bias) in registers: no split-K reduce launch, no logits round trip
-        {
-            SegSpec s{h_drop, R, w->logit_w, R, R, 1, pl_h_drop};
-            RC(gemm(stream, 0, 0, N, V1, r->partial, V1, &s, 1, r->partial, r->partial_capacity, 1, &splits, nullptr, nullptr, 0,
-                    pl_zero));
-        }
-        capmi_sample_filter flt{r->top_k, r->top_p};
-        capmi_next_embed ne{};
-        if ((!r->teacher || sched) && t + 1 < T) {
-            ne.E = w->embed; ne.Edim = E; ne.relu = 1;
-            ne.mask = r->drop_xt ? r->drop_xt + (size_t)(t + 1) * N * E : nullptr;
-            ne.x = r->xt + (size_t)(t + 1) * N * E;
-            ne.it_save = r->it_all ? r->it_all + (size_t)(t + 1) * N : nullptr;
-            ne.x_planes = pl_xt;
-        }
-        if (ee) ne.alive = r->alive_host + t;
-        if (sched && t + 1 < T) {
-            // AttModel.py:145-154: the token chosen here is the INPUT of step t+1 -- forced[:, t+1] (mode 2 rows) or a
-            // categorical draw from this step's log-probs (mode 1 rows, temperature 1); it is embedded by the same launch
-            RC(capmi_logsoftmax_select_partial(r->partial + CAPMI_WS_COUNTER_FLOATS, splits, (int64_t)N * V1, w->logit_b, N, V1,
-                                               t, L, 2, r->ss_mode + (size_t)(t + 1) * N, 1.f,
-                                               r->gumbel ? r->gumbel + (size_t)t * N * V1 : nullptr, r->seed, r->forced + 1,
-                                               r->forced_ld, 1, r->seq, L, r->it, r->unfinished, r->seq_logp, r->sel_logp,
-                                               r->live, &ne, nullptr, stream));
-            continue;
-        }
+        RC(logit_slabs(stream, h_drop, w->logit_w, N, V1, R, r->partial, r->partial_capacity, &splits, pl_h_drop, pl_zero));
         preA_valid = false;
         if (use_pre && t + 1 < T) {
             // select of step t + [h_lang(t) | h_att(t)] . [W_ih(:, 0:R) | W_hh]^T of step t+1's attention LSTM in ONE launch
@@ -347,19 +329,16 @@ int capmi_updown_rollout_fwd(const capmi_updown_weights *w, capmi_updown_rollout
             ah.partial = preA; ah.partial_capacity = r->pre_capacity;
             ah.splits = 6;                            // 32 column blocks x 6 K slices = 192 workgroups beside the N select rows
             ah.defer_reduce = 1;
+            const capmi_next_embed ne = next_embed(io, t, emb);
             RC(capmi_logsoftmax_select_partial_gemm(r->partial + CAPMI_WS_COUNTER_FLOATS, splits, (int64_t)N * V1, w->logit_b, N, V1, t, L,
                                                     r->mode | raw_flag, r->row_mode, r->temperature,
                                                     r->gumbel ? r->gumbel + (size_t)t * N * V1 : nullptr, r->seed, r->forced,
                                                     r->forced_ld, 0, r->seq, L, r->it, r->unfinished, r->seq_logp, r->sel_logp,
-                                                    r->live, &ne, (r->top_k > 0 || r->top_p > 0.f) ? &flt : nullptr, &ah, stream));
+                                                    r->live, &ne, (r->top_k > 0 || r->top_p > 0.f) ? &io.filter : nullptr, &ah, stream));
             preA_splits = ah.splits_used;
             preA_valid = true;
-        } else
-        RC(capmi_logsoftmax_select_partial(r->partial + CAPMI_WS_COUNTER_FLOATS, splits, (int64_t)N * V1, w->logit_b, N, V1, t,
-                                           L, r->teacher ? 2 : (r->mode | raw_flag), r->teacher ? nullptr : r->row_mode, r->temperature,
-                                           r->gumbel ? r->gumbel + (size_t)t * N * V1 : nullptr, r->seed, r->forced,
-                                           r->forced_ld, r->teacher ? 1 : 0, r->seq, L, r->it, r->unfinished, r->seq_logp,
-                                           r->sel_logp, r->live, &ne, (r->top_k > 0 || r->top_p > 0.f) ? &flt : nullptr, stream));
+        } else      // (scheduled sampling, teacher forcing without the batched logit, no ahead workspace)
+            RC(select_step(io, t, r->partial + CAPMI_WS_COUNTER_FLOATS, splits, w->logit_b, emb, stream));
         // (no check in the last 8 steps: after its last wait the host needs a lead of several decode steps to enqueue the reward
         //  and the backward behind the rollout without the device running dry -- a check at step 15 of 20 cost 2.5 % end to end)
         if (ee && ee_pending < 0 && t >= ee_from && (t + 1 - ee_from) % ee == 0 && t + 9 <= T) {
@@ -405,7 +384,7 @@ int capmi_updown_rollout_bwd(const capmi_updown_weights *w, const capmi_updown_r
 int capmi_updown_rollout_bwd_phases(const capmi_updown_weights *w, const capmi_updown_rollout *r, const float *g_seq_logp,
                                     capmi_updown_bwd_scratch *s, capmi_updown_grads *g, int phases, void *stream) {
     if (!w || !r || (!g_seq_logp && !(s && s->sparse)) || !s || !g || !(phases & CAPMI_BWD_ALL)) return CAPMI_EINVAL;
-    const int B = r->B, n = r->n, Nf = r->N, K = r->K, A = r->A, R = r->R, E = r->E, V1 = r->V1, T = r->T, L = r->L;
+    const int B = r->B, n = r->n, Nf = r->N, K = r->K, A = r->A, R = r->R, E = r->E, V1 = r->V1, T = r->T;
     hipStream_t st = (hipStream_t)stream;
     // Rows [0, N) of the rollout carry gradient.  N = all Nf rows, or -- fused SCST rollout, s->n_grad_rows -- the sampled rows
     // only: the greedy-baseline rows behind them would ride through every time-batched GEMM as zeros (K or M = T*60 instead of
@@ -545,9 +524,9 @@ int capmi_updown_rollout_bwd_phases(const capmi_updown_weights *w, const capmi_u
 
     // ---- logit layer, batched over all T*N rows ----------------------------------------------
     if (phases & CAPMI_BWD_LOGIT) {
-        RC(dlogits_bwd(r->raw_logits && !r->teacher, s->sparse, g_seq_logp, r->seq_logp, r->live, s->dlogits, N, L, T, V1, stream));
-        SegSpec a{s->dlogits, V1, w->logit_w, R, V1, 1};   // d_hdrop = dlogits W_logit          [TN,R]
-        RC(gemm(stream, 0, 1, TN, R, s->d_hdrop, R, &a, 1, P, cap, 0, nullptr));
+        SelectIO io = select_io(r);
+        io.N = N; io.raw_flag = r->raw_logits ? CAPMI_SELECT_RAW : 0;
+        RC(logit_bwd_head(io, s->sparse, g_seq_logp, s->dlogits, w->logit_w, R, s->d_hdrop, P, cap, stream));
         SegSpec b{s->dlogits, V1, a_hdrop, R, TN, 1};       // dW_logit = dlogits^T h_drop         [V1,R]
         // r5 (profiles/r05_scst_overlap.md): nothing reads dW_logit before the optimizer: it runs on the side stream beside the
         // time loop (no split-K workspace there: the loop owns P)
@@ -689,10 +668,8 @@ int capmi_updown_rollout_bwd_phases(const capmi_updown_weights *w, const capmi_u
             RC(gemm(stream, 0, 1, B, R, g->d_fc, R, &f, 1, P, cap, 0, nullptr));
         }
         // token embedding: d_xt = dg_att W_ih(:, 2R:) then scatter through ReLU/dropout
-        SegSpec x{s->dg_att, 4 * R, w->att_w_ih + 2 * R, ld_att_ih, 4 * R, 1};
-        RC(gemm(stream, 0, 1, TN, E, s->d_xt_all, E, &x, 1, P, cap, 0, nullptr));
-        HIP_RC(hipMemsetAsync(g->embed, 0, (size_t)V1 * E * sizeof(float), st));
-        RC(capmi_embed_bwd(a_it, s->d_xt_all, a_xt, a_dropxt, g->embed, TN, E, 1, stream));
+        RC(embed_grad(stream, SegSpec{s->dg_att, 4 * R, w->att_w_ih + 2 * R, ld_att_ih, 4 * R, 1}, TN, E, s->d_xt_all, a_it, a_xt,
+                      a_dropxt, 1, g->embed, V1, P, cap));
     }
     // language LSTM
     if (phases & CAPMI_BWD_LANG_LSTM) RC(colsum(s->dg_lang, TN, 4 * R, g->lang_b_ih, g->lang_b_hh));
