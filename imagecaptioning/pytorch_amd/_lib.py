@@ -228,6 +228,17 @@ class Ppo(C.Structure):
                 [(k, c_f) for k in ('lp_new', 'lp_old', 'seq', 'scores', 'row_stats', 'msum', 'out', 'loss_rows', 'g_out', 'grad')])
 
 
+LANGEVAL_LMAX = 64     # capmi.h CAPMI_LANGEVAL_LMAX
+LANGEVAL_E_TABLE_FULL, LANGEVAL_E_TOKEN, LANGEVAL_E_IMAGE = 1, 2, 4      # capmi.h CAPMI_LANGEVAL_E_*
+
+
+class LangEval(C.Structure):
+    """capmi_langeval (include/capmi.h): the references of a split, their document-frequency table and the per-image results"""
+    _fields_ = ([(k, C.c_int) for k in ('n_img', 'total_refs', 'ref_w')] +
+                [(k, c_f) for k in ('refs', 'ref_off', 'table_keys', 'table_counts')] + [('table_cap', C.c_uint32)] +
+                [(k, c_f) for k in ('ref_norm', 'cider', 'rouge', 'bleu_stats', 'lens', 'lcs', 'seen', 'err')])
+
+
 _I, _F, _P, _U64, _I64 = C.c_int, C.c_float, C.c_void_p, C.c_uint64, C.c_int64
 DECODE_NO_REPEAT, DECODE_NO_BAD_ENDING, DECODE_BLOCK_TRIGRAMS = 1, 2, 4      # capmi.h CAPMI_DECODE_*
 SELECT_RAW = 256       # capmi.h CAPMI_SELECT_RAW: OR into the select `mode` -- the stored rows are the logits, not the log-probabilities
@@ -350,6 +361,9 @@ SIGNATURES = {
     'capmi_ensemble_logprobs': [C.POINTER(Ensemble), _P],
     'capmi_ppo_loss_fwd': [C.POINTER(Ppo), _P],
     'capmi_ppo_loss_bwd': [C.POINTER(Ppo), _P],
+    'capmi_langeval_build': [C.POINTER(LangEval), _P],
+    'capmi_langeval_add': [C.POINTER(LangEval), _P, _I, _I, _P, _P],
+    'capmi_langeval_reduce': [C.POINTER(LangEval), _P, _P, _P],
     'capmi_updown_rollout_fwd': [C.POINTER(UpDownWeights), C.POINTER(UpDownRollout), _P],
     'capmi_updown_rollout_bwd': [C.POINTER(UpDownWeights), C.POINTER(UpDownRollout), _P, C.POINTER(UpDownBwdScratch),
                                  C.POINTER(UpDownGrads), _P],

@@ -174,6 +174,16 @@ class FeatureLoader:
         refs = [self.label[self.label_start_ix[ix] - 1: self.label_end_ix[ix]] for ix in self.split_ix['train']]
         return synthetic.document_frequency(refs)
 
+    def language_eval_refs(self, split):
+        """(rows int64 [total_refs, L], offsets [n_img + 1], image ix per position): all captions of the WHOLE split (not of
+        this rank's part: the document frequency is the split's), as eval_utils.language_eval scores against the annotation
+        file's captions of the evaluated images"""
+        ixs = list(self.split_ix[split])
+        parts = [self.label[self.label_start_ix[ix] - 1: self.label_end_ix[ix]] for ix in ixs]
+        off = np.concatenate([[0], np.cumsum([p.shape[0] for p in parts])]).astype(np.int64)
+        rows = (np.concatenate(parts) if parts else np.zeros((0, self.seq_length))).astype(np.int64)
+        return rows, off, ixs
+
     # ---- one image
     def _image(self, ix):
         return decode_image(self.att_dir, self.fc_dir, self.info['images'][ix]['id'], self.use_fc, self.norm_att_feat)

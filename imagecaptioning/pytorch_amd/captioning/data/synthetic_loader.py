@@ -39,6 +39,13 @@ class SyntheticLoader:
     def document_frequency(self):
         return synthetic.document_frequency(self.refs)
 
+    def language_eval_refs(self, split):
+        """(rows int64 [total_refs, L], offsets [n_img + 1], image ix per position): the references language_eval scores the
+        split against (every split of the synthetic corpus holds the same images)"""
+        n_img = len(self.refs)
+        rows = np.concatenate(self.refs).astype(np.int64)
+        return rows, np.arange(n_img + 1, dtype=np.int64) * 5, list(range(n_img))
+
     def reset_iterator(self, split):
         """DataLoader.reset_iterator (dataloader.py:356-358)"""
         self.pos[split] = 0

@@ -73,7 +73,8 @@ class LRSchedule:
       * linear warm-up                          tools/train.py:171-173  (use_warmup, noamopt_warmup)
       * Noam schedule                           misc.py:159-185 NoamOpt.rate(), get_std_opt(): lr ignores learning_rate
       * reduce on plateau                       misc.py:199-216 -> torch ReduceLROnPlateau(mode='min', rel threshold 1e-4),
-                                                stepped with the validation loss (tools/train.py:253-256)
+                                                stepped with the validation loss, or with -CIDEr under language_eval
+                                                (tools/train.py:252-256)
     """
 
     def __init__(self, opt, model_size=None):

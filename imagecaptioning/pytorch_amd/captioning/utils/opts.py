@@ -27,6 +27,9 @@ DEFAULTS = dict(
     group_size=1, diversity_lambda=0.5, decoding_constraint=0, block_trigrams=0, remove_bad_endings=0, sample_n=1,
     sample_n_method='sample', verbose_beam=0,                                # opts.py:288-330 add_eval_sample_opts
     split='test',                                                            # opts.py:314 add_eval_options
+    # opts.py:127 / :311 language_eval: corpus CIDEr / BLEU-1..4 / ROUGE-L on the device (imagecaptioning/pytorch_amd/langeval.py; METEOR
+    # and SPICE need Java).  eval_results_dir: where tools/eval.py writes <id>_<split>.json (the reference: always ./eval_results)
+    language_eval=0, eval_results_dir='eval_results',
     # data (synthetic only: the reference's h5/lmdb loaders are outside the hot path)
     input_synthetic=1, vocab_size=9487, synthetic_regions=36, synthetic_images=200,
     # real precomputed features (captioning/data/feature_loader.py; opts.py:23-37 of the reference)

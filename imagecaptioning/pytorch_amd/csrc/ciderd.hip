@@ -12,34 +12,20 @@
 // This kernel is latency bound (a few thousand dependent hash probes, < 0.5 MB touched): there is no
 // HBM or MFMA roofline to chase, the win is removing the device->host sync from the SCST step.
 #include "capmi_common.h"
+#include "ngram_common.h"
 #include "profile.h"
 #include "../../../include/capmi.h"
 
 namespace {
 
+using capmi::df_lookup;
+using capmi::ngram_tf;
+using capmi::pack_ngram;
+
 constexpr int LMAX = 64;            // max tokens per sequence (reference: seq_length 16..30)
 constexpr int NG = 4;               // n-gram orders 1..4
 constexpr int CT = NG * LMAX;       // one lane per (order, start position)
 constexpr double SIGMA = 6.0;
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {   // splitmix64 finaliser (host twin in ciderd.py)
-    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ULL;
-    x ^= x >> 27; x *= 0x94d049bb133111ebULL;
-    x ^= x >> 31;
-    return x;
-}
-
-__device__ __forceinline__ double df_lookup(const uint64_t *__restrict__ keys, const double *__restrict__ vals,
-                                            uint32_t cap, uint64_t key) {
-    uint32_t slot = (uint32_t)mix64(key) & (cap - 1);
-    for (uint32_t probe = 0; probe < cap; ++probe) {
-        const uint64_t k = keys[slot];
-        if (k == key) return vals[slot];
-        if (k == 0) return 0.0;           // missing n-gram: document frequency 0
-        slot = (slot + 1) & (cap - 1);
-    }
-    return 0.0;
-}
 
 struct Cooked {
     uint64_t key[CT];
@@ -65,21 +51,12 @@ __device__ void cook(const int *tok, int w, Cooked &c, const uint64_t *keys, con
     __syncthreads();
     const int len = c.len;
     const bool valid = (i + k + 1 <= len);
-    uint64_t key = 0;
-    if (valid)
-        for (int q = 0; q <= k; ++q) key |= (uint64_t)(tok[i + q] + 1) << (16 * q);
+    const uint64_t key = valid ? pack_ngram(tok, i, k) : 0;
     c.key[tid] = key;
     __syncthreads();
     int tf = 0;
     bool first = valid;
-    if (valid) {
-        const int cnt = len - k;      // positions of this order
-        for (int j = 0; j < cnt; ++j) {
-            const bool same = c.key[k * LMAX + j] == key;
-            tf += same;
-            if (same && j < i) first = false;
-        }
-    }
+    if (valid) tf = ngram_tf(&c.key[k * LMAX], len - k, key, i, first);      // len - k positions of this order
     double v = 0.0;
     if (first) {
         const double df = df_lookup(keys, vals, cap, key);

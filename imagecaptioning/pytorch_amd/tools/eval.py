@@ -2,10 +2,13 @@
 """Evaluation entrypoint on the MI355X backend -- the decode half of the reference's tools/eval.py:23-125 +
 eval_utils.eval_split / eval_split_n (eval_utils.py:128-290): XE validation loss, decode with every sampler option of the
 command line (beam / diverse beam search, sampling variants, decoding constraints), sample_n captions per image,
-per-caption entropy and perplexity from seqLogprobs (:173-174), decoded strings.  (language_eval needs coco-caption + Java: out of scope.)
+per-caption entropy and perplexity from seqLogprobs (:173-174), decoded strings.  --language_eval 1 (eval_utils.py:47-125): corpus
+CIDEr, BLEU-1..4 and ROUGE-L of the single-caption pass, scored on the device over token ids (imagecaptioning/pytorch_amd/langeval.py)
+and written to <eval_results_dir>/<id>_<split>.json as {'overall', 'imgToEval'}; METEOR and SPICE need Java and are absent.
 
     python -m imagecaptioning.pytorch_amd.tools.eval --caption_model updown --beam_size 5 --num_images 20 [--start_from DIR]
 """
+import json
 import os
 import sys
 
@@ -71,6 +74,10 @@ def eval_split(model, crit, loader, opt):
     model.eval()
     n, loss_sum, loss_n, preds, n_preds = 0, 0.0, 0, [], []
     split = getattr(opt, 'split', 'val')
+    lang = None
+    if getattr(opt, 'language_eval', 0):
+        from imagecaptioning.pytorch_amd.langeval import LanguageEval
+        lang = LanguageEval.for_loader(loader, split, dev)
     if hasattr(loader, 'reset_iterator'):
         loader.reset_iterator(split)                                                                           # eval_utils.py:145
     num_images = opt.num_images
@@ -104,6 +111,11 @@ def eval_split(model, crit, loader, opt):
                 print('--' * 10)
         sents = misc.decode_sequence(model.vocab, seq)
         rows_per_image = max(1, len(sents) // len(data['infos']))
+        if lang is not None:
+            # the first row of each image, images past num_images left out (eval_utils.py:209-210 pops their predictions); the rows
+            # stay on the device, nothing is read back before lang.compute()
+            keep = max(0, min(len(data['infos']), num_images - n))
+            lang.add_batch(data['infos'][:keep], seq[::rows_per_image][:keep])
         for k, s in enumerate(sents):
             preds.append({'image_id': data['infos'][k // rows_per_image]['id'], 'caption': s, 'perplexity': perplexity[k].item(),
                           'entropy': entropy[k].item()})
@@ -114,7 +126,26 @@ def eval_split(model, crit, loader, opt):
         n_preds = sorted(n_preds, key=lambda x: x['perplexity'])                                               # :217-218
     model.n_predictions = n_preds
     model.train()                                                                                              # :224-225
-    return loss_sum / max(loss_n, 1), preds[:num_images * max(1, len(preds) // max(n, 1))]
+    preds = preds[:num_images * max(1, len(preds) // max(n, 1))]
+    if lang is not None:
+        return loss_sum / max(loss_n, 1), preds, language_eval(lang, preds, opt, split)
+    return loss_sum / max(loss_n, 1), preds
+
+
+def language_eval(lang, preds, opt, split):
+    """eval_utils.language_eval (:47-125) for the Java-free scorers: lang_stats = {'Bleu_1'..'Bleu_4', 'ROUGE_L', 'CIDEr'}, written
+    with the per-image CIDEr and caption as {'overall', 'imgToEval'} to <eval_results_dir>/<id>_<split>.json (:122-124)."""
+    lang_stats, img_cider = lang.compute()
+    img_to_eval = {}
+    for p in preds:                                            # one entry per image: the first caption, the one that was scored
+        pos = lang.pos_of_id.get(p['image_id'])
+        if pos is not None and p['image_id'] not in img_to_eval and img_cider[pos] == img_cider[pos]:
+            img_to_eval[p['image_id']] = {'image_id': p['image_id'], 'CIDEr': float(img_cider[pos]), 'caption': p['caption']}
+    out_dir = getattr(opt, 'eval_results_dir', 'eval_results')
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, '%s_%s.json' % (getattr(opt, 'id', 'capmi'), split)), 'w') as f:
+        json.dump({'overall': lang_stats, 'imgToEval': img_to_eval}, f)
+    return lang_stats
 
 
 def build_loader(opt, dev):
@@ -148,11 +179,19 @@ def main(opt):
     if opt.start_from:
         model.load_state_dict(torch.load(os.path.join(opt.start_from, 'model.pth'), map_location=dev))
     crit = losses.LabelSmoothing(smoothing=opt.label_smoothing) if opt.label_smoothing > 0 else losses.LanguageModelCriterion()
-    loss, preds = eval_split(model, crit, loader, opt)
-    print('loss: ', loss)
-    for p in preds[:5]:
+    res = eval_split(model, crit, loader, opt)
+    report(res)
+    return res
+
+
+def report(res):
+    """tools/eval.py:107-109: the loss, the first captions, and lang_stats when the pass computed them"""
+    print('loss: ', res[0])
+    for p in res[1][:5]:
         print('image %s: %s' % (p['image_id'], p['caption']))
-    return loss, preds
+    if len(res) > 2:
+        print(res[2])
+        print('(METEOR and SPICE are absent: they need Java)')
 
 
 if __name__ == '__main__':

@@ -3,7 +3,8 @@
 every --ids entry names a training run's log directory, log_<id>/infos_<id>[-suffix].pkl and log_<id>/model[-suffix].pth
 (an id may carry a -suffix: the checkpoint misc.save_checkpoint(..., append=suffix) wrote).  Each member is rebuilt from its own
 infos' options, the vocabulary comes from the first infos, the ensemble (captioning.models.AttEnsemble) decodes for max_length
-steps, and eval.eval_split reports the validation loss of the teacher-forced ensemble and the captions.
+steps, and eval.eval_split reports the validation loss of the teacher-forced ensemble and the captions (with --language_eval 1
+also lang_stats: corpus CIDEr, BLEU-1..4 and ROUGE-L, as tools/eval.py).
 
     python -m imagecaptioning.pytorch_amd.tools.eval_ensemble --ids A B-best --weights 0.5 0.5 --beam_size 5 [--log_root DIR]
 
@@ -22,7 +23,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 # the options of the reference's add_eval_options / add_diversity_opts: command line or default, never the training run's
 EVAL_KEYS = ('beam_size', 'sample_method', 'temperature', 'suppress_UNK', 'length_penalty', 'group_size', 'diversity_lambda',
              'decoding_constraint', 'block_trigrams', 'remove_bad_endings', 'max_length', 'num_images', 'device', 'sample_n',
-             'sample_n_method', 'verbose_beam', 'split')
+             'sample_n_method', 'verbose_beam', 'split', 'language_eval', 'eval_results_dir')
 
 
 def split_id(entry):
@@ -97,11 +98,9 @@ def main(argv=None):
     opt.vocab = vocab
     opt.id = '+'.join('%s%s' % (i, w) for i, w in zip(ids, weights or [1.0] * len(ids)))   # :98
     crit = losses.LanguageModelCriterion()                              # :84
-    loss, preds = E.eval_split(model, crit, loader, opt)
-    print('loss: ', loss)
-    for p in preds[:5]:
-        print('image %s: %s' % (p['image_id'], p['caption']))
-    return loss, preds
+    res = E.eval_split(model, crit, loader, opt)           # (loss, preds), or (loss, preds, lang_stats) with --language_eval 1
+    E.report(res)
+    return res
 
 
 if __name__ == '__main__':

@@ -3,7 +3,9 @@
 hot path: learning-rate decay / warm-up / Noam / reduce-on-plateau (:94-102, :132-141, :171-173, :253-256), XE /
 self-critical / new-self-critical scheduling (:144-161), LossWrapper call (:185), backward, value clip + Adam
 (:193-196), `time/batch` print (:198-208), periodic validation loss and checkpoint (:228-285), bucketed flat-gradient
-RCCL all-reduce overlapped with the backward when launched with torch.distributed.run.
+RCCL all-reduce overlapped with the backward when launched with torch.distributed.run.  With language_eval 1 the validation
+pass also decodes and scores corpus CIDEr / BLEU / ROUGE-L on the device: CIDEr decides best_val_score, model-best.pth and the
+plateau schedule (:252-266, :284-286).
 
     python -m imagecaptioning.pytorch_amd.tools.train --caption_model updown --rnn_size 1000 --input_encoding_size 1000 \
         --self_critical_after 0 --train_sample_n 5 --max_iters 50
@@ -19,12 +21,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))           # so that `captioning` resolves to the mirror package
 
 
-def validation_loss(lw_model, loader, opt, dev, world=1):
+def validation_loss(lw_model, loader, opt, dev, world=1, lang=None):
     """XE loss over `val_images` images of the val split, teacher forced, eval mode (eval_utils.py:150-160).  With `world`
     data-parallel ranks the val split is partitioned like the train split: each rank scores at most its share
     (val_images / world, never more than its partition holds) and returns (sum of per-image losses, images) so that the caller
     can all-reduce BOTH and every image counts once, whatever the partition sizes.  A rank whose partition is empty (val split
-    smaller than world) contributes (0, 0)."""
+    smaller than world) contributes (0, 0).
+    lang: a langeval.LanguageEval of the val split -- every batch is also decoded with the command line's sampler options (the
+    reference hands vars(opt) to eval_split, tools/train.py:246-250) and its rows are scored where they are, on the device."""
     from captioning.data.feature_loader import EmptySplit
     model = lw_model.model
     model.eval()
@@ -48,6 +52,12 @@ def validation_loss(lw_model, loader, opt, dev, world=1):
             logp = model(fc, att, labels[..., :-1], att_masks)
             tot += float(lw_model.crit(logp, labels[..., 1:], masks[..., 1:])) * fc.shape[0]
             n += fc.shape[0]
+            if lang is not None:
+                from imagecaptioning.pytorch_amd.tools.eval import eval_kwargs_of
+                kw = eval_kwargs_of(opt)
+                kw['sample_n'] = 1                          # eval_utils.py:169-170
+                seq, _ = model(fc, att, att_masks, mode='sample', opt=kw)
+                lang.add_batch(data['infos'], seq[::max(1, seq.shape[0] // len(data['infos']))])
     model.train()
     return tot, n
 
@@ -152,15 +162,18 @@ def train(opt):
     histories = dict(infos.get('histories') or {'loss_history': {}, 'lr_history': {}, 'ss_prob_history': {}})
     best_val_score = infos.get('best_val_score')
 
-    def checkpoint():
+    def checkpoint(append=''):
         # the prefetcher runs ahead of the loop: the position to resume from is the one of the last CONSUMED batch
         misc.save_checkpoint(opt, model, {'iter': it, 'epoch': epoch, 'opt': opt, 'vocab': opt.vocab,
                                           'loader_pos': dict(last_pos),
                                           # (position of the dropout / sampling streams: the step record's epoch word under TrainStep)
                                           'rng_calls': ts.state_dict()['epoch'] if ts is not None else int(getattr(model, '_rng_calls', 0)),
                                           'best_val_score': best_val_score, 'histories': histories, **last_loader},
-                             optimizer_state={'flat': flat.state_dict(), 'sched': sched.state_dict()})
+                             optimizer_state={'flat': flat.state_dict(), 'sched': sched.state_dict()}, append=append)
 
+    # language_eval (tools/train.py:246-266): rank 0 decodes and scores ITS part of the val split; the references -- hence the
+    # document frequencies -- are the whole split's.  Built at the first validation.
+    lang = None
     iter_times = []
     loss_slots = [(torch.empty(1, dtype=torch.float32, pin_memory=True), torch.cuda.Event()) for _ in range(2)]
     prev_slot = None
@@ -249,8 +262,23 @@ def train(opt):
             epoch += 1
             epoch_done = True
         if opt.val_every and it % opt.val_every == 0:
-            val_sum, val_n = validation_loss(lw_model, loader, opt, dev, world)  # eval_utils.eval_split's loss half (:228-256)
-            if world > 1:
+            lang_stats = None
+            if getattr(opt, 'language_eval', 0) and rank == 0:
+                from imagecaptioning.pytorch_amd.langeval import LanguageEval
+                lang = lang or LanguageEval.for_loader(loader, 'val', dev)
+                lang.reset()
+            val_sum, val_n = validation_loss(lw_model, loader, opt, dev, world, lang)  # eval_utils.eval_split's loss half (:228-256)
+            if lang is not None:
+                lang_stats = lang.compute()[0]
+            if world > 1 and getattr(opt, 'language_eval', 0):
+                # no collective of its own: rank 0's CIDEr rides in the reduction of the loss (the other ranks add 0), so that every
+                # rank steps the plateau schedule on the same number
+                v = torch.tensor([val_sum, float(val_n), lang_stats['CIDEr'] if rank == 0 else 0.0], dtype=torch.float64, device=dev)
+                dist.all_reduce(v)
+                val_sum, val_n = float(v[0]), float(v[1])
+                if rank != 0:
+                    lang_stats = {'CIDEr': float(v[2])}
+            elif world > 1:
                 # every rank evaluates its own images: the plateau decision must see ONE number, or the ranks pick different
                 # learning rates and the replicas drift apart.  (sum, count) are reduced, not per-rank means: partitions of
                 # unequal size (or an empty one) must not bias the mean
@@ -258,11 +286,26 @@ def train(opt):
                 dist.all_reduce(v)
                 val_sum, val_n = float(v[0]), float(v[1])
             val_loss = val_sum / max(val_n, 1.0)
-            sched.plateau_step(val_loss)
-            if best_val_score is None or -val_loss > best_val_score:           # tools/train.py:258-266 (language_eval off: -val_loss)
-                best_val_score = -val_loss
-            if rank == 0:
-                print('validation loss: %.3f (lr %.2e)' % (val_loss, sched.current_lr))
+            if lang_stats is not None:
+                # tools/train.py:252-286: the plateau schedule, best_val_score and model-best.pth follow CIDEr -- SCST raises it
+                # while the XE loss of the ground truth rises too
+                current_score = lang_stats['CIDEr']
+                sched.plateau_step(-current_score)
+                histories.setdefault('val_result_history', {})[it] = {'loss': val_loss, 'lang_stats': lang_stats}
+                best_flag = best_val_score is None or current_score > best_val_score
+                if best_flag:
+                    best_val_score = current_score
+                if rank == 0:
+                    print('validation loss: %.3f, %s (lr %.2e)' % (val_loss, ', '.join('%s %.4f' % kv for kv in lang_stats.items()),
+                                                                    sched.current_lr))
+                    if best_flag and opt.save_checkpoint_every:
+                        checkpoint(append='best')
+            else:
+                sched.plateau_step(val_loss)
+                if best_val_score is None or -val_loss > best_val_score:       # tools/train.py:258-266 (language_eval off: -val_loss)
+                    best_val_score = -val_loss
+                if rank == 0:
+                    print('validation loss: %.3f (lr %.2e)' % (val_loss, sched.current_lr))
         if rank == 0 and opt.save_checkpoint_every and it % opt.save_checkpoint_every == 0:
             checkpoint()
     if prev_slot is not None:            # the loop ended on max_epochs: the last iteration's loss is still in flight

@@ -1283,6 +1283,60 @@ typedef struct capmi_ppo {
 int capmi_ppo_loss_fwd(const capmi_ppo *p, void *stream);
 int capmi_ppo_loss_bwd(const capmi_ppo *p, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Corpus language evaluation without Java: coco-caption's Cider, Bleu (option 'closest') and Rouge over token ids, for the
+ * validation pass (eval_utils.language_eval -> lang_stats['CIDEr'], 'Bleu_1'..'Bleu_4', 'ROUGE_L').  A caption is the tokens of
+ * its int64 row before the first 0 (the whole row when it holds none); ids are below 65535.  Restated from the published
+ * formulas (coco-caption is not part of the reference checkout: PARITY UNPINNED, see tests/langeval_ref64.py).
+ *
+ * The references of a split are ragged: refs [total_refs, ref_w], image i owns rows ref_off[i] .. ref_off[i+1].
+ *   CIDEr    df(g) = number of images with n-gram g in any reference (counted once per image); idf(g) = log(n_img) - log(max(1, df));
+ *            vec = tf * idf per n-gram, per order n = 1..4 the cosine of hypothesis and reference (raw dot product where a norm is
+ *            0); image score = 10 * mean_n mean_ref cosine.  No clipping, no length penalty.  Corpus: mean over the added images.
+ *   BLEU     per image and n: guess = max(0, len - n + 1), correct = sum_g min(tf_hyp(g), max_ref tf_ref(g)); testlen = len, reflen =
+ *            the reference length closest to len (ties: the shorter).  Corpus: integer sums over the added images, then
+ *            p_n = (correct_n + 1e-15) / (guess_n + 1e-9), Bleu_n = (p_1 .. p_n)^(1/n), times exp(1 - 1/ratio) when
+ *            ratio = (testlen + 1e-15) / (reflen + 1e-9) < 1.
+ *   ROUGE_L  lcs against every reference; P = max lcs / len_hyp, R = max lcs / len_ref, F = (1 + b^2) P R / (R + b^2 P), b = 1.2
+ *            (0 when P or R is 0 -- an empty hypothesis scores 0).  Corpus: mean over the added images.
+ * Float arithmetic is double.
+ *
+ * capmi_langeval_build: two launches.  (1) one workgroup per image inserts its DISTINCT reference n-grams (first occurrence in
+ *   (reference, position) order: the same n-grams on every run) into table_keys / table_counts with atomicCAS / atomicAdd --
+ *   open addressing, linear probing, keys and hash of capmi_ciderd_score; both arrays zeroed by the caller, table_cap a power of
+ *   two.  (2) one workgroup per reference writes ref_norm [total_refs, 4].
+ * capmi_langeval_add: one launch, one workgroup per hypothesis row: hyp [H, L] int64, img_idx [H] int64 (which image each row
+ *   describes, any order).  Writes cider / rouge / bleu_stats / lens / lcs of those images and seen = 1; a later row for an image
+ *   replaces an earlier one (within one call too).  No host sync.
+ * capmi_langeval_reduce: one launch, one workgroup: out [8] = Bleu_1..4, ROUGE_L, CIDEr, number of images added, error bits;
+ *   totals [10] = guess_1..4, correct_1..4, testlen, reflen (int64 sums, the same bits whatever the order of the adds).
+ * err [1] (zeroed by the caller) collects CAPMI_LANGEVAL_E_*; the results are meaningless when it is not 0.
+ * CAPMI_EINVAL: a NULL pointer, n_img < 1, ref_w or L outside 1..CAPMI_LANGEVAL_LMAX (rows are never truncated), table_cap not a
+ * power of two.  H == 0: success, nothing launched.
+ * ------------------------------------------------------------------------------------------- */
+#define CAPMI_LANGEVAL_LMAX 64
+#define CAPMI_LANGEVAL_E_TABLE_FULL 1   /* more distinct n-grams than table_cap */
+#define CAPMI_LANGEVAL_E_TOKEN 2        /* a token id outside [0, 65535) */
+#define CAPMI_LANGEVAL_E_IMAGE 4        /* an image index outside [0, n_img) */
+typedef struct capmi_langeval {
+    int n_img, total_refs, ref_w;
+    const int64_t *refs;                     /* [total_refs, ref_w] */
+    const int32_t *ref_off;                  /* [n_img + 1] */
+    uint64_t *table_keys;                    /* [table_cap], empty slot = 0 */
+    int32_t *table_counts;                   /* [table_cap] document frequencies */
+    uint32_t table_cap;
+    double *ref_norm;                        /* [total_refs, 4] */
+    double *cider, *rouge;                   /* [n_img] */
+    int32_t *bleu_stats;                     /* [n_img, 4, 2] guess, correct */
+    int32_t *lens;                           /* [n_img, 2] testlen, reflen */
+    int32_t *lcs;                            /* [total_refs] lcs of the image's hypothesis and each reference */
+    int32_t *seen;                           /* [n_img] 1 once the image has a hypothesis */
+    int32_t *err;                            /* [1] */
+} capmi_langeval;
+int capmi_langeval_build(const capmi_langeval *e, void *stream);
+int capmi_langeval_add(const capmi_langeval *e, const int64_t *hyp, int H, int L, const int64_t *img_idx, void *stream);
+int capmi_langeval_reduce(const capmi_langeval *e, double *out, int64_t *totals, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
