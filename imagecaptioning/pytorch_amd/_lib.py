@@ -239,6 +239,16 @@ class LangEval(C.Structure):
                 [(k, c_f) for k in ('ref_norm', 'cider', 'rouge', 'bleu_stats', 'lens', 'lcs', 'seen', 'err')])
 
 
+DIVEVAL_NMAX, DIVEVAL_NOUT, DIVEVAL_VOCAB_WORDS = 32, 22, 2048      # capmi.h CAPMI_DIVEVAL_*
+
+
+class DivEval(C.Structure):
+    """capmi_diveval (include/capmi.h): n sampled captions per image on the tables of a capmi_langeval, per-image diversity results"""
+    _fields_ = ([('lang', LangEval), ('n', C.c_int), ('oracle', C.c_int)] +
+                [(k, c_f) for k in ('norm', 'slot_distinct', 'distinct', 'tokens', 'mbleu_stats', 'sent_bleu2', 'K', 'eig',
+                                    'self_cider', 'oracle_scores', 'seen', 'err', 'vocab_bits')])
+
+
 _I, _F, _P, _U64, _I64 = C.c_int, C.c_float, C.c_void_p, C.c_uint64, C.c_int64
 DECODE_NO_REPEAT, DECODE_NO_BAD_ENDING, DECODE_BLOCK_TRIGRAMS = 1, 2, 4      # capmi.h CAPMI_DECODE_*
 SELECT_RAW = 256       # capmi.h CAPMI_SELECT_RAW: OR into the select `mode` -- the stored rows are the logits, not the log-probabilities
@@ -364,6 +374,8 @@ SIGNATURES = {
     'capmi_langeval_build': [C.POINTER(LangEval), _P],
     'capmi_langeval_add': [C.POINTER(LangEval), _P, _I, _I, _P, _P],
     'capmi_langeval_reduce': [C.POINTER(LangEval), _P, _P, _P],
+    'capmi_diveval_add': [C.POINTER(DivEval), _P, _I, _I, _P, _P],
+    'capmi_diveval_reduce': [C.POINTER(DivEval), _P, _P, _P],
     'capmi_updown_rollout_fwd': [C.POINTER(UpDownWeights), C.POINTER(UpDownRollout), _P],
     'capmi_updown_rollout_bwd': [C.POINTER(UpDownWeights), C.POINTER(UpDownRollout), _P, C.POINTER(UpDownBwdScratch),
                                  C.POINTER(UpDownGrads), _P],

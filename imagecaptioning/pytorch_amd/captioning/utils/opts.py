@@ -30,6 +30,8 @@ DEFAULTS = dict(
     # opts.py:127 / :311 language_eval: corpus CIDEr / BLEU-1..4 / ROUGE-L on the device (imagecaptioning/pytorch_amd/langeval.py; METEOR
     # and SPICE need Java).  eval_results_dir: where tools/eval.py writes <id>_<split>.json (the reference: always ./eval_results)
     language_eval=0, eval_results_dir='eval_results',
+    # opts.py:331 eval_oracle: with language_eval and sample_n > 1, also oracle_X / avg_X over the sample_n captions (diveval.py)
+    eval_oracle=1,
     # data (synthetic only: the reference's h5/lmdb loaders are outside the hot path)
     input_synthetic=1, vocab_size=9487, synthetic_regions=36, synthetic_images=200,
     # real precomputed features (captioning/data/feature_loader.py; opts.py:23-37 of the reference)

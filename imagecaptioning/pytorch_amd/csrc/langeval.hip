@@ -102,7 +102,9 @@ __global__ __launch_bounds__(CT) void langeval_df_kernel(capmi_langeval e) {
 
 __device__ __forceinline__ double idf_of(const capmi_langeval &e, uint64_t key, double log_n) {
     const int df = df_lookup(e.table_keys, e.table_counts, e.table_cap, key);
-    return log_n - log(fmax(1.0, (double)df));
+    // an n-gram of every image weighs exactly 0, as log(n) - log(n) does on the host: log_n is the host's logarithm, which need
+    // not round like the device's, and a weight of one ulp would turn a zero norm into a cosine of order 1
+    return df >= e.n_img ? 0.0 : log_n - log(fmax(1.0, (double)df));
 }
 
 // per-order norm of vec[CT] (0 on the lanes that hold no distinct n-gram): threads 0..NG-1, fixed order
@@ -132,27 +134,34 @@ __global__ __launch_bounds__(CT) void langeval_ref_norm_kernel(capmi_langeval e,
     if (tid < NG) e.ref_norm[(size_t)r * NG + tid] = order_norm(vec, tid);
 }
 
-// One workgroup per hypothesis row.
-__global__ __launch_bounds__(CT) void langeval_add_kernel(capmi_langeval e, const int64_t *__restrict__ hyp, int H, int L,
-                                                         const int64_t *__restrict__ img_idx, double log_n) {
+// The entry of position g of img_idx [G] counts when no later entry names the same image and the image is inside the split.
+// Every thread of the workgroup calls it.
+__device__ __forceinline__ bool entry_counts(const int64_t *__restrict__ img_idx, int G, int g, int n_img, int32_t *err, int *img) {
+    const int64_t img64 = img_idx[g];
+    int later = 0;
+    for (int j = g + 1 + threadIdx.x; j < G; j += blockDim.x) later |= img_idx[j] == img64;
+    if (__syncthreads_or(later)) return false;
+    if (img64 < 0 || img64 >= n_img) {
+        if (threadIdx.x == 0) atomicOr(err, CAPMI_LANGEVAL_E_IMAGE);
+        return false;
+    }
+    *img = (int)img64;
+    return true;
+}
+
+// One workgroup scores one row against the references of image img: cider / rouge / bleu_stats / lens [oi], lcs [reference]
+// (skipped when NULL).  oi is the image for capmi_langeval_add and (image, slot) for the oracle scores of capmi_diveval_add.
+__device__ __forceinline__ void score_row(const capmi_langeval &e, const int64_t *__restrict__ row, int L, int img, size_t oi,
+                                          int32_t *__restrict__ lcs_out, double log_n) {
     __shared__ int tok_h[LMAX], tok_r[LMAX], len_s[2];
     __shared__ uint64_t key_h[CT], key_r[CT];
     __shared__ double contrib[CT], norm_h[NG], score[NG], wave_p[NG], wave_r[NG];
     __shared__ int icontrib[CT];
-    const int h = blockIdx.x, tid = threadIdx.x, k = tid / LMAX, i = tid % LMAX;
-    const int64_t img64 = img_idx[h];
-    int later = 0;                                           // a later row of this call describes the same image: it counts
-    for (int j = h + 1 + tid; j < H; j += CT) later |= img_idx[j] == img64;
-    if (__syncthreads_or(later)) return;
-    if (img64 < 0 || img64 >= e.n_img) {
-        if (tid == 0) atomicOr(e.err, CAPMI_LANGEVAL_E_IMAGE);
-        return;
-    }
-    const int img = (int)img64;
+    const int tid = threadIdx.x, k = tid / LMAX, i = tid % LMAX;
     const int r0 = e.ref_off[img], r1 = e.ref_off[img + 1];
 
     // ---- the hypothesis: distinct n-grams, their counts and tf-idf weights
-    stage_row(hyp + (size_t)h * L, L, tok_h, &len_s[0], e.err);
+    stage_row(row, L, tok_h, &len_s[0], e.err);
     const int len_h = len_s[0];
     const bool valid = i + k + 1 <= len_h;
     const uint64_t key = valid ? pack_ngram(tok_h, i, k) : 0;
@@ -200,15 +209,15 @@ __global__ __launch_bounds__(CT) void langeval_add_kernel(capmi_langeval e, cons
     if (tid < NG) {
         int correct = 0;
         for (int j = 0; j < LMAX; ++j) correct += icontrib[tid * LMAX + j];
-        e.bleu_stats[((size_t)img * NG + tid) * 2 + 0] = max(0, len_h - tid);
-        e.bleu_stats[((size_t)img * NG + tid) * 2 + 1] = correct;
+        e.bleu_stats[(oi * NG + tid) * 2 + 0] = max(0, len_h - tid);
+        e.bleu_stats[(oi * NG + tid) * 2 + 1] = correct;
     }
     if (tid == 0) {
         double m = 0.0;
         for (int q = 0; q < NG; ++q) m += score[q];
-        e.cider[img] = r1 > r0 ? m / NG / (double)(r1 - r0) * 10.0 : 0.0;
-        e.lens[(size_t)img * 2 + 0] = len_h;
-        e.lens[(size_t)img * 2 + 1] = best_l;
+        e.cider[oi] = r1 > r0 ? m / NG / (double)(r1 - r0) * 10.0 : 0.0;
+        e.lens[oi * 2 + 0] = len_h;
+        e.lens[oi * 2 + 1] = best_l;
     }
 
     // ---- ROUGE-L: wave w takes references w, w + 4, ...; lane j holds column j + 1 of the LCS table's current row.
@@ -233,7 +242,7 @@ __global__ __launch_bounds__(CT) void langeval_add_kernel(capmi_langeval e, cons
             row = x;
         }
         const int lcs = __shfl(row, CAPMI_WAVE - 1);         // columns past the hypothesis carry the last value on
-        if (lane == 0) e.lcs[r] = lcs;
+        if (lane == 0 && lcs_out) lcs_out[r] = lcs;
         if (len_h > 0) p_max = fmax(p_max, (double)lcs / (double)len_h);
         if (len_r > 0) r_max = fmax(r_max, (double)lcs / (double)len_r);
     }
@@ -242,9 +251,17 @@ __global__ __launch_bounds__(CT) void langeval_add_kernel(capmi_langeval e, cons
     if (tid == 0) {
         double p = 0.0, q = 0.0;
         for (int w = 0; w < NG; ++w) { p = fmax(p, wave_p[w]); q = fmax(q, wave_r[w]); }
-        e.rouge[img] = (p != 0.0 && q != 0.0) ? (1.0 + BETA * BETA) * p * q / (q + BETA * BETA * p) : 0.0;
-        e.seen[img] = 1;
+        e.rouge[oi] = (p != 0.0 && q != 0.0) ? (1.0 + BETA * BETA) * p * q / (q + BETA * BETA * p) : 0.0;
     }
+}
+
+// One workgroup per hypothesis row; a later row of the call that describes the same image counts.
+__global__ __launch_bounds__(CT) void langeval_add_kernel(capmi_langeval e, const int64_t *__restrict__ hyp, int H, int L,
+                                                         const int64_t *__restrict__ img_idx, double log_n) {
+    int img;
+    if (!entry_counts(img_idx, H, blockIdx.x, e.n_img, e.err, &img)) return;
+    score_row(e, hyp + (size_t)blockIdx.x * L, L, img, (size_t)img, e.lcs, log_n);
+    if (threadIdx.x == 0) e.seen[img] = 1;
 }
 
 constexpr int NI = 10;    // integer totals: guess 1..4, correct 1..4, testlen, reflen
@@ -336,6 +353,352 @@ extern "C" int capmi_langeval_add(const capmi_langeval *e, const int64_t *hyp, i
 extern "C" int capmi_langeval_reduce(const capmi_langeval *e, double *out, int64_t *totals, void *stream) {
     if (!langeval_valid(e) || !out || !totals) return CAPMI_EINVAL;
     hipLaunchKernelGGL(langeval_reduce_kernel, dim3(1), dim3(RT), 0, (hipStream_t)stream, *e, out, totals);
+    CAPMI_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Diversity of n sampled captions per image (eval_multi: Div-n, mBLEU, self-CIDEr, oracle scores; formulas in include/capmi.h).
+// The same cooking and the same walk as above with the image's other sampled captions in the place of its references, then one
+// small symmetric eigenproblem per image.  Rows g*n .. g*n+n-1 of hyp are group g, the captions of image img_idx[g].
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int NMAX = CAPMI_DIVEVAL_NMAX;
+constexpr int NO = 6;                       // oracle scores per slot: CIDEr, Bleu_1..4, ROUGE_L
+constexpr int ET = CAPMI_WAVE;              // one wave per image solves the eigenproblem
+static_assert(NMAX <= ET, "one lane per row of K");
+
+// bleu_scorer's score of one set of counts (an instance's or a corpus's): st = guess 1..4, correct 1..4, testlen, reflen
+template <typename I>
+__device__ __forceinline__ void bleu_of_counts(const I *st, double *out) {
+    const double tiny = 1e-15, small = 1e-9;
+    const double ratio = ((double)st[8] + tiny) / ((double)st[9] + small);
+    const double bp = ratio < 1.0 ? exp(1.0 - 1.0 / ratio) : 1.0;
+    double bleu = 1.0;
+    for (int q = 0; q < NG; ++q) {
+        bleu *= ((double)st[NG + q] + tiny) / ((double)st[q] + small);
+        out[q] = pow(bleu, 1.0 / (q + 1)) * bp;
+    }
+}
+
+// One workgroup per caption: norm [img, slot, 4], as langeval_ref_norm_kernel does for a reference.
+__global__ __launch_bounds__(CT) void diveval_norm_kernel(capmi_diveval d, const int64_t *__restrict__ hyp, int B, int L,
+                                                         const int64_t *__restrict__ img_idx, double log_n) {
+    __shared__ int tok[LMAX], len_s;
+    __shared__ uint64_t keys[CT];
+    __shared__ double vec[CT];
+    const int tid = threadIdx.x, k = tid / LMAX, i = tid % LMAX, g = blockIdx.x / d.n, s = blockIdx.x % d.n;
+    int img;
+    if (!entry_counts(img_idx, B, g, d.lang.n_img, d.err, &img)) return;
+    stage_row(hyp + (size_t)blockIdx.x * L, L, tok, &len_s, d.err);
+    const int len = len_s;
+    const bool valid = i + k + 1 <= len;
+    const uint64_t key = valid ? pack_ngram(tok, i, k) : 0;
+    keys[tid] = key;
+    __syncthreads();
+    bool first = valid;
+    int tf = 0;
+    if (valid) tf = ngram_tf(&keys[k * LMAX], len - k, key, i, first);
+    vec[tid] = first ? (double)tf * idf_of(d.lang, key, log_n) : 0.0;
+    __syncthreads();
+    if (tid < NG) d.norm[((size_t)img * d.n + s) * NG + tid] = order_norm(vec, tid);
+}
+
+// One workgroup per caption (image, slot s) walks the n captions of its image once.  Slot o >= s: K[s][o] and its mirror.
+// Slot o != s: the clip counts and the closest length of mBLEU with the other captions as references.  Slot o < s: an n-gram
+// that o holds is not first seen in s.
+__global__ __launch_bounds__(CT) void diveval_walk_kernel(capmi_diveval d, const int64_t *__restrict__ hyp, int B, int L,
+                                                         const int64_t *__restrict__ img_idx, double log_n) {
+    __shared__ int tok_h[LMAX], tok_r[LMAX], len_s[2], icontrib[CT], correct_s[NG];
+    __shared__ uint64_t key_h[CT], key_r[CT];
+    __shared__ double contrib[CT], cos_s[NG];
+    const int n = d.n, tid = threadIdx.x, k = tid / LMAX, i = tid % LMAX, g = blockIdx.x / n, s = blockIdx.x % n;
+    int img;
+    if (!entry_counts(img_idx, B, g, d.lang.n_img, d.err, &img)) return;
+    const int64_t *rows = hyp + (size_t)g * n * L;
+
+    stage_row(rows + (size_t)s * L, L, tok_h, &len_s[0], d.err);
+    const int len_h = len_s[0];
+    const bool valid = i + k + 1 <= len_h;
+    const uint64_t key = valid ? pack_ngram(tok_h, i, k) : 0;
+    key_h[tid] = key;
+    __syncthreads();
+    bool first = valid;
+    int tf_h = 0;
+    if (valid) tf_h = ngram_tf(&key_h[k * LMAX], len_h - k, key, i, first);
+    const double idf = first ? idf_of(d.lang, key, log_n) : 0.0;
+    const double vh = (double)tf_h * idf;
+    if (k == 0 && first) atomicOr(d.vocab_bits + (tok_h[i] >> 5), 1u << (tok_h[i] & 31));      // ids < 65535: inside the bitmap
+
+    const double *norm = d.norm + (size_t)img * n * NG;
+    double *K = d.K + (size_t)img * n * n;
+    bool first_in_image = first;
+    int max_tf = 0, best_d = 1 << 30, best_l = 0;
+    for (int o = 0; o < n; ++o) {
+        __syncthreads();                                     // tok_r / key_r / contrib / cos_s of the previous caption are consumed
+        stage_row(rows + (size_t)o * L, L, tok_r, &len_s[1], d.err);
+        const int len_r = len_s[1];
+        key_r[tid] = i + k + 1 <= len_r ? pack_ngram(tok_r, i, k) : 0;
+        __syncthreads();
+        int tf_r = 0;
+        if (first)
+            for (int j = 0; j < len_r - k; ++j) tf_r += key_r[k * LMAX + j] == key;
+        if (o != s) {
+            max_tf = max(max_tf, tf_r);
+            const int dl = abs(len_r - len_h);
+            if (dl < best_d || (dl == best_d && len_r < best_l)) { best_d = dl; best_l = len_r; }
+            if (o < s && tf_r) first_in_image = false;
+        }
+        if (o >= s) {
+            contrib[tid] = first ? vh * ((double)tf_r * idf) : 0.0;
+            __syncthreads();
+            if (tid < NG) {
+                double dot = 0.0;
+                for (int j = 0; j < LMAX; ++j) dot += contrib[tid * LMAX + j];
+                const double nh = norm[s * NG + tid], nr = norm[o * NG + tid];
+                cos_s[tid] = (nh != 0.0 && nr != 0.0) ? dot / (nh * nr) : 0.0;
+            }
+            __syncthreads();
+            if (tid == 0) {
+                double m = 0.0;
+                for (int q = 0; q < NG; ++q) m += cos_s[q];
+                const double v = m / NG * 10.0;
+                K[(size_t)s * n + o] = v;
+                K[(size_t)o * n + s] = v;
+            }
+        }
+    }
+    __syncthreads();
+    icontrib[tid] = first ? min(tf_h, max_tf) : 0;
+    __syncthreads();
+    int32_t *st = d.mbleu_stats + ((size_t)img * n + s) * 10;
+    if (tid < NG) {
+        int correct = 0;
+        for (int j = 0; j < LMAX; ++j) correct += icontrib[tid * LMAX + j];
+        st[tid] = max(0, len_h - tid);
+        st[NG + tid] = correct;
+        correct_s[tid] = correct;
+    }
+    __syncthreads();
+    icontrib[tid] = first_in_image;
+    __syncthreads();
+    if (tid < 2) {
+        int cnt = 0;
+        for (int j = 0; j < LMAX; ++j) cnt += icontrib[tid * LMAX + j];
+        d.slot_distinct[((size_t)img * n + s) * 2 + tid] = cnt;
+    }
+    if (tid == 0) {
+        st[8] = len_h;
+        st[9] = best_l;
+        int cnt[10];
+        for (int q = 0; q < NG; ++q) { cnt[q] = max(0, len_h - q); cnt[NG + q] = correct_s[q]; }
+        cnt[8] = len_h;
+        cnt[9] = best_l;
+        double b[NG];
+        bleu_of_counts(cnt, b);
+        d.sent_bleu2[(size_t)img * n + s] = b[1];
+    }
+}
+
+// One workgroup per caption against the image's references; e is d.lang with its outputs indexed by (image, slot).
+__global__ __launch_bounds__(CT) void diveval_oracle_kernel(capmi_langeval e, int n, const int64_t *__restrict__ hyp, int B, int L,
+                                                           const int64_t *__restrict__ img_idx, double log_n) {
+    int img;
+    if (!entry_counts(img_idx, B, blockIdx.x / n, e.n_img, e.err, &img)) return;
+    score_row(e, hyp + (size_t)blockIdx.x * L, L, img, (size_t)img * n + blockIdx.x % n, nullptr, log_n);
+}
+
+// One wave per image: the eigenvalues of K/10 by cyclic Jacobi in LDS, self_cider, and the image's sums over its slots.
+// Lane r owns row r of the rotation.  Rotation (p, q) reads column p and q of every row, then writes them and (by symmetry) rows
+// p and q; the pivot entries are lane 0's.  Every branch is uniform: all lanes read the same LDS words.
+__global__ __launch_bounds__(ET) void diveval_finish_kernel(capmi_diveval d, int B, const int64_t *__restrict__ img_idx) {
+    __shared__ double A[NMAX][NMAX + 1], ev[NMAX];
+    const int n = d.n, lane = threadIdx.x;
+    int img;
+    if (!entry_counts(img_idx, B, blockIdx.x, d.lang.n_img, d.err, &img)) return;
+    const double *K = d.K + (size_t)img * n * n;
+    for (int idx = lane; idx < n * n; idx += ET) A[idx / n][idx % n] = K[idx] / 10.0;
+    __syncthreads();
+    double trace = 0.0;
+    for (int r = 0; r < n; ++r) trace += A[r][r];
+    const double eps = 0x1p-52 * trace, thresh = eps * eps;
+    for (int sweep = 0; sweep < CAPMI_DIVEVAL_SWEEPS; ++sweep) {
+        double off = 0.0;
+        for (int p = 0; p < n - 1; ++p)
+            for (int q = p + 1; q < n; ++q) off += A[p][q] * A[p][q];
+        if (off <= thresh) break;
+        for (int p = 0; p < n - 1; ++p)
+            for (int q = p + 1; q < n; ++q) {
+                const double apq = A[p][q];
+                if (apq == 0.0) continue;
+                const double app = A[p][p], aqq = A[q][q];
+                const double theta = (aqq - app) / (2.0 * apq);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
+                const bool mine = lane < n && lane != p && lane != q;
+                const double arp = mine ? A[lane][p] : 0.0, arq = mine ? A[lane][q] : 0.0;
+                __syncthreads();
+                if (mine) {
+                    const double np_ = c * arp - sn * arq, nq_ = sn * arp + c * arq;
+                    A[lane][p] = np_; A[p][lane] = np_;
+                    A[lane][q] = nq_; A[q][lane] = nq_;
+                }
+                if (lane == 0) {
+                    A[p][p] = app - t * apq;
+                    A[q][q] = aqq + t * apq;
+                    A[p][q] = 0.0;
+                    A[q][p] = 0.0;
+                }
+                __syncthreads();
+            }
+    }
+    // ascending: the rank of an eigenvalue is the number of smaller ones (ties: the lower index first)
+    if (lane < n) {
+        const double x = A[lane][lane];
+        int rank = 0;
+        for (int r = 0; r < n; ++r) {
+            const double y = A[r][r];
+            rank += y < x || (y == x && r < lane);
+        }
+        ev[rank] = x;
+    }
+    __syncthreads();
+    if (lane < n) d.eig[(size_t)img * n + lane] = ev[lane];
+    if (lane == 0) {
+        double sum = 0.0;
+        for (int r = 0; r < n; ++r) sum += sqrt(fmax(0.0, ev[r]));
+        const double top = sqrt(fmax(0.0, ev[n - 1]));
+        d.self_cider[img] = sum > 0.0 ? -log(top / sum) / log((double)n) : 0.0;     // every caption empty: 0, not NaN
+        d.seen[img] = 1;
+    }
+    if (lane < 3) {                                          // distinct 1-grams, distinct 2-grams, tokens
+        int total = 0;
+        for (int s = 0; s < n; ++s)
+            total += lane < 2 ? d.slot_distinct[((size_t)img * n + s) * 2 + lane] : d.mbleu_stats[((size_t)img * n + s) * 10 + 8];
+        if (lane < 2) d.distinct[(size_t)img * 2 + lane] = total;
+        else d.tokens[img] = total;
+    }
+    if (d.oracle && lane < n) {
+        const size_t oi = (size_t)img * n + lane;
+        int cnt[10];
+        for (int q = 0; q < NG; ++q) {
+            cnt[q] = d.lang.bleu_stats[(oi * NG + q) * 2 + 0];
+            cnt[NG + q] = d.lang.bleu_stats[(oi * NG + q) * 2 + 1];
+        }
+        cnt[8] = d.lang.lens[oi * 2 + 0];
+        cnt[9] = d.lang.lens[oi * 2 + 1];
+        double b[NG];
+        bleu_of_counts(cnt, b);
+        double *o = d.oracle_scores + oi * NO;
+        o[0] = d.lang.cider[oi];
+        for (int q = 0; q < NG; ++q) o[1 + q] = b[q];
+        o[5] = d.lang.rouge[oi];
+    }
+}
+
+constexpr int NF = 3 + 2 * NO;   // float sums: Div1, Div2, self_cider, oracle max x 6, oracle mean x 6
+
+// One workgroup.  Integers (the per-slot BLEU counts, the bitmap's popcount, the images) are added with LDS integer atomics; every
+// thread sums the floats of its images (stride RT), then one thread per quantity adds the RT partial sums in index order.
+__global__ __launch_bounds__(RT) void diveval_reduce_kernel(capmi_diveval d, double *__restrict__ out, int64_t *__restrict__ totals) {
+    __shared__ unsigned long long ti[NMAX * 10], n_seen, n_words;
+    __shared__ double sd[NF][RT], td[NF];
+    const int tid = threadIdx.x, n = d.n, per = n * 10;
+    for (int q = tid; q < per; q += RT) ti[q] = 0;
+    if (tid == 0) { n_seen = 0; n_words = 0; }
+    __syncthreads();
+    for (size_t idx = tid; idx < (size_t)d.lang.n_img * per; idx += RT)
+        if (d.seen[idx / per]) atomicAdd(&ti[idx % per], (unsigned long long)d.mbleu_stats[idx]);
+    int bits = 0;
+    for (int w = tid; w < CAPMI_DIVEVAL_VOCAB_WORDS; w += RT) bits += __popc(d.vocab_bits[w]);
+    atomicAdd(&n_words, (unsigned long long)bits);
+    double acc[NF] = {};
+    int mine = 0;
+    for (int img = tid; img < d.lang.n_img; img += RT) {
+        if (!d.seen[img]) continue;
+        ++mine;
+        const double tokens = 1e-6 + (double)d.tokens[img];
+        acc[0] += (double)d.distinct[(size_t)img * 2 + 0] / tokens;
+        acc[1] += (double)d.distinct[(size_t)img * 2 + 1] / tokens;
+        acc[2] += d.self_cider[img];
+        if (d.oracle)
+            for (int x = 0; x < NO; ++x) {
+                const double *o = d.oracle_scores + (size_t)img * n * NO + x;
+                double best = o[0], sum = o[0];
+                for (int s = 1; s < n; ++s) { best = fmax(best, o[(size_t)s * NO]); sum += o[(size_t)s * NO]; }
+                acc[3 + x] += best;
+                acc[3 + NO + x] += sum / (double)n;
+            }
+    }
+    atomicAdd(&n_seen, (unsigned long long)mine);
+    for (int q = 0; q < NF; ++q) sd[q][tid] = acc[q];
+    __syncthreads();
+    if (tid < NF) {
+        double sum = 0.0;
+        for (int j = 0; j < RT; ++j) sum += sd[tid][j];
+        td[tid] = sum;
+    }
+    for (int q = tid; q < per; q += RT) totals[q] = (int64_t)ti[q];
+    __syncthreads();
+    if (tid == 0) {
+        const double cnt = (double)n_seen;
+        double mb[NG] = {};
+        for (int s = 0; s < n; ++s) {                        // the corpus Bleu of slot s, then the mean over the slots
+            double b[NG];
+            bleu_of_counts(&ti[s * 10], b);
+            for (int q = 0; q < NG; ++q) mb[q] += b[q];
+        }
+        out[0] = cnt > 0 ? td[0] / cnt : 0.0;
+        out[1] = cnt > 0 ? td[1] / cnt : 0.0;
+        out[2] = (double)n_words;
+        for (int q = 0; q < NG; ++q) out[3 + q] = cnt > 0 ? mb[q] / (double)n : 0.0;
+        out[7] = cnt > 0 ? td[2] / cnt : 0.0;
+        out[8] = cnt;
+        out[9] = (double)*d.err;
+        for (int x = 0; x < 2 * NO; ++x) out[10 + x] = (d.oracle && cnt > 0) ? td[3 + x] / cnt : 0.0;
+    }
+}
+static_assert(10 + 2 * NO == CAPMI_DIVEVAL_NOUT, "out [CAPMI_DIVEVAL_NOUT]");
+
+bool diveval_valid(const capmi_diveval *d) {
+    if (!d) return false;
+    const capmi_langeval &e = d->lang;
+    if (!e.table_keys || !e.table_counts || e.n_img < 1 || e.table_cap == 0 || (e.table_cap & (e.table_cap - 1))) return false;
+    if (d->n < 2 || d->n > NMAX) return false;
+    if (!d->norm || !d->slot_distinct || !d->distinct || !d->tokens || !d->mbleu_stats || !d->sent_bleu2 || !d->K || !d->eig ||
+        !d->self_cider || !d->seen || !d->err || !d->vocab_bits || e.err != d->err)
+        return false;
+    if (d->oracle && (!d->oracle_scores || !e.refs || !e.ref_off || !e.ref_norm || !e.cider || !e.rouge || !e.bleu_stats || !e.lens ||
+                      e.total_refs < 0 || e.ref_w < 1 || e.ref_w > LMAX))
+        return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" int capmi_diveval_add(const capmi_diveval *d, const int64_t *hyp, int B, int L, const int64_t *img_idx, void *stream) {
+    if (!diveval_valid(d) || B < 0 || L < 1 || L > LMAX) return CAPMI_EINVAL;
+    if (B == 0) return 0;
+    if (!hyp || !img_idx) return CAPMI_EINVAL;
+    const double log_n = log((double)d->lang.n_img);
+    hipLaunchKernelGGL(diveval_norm_kernel, dim3(B * d->n), dim3(CT), 0, (hipStream_t)stream, *d, hyp, B, L, img_idx, log_n);
+    CAPMI_CHECK_LAUNCH();
+    hipLaunchKernelGGL(diveval_walk_kernel, dim3(B * d->n), dim3(CT), 0, (hipStream_t)stream, *d, hyp, B, L, img_idx, log_n);
+    CAPMI_CHECK_LAUNCH();
+    if (d->oracle) {
+        hipLaunchKernelGGL(diveval_oracle_kernel, dim3(B * d->n), dim3(CT), 0, (hipStream_t)stream, d->lang, d->n, hyp, B, L, img_idx,
+                           log_n);
+        CAPMI_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(diveval_finish_kernel, dim3(B), dim3(ET), 0, (hipStream_t)stream, *d, B, img_idx);
+    CAPMI_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int capmi_diveval_reduce(const capmi_diveval *d, double *out, int64_t *totals, void *stream) {
+    if (!diveval_valid(d) || !out || !totals) return CAPMI_EINVAL;
+    hipLaunchKernelGGL(diveval_reduce_kernel, dim3(1), dim3(RT), 0, (hipStream_t)stream, *d, out, totals);
     CAPMI_CHECK_LAUNCH();
     return 0;
 }

@@ -5,6 +5,9 @@ command line (beam / diverse beam search, sampling variants, decoding constraint
 per-caption entropy and perplexity from seqLogprobs (:173-174), decoded strings.  --language_eval 1 (eval_utils.py:47-125): corpus
 CIDEr, BLEU-1..4 and ROUGE-L of the single-caption pass, scored on the device over token ids (imagecaptioning/pytorch_amd/langeval.py)
 and written to <eval_results_dir>/<id>_<split>.json as {'overall', 'imgToEval'}; METEOR and SPICE need Java and are absent.
+With --sample_n N > 1 the N captions per image are also scored for diversity on the device (captioning/utils/eval_multi.py ->
+imagecaptioning/pytorch_amd/diveval.py): Div1, Div2, gDiv1, mBLeu_1..4, self_cider and, with --eval_oracle 1, oracle_X / avg_X; they
+join lang_stats and are written to <id>_<split>_n.json.  AllSPICE (Java) and novel_sentences (training captions as strings) are absent.
 
     python -m imagecaptioning.pytorch_amd.tools.eval --caption_model updown --beam_size 5 --num_images 20 [--start_from DIR]
 """
@@ -30,7 +33,8 @@ def eval_kwargs_of(opt):
 
 def eval_split_n(model, n_predictions, fc, att, att_masks, data, opt):
     """eval_utils.eval_split_n (eval_utils.py:228-290): sample_n captions per image by beam search ('bs'), sampling
-    ('sample' / 'gumbel' / 'top<k|p>'), diverse beam search ('dbs') or diverse sampling ('d<method>')."""
+    ('sample' / 'gumbel' / 'top<k|p>'), diverse beam search ('dbs') or diverse sampling ('d<method>').  Returns the token rows of
+    what it decoded, int64 [B, sample_n, L] on the device (finished beams padded with 0), in the order of the appended predictions."""
     from captioning.utils import misc
     kw = eval_kwargs_of(opt)
     sample_n, method, beam_size = opt.sample_n, opt.sample_n_method, opt.beam_size
@@ -38,8 +42,9 @@ def eval_split_n(model, n_predictions, fc, att, att_masks, data, opt):
         if method == 'bs':                                                  # :243-252
             kw.update(sample_n=1, beam_size=sample_n, group_size=1, sample_method='beam_search')
             model(fc, att, att_masks, opt=kw, mode='sample')
+            rows = _pad_stack([model.done_beams[k][i]['seq'] for k in range(fc.shape[0]) for i in range(sample_n)])
             for k in range(fc.shape[0]):
-                for sent in misc.decode_sequence(model.vocab, _pad_stack([model.done_beams[k][i]['seq'] for i in range(sample_n)])):
+                for sent in misc.decode_sequence(model.vocab, rows[k * sample_n:(k + 1) * sample_n]):
                     n_predictions.append({'image_id': data['infos'][k]['id'], 'caption': sent})
         elif method in ('sample', 'gumbel') or method.startswith('top'):   # :254-264
             kw.update(sample_n=sample_n, sample_method=method, beam_size=1)
@@ -47,18 +52,22 @@ def eval_split_n(model, n_predictions, fc, att, att_masks, data, opt):
             ppl = -logp.gather(2, seq.unsqueeze(2)).squeeze(2).sum(1) / ((seq > 0).to(logp).sum(1) + 1)
             for k, sent in enumerate(misc.decode_sequence(model.vocab, seq)):
                 n_predictions.append({'image_id': data['infos'][k // sample_n]['id'], 'caption': sent, 'perplexity': ppl[k].item()})
+            rows = seq
         elif method == 'dbs':                                               # :265-274
             kw.update(beam_size=sample_n * beam_size, group_size=sample_n, sample_method='beam_search', sample_n=1)
             model(fc, att, att_masks, opt=kw, mode='sample')
+            rows = _pad_stack([model.done_beams[k][i]['seq'] for k in range(fc.shape[0])
+                               for i in range(0, sample_n * beam_size, beam_size)])      # the first beam of each group
             for k in range(fc.shape[0]):
-                picks = [model.done_beams[k][i]['seq'] for i in range(0, sample_n * beam_size, beam_size)]
-                for sent in misc.decode_sequence(model.vocab, _pad_stack(picks)):
+                for sent in misc.decode_sequence(model.vocab, rows[k * sample_n:(k + 1) * sample_n]):
                     n_predictions.append({'image_id': data['infos'][k]['id'], 'caption': sent})
         else:                                                               # :275-283 diverse sampling, 'd' + method
             kw.update(sample_method=method[1:], group_size=sample_n, beam_size=1)
             seq, _ = model(fc, att, att_masks, opt=kw, mode='sample')
             for k, sent in enumerate(misc.decode_sequence(model.vocab, seq)):
                 n_predictions.append({'image_id': data['infos'][k // sample_n]['id'], 'caption': sent})
+            rows = seq
+    return rows.to(torch.long).reshape(fc.shape[0], sample_n, -1)
 
 
 def _pad_stack(seqs):
@@ -78,6 +87,10 @@ def eval_split(model, crit, loader, opt):
     if getattr(opt, 'language_eval', 0):
         from imagecaptioning.pytorch_amd.langeval import LanguageEval
         lang = LanguageEval.for_loader(loader, split, dev)
+    div, groups = None, []               # groups: (image_id, the image's n prediction dicts in slot order), before any sorting
+    if lang is not None and opt.sample_n > 1:
+        from imagecaptioning.pytorch_amd.diveval import DiversityEval
+        div = DiversityEval(lang, opt.sample_n, oracle=bool(getattr(opt, 'eval_oracle', 0)))
     if hasattr(loader, 'reset_iterator'):
         loader.reset_iterator(split)                                                                           # eval_utils.py:145
     num_images = opt.num_images
@@ -120,7 +133,12 @@ def eval_split(model, crit, loader, opt):
             preds.append({'image_id': data['infos'][k // rows_per_image]['id'], 'caption': s, 'perplexity': perplexity[k].item(),
                           'entropy': entropy[k].item()})
         if opt.sample_n > 1:                                                                                   # :199-200
-            eval_split_n(model, n_preds, fc, att, att_masks, data, opt)                                       # :198
+            first = len(n_preds)
+            rows = eval_split_n(model, n_preds, fc, att, att_masks, data, opt)                                # :198
+            if div is not None:          # the same cut at num_images as the single-caption pass; the rows stay on the device
+                div.add_batch(data['infos'][:keep], rows[:keep])
+                groups += [(data['infos'][k]['id'], n_preds[first + k * opt.sample_n:first + (k + 1) * opt.sample_n])
+                           for k in range(keep)]
         n += len(data['infos'])
     if n_preds and 'perplexity' in n_preds[0]:
         n_preds = sorted(n_preds, key=lambda x: x['perplexity'])                                               # :217-218
@@ -128,7 +146,10 @@ def eval_split(model, crit, loader, opt):
     model.train()                                                                                              # :224-225
     preds = preds[:num_images * max(1, len(preds) // max(n, 1))]
     if lang is not None:
-        return loss_sum / max(loss_n, 1), preds, language_eval(lang, preds, opt, split)
+        lang_stats = language_eval(lang, preds, opt, split)
+        if div is not None:
+            lang_stats.update(language_eval_n(div, groups, opt, split))
+        return loss_sum / max(loss_n, 1), preds, lang_stats
     return loss_sum / max(loss_n, 1), preds
 
 
@@ -146,6 +167,43 @@ def language_eval(lang, preds, opt, split):
     with open(os.path.join(out_dir, '%s_%s.json' % (getattr(opt, 'id', 'capmi'), split)), 'w') as f:
         json.dump({'overall': lang_stats, 'imgToEval': img_to_eval}, f)
     return lang_stats
+
+
+def assemble_n(overall, per_image, groups, pos_of_id, oracle):
+    """The reference's <id>_<split>_n.json (eval_utils.py:104-119) from DiversityEval.compute(): {'div_stats': eval_div_stats's
+    {'overall', 'ImgToEval'}, 'self_cider': eval_self_cider's {'overall', 'imgToEval'}[, 'oracle': eval_oracle's {'overall',
+    'ImgToEval'}]}.  groups: (image_id, the image's prediction dicts in slot order); as in the reference each dict gains its
+    'mBleu_2' (and, with oracle, its 'scores')."""
+    from imagecaptioning.pytorch_amd.diveval import DIV_KEYS, ORACLE_KEYS
+    oracle_keys = [p + k for k in ORACLE_KEYS for p in ('oracle_', 'avg_')]
+    out = {'div_stats': {'overall': {k: overall[k] for k in DIV_KEYS}, 'ImgToEval': {}},
+           'self_cider': {'overall': {'self_cider': overall['self_cider']}, 'imgToEval': {}}}
+    if oracle:
+        out['oracle'] = {'overall': {k: overall[k] for k in oracle_keys}, 'ImgToEval': {}}
+    for image_id, caps in groups:
+        pos = pos_of_id[image_id]
+        for j, p in enumerate(caps):
+            p['mBleu_2'] = float(per_image['individual_mBleu_2'][pos, j])
+            if oracle:
+                p['scores'] = {k: float(per_image['scores'][pos, j, x]) for x, k in enumerate(ORACLE_KEYS)}
+        out['div_stats']['ImgToEval'][image_id] = {'mBleu_2': float(per_image['mBleu_2'][pos]), 'individuals': caps}
+        out['self_cider']['imgToEval'][image_id] = {'self_cider': float(per_image['self_cider'][pos]),
+                                                    'self_cider_mat': per_image['self_cider_mat'][pos].tolist()}
+        if oracle:
+            entry = {k: float(per_image[k][pos]) for k in oracle_keys}
+            entry['captions'] = caps
+            out['oracle']['ImgToEval'][image_id] = entry
+    return out
+
+
+def language_eval_n(div, groups, opt, split):
+    """the diversity half of eval_utils.language_eval (:104-119): the overall numbers, <eval_results_dir>/<id>_<split>_n.json"""
+    overall, per_image = div.compute()
+    out_dir = getattr(opt, 'eval_results_dir', 'eval_results')
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, '%s_%s_n.json' % (getattr(opt, 'id', 'capmi'), split)), 'w') as f:
+        json.dump(assemble_n(overall, per_image, groups, div.pos_of_id, div.oracle), f)
+    return overall
 
 
 def build_loader(opt, dev):

@@ -1337,6 +1337,59 @@ int capmi_langeval_build(const capmi_langeval *e, void *stream);
 int capmi_langeval_add(const capmi_langeval *e, const int64_t *hyp, int H, int L, const int64_t *img_idx, void *stream);
 int capmi_langeval_reduce(const capmi_langeval *e, double *out, int64_t *totals, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Diversity evaluation of n sampled captions per image (eval_multi.eval_div_stats / eval_self_cider / eval_oracle), on the
+ * tables of a capmi_langeval.  Captions are token-id rows as above; 2 <= n <= CAPMI_DIVEVAL_NMAX.  div_utils.py is pinned by
+ * tests/golden/diveval_ref.npz; mBLEU and self-CIDEr are restated (PARITY UNPINNED, tests/diveval_ref64.py).  Double throughout.
+ *   Div1, Div2  per image: distinct k-grams over the n captions / (1e-6 + tokens of the n captions), k = 1, 2 (the denominator is
+ *               the token count for k = 2 too).  Corpus: mean over the added images.
+ *   gDiv1       distinct unigrams over every caption added since the bitmap was zeroed (replaced groups included).
+ *   mBLeu_1..4  per slot i the corpus Bleu ('closest') of caption i against the image's other n-1 captions; the mean over i.
+ *               sent_bleu2 [img, i]: bleu_scorer's per-instance Bleu_2 of the same counts.
+ *   self_cider  K[i][j] = 10 * (1/4) sum_k cos_k(c_i, c_j) on the tf-idf vectors of the langeval table (an order with a zero norm
+ *               contributes 0); i <= j computed, mirrored.  lambda = eigenvalues of K/10 clipped at 0:
+ *               -log(sqrt(lambda_max) / sum sqrt(lambda)) / log(n); 0.0 when the sum is 0 (every caption empty; numpy gives NaN).
+ *   oracle      (oracle != 0) every slot scored against the image's references exactly as capmi_langeval_add scores a hypothesis:
+ *               oracle_scores [img, i, 6] = CIDEr, sentence Bleu_1..4, ROUGE_L.
+ *
+ * capmi_diveval_add: hyp [B * n, L] int64, rows k*n .. k*n+n-1 describe image img_idx[k].  Launches: (1) a workgroup per row: the
+ *   four tf-idf norms; (2) a workgroup per row walks the image's n rows once: its row of K (upper triangle, mirrored), the clip
+ *   counts and closest length of mBLEU, the n-grams no earlier position and no earlier slot holds (slot_distinct), atomicOr into
+ *   vocab_bits; (3) with oracle, a workgroup per row against the references; (4) a wave per image: cyclic Jacobi on K/10 (row-cyclic
+ *   sweeps until the off-diagonal square sum is <= (2^-52 trace)^2, at most CAPMI_DIVEVAL_SWEEPS), eig ascending, self_cider, the
+ *   per-image sums.  A later group for an image replaces an earlier one (within one call too).  No host sync, no allocation.
+ * capmi_diveval_reduce: one workgroup.  out [CAPMI_DIVEVAL_NOUT] = Div1, Div2, gDiv1, mBLeu_1..4, self_cider, images added, error
+ *   bits, oracle_{CIDEr, Bleu_1..4, ROUGE_L}, avg_{the same}; totals [n, 10] = per slot guess_1..4, correct_1..4, testlen, reflen.
+ *   Integers are summed as integers, floats in index order: the same bits whatever the order of the adds.
+ * err collects CAPMI_LANGEVAL_E_*.  CAPMI_EINVAL: a NULL pointer, n outside 2..CAPMI_DIVEVAL_NMAX, L outside 1..CAPMI_LANGEVAL_LMAX,
+ * an invalid table.  B == 0: success, nothing launched.
+ * ------------------------------------------------------------------------------------------- */
+#define CAPMI_DIVEVAL_NMAX 32
+#define CAPMI_DIVEVAL_SWEEPS 30
+#define CAPMI_DIVEVAL_NOUT 22
+#define CAPMI_DIVEVAL_VOCAB_WORDS 2048   /* 65 536 bits */
+typedef struct capmi_diveval {
+    capmi_langeval lang;                     /* tables and references; with oracle its output pointers are the scratch
+                                                [n_img * n] rows of cider / rouge / bleu_stats / lens, lcs and seen unused;
+                                                lang.err must be err below */
+    int n, oracle;
+    double *norm;                            /* [n_img, n, 4] tf-idf norms of the captions */
+    int32_t *slot_distinct;                  /* [n_img, n, 2] n-grams first seen in this slot, orders 1 and 2 */
+    int32_t *distinct;                       /* [n_img, 2] */
+    int32_t *tokens;                         /* [n_img] */
+    int32_t *mbleu_stats;                    /* [n_img, n, 10] guess 1..4, correct 1..4, testlen, reflen */
+    double *sent_bleu2;                      /* [n_img, n] */
+    double *K;                               /* [n_img, n, n] */
+    double *eig;                             /* [n_img, n] ascending */
+    double *self_cider;                      /* [n_img] */
+    double *oracle_scores;                   /* [n_img, n, 6] (oracle only) */
+    int32_t *seen;                           /* [n_img] */
+    int32_t *err;                            /* [1] */
+    uint32_t *vocab_bits;                    /* [CAPMI_DIVEVAL_VOCAB_WORDS] */
+} capmi_diveval;
+int capmi_diveval_add(const capmi_diveval *d, const int64_t *hyp, int B, int L, const int64_t *img_idx, void *stream);
+int capmi_diveval_reduce(const capmi_diveval *d, double *out, int64_t *totals, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
