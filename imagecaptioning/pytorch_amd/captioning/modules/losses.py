@@ -9,7 +9,8 @@ import math
 import torch
 import torch.nn as nn
 
-from ..utils.rewards import get_scores
+from ..utils.rewards import get_scores, get_self_cider_scores
+from imagecaptioning.pytorch_amd.ciderd import nsc_advantage
 from imagecaptioning.pytorch_amd.sparse_logp import select_logp, sum_logp, fused_reward_criterion
 
 
@@ -84,7 +85,9 @@ class StructureLosses(nn.Module):
     the margin types that take RAW LOGITS -- 'max_margin' (105-114), 'multi_margin' (128-137), 'real_softmax_margin' (157-166):
     sampled with output_logsoftmax=0 (loss_wrapper.py:31-37), served by rollouts that store the logits (capmi.h CAPMI_SELECT_RAW).
     The optional ``entropy_reward_weight`` (66-69) is supported.  All of them only read the entries of the sampled tokens, so the
-    gradient stays sparse (``select_logp``).  The self-CIDEr reward is not implemented."""
+    gradient stays sparse (``select_logp``).  ``self_cider_reward_weight`` (175-182) is read by 'new_self_critical' alone, as in the
+    reference: the self-CIDEr of the image's n samples times the weight joins each of its n rows after the leave-one-out baseline
+    has been subtracted; with any other type it raises.  ``out['reward']`` is the mixed CIDEr-D / BLEU-4 score before either."""
 
     LOGPROB_TYPES = ('new_self_critical', 'seqnll', 'risk', 'softmax_margin', 'best_of_n')
     LOGIT_TYPES = ('max_margin', 'multi_margin', 'real_softmax_margin')
@@ -98,8 +101,10 @@ class StructureLosses(nn.Module):
         if self.loss_type not in self.LOGPROB_TYPES + self.LOGIT_TYPES:
             raise NotImplementedError('structure_loss_type %r: implemented are %s'
                                       % (self.loss_type, ', '.join(self.LOGPROB_TYPES + self.LOGIT_TYPES)))
-        if getattr(self.opt, 'self_cider_reward_weight', 0) > 0:
-            raise NotImplementedError('self_cider_reward_weight (get_self_cider_scores, rewards.py:116-137) is out of scope')
+        sw = getattr(self.opt, 'self_cider_reward_weight', 0)
+        if sw > 0 and self.loss_type != 'new_self_critical':
+            raise NotImplementedError('self_cider_reward_weight is read by structure_loss_type new_self_critical alone '
+                                      '(losses.py:175-182), not by %r' % self.loss_type)
         out = {}
         N = input.size(0)
         n = N // len(data_gts)
@@ -113,14 +118,27 @@ class StructureLosses(nn.Module):
         sel = select_logp(input, seq)
         mask = _shifted_mask(seq, sel)
         scores = get_scores(data_gts, seq, self.opt, as_tensor=True)
-        scores = (scores if torch.is_tensor(scores) else torch.as_tensor(scores)).to(sel).view(-1, n)
+        w_fused = None
+        if sw > 0:
+            selfc = get_self_cider_scores(data_gts, seq, self.opt, as_tensor=True)
+            selfc = selfc if torch.is_tensor(selfc) else torch.as_tensor(selfc)
+            if (ent is None and torch.is_tensor(scores) and scores.is_cuda and scores.dtype == torch.float64 and n >= 2
+                    and sel.dtype == torch.float32 and selfc.is_cuda and selfc.dtype == torch.float64):
+                # float32 scores, leave-one-out advantage and the self-CIDEr term in one launch
+                scores, w_fused = nsc_advantage(scores.contiguous(), n, selfc.contiguous(), sw)
+        if w_fused is None:
+            scores = (scores if torch.is_tensor(scores) else torch.as_tensor(scores)).to(sel).view(-1, n)
         out['reward'] = scores
         if ent is not None:
             scores = scores + ew * ((ent * mask).sum(1) / mask.sum(1)).view(-1, n)
         lt = self.loss_type
         if lt in ('new_self_critical', 'best_of_n'):
-            if lt == 'new_self_critical':           # leave-one-out baseline: the mean score of the image's other samples
+            if w_fused is not None:
+                w = w_fused
+            elif lt == 'new_self_critical':         # leave-one-out baseline: the mean score of the image's other samples
                 w = scores - (scores.sum(1, keepdim=True) - scores) / (scores.shape[1] - 1)
+                if sw > 0:
+                    w = w + sw * selfc.to(w).view(-1, 1)
             else:                                   # supervise only the best-scoring sample(s) of each image
                 w = (scores == scores.max(1, keepdim=True)[0]).to(sel)
             output = -sel * mask * w.reshape(-1, 1)

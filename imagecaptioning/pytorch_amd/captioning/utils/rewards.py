@@ -1,10 +1,16 @@
-"""Reward plumbing of SCST (reference captioning/utils/rewards.py), CIDEr-D on the device.
+"""Reward plumbing of SCST (reference captioning/utils/rewards.py): CIDEr-D, sentence BLEU-4 and self-CIDEr on the device.
 
 ``init_scorer(cached_tokens)`` loads ``data/<cached_tokens>.p`` (scripts/prepro_ngrams.py:79-80) into a
 device hash table once.  ``get_self_critical_reward`` keeps the reference signature and return type
 (np.ndarray [N,L] float64, rewards.py:41-81) for drop-in callers; ``self_critical_reward_device``
 is the sync-free variant our LossWrapper uses (advantage stays in HBM).
 The CIDEr-D arithmetic restates the external pyciderevalcap package: PARITY UNPINNED (oracle/ciderd.py).
+
+``bleu_reward_weight > 0`` mixes ``Bleu(4)``'s per-sentence BLEU-4 in (rewards.py:68-74, 105-112): scores = cider_reward_weight *
+CIDEr-D + bleu_reward_weight * BLEU-4 over sampled and greedy rows alike, one extra launch that does the mix as it writes; a
+weight of 0 skips that scorer, as the reference does.  ``get_self_cider_scores`` is rewards.py:116-136 against the same training
+document frequencies; an image whose n-grams all weigh 0 scores 0.0 where numpy's route gives NaN.  Both restate packages absent
+from the reference checkout (PARITY UNPINNED, tests/rewards_ref64.py).  With both weights 0 nothing new is launched.
 """
 import os
 
@@ -72,9 +78,8 @@ def _pack(data_gts):
 
 
 def self_critical_reward_device(greedy_res, data_gts, gen_result, opt):
-    """advantage [N] float32 on device + raw scores [N+B] float64; no host synchronisation."""
-    if getattr(opt, 'bleu_reward_weight', 0) > 0:
-        raise NotImplementedError('BLEU reward (default weight 0, opts.py:185) is out of scope')
+    """advantage [N] float32 on device + scores [N+B] float64; no host synchronisation.  The scores are the raw CIDEr-D ones, or,
+    with bleu_reward_weight > 0, the mix cider_reward_weight * CIDEr-D + bleu_reward_weight * BLEU-4 the advantage is taken of."""
     B = len(data_gts)
     n = gen_result.shape[0] // B
     packed = _pack(data_gts)
@@ -83,10 +88,14 @@ def self_critical_reward_device(greedy_res, data_gts, gen_result, opt):
     if hyp_all is not None and not (hyp_all.dtype == torch.long and hyp_all.is_contiguous() and
                                     hyp_all.shape[0] == gen_result.shape[0] + greedy_res.shape[0]):
         hyp_all = None
+    w = getattr(opt, 'cider_reward_weight', 1)
+    bw = getattr(opt, 'bleu_reward_weight', 0)
+    if bw > 0:
+        return CiderD_scorer.self_critical_reward(greedy_res.long().contiguous(), gen_result.long().contiguous(), refs, n_refs, n,
+                                                  hyp_all=hyp_all, cooked=getattr(packed, 'cooked', None), mix=(w, bw))
     reward, scores = CiderD_scorer.self_critical_reward(greedy_res.long().contiguous(), gen_result.long().contiguous(),
                                                          refs, n_refs, n, hyp_all=hyp_all,
                                                          cooked=getattr(packed, 'cooked', None))
-    w = getattr(opt, 'cider_reward_weight', 1)
     if w != 1:
         reward = reward * w
     return reward, scores
@@ -97,19 +106,36 @@ def get_self_critical_reward(greedy_res, data_gts, gen_result, opt):
     reward, scores = self_critical_reward_device(greedy_res, data_gts, gen_result, opt)
     N = gen_result.shape[0]
     B = len(data_gts)
-    s = scores.cpu().numpy() * getattr(opt, 'cider_reward_weight', 1)
+    s = scores.cpu().numpy()
+    if not getattr(opt, 'bleu_reward_weight', 0) > 0:        # (with a BLEU weight the scores come back mixed)
+        s = s * getattr(opt, 'cider_reward_weight', 1)
     adv = s[:N].reshape(B, N // B) - s[N:][:, None]
     return np.repeat(adv.reshape(N)[:, None], gen_result.shape[1], 1)
 
 
 def get_scores(data_gts, gen_result, opt, as_tensor=False):
-    """rewards.py:83-114: CIDEr-D of each sampled row (np.ndarray [N], or a device tensor)."""
+    """rewards.py:83-114: cider_reward_weight * CIDEr-D (+ bleu_reward_weight * BLEU-4) of each sampled row (np.ndarray [N], or a
+    device tensor)."""
     B = len(data_gts)
     N = gen_result.shape[0]
     n = N // B
     packed = _pack(data_gts)
     refs, n_refs = packed
     img = (torch.arange(N, device=gen_result.device) // n).to(torch.int32)
+    w, bw = getattr(opt, 'cider_reward_weight', 1), getattr(opt, 'bleu_reward_weight', 0)
+    if bw > 0:
+        hyp = gen_result.long().contiguous()
+        base = CiderD_scorer.score(hyp, img, refs, n_refs, getattr(packed, 'cooked', None)) if w > 0 else None
+        scores = CiderD_scorer.bleu4(hyp, img, packed, w, bw, base)
+        return scores if as_tensor else scores.cpu().numpy()
     scores = CiderD_scorer.score(gen_result.long().contiguous(), img, refs, n_refs, getattr(packed, 'cooked', None)) * \
         getattr(opt, 'cider_reward_weight', 1)
+    return scores if as_tensor else scores.cpu().numpy()
+
+
+def get_self_cider_scores(data_gts, gen_result, opt, as_tensor=False):
+    """rewards.py:116-136: the self-CIDEr diversity of each image's sampled rows against the training document frequencies
+    (np.ndarray [B], or a device tensor).  0.0, not NaN, for an image whose n-grams all weigh 0."""
+    n = gen_result.shape[0] // len(data_gts)
+    scores = CiderD_scorer.self_cider(gen_result.long().contiguous(), n)
     return scores if as_tensor else scores.cpu().numpy()

@@ -95,6 +95,17 @@ class PackedRefs(tuple):
         return self
 
 
+def nsc_advantage(scores, n, add=None, add_w=0.0):
+    """new_self_critical's weights from float64 device scores [N] in one launch (capmi_nsc_advantage): (reward float32 [B,n] = the
+    scores, adv float32 [N] = leave-one-out advantage + add_w * add[image]); add: float64 [B] or None."""
+    N = scores.shape[0]
+    assert scores.dtype == torch.float64 and scores.is_contiguous() and (add is None or (add.dtype == torch.float64 and add.is_contiguous()))
+    buf = torch.empty(2, N, dtype=torch.float32, device=scores.device)
+    check(lib.capmi_nsc_advantage(ptr(scores), ptr(add), float(add_w), N, n, ptr(buf), buf.data_ptr() + 4 * N, stream_ptr()),
+          'capmi_nsc_advantage')
+    return buf[0].view(-1, n), buf[1]
+
+
 class DeviceCiderD:
     def __init__(self, document_frequency, ref_len, device, _table=None):
         keys, vals = _table if _table is not None else build_table(document_frequency)
@@ -161,10 +172,47 @@ class DeviceCiderD:
                                      stream_ptr()), 'capmi_ciderd_score')
         return scores
 
-    def self_critical_reward(self, greedy, sampled, refs, n_refs, n, hyp_all=None, cooked=None):
+    SELF_CIDER_NMAX = 32           # capmi.h CAPMI_SELF_CIDER_NMAX
+
+    def bleu4(self, hyp, hyp_img, packed, cw, bw, base=None, stats=None):
+        """cw * base + bw * BLEU-4 of every row of hyp int64 [H,L] against the references of image hyp_img[h] (`packed`: what
+        pack_refs returns), float64 [H], one launch (capmi_reward_bleu4).  base: the CIDEr-D scores [H], mixed IN PLACE and
+        returned; None: a new tensor of bw * BLEU-4.  Tokens follow the training convention (the first 0 is a word).
+        stats: an int32 [H,10] tensor to receive guess 1..4, correct 1..4, length, closest reference length."""
+        assert hyp.dtype == torch.long and hyp.is_contiguous() and hyp.is_cuda
+        refs, n_refs = packed
+        H, L = hyp.shape
+        if base is not None:
+            assert base.dtype == torch.float64 and base.is_contiguous() and base.shape == (H,)
+        out = base if base is not None else torch.empty(H, dtype=torch.float64, device=hyp.device)
+        check(lib.capmi_reward_bleu4(ptr(hyp), H, L, ptr(hyp_img), ptr(refs), ptr(n_refs), refs.shape[0], refs.shape[1],
+                                     refs.shape[2], ptr(base), float(cw), float(bw), ptr(out), ptr(stats), stream_ptr()),
+              'capmi_reward_bleu4')
+        return out
+
+    def self_cider(self, hyp, n, parts=False):
+        """self-CIDEr diversity of each image's n sampled rows (hyp int64 [B*n, L]) against this table's document frequencies:
+        float64 [B], two launches (capmi_self_cider_reward), no host sync.  An image whose n-grams all weigh 0 scores 0.0
+        (numpy's eigvalsh route gives NaN).  parts: also return K [B,n,n] and the ascending eigenvalues of K/10 [B,n]."""
+        assert hyp.dtype == torch.long and hyp.is_contiguous() and hyp.is_cuda
+        N, L = hyp.shape
+        if not 2 <= n <= self.SELF_CIDER_NMAX or N % n or N == 0:
+            raise ValueError('self-CIDEr needs 2 <= n <= %d samples per image, got %d rows with n = %d' % (self.SELF_CIDER_NMAX, N, n))
+        B = N // n
+        scratch = torch.empty(N * 4 * (1 + n), dtype=torch.float64, device=hyp.device)      # norm [N,4] | dots [N,n,4]
+        out = torch.empty(B, dtype=torch.float64, device=hyp.device)
+        K = torch.empty(B, n, n, dtype=torch.float64, device=hyp.device) if parts else None
+        eig = torch.empty(B, n, dtype=torch.float64, device=hyp.device) if parts else None
+        check(lib.capmi_self_cider_reward(ptr(hyp), B, n, L, ptr(self.keys), ptr(self.vals), self.cap, self.log_ref_len,
+                                          scratch.data_ptr(), scratch.data_ptr() + 8 * N * 4, ptr(out), ptr(K), ptr(eig),
+                                          stream_ptr()), 'capmi_self_cider_reward')
+        return (out, K, eig) if parts else out
+
+    def self_critical_reward(self, greedy, sampled, refs, n_refs, n, hyp_all=None, cooked=None, mix=None):
         """rewards.py:41-81 on device: scores of N sampled + B greedy rows, advantage [N] float32.
         hyp_all: the [N+B, L] tensor holding `sampled` then `greedy` already side by side (the fused SCST rollout writes them
-        that way): scored in place, no concatenation."""
+        that way): scored in place, no concatenation.
+        mix: (cw, bw) with bw > 0 -- the scores are cw * CIDEr-D + bw * BLEU-4 (CIDEr-D not launched when cw == 0)."""
         N = sampled.shape[0]
         B = greedy.shape[0]
         hyp = hyp_all if hyp_all is not None else torch.cat([sampled, greedy], 0).contiguous()
@@ -175,7 +223,11 @@ class DeviceCiderD:
                 self._img_cache = {}
             img = torch.cat([torch.arange(N, device=hyp.device) // n, torch.arange(B, device=hyp.device)]).to(torch.int32)
             self._img_cache[key] = img
-        scores = self.score(hyp, img, refs, n_refs, cooked)
+        if mix is None:
+            scores = self.score(hyp, img, refs, n_refs, cooked)
+        else:
+            cw, bw = mix
+            scores = self.bleu4(hyp, img, (refs, n_refs), cw, bw, self.score(hyp, img, refs, n_refs, cooked) if cw > 0 else None)
         buf = torch.empty(N + 1, dtype=torch.float32, device=hyp.device)      # [advantage of the N rows | their mean]
         reward = buf[:N]
         check(lib.capmi_scst_advantage_mean(ptr(scores), N, n, ptr(buf), buf.data_ptr() + 4 * N, stream_ptr()),

@@ -13,20 +13,30 @@
 // leave HBM and the host reads eight doubles per evaluation.
 #include "capmi_common.h"
 #include "ngram_common.h"
+#include "ngram_metrics.h"
 #include "../../../include/capmi.h"
 
 namespace {
 
+using capmi::bleu_of_counts;
+using capmi::clipped_matches;
+using capmi::ClosestLen;
 using capmi::df_lookup;
+using capmi::jacobi_eigenvalues;
 using capmi::mix64;
+using capmi::ngram_count;
 using capmi::ngram_tf;
+using capmi::order_cosine;
+using capmi::order_dot;
+using capmi::order_norm;
 using capmi::pack_ngram;
+using capmi::self_cider_of;
 
-constexpr int LMAX = CAPMI_LANGEVAL_LMAX;   // max tokens per row: one wave holds a row
-constexpr int NG = 4;                       // n-gram orders 1..4
-constexpr int CT = NG * LMAX;               // one lane per (order, start position)
+constexpr int LMAX = capmi::NM_LMAX;        // max tokens per row: one wave holds a row
+constexpr int NG = capmi::NM_NG;            // n-gram orders 1..4
+constexpr int CT = capmi::NM_CT;            // one lane per (order, start position)
 constexpr double BETA = 1.2;
-static_assert(LMAX == CAPMI_WAVE, "a caption row is staged and measured by one wave");
+static_assert(LMAX == CAPMI_LANGEVAL_LMAX, "capmi.h CAPMI_LANGEVAL_LMAX is the width the shared n-gram code is built for");
 
 // one token of a row (0 beyond its width); an id the 16-bit key fields cannot hold is reported and ends the caption
 __device__ __forceinline__ int load_token(const int64_t *row, int w, int lane, int32_t *err) {
@@ -38,11 +48,8 @@ __device__ __forceinline__ int load_token(const int64_t *row, int w, int lane, i
     return (int)t;
 }
 
-// caption length of the row whose lane-th token is t: tokens before the first 0.  Whole wave.
-__device__ __forceinline__ int caption_len(int t, int w, int lane) {
-    const unsigned long long ends = __ballot(lane >= w || t == 0);
-    return ends ? __builtin_ctzll(ends) : LMAX;
-}
+// caption length of the row whose lane-th token is t: the evaluation convention, tokens before the first 0.  Whole wave.
+__device__ __forceinline__ int caption_len(int t, int w, int lane) { return capmi::caption_len<false>(t, w, lane); }
 
 // row -> tok[LMAX], *len (LDS); every thread of the workgroup calls it, wave 0 works; ends with a barrier
 __device__ __forceinline__ void stage_row(const int64_t *row, int w, int *tok, int *len, int32_t *err) {
@@ -105,13 +112,6 @@ __device__ __forceinline__ double idf_of(const capmi_langeval &e, uint64_t key, 
     // an n-gram of every image weighs exactly 0, as log(n) - log(n) does on the host: log_n is the host's logarithm, which need
     // not round like the device's, and a weight of one ulp would turn a zero norm into a cosine of order 1
     return df >= e.n_img ? 0.0 : log_n - log(fmax(1.0, (double)df));
-}
-
-// per-order norm of vec[CT] (0 on the lanes that hold no distinct n-gram): threads 0..NG-1, fixed order
-__device__ __forceinline__ double order_norm(const double *vec, int k) {
-    double s = 0.0;
-    for (int j = 0; j < LMAX; ++j) s += vec[k * LMAX + j] * vec[k * LMAX + j];
-    return sqrt(s);
 }
 
 // One workgroup per reference: ref_norm [total_refs, 4].
@@ -180,35 +180,24 @@ __device__ __forceinline__ void score_row(const capmi_langeval &e, const int64_t
     }
 
     // ---- one walk over the references: CIDEr dot products, BLEU clip counts, the closest length
-    int max_tf = 0, best_d = 1 << 30, best_l = 0;
+    int max_tf = 0;
+    ClosestLen closest;
     for (int r = r0; r < r1; ++r) {
         __syncthreads();                                     // contrib / tok_r / key_r of the previous reference are consumed
         stage_row(e.refs + (size_t)r * e.ref_w, e.ref_w, tok_r, &len_s[1], e.err);
         const int len_r = len_s[1];
         key_r[tid] = i + k + 1 <= len_r ? pack_ngram(tok_r, i, k) : 0;
         __syncthreads();
-        int tf_r = 0;
-        if (first)
-            for (int j = 0; j < len_r - k; ++j) tf_r += key_r[k * LMAX + j] == key;
+        const int tf_r = first ? ngram_count(&key_r[k * LMAX], len_r - k, key) : 0;
         max_tf = max(max_tf, tf_r);
         contrib[tid] = first ? vh * ((double)tf_r * idf) : 0.0;     // the reference's weight of the same n-gram: same idf
         __syncthreads();
-        if (tid < NG) {
-            double s = 0.0;
-            for (int j = 0; j < LMAX; ++j) s += contrib[tid * LMAX + j];
-            const double nh = norm_h[tid], nr = e.ref_norm[(size_t)r * NG + tid];
-            if (nh != 0.0 && nr != 0.0) s /= nh * nr;
-            score[tid] += s;
-        }
-        const int d = abs(len_r - len_h);
-        if (d < best_d || (d == best_d && len_r < best_l)) { best_d = d; best_l = len_r; }
+        if (tid < NG) score[tid] += order_cosine(order_dot(contrib, tid), norm_h[tid], e.ref_norm[(size_t)r * NG + tid]);
+        closest.see(len_r, len_h);
     }
-    __syncthreads();
-    icontrib[tid] = first ? min(tf_h, max_tf) : 0;
-    __syncthreads();
+    const int best_l = closest.len;
+    const int correct = clipped_matches(icontrib, first, tf_h, max_tf);
     if (tid < NG) {
-        int correct = 0;
-        for (int j = 0; j < LMAX; ++j) correct += icontrib[tid * LMAX + j];
         e.bleu_stats[(oi * NG + tid) * 2 + 0] = max(0, len_h - tid);
         e.bleu_stats[(oi * NG + tid) * 2 + 1] = correct;
     }
@@ -367,20 +356,7 @@ namespace {
 constexpr int NMAX = CAPMI_DIVEVAL_NMAX;
 constexpr int NO = 6;                       // oracle scores per slot: CIDEr, Bleu_1..4, ROUGE_L
 constexpr int ET = CAPMI_WAVE;              // one wave per image solves the eigenproblem
-static_assert(NMAX <= ET, "one lane per row of K");
-
-// bleu_scorer's score of one set of counts (an instance's or a corpus's): st = guess 1..4, correct 1..4, testlen, reflen
-template <typename I>
-__device__ __forceinline__ void bleu_of_counts(const I *st, double *out) {
-    const double tiny = 1e-15, small = 1e-9;
-    const double ratio = ((double)st[8] + tiny) / ((double)st[9] + small);
-    const double bp = ratio < 1.0 ? exp(1.0 - 1.0 / ratio) : 1.0;
-    double bleu = 1.0;
-    for (int q = 0; q < NG; ++q) {
-        bleu *= ((double)st[NG + q] + tiny) / ((double)st[q] + small);
-        out[q] = pow(bleu, 1.0 / (q + 1)) * bp;
-    }
-}
+static_assert(NMAX == capmi::NM_NMAX, "capmi.h CAPMI_DIVEVAL_NMAX is the matrix size the shared Jacobi is built for");
 
 // One workgroup per caption: norm [img, slot, 4], as langeval_ref_norm_kernel does for a reference.
 __global__ __launch_bounds__(CT) void diveval_norm_kernel(capmi_diveval d, const int64_t *__restrict__ hyp, int B, int L,
@@ -434,31 +410,24 @@ __global__ __launch_bounds__(CT) void diveval_walk_kernel(capmi_diveval d, const
     const double *norm = d.norm + (size_t)img * n * NG;
     double *K = d.K + (size_t)img * n * n;
     bool first_in_image = first;
-    int max_tf = 0, best_d = 1 << 30, best_l = 0;
+    int max_tf = 0;
+    ClosestLen closest;
     for (int o = 0; o < n; ++o) {
         __syncthreads();                                     // tok_r / key_r / contrib / cos_s of the previous caption are consumed
         stage_row(rows + (size_t)o * L, L, tok_r, &len_s[1], d.err);
         const int len_r = len_s[1];
         key_r[tid] = i + k + 1 <= len_r ? pack_ngram(tok_r, i, k) : 0;
         __syncthreads();
-        int tf_r = 0;
-        if (first)
-            for (int j = 0; j < len_r - k; ++j) tf_r += key_r[k * LMAX + j] == key;
+        const int tf_r = first ? ngram_count(&key_r[k * LMAX], len_r - k, key) : 0;
         if (o != s) {
             max_tf = max(max_tf, tf_r);
-            const int dl = abs(len_r - len_h);
-            if (dl < best_d || (dl == best_d && len_r < best_l)) { best_d = dl; best_l = len_r; }
+            closest.see(len_r, len_h);
             if (o < s && tf_r) first_in_image = false;
         }
         if (o >= s) {
             contrib[tid] = first ? vh * ((double)tf_r * idf) : 0.0;
             __syncthreads();
-            if (tid < NG) {
-                double dot = 0.0;
-                for (int j = 0; j < LMAX; ++j) dot += contrib[tid * LMAX + j];
-                const double nh = norm[s * NG + tid], nr = norm[o * NG + tid];
-                cos_s[tid] = (nh != 0.0 && nr != 0.0) ? dot / (nh * nr) : 0.0;
-            }
+            if (tid < NG) cos_s[tid] = order_cosine(order_dot(contrib, tid), norm[s * NG + tid], norm[o * NG + tid]);
             __syncthreads();
             if (tid == 0) {
                 double m = 0.0;
@@ -469,13 +438,10 @@ __global__ __launch_bounds__(CT) void diveval_walk_kernel(capmi_diveval d, const
             }
         }
     }
-    __syncthreads();
-    icontrib[tid] = first ? min(tf_h, max_tf) : 0;
-    __syncthreads();
+    const int best_l = closest.len;
+    const int correct = clipped_matches(icontrib, first, tf_h, max_tf);
     int32_t *st = d.mbleu_stats + ((size_t)img * n + s) * 10;
     if (tid < NG) {
-        int correct = 0;
-        for (int j = 0; j < LMAX; ++j) correct += icontrib[tid * LMAX + j];
         st[tid] = max(0, len_h - tid);
         st[NG + tid] = correct;
         correct_s[tid] = correct;
@@ -509,9 +475,8 @@ __global__ __launch_bounds__(CT) void diveval_oracle_kernel(capmi_langeval e, in
     score_row(e, hyp + (size_t)blockIdx.x * L, L, img, (size_t)img * n + blockIdx.x % n, nullptr, log_n);
 }
 
-// One wave per image: the eigenvalues of K/10 by cyclic Jacobi in LDS, self_cider, and the image's sums over its slots.
-// Lane r owns row r of the rotation.  Rotation (p, q) reads column p and q of every row, then writes them and (by symmetry) rows
-// p and q; the pivot entries are lane 0's.  Every branch is uniform: all lanes read the same LDS words.
+// One wave per image: the eigenvalues of K/10 by cyclic Jacobi in LDS (ngram_metrics.h), self_cider, and the image's sums over
+// its slots.
 __global__ __launch_bounds__(ET) void diveval_finish_kernel(capmi_diveval d, int B, const int64_t *__restrict__ img_idx) {
     __shared__ double A[NMAX][NMAX + 1], ev[NMAX];
     const int n = d.n, lane = threadIdx.x;
@@ -520,56 +485,10 @@ __global__ __launch_bounds__(ET) void diveval_finish_kernel(capmi_diveval d, int
     const double *K = d.K + (size_t)img * n * n;
     for (int idx = lane; idx < n * n; idx += ET) A[idx / n][idx % n] = K[idx] / 10.0;
     __syncthreads();
-    double trace = 0.0;
-    for (int r = 0; r < n; ++r) trace += A[r][r];
-    const double eps = 0x1p-52 * trace, thresh = eps * eps;
-    for (int sweep = 0; sweep < CAPMI_DIVEVAL_SWEEPS; ++sweep) {
-        double off = 0.0;
-        for (int p = 0; p < n - 1; ++p)
-            for (int q = p + 1; q < n; ++q) off += A[p][q] * A[p][q];
-        if (off <= thresh) break;
-        for (int p = 0; p < n - 1; ++p)
-            for (int q = p + 1; q < n; ++q) {
-                const double apq = A[p][q];
-                if (apq == 0.0) continue;
-                const double app = A[p][p], aqq = A[q][q];
-                const double theta = (aqq - app) / (2.0 * apq);
-                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
-                const bool mine = lane < n && lane != p && lane != q;
-                const double arp = mine ? A[lane][p] : 0.0, arq = mine ? A[lane][q] : 0.0;
-                __syncthreads();
-                if (mine) {
-                    const double np_ = c * arp - sn * arq, nq_ = sn * arp + c * arq;
-                    A[lane][p] = np_; A[p][lane] = np_;
-                    A[lane][q] = nq_; A[q][lane] = nq_;
-                }
-                if (lane == 0) {
-                    A[p][p] = app - t * apq;
-                    A[q][q] = aqq + t * apq;
-                    A[p][q] = 0.0;
-                    A[q][p] = 0.0;
-                }
-                __syncthreads();
-            }
-    }
-    // ascending: the rank of an eigenvalue is the number of smaller ones (ties: the lower index first)
-    if (lane < n) {
-        const double x = A[lane][lane];
-        int rank = 0;
-        for (int r = 0; r < n; ++r) {
-            const double y = A[r][r];
-            rank += y < x || (y == x && r < lane);
-        }
-        ev[rank] = x;
-    }
-    __syncthreads();
+    jacobi_eigenvalues(A, n, lane, ev, CAPMI_DIVEVAL_SWEEPS);
     if (lane < n) d.eig[(size_t)img * n + lane] = ev[lane];
     if (lane == 0) {
-        double sum = 0.0;
-        for (int r = 0; r < n; ++r) sum += sqrt(fmax(0.0, ev[r]));
-        const double top = sqrt(fmax(0.0, ev[n - 1]));
-        d.self_cider[img] = sum > 0.0 ? -log(top / sum) / log((double)n) : 0.0;     // every caption empty: 0, not NaN
+        d.self_cider[img] = self_cider_of(ev, n);            // every caption empty: 0, not NaN
         d.seen[img] = 1;
     }
     if (lane < 3) {                                          // distinct 1-grams, distinct 2-grams, tokens

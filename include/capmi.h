@@ -520,6 +520,41 @@ int capmi_scst_advantage(const double *scores, int N, int n, float *reward, void
 int capmi_scst_advantage_mean(const double *scores, int N, int n, float *reward, float *mean_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Sentence BLEU-4 and self-CIDEr as training rewards (bleu_reward_weight: rewards.py:68-74, 105-112; self_cider_reward_weight:
+ * rewards.py:116-136 used by losses.py:175-182).  coco-caption and the cider submodule are not part of the reference checkout:
+ * PARITY UNPINNED, restated in tests/rewards_ref64.py.  Token rows follow the convention of capmi_ciderd_score (cut AFTER the
+ * first 0, which is a word; a negative entry ends a reference without one), not that of capmi_langeval.  Double throughout; no
+ * allocation, no host sync, no atomics: the same bits on every run.
+ *
+ * capmi_reward_bleu4: one launch, one workgroup per row of hyp [H, L] against the references of image hyp_img[h] (refs
+ *   [B, max_refs, ref_w] int32, n_refs [B], as for capmi_ciderd_score; an image index outside [0, B) has no references).
+ *   bleu4 = bleu_scorer's per-sentence Bleu_4, option 'closest' (ties to the shorter reference): p_k = (correct_k + 1e-15) /
+ *   (guess_k + 1e-9) with the clipped counts of order k, (p_1 p_2 p_3 p_4)^(1/4), times exp(1 - 1/ratio) when ratio =
+ *   (len + 1e-15) / (reflen + 1e-9) < 1.  scores[h] = cw * base[h] + bw * bleu4, or bw * bleu4 when base is NULL; base may be
+ *   `scores` itself (the CIDEr-D scores mixed in place).  stats [H, 10] int32, when not NULL, receives guess_1..4, correct_1..4,
+ *   len, reflen.  CAPMI_EINVAL: a NULL pointer, L or ref_w outside 1..64, H, B or max_refs
+ *   < 1.  Token ids must be below 65535, as for capmi_ciderd_score.
+ * capmi_self_cider_reward: two launches over hyp [B * n, L], rows g*n .. g*n+n-1 the samples of image g, 2 <= n <=
+ *   CAPMI_SELF_CIDER_NMAX.  K[i][j] = 10 * (1/4) sum_k cos_k on vectors tf * (log_ref_len - log(max(1, df))) with df from the table
+ *   of capmi_ciderd_score (an order with a zero norm contributes 0; i <= j computed, mirrored); lambda = eigenvalues of K/10 by
+ *   the cyclic Jacobi of capmi_diveval_add, clipped at 0; scores[g] = -log(sqrt(lambda_max) / sum sqrt(lambda)) / log(n), and 0.0
+ *   where the sum is 0 (numpy gives NaN).  A weight below 1e-12 in magnitude is 0: an n-gram of every image must weigh
+ *   exactly 0 although log_ref_len is the host's logarithm.  Scratch: norm [B * n, 4], dots [B * n, n, 4] doubles.  K [B, n, n] and eig [B, n]
+ *   (ascending) are written when not NULL.  CAPMI_EINVAL: a NULL pointer, n or L out of range, B < 1, an invalid table.
+ * capmi_nsc_advantage: one launch.  reward[r] = (float)scores[r]; adv[r] = reward[r] - (sum of the image's other n-1 rewards) /
+ *   (n - 1) + (float)add_w * (float)add[r / n]  (float32 arithmetic in the order of losses.py:175-182; add may be NULL).
+ * ------------------------------------------------------------------------------------------- */
+#define CAPMI_SELF_CIDER_NMAX 32
+int capmi_reward_bleu4(const int64_t *hyp, int H, int L, const int32_t *hyp_img, const int32_t *refs, const int32_t *n_refs, int B,
+                       int max_refs, int ref_w, const double *base, double cw, double bw, double *scores, int32_t *stats,
+                       void *stream);
+int capmi_self_cider_reward(const int64_t *hyp, int B, int n, int L, const uint64_t *table_keys, const double *table_vals,
+                            uint32_t table_cap, double log_ref_len, double *norm, double *dots, double *scores, double *K,
+                            double *eig, void *stream);
+int capmi_nsc_advantage(const double *scores, const double *add, double add_w, int N, int n, float *reward, float *adv,
+                        void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Launch instrumentation (counterpart of the reference's `time/batch` prints, train.py:198-208).
  * capmi_prof_enable(class_mask): launches of the selected kernel classes carry a HIP event pair in the
  * dispatch itself (hipExtLaunchKernelGGL start/stop events on the kernel's own stream: no extra queue
