@@ -229,6 +229,8 @@ class Ppo(C.Structure):
 
 
 LANGEVAL_LMAX = 64     # capmi.h CAPMI_LANGEVAL_LMAX
+CIDERD_COOKED_BYTES = 4392     # capmi.h CAPMI_CIDERD_COOKED_BYTES
+SELF_CIDER_NMAX = 32   # capmi.h CAPMI_SELF_CIDER_NMAX
 LANGEVAL_E_TABLE_FULL, LANGEVAL_E_TOKEN, LANGEVAL_E_IMAGE = 1, 2, 4      # capmi.h CAPMI_LANGEVAL_E_*
 
 

@@ -18,7 +18,7 @@ _M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
 def _mix64(x):
-    """splitmix64 finaliser on a uint64 array (twin of mix64 in csrc/ciderd.hip)."""
+    """splitmix64 finaliser on a uint64 array (twin of mix64 in csrc/ngram_metrics.h)."""
     x = x.copy()
     with np.errstate(over='ignore'):
         x ^= x >> np.uint64(30)
@@ -146,7 +146,7 @@ class DeviceCiderD:
         refs_d, n_refs_d = torch.from_numpy(refs).to(self.device), torch.from_numpy(n_refs).to(self.device)
         return PackedRefs(refs_d, n_refs_d, self.cook(refs_d, n_refs_d))
 
-    COOKED_BYTES = 4392            # capmi.h CAPMI_CIDERD_COOKED_BYTES
+    COOKED_BYTES = _lib.CIDERD_COOKED_BYTES
 
     def cook(self, refs, n_refs):
         """references cooked once per batch (capmi_ciderd_cook_refs): uint8 [B*max_refs, COOKED_BYTES] on the device"""
@@ -172,7 +172,7 @@ class DeviceCiderD:
                                      stream_ptr()), 'capmi_ciderd_score')
         return scores
 
-    SELF_CIDER_NMAX = 32           # capmi.h CAPMI_SELF_CIDER_NMAX
+    SELF_CIDER_NMAX = _lib.SELF_CIDER_NMAX
 
     def bleu4(self, hyp, hyp_img, packed, cw, bw, base=None, stats=None):
         """cw * base + bw * BLEU-4 of every row of hyp int64 [H,L] against the references of image hyp_img[h] (`packed`: what

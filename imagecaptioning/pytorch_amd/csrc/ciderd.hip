@@ -11,20 +11,16 @@
 //
 // This kernel is latency bound (a few thousand dependent hash probes, < 0.5 MB touched): there is no
 // HBM or MFMA roofline to chase, the win is removing the device->host sync from the SCST step.
-#include "capmi_common.h"
-#include "ngram_common.h"
+//
+// Keys, the token convention (cut after the first 0), the cooking of a row and the per-order norm / dot / cosine are the
+// family's (ngram_metrics.h); this file keeps what is CIDEr-D's own: the cooked blob, the clipped product, the length penalty.
+#include "ngram_metrics.h"
 #include "profile.h"
-#include "../../../include/capmi.h"
+
+using namespace capmi;
 
 namespace {
 
-using capmi::df_lookup;
-using capmi::ngram_tf;
-using capmi::pack_ngram;
-
-constexpr int LMAX = 64;            // max tokens per sequence (reference: seq_length 16..30)
-constexpr int NG = 4;               // n-gram orders 1..4
-constexpr int CT = NG * LMAX;       // one lane per (order, start position)
 constexpr double SIGMA = 6.0;
 
 struct Cooked {
@@ -35,41 +31,19 @@ struct Cooked {
     int len;             // tokens kept (up to and including the first 0)
 };
 
-// all CT threads participate.  tok[] holds the raw row (width w).
-__device__ void cook(const int *tok, int w, Cooked &c, const uint64_t *keys, const double *vals, uint32_t cap,
-                     double log_ref_len) {
+// all CT threads participate.  row: int64 (hypotheses) or int32 (packed references), w tokens wide; R is scratch.
+template <typename T>
+__device__ void cook(Row &R, const T *row, int w, Cooked &c, const RewardIdf &idf) {
     const int tid = threadIdx.x;
-    const int k = tid / LMAX, i = tid % LMAX;
-    if (tid == 0) {
-        int len = w;
-        for (int j = 0; j < w; ++j) {
-            if (tok[j] == 0) { len = j + 1; break; }     // rewards.py:33-39: the first 0 is kept
-            if (tok[j] < 0) { len = j; break; }          // packing sentinel: the source row was narrower and had no 0
-        }
-        c.len = len;
-    }
-    __syncthreads();
-    const int len = c.len;
-    const bool valid = (i + k + 1 <= len);
-    const uint64_t key = valid ? pack_ngram(tok, i, k) : 0;
-    c.key[tid] = key;
-    __syncthreads();
-    int tf = 0;
-    bool first = valid;
-    if (valid) tf = ngram_tf(&c.key[k * LMAX], len - k, key, i, first);      // len - k positions of this order
+    const Lane l = cook_row(R, row, w, RewardTokens());
     double v = 0.0;
-    if (first) {
-        const double df = df_lookup(keys, vals, cap, key);
-        v = (double)tf * (log_ref_len - log(fmax(1.0, df)));
-    }
+    if (l.first) v = (double)l.tf * idf(l.key);
+    c.key[tid] = l.key;
     c.vec[tid] = v;
-    c.first[tid] = first ? 1 : 0;
+    c.first[tid] = l.first ? 1 : 0;
+    if (tid == 0) c.len = R.len;
     __syncthreads();
-    if (tid < NG) {
-        double s = 0.0;
-        for (int j = 0; j < LMAX; ++j) s += c.vec[tid * LMAX + j] * c.vec[tid * LMAX + j];
-        c.norm[tid] = sqrt(s);
-    }
+    if (tid < NG) c.norm[tid] = order_norm(c.vec, tid);
     __syncthreads();
 }
 
@@ -83,12 +57,10 @@ __global__ __launch_bounds__(CT) void ciderd_cook_refs_kernel(const int32_t *__r
                                                              const double *__restrict__ vals, uint32_t cap, double log_ref_len,
                                                              Cooked *__restrict__ out) {
     __shared__ Cooked Rf;
-    __shared__ int tok_r[LMAX];
+    __shared__ Row R;
     const int img = blockIdx.x / max_refs, r = blockIdx.x % max_refs;
     if (r >= n_refs[img]) return;
-    if (threadIdx.x < ref_w) tok_r[threadIdx.x] = refs[((size_t)img * max_refs + r) * ref_w + threadIdx.x];
-    __syncthreads();
-    cook(tok_r, ref_w, Rf, keys, vals, cap, log_ref_len);
+    cook(R, refs + ((size_t)img * max_refs + r) * ref_w, ref_w, Rf, RewardIdf{keys, vals, cap, log_ref_len});
     const uint64_t *src = reinterpret_cast<const uint64_t *>(&Rf);
     uint64_t *dst = reinterpret_cast<uint64_t *>(out + blockIdx.x);
     for (int i = threadIdx.x; i < (int)(sizeof(Cooked) / 8); i += CT) dst[i] = src[i];
@@ -104,15 +76,14 @@ __global__ __launch_bounds__(CT) void ciderd_kernel(const int64_t *__restrict__ 
                                                    uint32_t cap, double log_ref_len, double *__restrict__ scores,
                                                    const Cooked *__restrict__ cooked) {
     __shared__ Cooked H, Rf;
-    __shared__ int tok_h[LMAX], tok_r[LMAX];
+    __shared__ Row R;
     __shared__ double contrib[CT];
     __shared__ double score[NG];
     const int h = blockIdx.x, tid = threadIdx.x;
     const int k = tid / LMAX;
-    if (tid < L) tok_h[tid] = (int)hyp[(size_t)h * L + tid];
+    const RewardIdf idf{keys, vals, cap, log_ref_len};
     if (tid < NG) score[tid] = 0.0;
-    __syncthreads();
-    cook(tok_h, L, H, keys, vals, cap, log_ref_len);
+    cook(R, hyp + (size_t)h * L, L, H, idf);
     const int img = hyp_img[h];
     const int nr = n_refs[img];
     const int len_h_bi = H.len > 0 ? H.len - 1 : 0;      // upstream "length" = number of bigrams
@@ -123,9 +94,7 @@ __global__ __launch_bounds__(CT) void ciderd_kernel(const int64_t *__restrict__ 
             for (int i = tid; i < (int)(sizeof(Cooked) / 8); i += CT) dst[i] = src[i];
             __syncthreads();
         } else {
-            if (tid < ref_w) tok_r[tid] = refs[((size_t)img * max_refs + r) * ref_w + tid];
-            __syncthreads();
-            cook(tok_r, ref_w, Rf, keys, vals, cap, log_ref_len);
+            cook(R, refs + ((size_t)img * max_refs + r) * ref_w, ref_w, Rf, idf);
         }
         double cv = 0.0;
         if (H.first[tid]) {
@@ -140,9 +109,7 @@ __global__ __launch_bounds__(CT) void ciderd_kernel(const int64_t *__restrict__ 
         contrib[tid] = cv;
         __syncthreads();
         if (tid < NG) {
-            double s = 0.0;
-            for (int j = 0; j < LMAX; ++j) s += contrib[tid * LMAX + j];
-            if (H.norm[tid] != 0.0 && Rf.norm[tid] != 0.0) s /= H.norm[tid] * Rf.norm[tid];
+            double s = order_cosine(order_dot(contrib, tid), H.norm[tid], Rf.norm[tid]);
             const int len_r_bi = Rf.len > 0 ? Rf.len - 1 : 0;
             const double delta = (double)(len_h_bi - len_r_bi);
             s *= exp(-(delta * delta) / (2.0 * SIGMA * SIGMA));
@@ -166,7 +133,7 @@ extern "C" int capmi_ciderd_score(const int64_t *hyp, int H, int L, const int32_
                                   void *stream) {
     if (!hyp || !hyp_img || !refs || !n_refs || !table_keys || !table_vals || !scores) return CAPMI_EINVAL;
     if (H <= 0 || L <= 0 || L > LMAX || ref_w <= 0 || ref_w > LMAX || max_refs <= 0) return CAPMI_EINVAL;
-    if (table_cap == 0 || (table_cap & (table_cap - 1))) return CAPMI_EINVAL;
+    if (!table_cap_ok(table_cap)) return CAPMI_EINVAL;
     hipLaunchKernelGGL(ciderd_kernel<false>, dim3(H), dim3(CT), 0, (hipStream_t)stream, hyp, L, hyp_img, refs, n_refs, max_refs,
                        ref_w, table_keys, table_vals, table_cap, log_ref_len, scores, (const Cooked *)nullptr);
     CAPMI_CHECK_LAUNCH();
@@ -178,7 +145,7 @@ extern "C" int capmi_ciderd_cook_refs(const int32_t *refs, const int32_t *n_refs
                                       double log_ref_len, void *cooked, void *stream) {
     if (!refs || !n_refs || !table_keys || !table_vals || !cooked || B <= 0 || max_refs <= 0 || ref_w <= 0 || ref_w > LMAX)
         return CAPMI_EINVAL;
-    if (table_cap == 0 || (table_cap & (table_cap - 1)) || (reinterpret_cast<uintptr_t>(cooked) & 7)) return CAPMI_EINVAL;
+    if (!table_cap_ok(table_cap) || (reinterpret_cast<uintptr_t>(cooked) & 7)) return CAPMI_EINVAL;
     hipLaunchKernelGGL(ciderd_cook_refs_kernel, dim3(B * max_refs), dim3(CT), 0, (hipStream_t)stream, refs, n_refs, max_refs, ref_w,
                        table_keys, table_vals, table_cap, log_ref_len, reinterpret_cast<Cooked *>(cooked));
     CAPMI_CHECK_LAUNCH();
@@ -191,7 +158,7 @@ extern "C" int capmi_ciderd_score_cooked(const int64_t *hyp, int H, int L, const
                                          void *stream) {
     if (!hyp || !hyp_img || !cooked || !n_refs || !table_keys || !table_vals || !scores) return CAPMI_EINVAL;
     if (H <= 0 || L <= 0 || L > LMAX || max_refs <= 0) return CAPMI_EINVAL;
-    if (table_cap == 0 || (table_cap & (table_cap - 1))) return CAPMI_EINVAL;
+    if (!table_cap_ok(table_cap)) return CAPMI_EINVAL;
     hipLaunchKernelGGL(ciderd_kernel<true>, dim3(H), dim3(CT), 0, (hipStream_t)stream, hyp, L, hyp_img, (const int32_t *)nullptr,
                        n_refs, max_refs, 0, table_keys, table_vals, table_cap, log_ref_len, scores,
                        reinterpret_cast<const Cooked *>(cooked));

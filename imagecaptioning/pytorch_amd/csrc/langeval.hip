@@ -4,63 +4,23 @@
 // Three kinds of launch.  Building (once per split): a workgroup per image inserts the image's distinct reference n-grams into an
 // open-addressing table in HBM (atomicCAS on the key, atomicAdd on the count), then a workgroup per reference stores the four
 // tf-idf norms, so that scoring never looks a reference n-gram up.  Adding (once per decoded batch): a workgroup per hypothesis
-// row cooks the row in LDS -- one lane per (order, start position), as ciderd.hip does -- and walks the image's references once:
+// row cooks the row in LDS -- one lane per (order, start position), ngram_metrics.h -- and walks the image's references once:
 // the occurrences of each hypothesis n-gram in the reference feed the CIDEr dot product and BLEU's clip count together; then one
 // wave per reference runs the LCS rows of ROUGE-L in registers (a row of the table is a prefix maximum across the lanes).
 // Reducing: one workgroup sums the per-image integers as integers and the scores in a fixed order.
 //
 // All of it is latency bound (a few hundred hash probes and LDS compares per caption): the point is that the decoded rows never
 // leave HBM and the host reads eight doubles per evaluation.
-#include "capmi_common.h"
-#include "ngram_common.h"
+//
+// Cooking, staging, the token convention (EvalTokens) and the idf rule (CorpusIdf) are the family's (ngram_metrics.h); this file
+// keeps the document-frequency build, ROUGE-L, the walks' per-pair logic and the reductions.
 #include "ngram_metrics.h"
-#include "../../../include/capmi.h"
+
+using namespace capmi;
 
 namespace {
 
-using capmi::bleu_of_counts;
-using capmi::clipped_matches;
-using capmi::ClosestLen;
-using capmi::df_lookup;
-using capmi::jacobi_eigenvalues;
-using capmi::mix64;
-using capmi::ngram_count;
-using capmi::ngram_tf;
-using capmi::order_cosine;
-using capmi::order_dot;
-using capmi::order_norm;
-using capmi::pack_ngram;
-using capmi::self_cider_of;
-
-constexpr int LMAX = capmi::NM_LMAX;        // max tokens per row: one wave holds a row
-constexpr int NG = capmi::NM_NG;            // n-gram orders 1..4
-constexpr int CT = capmi::NM_CT;            // one lane per (order, start position)
 constexpr double BETA = 1.2;
-static_assert(LMAX == CAPMI_LANGEVAL_LMAX, "capmi.h CAPMI_LANGEVAL_LMAX is the width the shared n-gram code is built for");
-
-// one token of a row (0 beyond its width); an id the 16-bit key fields cannot hold is reported and ends the caption
-__device__ __forceinline__ int load_token(const int64_t *row, int w, int lane, int32_t *err) {
-    const int64_t t = lane < w ? row[lane] : 0;
-    if (t < 0 || t >= 65535) {
-        atomicOr(err, CAPMI_LANGEVAL_E_TOKEN);
-        return 0;
-    }
-    return (int)t;
-}
-
-// caption length of the row whose lane-th token is t: the evaluation convention, tokens before the first 0.  Whole wave.
-__device__ __forceinline__ int caption_len(int t, int w, int lane) { return capmi::caption_len<false>(t, w, lane); }
-
-// row -> tok[LMAX], *len (LDS); every thread of the workgroup calls it, wave 0 works; ends with a barrier
-__device__ __forceinline__ void stage_row(const int64_t *row, int w, int *tok, int *len, int32_t *err) {
-    if (threadIdx.x < LMAX) {
-        const int t = load_token(row, w, threadIdx.x, err);
-        tok[threadIdx.x] = t;
-        const int n = caption_len(t, w, threadIdx.x);
-        if (threadIdx.x == 0) *len = n;
-    }
-    __syncthreads();
-}
 
 __device__ __forceinline__ void df_insert(uint64_t *keys, int32_t *counts, uint32_t cap, uint64_t key, int32_t *err) {
     uint32_t slot = (uint32_t)mix64(key) & (cap - 1);
@@ -79,59 +39,29 @@ __device__ __forceinline__ void df_insert(uint64_t *keys, int32_t *counts, uint3
 // n-gram: the set of insertions is the same on every run, only their order -- hence the slots -- is not, and a lookup does not
 // see the slots.
 __global__ __launch_bounds__(CT) void langeval_df_kernel(capmi_langeval e) {
-    __shared__ int tok_c[LMAX], tok_o[LMAX], len_s[2];
-    __shared__ uint64_t key_c[CT], key_o[CT];
-    const int tid = threadIdx.x, k = tid / LMAX, i = tid % LMAX;
+    __shared__ Row Cur, Old;
+    const EvalTokens tokens{e.err};
     const int r0 = e.ref_off[blockIdx.x], r1 = e.ref_off[blockIdx.x + 1];
     for (int r = r0; r < r1; ++r) {
-        stage_row(e.refs + (size_t)r * e.ref_w, e.ref_w, tok_c, &len_s[0], e.err);
-        const int len = len_s[0];
-        const bool valid = i + k + 1 <= len;
-        const uint64_t key = valid ? pack_ngram(tok_c, i, k) : 0;
-        key_c[tid] = key;
-        __syncthreads();
-        bool first = valid;
-        if (valid) ngram_tf(&key_c[k * LMAX], len - k, key, i, first);
+        Lane c = cook_row(Cur, e.refs + (size_t)r * e.ref_w, e.ref_w, tokens);
         for (int o = r0; o < r; ++o) {                       // the image's earlier references
-            stage_row(e.refs + (size_t)o * e.ref_w, e.ref_w, tok_o, &len_s[1], e.err);
-            const int lo = len_s[1];
-            key_o[tid] = i + k + 1 <= lo ? pack_ngram(tok_o, i, k) : 0;
-            __syncthreads();
-            if (first)
-                for (int j = 0; j < lo - k; ++j)
-                    if (key_o[k * LMAX + j] == key) { first = false; break; }
+            stage_keys(Old, e.refs + (size_t)o * e.ref_w, e.ref_w, tokens);
+            if (c.first && Old.count(c.k(), c.key)) c.first = false;
             __syncthreads();
         }
-        if (first) df_insert(e.table_keys, e.table_counts, e.table_cap, key, e.err);
+        if (c.first) df_insert(e.table_keys, e.table_counts, e.table_cap, c.key, e.err);
         __syncthreads();
     }
 }
 
-__device__ __forceinline__ double idf_of(const capmi_langeval &e, uint64_t key, double log_n) {
-    const int df = df_lookup(e.table_keys, e.table_counts, e.table_cap, key);
-    // an n-gram of every image weighs exactly 0, as log(n) - log(n) does on the host: log_n is the host's logarithm, which need
-    // not round like the device's, and a weight of one ulp would turn a zero norm into a cosine of order 1
-    return df >= e.n_img ? 0.0 : log_n - log(fmax(1.0, (double)df));
+__device__ __forceinline__ CorpusIdf idf_of(const capmi_langeval &e, double log_n) {
+    return CorpusIdf{e.table_keys, e.table_counts, e.table_cap, e.n_img, log_n};
 }
 
 // One workgroup per reference: ref_norm [total_refs, 4].
 __global__ __launch_bounds__(CT) void langeval_ref_norm_kernel(capmi_langeval e, double log_n) {
-    __shared__ int tok[LMAX], len_s;
-    __shared__ uint64_t keys[CT];
-    __shared__ double vec[CT];
-    const int tid = threadIdx.x, k = tid / LMAX, i = tid % LMAX, r = blockIdx.x;
-    stage_row(e.refs + (size_t)r * e.ref_w, e.ref_w, tok, &len_s, e.err);
-    const int len = len_s;
-    const bool valid = i + k + 1 <= len;
-    const uint64_t key = valid ? pack_ngram(tok, i, k) : 0;
-    keys[tid] = key;
-    __syncthreads();
-    bool first = valid;
-    int tf = 0;
-    if (valid) tf = ngram_tf(&keys[k * LMAX], len - k, key, i, first);
-    vec[tid] = first ? (double)tf * idf_of(e, key, log_n) : 0.0;
-    __syncthreads();
-    if (tid < NG) e.ref_norm[(size_t)r * NG + tid] = order_norm(vec, tid);
+    const int r = blockIdx.x;
+    row_norms(e.refs + (size_t)r * e.ref_w, e.ref_w, EvalTokens{e.err}, idf_of(e, log_n), e.ref_norm + (size_t)r * NG);
 }
 
 // The entry of position g of img_idx [G] counts when no later entry names the same image and the image is inside the split.
@@ -153,26 +83,19 @@ __device__ __forceinline__ bool entry_counts(const int64_t *__restrict__ img_idx
 // (skipped when NULL).  oi is the image for capmi_langeval_add and (image, slot) for the oracle scores of capmi_diveval_add.
 __device__ __forceinline__ void score_row(const capmi_langeval &e, const int64_t *__restrict__ row, int L, int img, size_t oi,
                                           int32_t *__restrict__ lcs_out, double log_n) {
-    __shared__ int tok_h[LMAX], tok_r[LMAX], len_s[2];
-    __shared__ uint64_t key_h[CT], key_r[CT];
+    __shared__ Row Hr, Rr;
     __shared__ double contrib[CT], norm_h[NG], score[NG], wave_p[NG], wave_r[NG];
     __shared__ int icontrib[CT];
-    const int tid = threadIdx.x, k = tid / LMAX, i = tid % LMAX;
+    const EvalTokens tokens{e.err};
+    const int tid = threadIdx.x;
     const int r0 = e.ref_off[img], r1 = e.ref_off[img + 1];
 
     // ---- the hypothesis: distinct n-grams, their counts and tf-idf weights
-    stage_row(row, L, tok_h, &len_s[0], e.err);
-    const int len_h = len_s[0];
-    const bool valid = i + k + 1 <= len_h;
-    const uint64_t key = valid ? pack_ngram(tok_h, i, k) : 0;
-    key_h[tid] = key;
-    __syncthreads();
-    bool first = valid;
-    int tf_h = 0;
-    if (valid) tf_h = ngram_tf(&key_h[k * LMAX], len_h - k, key, i, first);
-    const double idf = first ? idf_of(e, key, log_n) : 0.0;
-    const double vh = (double)tf_h * idf;
-    contrib[tid] = first ? vh : 0.0;
+    const Lane c = cook_row(Hr, row, L, tokens);
+    const int len_h = Hr.len;
+    const double idf = c.first ? idf_of(e, log_n)(c.key) : 0.0;
+    const double vh = (double)c.tf * idf;
+    contrib[tid] = c.first ? vh : 0.0;
     __syncthreads();
     if (tid < NG) {
         norm_h[tid] = order_norm(contrib, tid);
@@ -183,20 +106,17 @@ __device__ __forceinline__ void score_row(const capmi_langeval &e, const int64_t
     int max_tf = 0;
     ClosestLen closest;
     for (int r = r0; r < r1; ++r) {
-        __syncthreads();                                     // contrib / tok_r / key_r of the previous reference are consumed
-        stage_row(e.refs + (size_t)r * e.ref_w, e.ref_w, tok_r, &len_s[1], e.err);
-        const int len_r = len_s[1];
-        key_r[tid] = i + k + 1 <= len_r ? pack_ngram(tok_r, i, k) : 0;
-        __syncthreads();
-        const int tf_r = first ? ngram_count(&key_r[k * LMAX], len_r - k, key) : 0;
+        __syncthreads();                                     // contrib / Rr of the previous reference are consumed
+        stage_keys(Rr, e.refs + (size_t)r * e.ref_w, e.ref_w, tokens);
+        const int tf_r = c.first ? Rr.count(c.k(), c.key) : 0;
         max_tf = max(max_tf, tf_r);
-        contrib[tid] = first ? vh * ((double)tf_r * idf) : 0.0;     // the reference's weight of the same n-gram: same idf
+        contrib[tid] = c.first ? vh * ((double)tf_r * idf) : 0.0;     // the reference's weight of the same n-gram: same idf
         __syncthreads();
         if (tid < NG) score[tid] += order_cosine(order_dot(contrib, tid), norm_h[tid], e.ref_norm[(size_t)r * NG + tid]);
-        closest.see(len_r, len_h);
+        closest.see(Rr.len, len_h);
     }
     const int best_l = closest.len;
-    const int correct = clipped_matches(icontrib, first, tf_h, max_tf);
+    const int correct = clipped_matches(icontrib, c.first, c.tf, max_tf);
     if (tid < NG) {
         e.bleu_stats[(oi * NG + tid) * 2 + 0] = max(0, len_h - tid);
         e.bleu_stats[(oi * NG + tid) * 2 + 1] = correct;
@@ -212,11 +132,11 @@ __device__ __forceinline__ void score_row(const capmi_langeval &e, const int64_t
     // ---- ROUGE-L: wave w takes references w, w + 4, ...; lane j holds column j + 1 of the LCS table's current row.
     // With x[j] = row[i-1][j-1] + 1 where the tokens match and row[i-1][j] elsewhere, row[i] is the prefix maximum of x.
     const int wave = tid / CAPMI_WAVE, lane = tid % CAPMI_WAVE;
-    const int th = lane < len_h ? tok_h[lane] : -1;
+    const int th = lane < len_h ? Hr.tok[lane] : -1;
     double p_max = 0.0, r_max = 0.0;
     for (int r = r0 + wave; r < r1; r += NG) {
-        const int tr = load_token(e.refs + (size_t)r * e.ref_w, e.ref_w, lane, e.err);
-        const int len_r = caption_len(tr, e.ref_w, lane);
+        const int tr = tokens.load(e.refs + (size_t)r * e.ref_w, e.ref_w, lane);
+        const int len_r = caption_len<EvalTokens::KEEP_EOS>(tr, e.ref_w, lane);
         int row = 0;
         for (int a = 0; a < len_r; ++a) {
             const int ta = __shfl(tr, a);
@@ -292,14 +212,7 @@ __global__ __launch_bounds__(RT) void langeval_reduce_kernel(capmi_langeval e, d
     }
     __syncthreads();
     if (tid == 0) {
-        const double tiny = 1e-15, small = 1e-9;             // bleu_scorer.py
-        const double ratio = ((double)ti[8] + tiny) / ((double)ti[9] + small);
-        const double bp = ratio < 1.0 ? exp(1.0 - 1.0 / ratio) : 1.0;
-        double bleu = 1.0;
-        for (int q = 0; q < NG; ++q) {
-            bleu *= ((double)ti[NG + q] + tiny) / ((double)ti[q] + small);
-            out[q] = pow(bleu, 1.0 / (q + 1)) * bp;
-        }
+        bleu_of_counts(ti, out);
         const double n = (double)ti[NI];
         out[4] = n > 0 ? td[1] / n : 0.0;
         out[5] = n > 0 ? td[0] / n : 0.0;
@@ -314,7 +227,7 @@ bool langeval_valid(const capmi_langeval *e) {
         !e->bleu_stats || !e->lens || !e->lcs || !e->seen || !e->err)
         return false;
     if (e->n_img < 1 || e->total_refs < 0 || e->ref_w < 1 || e->ref_w > LMAX) return false;
-    return e->table_cap != 0 && !(e->table_cap & (e->table_cap - 1));
+    return table_cap_ok(e->table_cap);
 }
 
 }  // namespace
@@ -353,32 +266,16 @@ extern "C" int capmi_langeval_reduce(const capmi_langeval *e, double *out, int64
 // ---------------------------------------------------------------------------------------------------------------------------
 namespace {
 
-constexpr int NMAX = CAPMI_DIVEVAL_NMAX;
 constexpr int NO = 6;                       // oracle scores per slot: CIDEr, Bleu_1..4, ROUGE_L
 constexpr int ET = CAPMI_WAVE;              // one wave per image solves the eigenproblem
-static_assert(NMAX == capmi::NM_NMAX, "capmi.h CAPMI_DIVEVAL_NMAX is the matrix size the shared Jacobi is built for");
 
 // One workgroup per caption: norm [img, slot, 4], as langeval_ref_norm_kernel does for a reference.
 __global__ __launch_bounds__(CT) void diveval_norm_kernel(capmi_diveval d, const int64_t *__restrict__ hyp, int B, int L,
                                                          const int64_t *__restrict__ img_idx, double log_n) {
-    __shared__ int tok[LMAX], len_s;
-    __shared__ uint64_t keys[CT];
-    __shared__ double vec[CT];
-    const int tid = threadIdx.x, k = tid / LMAX, i = tid % LMAX, g = blockIdx.x / d.n, s = blockIdx.x % d.n;
+    const int g = blockIdx.x / d.n, s = blockIdx.x % d.n;
     int img;
     if (!entry_counts(img_idx, B, g, d.lang.n_img, d.err, &img)) return;
-    stage_row(hyp + (size_t)blockIdx.x * L, L, tok, &len_s, d.err);
-    const int len = len_s;
-    const bool valid = i + k + 1 <= len;
-    const uint64_t key = valid ? pack_ngram(tok, i, k) : 0;
-    keys[tid] = key;
-    __syncthreads();
-    bool first = valid;
-    int tf = 0;
-    if (valid) tf = ngram_tf(&keys[k * LMAX], len - k, key, i, first);
-    vec[tid] = first ? (double)tf * idf_of(d.lang, key, log_n) : 0.0;
-    __syncthreads();
-    if (tid < NG) d.norm[((size_t)img * d.n + s) * NG + tid] = order_norm(vec, tid);
+    row_norms(hyp + (size_t)blockIdx.x * L, L, EvalTokens{d.err}, idf_of(d.lang, log_n), d.norm + ((size_t)img * d.n + s) * NG);
 }
 
 // One workgroup per caption (image, slot s) walks the n captions of its image once.  Slot o >= s: K[s][o] and its mirror.
@@ -386,46 +283,37 @@ __global__ __launch_bounds__(CT) void diveval_norm_kernel(capmi_diveval d, const
 // that o holds is not first seen in s.
 __global__ __launch_bounds__(CT) void diveval_walk_kernel(capmi_diveval d, const int64_t *__restrict__ hyp, int B, int L,
                                                          const int64_t *__restrict__ img_idx, double log_n) {
-    __shared__ int tok_h[LMAX], tok_r[LMAX], len_s[2], icontrib[CT], correct_s[NG];
-    __shared__ uint64_t key_h[CT], key_r[CT];
+    __shared__ Row Hr, Rr;
+    __shared__ int icontrib[CT], correct_s[NG];
     __shared__ double contrib[CT], cos_s[NG];
-    const int n = d.n, tid = threadIdx.x, k = tid / LMAX, i = tid % LMAX, g = blockIdx.x / n, s = blockIdx.x % n;
+    const EvalTokens tokens{d.err};
+    const int n = d.n, tid = threadIdx.x, g = blockIdx.x / n, s = blockIdx.x % n;
     int img;
     if (!entry_counts(img_idx, B, g, d.lang.n_img, d.err, &img)) return;
     const int64_t *rows = hyp + (size_t)g * n * L;
 
-    stage_row(rows + (size_t)s * L, L, tok_h, &len_s[0], d.err);
-    const int len_h = len_s[0];
-    const bool valid = i + k + 1 <= len_h;
-    const uint64_t key = valid ? pack_ngram(tok_h, i, k) : 0;
-    key_h[tid] = key;
-    __syncthreads();
-    bool first = valid;
-    int tf_h = 0;
-    if (valid) tf_h = ngram_tf(&key_h[k * LMAX], len_h - k, key, i, first);
-    const double idf = first ? idf_of(d.lang, key, log_n) : 0.0;
-    const double vh = (double)tf_h * idf;
-    if (k == 0 && first) atomicOr(d.vocab_bits + (tok_h[i] >> 5), 1u << (tok_h[i] & 31));      // ids < 65535: inside the bitmap
+    const Lane c = cook_row(Hr, rows + (size_t)s * L, L, tokens);
+    const int len_h = Hr.len;
+    const double idf = c.first ? idf_of(d.lang, log_n)(c.key) : 0.0;
+    const double vh = (double)c.tf * idf;
+    if (c.k() == 0 && c.first) atomicOr(d.vocab_bits + (Hr.tok[c.i()] >> 5), 1u << (Hr.tok[c.i()] & 31));      // ids < 65535: inside the bitmap
 
     const double *norm = d.norm + (size_t)img * n * NG;
     double *K = d.K + (size_t)img * n * n;
-    bool first_in_image = first;
+    bool first_in_image = c.first;
     int max_tf = 0;
     ClosestLen closest;
     for (int o = 0; o < n; ++o) {
-        __syncthreads();                                     // tok_r / key_r / contrib / cos_s of the previous caption are consumed
-        stage_row(rows + (size_t)o * L, L, tok_r, &len_s[1], d.err);
-        const int len_r = len_s[1];
-        key_r[tid] = i + k + 1 <= len_r ? pack_ngram(tok_r, i, k) : 0;
-        __syncthreads();
-        const int tf_r = first ? ngram_count(&key_r[k * LMAX], len_r - k, key) : 0;
+        __syncthreads();                                     // Rr / contrib / cos_s of the previous caption are consumed
+        stage_keys(Rr, rows + (size_t)o * L, L, tokens);
+        const int tf_r = c.first ? Rr.count(c.k(), c.key) : 0;
         if (o != s) {
             max_tf = max(max_tf, tf_r);
-            closest.see(len_r, len_h);
+            closest.see(Rr.len, len_h);
             if (o < s && tf_r) first_in_image = false;
         }
         if (o >= s) {
-            contrib[tid] = first ? vh * ((double)tf_r * idf) : 0.0;
+            contrib[tid] = c.first ? vh * ((double)tf_r * idf) : 0.0;
             __syncthreads();
             if (tid < NG) cos_s[tid] = order_cosine(order_dot(contrib, tid), norm[s * NG + tid], norm[o * NG + tid]);
             __syncthreads();
@@ -438,14 +326,8 @@ __global__ __launch_bounds__(CT) void diveval_walk_kernel(capmi_diveval d, const
             }
         }
     }
-    const int best_l = closest.len;
-    const int correct = clipped_matches(icontrib, first, tf_h, max_tf);
-    int32_t *st = d.mbleu_stats + ((size_t)img * n + s) * 10;
-    if (tid < NG) {
-        st[tid] = max(0, len_h - tid);
-        st[NG + tid] = correct;
-        correct_s[tid] = correct;
-    }
+    const int correct = clipped_matches(icontrib, c.first, c.tf, max_tf);
+    if (tid < NG) correct_s[tid] = correct;
     __syncthreads();
     icontrib[tid] = first_in_image;
     __syncthreads();
@@ -455,12 +337,10 @@ __global__ __launch_bounds__(CT) void diveval_walk_kernel(capmi_diveval d, const
         d.slot_distinct[((size_t)img * n + s) * 2 + tid] = cnt;
     }
     if (tid == 0) {
-        st[8] = len_h;
-        st[9] = best_l;
+        int32_t *st = d.mbleu_stats + ((size_t)img * n + s) * 10;
         int cnt[10];
-        for (int q = 0; q < NG; ++q) { cnt[q] = max(0, len_h - q); cnt[NG + q] = correct_s[q]; }
-        cnt[8] = len_h;
-        cnt[9] = best_l;
+        bleu_counts(cnt, len_h, correct_s, 1, closest.len);
+        for (int q = 0; q < 10; ++q) st[q] = cnt[q];
         double b[NG];
         bleu_of_counts(cnt, b);
         d.sent_bleu2[(size_t)img * n + s] = b[1];
@@ -501,12 +381,7 @@ __global__ __launch_bounds__(ET) void diveval_finish_kernel(capmi_diveval d, int
     if (d.oracle && lane < n) {
         const size_t oi = (size_t)img * n + lane;
         int cnt[10];
-        for (int q = 0; q < NG; ++q) {
-            cnt[q] = d.lang.bleu_stats[(oi * NG + q) * 2 + 0];
-            cnt[NG + q] = d.lang.bleu_stats[(oi * NG + q) * 2 + 1];
-        }
-        cnt[8] = d.lang.lens[oi * 2 + 0];
-        cnt[9] = d.lang.lens[oi * 2 + 1];
+        bleu_counts(cnt, d.lang.lens[oi * 2 + 0], d.lang.bleu_stats + oi * NG * 2 + 1, 2, d.lang.lens[oi * 2 + 1]);
         double b[NG];
         bleu_of_counts(cnt, b);
         double *o = d.oracle_scores + oi * NO;
@@ -583,7 +458,7 @@ static_assert(10 + 2 * NO == CAPMI_DIVEVAL_NOUT, "out [CAPMI_DIVEVAL_NOUT]");
 bool diveval_valid(const capmi_diveval *d) {
     if (!d) return false;
     const capmi_langeval &e = d->lang;
-    if (!e.table_keys || !e.table_counts || e.n_img < 1 || e.table_cap == 0 || (e.table_cap & (e.table_cap - 1))) return false;
+    if (!e.table_keys || !e.table_counts || e.n_img < 1 || !table_cap_ok(e.table_cap)) return false;
     if (d->n < 2 || d->n > NMAX) return false;
     if (!d->norm || !d->slot_distinct || !d->distinct || !d->tokens || !d->mbleu_stats || !d->sent_bleu2 || !d->K || !d->eig ||
         !d->self_cider || !d->seen || !d->err || !d->vocab_bits || e.err != d->err)

@@ -1,52 +1,20 @@
 // Sentence BLEU-4 and self-CIDEr as training rewards on the GPU (gfx950): bleu_reward_weight (reference rewards.py:68-74, 105-112)
 // and self_cider_reward_weight (rewards.py:116-136, losses.py:175-182), float64 like the CIDEr-D reward beside them.
 //
-// The n-gram arithmetic is the evaluation's (ngram_metrics.h, shared with langeval.hip); what differs is the convention of the
-// call site.  Tokens: a row is cut AFTER its first 0 (array_to_str keeps the 0 as a word), a negative token is pack_refs' marker
-// behind a full row of a narrower reference array.  Document frequencies of self-CIDEr: the training table of the CIDEr-D reward
-// (float64 counts, log_ref_len), weight of an n-gram = tf * (log_ref_len - log(max(1, df))).
+// Cooking a row, staging the rows it is walked against and the n-gram arithmetic are the family's (ngram_metrics.h); this file
+// keeps the walks' per-pair logic, the reward mix and the advantage.  What differs from the evaluation is the convention of the
+// call site, both named there.  Tokens (RewardTokens): a row is cut AFTER its first 0 (array_to_str keeps the 0 as a word), a
+// negative token is pack_refs' marker behind a full row of a narrower reference array.  Document frequencies of self-CIDEr
+// (SnappedRewardIdf): the training table of the CIDEr-D reward (float64 counts, log_ref_len), weight of an n-gram =
+// tf * (log_ref_len - log(max(1, df))).
 //
 // Like ciderd.hip this is latency bound (a few LDS compares and hash probes per caption): the point is that the sampled rows
 // never leave HBM, that the reward mix costs no launch of its own, and that a step with these rewards can be captured.
-#include "capmi_common.h"
-#include "ngram_common.h"
 #include "ngram_metrics.h"
-#include "../../../include/capmi.h"
+
+using namespace capmi;
 
 namespace {
-
-using capmi::bleu_of_counts;
-using capmi::clipped_matches;
-using capmi::ClosestLen;
-using capmi::df_lookup;
-using capmi::jacobi_eigenvalues;
-using capmi::ngram_count;
-using capmi::ngram_tf;
-using capmi::order_cosine;
-using capmi::order_dot;
-using capmi::order_norm;
-using capmi::pack_ngram;
-using capmi::self_cider_of;
-
-constexpr int LMAX = capmi::NM_LMAX;
-constexpr int NG = capmi::NM_NG;
-constexpr int CT = capmi::NM_CT;            // one lane per (order, start position)
-constexpr int NMAX = capmi::NM_NMAX;
-static_assert(NMAX == CAPMI_SELF_CIDER_NMAX, "capmi.h CAPMI_SELF_CIDER_NMAX");
-
-// row -> tok[LMAX], *len (LDS) under the training convention; every thread of the workgroup calls it, wave 0 works; ends with a
-// barrier.  T: int64 (sampled rows) or int32 (packed references).
-template <typename T>
-__device__ __forceinline__ void stage_reward_row(const T *row, int w, int *tok, int *len) {
-    if (threadIdx.x < LMAX) {
-        const int lane = threadIdx.x;
-        const int t = lane < w ? (int)row[lane] : 0;
-        tok[lane] = t;
-        const int n = capmi::caption_len<true>(t, w, lane);
-        if (lane == 0) *len = n;
-    }
-    __syncthreads();
-}
 
 // This file is built with -ffp-contract=off (build.py EXTRA_FLAGS): the call site's arithmetic must round like the reference's
 // separate numpy / torch operations -- cider_reward_weight * cider + bleu_reward_weight * bleu is two rounded products and a
@@ -61,42 +29,29 @@ __global__ __launch_bounds__(CT) void reward_bleu4_kernel(const int64_t *__restr
                                                          const int32_t *__restrict__ refs, const int32_t *__restrict__ n_refs, int B,
                                                          int max_refs, int ref_w, const double *base, double cw, double bw,
                                                          double *out, int32_t *__restrict__ stats) {
-    __shared__ int tok_h[LMAX], tok_r[LMAX], len_s[2], icontrib[CT], correct_s[NG];
-    __shared__ uint64_t key_h[CT], key_r[CT];
-    const int h = blockIdx.x, tid = threadIdx.x, k = tid / LMAX, i = tid % LMAX;
-
-    stage_reward_row(hyp + (size_t)h * L, L, tok_h, &len_s[0]);
-    const int len_h = len_s[0];
-    const bool valid = i + k + 1 <= len_h;
-    const uint64_t key = valid ? pack_ngram(tok_h, i, k) : 0;
-    key_h[tid] = key;
-    __syncthreads();
-    bool first = valid;
-    int tf_h = 0;
-    if (valid) tf_h = ngram_tf(&key_h[k * LMAX], len_h - k, key, i, first);
+    __shared__ Row Hr, Rr;
+    __shared__ int icontrib[CT], correct_s[NG];
+    const int h = blockIdx.x, tid = threadIdx.x;
+    const Lane c = cook_row(Hr, hyp + (size_t)h * L, L, RewardTokens());
+    const int len_h = Hr.len;
 
     const int img = hyp_img[h];
     const int nr = (img >= 0 && img < B) ? min(n_refs[img], max_refs) : 0;
     int max_tf = 0;
     ClosestLen closest;
     for (int r = 0; r < nr; ++r) {
-        __syncthreads();                                     // tok_r / key_r of the previous reference are consumed
-        stage_reward_row(refs + ((size_t)img * max_refs + r) * ref_w, ref_w, tok_r, &len_s[1]);
-        const int len_r = len_s[1];
-        key_r[tid] = i + k + 1 <= len_r ? pack_ngram(tok_r, i, k) : 0;
-        __syncthreads();
-        const int tf_r = first ? ngram_count(&key_r[k * LMAX], len_r - k, key) : 0;
+        __syncthreads();                                     // Rr of the previous reference is consumed
+        stage_keys(Rr, refs + ((size_t)img * max_refs + r) * ref_w, ref_w, RewardTokens());
+        const int tf_r = c.first ? Rr.count(c.k(), c.key) : 0;
         max_tf = max(max_tf, tf_r);
-        closest.see(len_r, len_h);
+        closest.see(Rr.len, len_h);
     }
-    const int correct = clipped_matches(icontrib, first, tf_h, max_tf);
+    const int correct = clipped_matches(icontrib, c.first, c.tf, max_tf);
     if (tid < NG) correct_s[tid] = correct;
     __syncthreads();
     if (tid == 0) {
         int cnt[10];
-        for (int q = 0; q < NG; ++q) { cnt[q] = max(0, len_h - q); cnt[NG + q] = correct_s[q]; }
-        cnt[8] = len_h;
-        cnt[9] = closest.len;
+        bleu_counts(cnt, len_h, correct_s, 1, closest.len);
         double b[NG];
         bleu_of_counts(cnt, b);
         if (stats)
@@ -111,39 +66,23 @@ __global__ __launch_bounds__(CT) void self_cider_walk_kernel(const int64_t *__re
                                                             const uint64_t *__restrict__ keys, const double *__restrict__ vals,
                                                             uint32_t cap, double log_ref_len, double *__restrict__ norm,
                                                             double *__restrict__ dots) {
-    __shared__ int tok_h[LMAX], tok_r[LMAX], len_s[2];
-    __shared__ uint64_t key_h[CT], key_r[CT];
+    __shared__ Row Hr, Rr;
     __shared__ double contrib[CT];
-    const int tid = threadIdx.x, k = tid / LMAX, i = tid % LMAX, g = blockIdx.x / n, s = blockIdx.x % n;
+    const int tid = threadIdx.x, g = blockIdx.x / n, s = blockIdx.x % n;
     const int64_t *rows = hyp + (size_t)g * n * L;
 
-    stage_reward_row(rows + (size_t)s * L, L, tok_h, &len_s[0]);
-    const int len_h = len_s[0];
-    const bool valid = i + k + 1 <= len_h;
-    const uint64_t key = valid ? pack_ngram(tok_h, i, k) : 0;
-    key_h[tid] = key;
-    __syncthreads();
-    bool first = valid;
-    int tf_h = 0;
-    if (valid) tf_h = ngram_tf(&key_h[k * LMAX], len_h - k, key, i, first);
-    // an n-gram of every image weighs exactly 0, as log(ref_len) - log(ref_len) does on the host: log_ref_len is the host's
-    // logarithm, which need not round like the device's, and a weight of one ulp would turn a zero norm into a cosine of order 1.
-    // Two different counts below 1e9 have logarithms at least 1e-9 apart, so a difference under 1e-12 is that rounding.
-    double idf = first ? log_ref_len - log(fmax(1.0, df_lookup(keys, vals, cap, key))) : 0.0;
-    if (fabs(idf) < 1e-12) idf = 0.0;
-    const double vh = (double)tf_h * idf;
-    contrib[tid] = first ? vh : 0.0;
+    const Lane c = cook_row(Hr, rows + (size_t)s * L, L, RewardTokens());
+    const double idf = c.first ? SnappedRewardIdf{{keys, vals, cap, log_ref_len}}(c.key) : 0.0;
+    const double vh = (double)c.tf * idf;
+    contrib[tid] = c.first ? vh : 0.0;
     __syncthreads();
     if (tid < NG) norm[(size_t)blockIdx.x * NG + tid] = order_norm(contrib, tid);
 
     for (int o = s; o < n; ++o) {
-        __syncthreads();                                     // tok_r / key_r / contrib of the previous caption are consumed
-        stage_reward_row(rows + (size_t)o * L, L, tok_r, &len_s[1]);
-        const int len_r = len_s[1];
-        key_r[tid] = i + k + 1 <= len_r ? pack_ngram(tok_r, i, k) : 0;
-        __syncthreads();
-        const int tf_r = first ? ngram_count(&key_r[k * LMAX], len_r - k, key) : 0;
-        contrib[tid] = first ? vh * ((double)tf_r * idf) : 0.0;
+        __syncthreads();                                     // Rr / contrib of the previous caption are consumed
+        stage_keys(Rr, rows + (size_t)o * L, L, RewardTokens());
+        const int tf_r = c.first ? Rr.count(c.k(), c.key) : 0;
+        contrib[tid] = c.first ? vh * ((double)tf_r * idf) : 0.0;
         __syncthreads();
         if (tid < NG) dots[((size_t)blockIdx.x * n + o) * NG + tid] = order_dot(contrib, tid);
     }
@@ -192,8 +131,6 @@ __global__ void nsc_advantage_kernel(const double *__restrict__ scores, const do
     }
 }
 
-bool table_ok(const uint64_t *keys, const double *vals, uint32_t cap) { return keys && vals && cap != 0 && !(cap & (cap - 1)); }
-
 }  // namespace
 
 extern "C" int capmi_reward_bleu4(const int64_t *hyp, int H, int L, const int32_t *hyp_img, const int32_t *refs,
@@ -210,7 +147,7 @@ extern "C" int capmi_reward_bleu4(const int64_t *hyp, int H, int L, const int32_
 extern "C" int capmi_self_cider_reward(const int64_t *hyp, int B, int n, int L, const uint64_t *table_keys, const double *table_vals,
                                        uint32_t table_cap, double log_ref_len, double *norm, double *dots, double *scores, double *K,
                                        double *eig, void *stream) {
-    if (!hyp || !norm || !dots || !scores || !table_ok(table_keys, table_vals, table_cap)) return CAPMI_EINVAL;
+    if (!hyp || !norm || !dots || !scores || !table_keys || !table_vals || !table_cap_ok(table_cap)) return CAPMI_EINVAL;
     if (B <= 0 || n < 2 || n > NMAX || L <= 0 || L > LMAX) return CAPMI_EINVAL;
     hipLaunchKernelGGL(self_cider_walk_kernel, dim3(B * n), dim3(CT), 0, (hipStream_t)stream, hyp, n, L, table_keys, table_vals,
                        table_cap, log_ref_len, norm, dots);

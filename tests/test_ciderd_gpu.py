@@ -113,3 +113,45 @@ def test_ciderd_edge_cases_empty_ragged_and_full_length():
     reward2, scores2 = dev.self_critical_reward(torch.from_numpy(greedy).to(DEV), torch.from_numpy(sampled).to(DEV), refs,
                                                 n_refs, n, cooked=packed.cooked)
     assert torch.equal(scores, scores2) and torch.equal(reward, reward2)
+
+
+def test_ciderd_at_the_compiled_row_width():
+    """Rows of LMAX = 64 tokens, the width the kernel is compiled for: a hypothesis of 64 non-zero tokens, one whose only 0 is its
+    last column, one that is 0 at column 0; a reference of 64 non-zero tokens, and in the image whose reference array is 61 wide a
+    completely filled reference, behind which pack_refs puts its -1 marker.  The oracle is pure Python and has no width bound."""
+    from oracle import ciderd as C
+    from imagecaptioning.pytorch_amd import ciderd as D
+    vocab, L, B, n = 12, 64, 2, 2
+    rng = np.random.default_rng(64)
+    corpus = C.synthetic_corpus(100, vocab, 5, 20, seed=7)
+    df, ref_len = C.build_document_frequency([[C.tokens_of(r) for r in g] for g in corpus])
+    oracle = C.CiderD(df, ref_len)
+    gts = [np.zeros((3, 64), dtype=np.uint32), np.zeros((2, 61), dtype=np.uint32)]
+    gts[0][0] = rng.integers(1, vocab + 1, size=64)              # 64 non-zero tokens
+    gts[0][1, :30] = rng.integers(1, vocab + 1, size=30)
+    gts[0][2, :63] = rng.integers(1, vocab + 1, size=63)         # its only 0 is column 63
+    gts[1][0] = rng.integers(1, vocab + 1, size=61)              # completely filled, in the narrower array
+    gts[1][1, :17] = rng.integers(1, vocab + 1, size=17)
+    sampled = np.zeros((B * n, L), dtype=np.int64)
+    sampled[0] = gts[0][0]
+    sampled[0, ::5] = rng.integers(1, vocab + 1, size=13)        # 64 non-zero tokens
+    sampled[1, :63] = gts[0][2, :63]                             # the only 0 is at column 63
+    sampled[2, 1:] = rng.integers(1, vocab + 1, size=63)         # 0 at column 0
+    sampled[3, :61] = gts[1][0]
+    sampled[3, 61:] = rng.integers(1, vocab + 1, size=3)
+    greedy = np.zeros((B, L), dtype=np.int64)
+    greedy[0, :30] = gts[0][1, :30]
+    greedy[1] = rng.integers(1, vocab + 1, size=64)
+    assert (sampled[0] != 0).all() and np.flatnonzero(sampled[1] == 0).tolist() == [63] and sampled[2, 0] == 0
+    rewards_ref, scores_ref = C.self_critical_reward(oracle, greedy, gts, sampled)
+    dev = D.DeviceCiderD(df, ref_len, DEV)
+    packed = dev.pack_refs(gts)
+    refs, n_refs = packed
+    assert refs.shape == (2, 3, 64) and refs[1, 0, 61].item() == -1 and (refs[0, 0] != 0).all()
+    g_t, s_t = torch.from_numpy(greedy).to(DEV), torch.from_numpy(sampled).to(DEV)
+    reward, scores = dev.self_critical_reward(g_t, s_t, refs, n_refs, n)
+    np.testing.assert_allclose(scores.cpu().numpy(), scores_ref, rtol=1e-10, atol=1e-12)
+    np.testing.assert_allclose(reward.cpu().numpy(), rewards_ref[:, 0], rtol=1e-5, atol=1e-6)
+    assert scores_ref[:B * n].min() >= 0 and scores_ref[1] > 1.0         # the near copy of a reference scores
+    reward2, scores2 = dev.self_critical_reward(g_t, s_t, refs, n_refs, n, cooked=packed.cooked)
+    assert torch.equal(scores, scores2) and torch.equal(reward, reward2)

@@ -5,6 +5,7 @@ new_self_critical.  CPU only."""
 import argparse
 import math
 import os
+import re
 
 import numpy as np
 import pytest
@@ -28,6 +29,14 @@ def _bleu_of(guess, correct, testlen, reflen):
     b **= 0.25
     ratio = (testlen + TINY) / (reflen + SMALL)
     return b * math.exp(1 - 1 / ratio) if ratio < 1 else b
+
+
+def test_host_constants_match_the_header():
+    from imagecaptioning.pytorch_amd import _lib
+    from imagecaptioning.pytorch_amd.ciderd import DeviceCiderD
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'capmi.h')).read()
+    assert int(re.search(r'#define CAPMI_CIDERD_COOKED_BYTES (\d+)', src).group(1)) == _lib.CIDERD_COOKED_BYTES == DeviceCiderD.COOKED_BYTES
+    assert int(re.search(r'#define CAPMI_SELF_CIDER_NMAX (\d+)', src).group(1)) == _lib.SELF_CIDER_NMAX == DeviceCiderD.SELF_CIDER_NMAX
 
 
 def test_tokens_keep_the_first_zero():
