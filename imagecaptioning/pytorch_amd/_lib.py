@@ -40,6 +40,16 @@ class NextEmbed(C.Structure):
                 ('alive', c_f)]
 
 
+class CtxStep(C.Structure):
+    """capmi_ctx_step (include/capmi.h): the att2ctx stage of an AoA decode step, every decoder_type"""
+    _fields_ = [(k, c_f) for k in ('slabs', 'bias', 'bias2', 'pre', 'c_prev', 'c', 'out', 'resid', 'mask_a', 'out_a', 'planes_a',
+                                   'mask_b', 'out_b', 'planes_b')] + \
+        [('stride', C.c_int64), ('kind', C.c_int), ('splits', C.c_int), ('M', C.c_int), ('R', C.c_int)]
+
+
+CTX_GLU, CTX_RELU, CTX_LSTM = 0, 1, 2        # capmi.h CAPMI_CTX_*
+
+
 class UpDownWeights(C.Structure):
     _fields_ = [(k, c_f) for k in (
         'embed', 'att_w_ih', 'att_w_hh', 'att_b_ih', 'att_b_hh', 'lang_w_ih', 'lang_w_hh', 'lang_b_ih', 'lang_b_hh',
@@ -340,6 +350,8 @@ SIGNATURES = {
     'capmi_glu_fwd': [_P, _P, _P, _P, _I, _I, _P],
     'capmi_glu_fwd_fused': [_P, _I, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
     'capmi_glu_bwd': [_P, _P, _P, _P, _I, _I, _P],
+    'capmi_ctx_fwd_fused': [_P, _P],
+    'capmi_relu_bwd_add': [_P, _P, _I, _I64, _P, _P, _P, _I, _I, _P],
     'capmi_glu_bwd_add': [_P, _P, _P, _I, _I64, _P, _P, _P, _I, _I, _P],
     'capmi_layernorm_bwd_slabs': [_P, _I, _I64, _P, _P, _P, _P, _P, _P, _I, _I64, _I, _P, _P, _I, _I, _F, _P],
     'capmi_mha_fwd_qslabs': [_P, _I, _I, _I64, _P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],

@@ -1,4 +1,5 @@
-"""Host-side driver of the AoANet captioner (BASELINE configs[4], configs/aoa.yml) on libcapmi.
+"""Host-side driver of the AoANet captioner (BASELINE configs[4], configs/aoa.yml, and the ablation switches of the AoANet
+paper: `Variant`) on libcapmi.
 
 Restates AoAModel.py of the reference (refine 1, refine_aoa 1, use_ff 0, decoder_type AoA, use_multi_head 2,
 mean_feats 1, ctx_drop 1) as C-ABI launches with a hand-written backward:
@@ -9,15 +10,31 @@ MI355X-first: K/V stay per IMAGE (the attention kernel serves the n caption rows
 key stride 2R inside p_att rows, no repeat_tensors / narrow copies); the mean-feature term of the LSTM gates is
 constant over time and enters as a per-image row bias; every core weight gradient is one time-batched GEMM.
 """
+import collections
+import ctypes as C
 import os
 
 import torch
 
 from . import _lib, ops
 from ._lib import lib, ptr, check, stream_ptr
-from .transformer_engine import Lin, Norm, Dropper, mha_fwd, mha_bwd, layernorm_fwd, layernorm_bwd, EPS, fused_lin, deferred_grads
+from ._lib import CapmiError
+from .transformer_engine import Lin, Norm, FFN, Dropper, mha_fwd, mha_bwd, layernorm_fwd, layernorm_bwd, EPS, fused_lin, deferred_grads
 
 _f32 = torch.float32
+
+# The ablation switches of AoAModel.py:100-226; the defaults are configs/aoa.yml.
+#   decoder     'AoA' att2ctx = Linear -> GLU | 'LSTM' an nn.LSTMCell over [att, h_att] with (h, c) = (state[0][1], state[1][1]) |
+#               'base' Linear -> ReLU                                                                        (:141-149, 172-179)
+#   out_res     output += h_att before out_drop (:181-183); the carried context stays without it
+#   ctx_drop    dropout on the carried context entering att_lstm, or none (:158-165)
+#   mean_feats  masked mean of the refined regions, or fc_embed(fc_feats) (:193-221)
+#   refine      six refiner layers + LayerNorm, or identity (:200-203)
+#   refine_aoa  the refiner's attention ends in the AoA block, or in the plain output_layer Linear (:38-51, 90-93)
+#   use_ff      a second SublayerConnection with PositionwiseFeedForward(rnn_size, 2048, 0.1) (:100-113, 119)
+Variant = collections.namedtuple('Variant', 'decoder out_res ctx_drop mean_feats refine refine_aoa use_ff',
+                                 defaults=('AoA', 0, 1, 1, 1, 1, 0))
+AOA_YML = Variant()
 
 
 def glu_fwd(pre, mask=None, residual=None):
@@ -97,18 +114,24 @@ def _colsum(x, out):
 
 
 class AoAGraph:
-    def __init__(self, P, grads, h, drop_prob_lm, dropout_aoa, training, seed):
+    def __init__(self, P, grads, h, drop_prob_lm, dropout_aoa, training, seed, variant=None):
         self.P, self.g, self.h = P, grads, h
+        self.v = variant or AOA_YML
+        # the aoa.yml step (GLU, no residual) keeps its launches; every other decoder goes through capmi_ctx_fwd_fused
+        self.plain = self.v.decoder == 'AoA' and not self.v.out_res
         dev = P['logit.weight'].device
         self.dev = dev
         self.d_lm = Dropper(drop_prob_lm, seed, dev, training)               # embed / att_embed / ctx_drop / out_drop
         self.d_att = Dropper(0.1, seed ^ 0x1234567, dev, training)            # attention probabilities (AoAModel.py:18,53)
         self.d_res = Dropper(0.1, seed ^ 0x7654321, dev, training)            # refiner SublayerConnection (AoAModel.py:119)
         self.d_aoa = Dropper(dropout_aoa, seed ^ 0x2468ace, dev, training)    # AoA input (AoAModel.py:44-48)
+        # the sites only a variant has, on streams of their own (the four above draw what they always drew)
+        self.d_ff = Dropper(0.1, seed ^ 0x0f1e2d3, dev, training)             # use_ff: FFN hidden + second sublayer (AoAModel.py:119)
+        self.d_fc = Dropper(drop_prob_lm, seed ^ 0x3c5a69b, dev, training)    # mean_feats 0: fc_embed (AttModel.py:77-79)
 
     # ------------------------------------------------------------------ prefill
-    def prepare(self, att_feats, att_masks):
-        P, g, h = self.P, self.g, self.h
+    def prepare(self, att_feats, att_masks, fc_feats=None):
+        P, g, h, va = self.P, self.g, self.h, self.v
         B, K, F = att_feats.shape
         R = P['att_embed.0.weight'].shape[0]
         self.B, self.K, self.R = B, K, R
@@ -125,10 +148,14 @@ class AoAGraph:
         self.ref = []
         # the refiner's dropout masks of all 6 layers, 4 per launch and per dropper, drawn in the order the layers consume them
         # (same Philox offsets as one launch per mask: 24 -> 7 launches)
-        att_masks_it = iter(self.d_att.many([(B, h, K, K)] * 6))
-        aoa_masks_it = iter(self.d_aoa.many([(B * K, R)] * 12))
-        res_masks_it = iter(self.d_res.many([(B * K, R)] * 6))
-        for i in range(6):
+        nl = 6 if va.refine else 0
+        att_masks_it = iter(self.d_att.many([(B, h, K, K)] * nl))
+        aoa_masks_it = iter(self.d_aoa.many([(B * K, R)] * (2 * nl if va.refine_aoa else 0)))      # refine_aoa 0: no dropout_aoa site
+        res_masks_it = iter(self.d_res.many([(B * K, R)] * nl))
+        if va.use_ff and nl:
+            Fh = P['refiner.layers.0.feed_forward.w_1.weight'].shape[0]
+            ff_masks_it = iter(self.d_ff.many([(B * K, Fh), (B * K, R)] * nl))                   # FFN hidden, second sublayer
+        for i in range(nl):
             pre = 'refiner.layers.%d' % i
             n0 = Norm(P, g, pre + '.sublayer.0.norm')
             y = n0.fwd(x)
@@ -147,21 +174,40 @@ class AoAGraph:
                 q, k, v = lq.fwd(y), lk.fwd(y), lv.fwd(y)
                 o, p = mha_fwd(q, k, v, K * R, B, 1, K, K, h, self.smask, 1, 1, 0, 0, dp)
             o2 = o.view(B * K, R)
-            m_o, m_y = next(aoa_masks_it), next(aoa_masks_it)
-            od, yd = mul_mask(o2, m_o), mul_mask(y, m_y)
-            W = P[pre + '.self_attn.aoa_layer.0.weight']                      # [2R, 2R], input [att | query]
-            pre_act = torch.empty(B * K, 2 * R, dtype=_f32, device=self.dev)
-            ops.gemm([(od, R, W, 2 * R, R, 1), (yd, R, (W, R), 2 * R, R, 1)], B * K, 2 * R, pre_act,
-                     bias=P[pre + '.self_attn.aoa_layer.0.bias'])
             m_res = next(res_masks_it)
-            x_new = glu_fwd(pre_act, m_res, x)
-            self.ref.append(dict(pre=pre, n0=n0, lq=lq, lk=lk, lv=lv, lqkv=lqkv, q=q, k=k, v=v, p=p, dp=dp, od=od, yd=yd, m_o=m_o, m_y=m_y,
-                                 pre_act=pre_act, m_res=m_res))
+            lay = dict(pre=pre, n0=n0, lq=lq, lk=lk, lv=lv, lqkv=lqkv, q=q, k=k, v=v, p=p, dp=dp, m_res=m_res)
+            if va.refine_aoa:
+                m_o, m_y = next(aoa_masks_it), next(aoa_masks_it)
+                od, yd = mul_mask(o2, m_o), mul_mask(y, m_y)
+                W = P[pre + '.self_attn.aoa_layer.0.weight']                      # [2R, 2R], input [att | query]
+                pre_act = torch.empty(B * K, 2 * R, dtype=_f32, device=self.dev)
+                ops.gemm([(od, R, W, 2 * R, R, 1), (yd, R, (W, R), 2 * R, R, 1)], B * K, 2 * R, pre_act,
+                         bias=P[pre + '.self_attn.aoa_layer.0.bias'])
+                x_new = glu_fwd(pre_act, m_res, x)
+                lay.update(od=od, yd=yd, m_o=m_o, m_y=m_y, pre_act=pre_act)
+            else:
+                # the plain output_layer Linear (AoAModel.py:36,93), the sublayer's dropout and residual in the GEMM's epilogue
+                lay['lo'] = Lin(P, g, pre + '.self_attn.output_layer.weight', pre + '.self_attn.output_layer.bias')
+                x_new = lay['lo'].fwd(o2, mask=m_res, residual=x)
+            if va.use_ff:                                                          # AoA_Refiner_Layer.forward, AoAModel.py:111-113
+                lay['n1'], lay['ff'] = Norm(P, g, pre + '.sublayer.1.norm'), FFN(P, g, pre + '.feed_forward')
+                m_ff, m_res2 = next(ff_masks_it), next(ff_masks_it)
+                x_new = lay['ff'].fwd(lay['n1'].fwd(x_new), m_ff, residual=x_new, res_mask=m_res2)
+            self.ref.append(lay)
             x = x_new
-        self.ref_norm = Norm(P, g, 'refiner.norm')
-        self.att = self.ref_norm.fwd(x)                                        # [B*K, R]
-        self.mean = torch.empty(B, R, dtype=_f32, device=self.dev)
-        check(lib.capmi_meanpool_fwd(ptr(self.att), ptr(att_masks), ptr(self.mean), B, K, R, stream_ptr()), 'meanpool_fwd')
+        if va.refine:
+            self.ref_norm = Norm(P, g, 'refiner.norm')
+            self.att = self.ref_norm.fwd(x)                                    # [B*K, R]
+        else:
+            self.att = x                                                       # refiner = identity (AoAModel.py:203)
+        if va.mean_feats:
+            self.mean = torch.empty(B, R, dtype=_f32, device=self.dev)
+            check(lib.capmi_meanpool_fwd(ptr(self.att), ptr(att_masks), ptr(self.mean), B, K, R, stream_ptr()), 'meanpool_fwd')
+        else:                                                                  # fc_embed(fc_feats), AoAModel.py:221
+            if fc_feats is None or fc_feats.shape[0] != B:
+                raise CapmiError('mean_feats 0 reads one row of fc_feats per image')
+            self.fc_lin = Lin(P, g, 'fc_embed.0.weight', 'fc_embed.0.bias')
+            self.mean = self.fc_lin.fwd(fc_feats, relu=True, mask=self.d_fc(B, R))
         self.ctx2att = Lin(P, g, 'ctx2att.weight', 'ctx2att.bias')
         self.p_att = self.ctx2att.fwd(self.att)                               # [B*K, 2R]  value | key
         return self.mean, self.att, self.p_att
@@ -195,11 +241,21 @@ class AoAGraph:
             torch.zeros(T + 1, N, R, device=dev)
         self.xt, self.ctx_in, self.gates = z(T, N, E), z(T, N, R), z(T, N, 4 * R)
         self.qn, self.q_ln_mean, self.q_ln_inv = z(T, N, R), z(T, N), z(T, N)
-        self.q, self.att_o, self.pre2, self.out_drop = z(T, N, R), z(T, N, R), z(T, N, 2 * R), z(T, N, R)
+        self.q, self.att_o, self.out_drop = z(T, N, R), z(T, N, R), z(T, N, R)
+        v, plain, dec = self.v, self.plain, self.v.decoder
+        if not plain and (R % 4 or E % 4):
+            raise CapmiError('the AoA ablation decoders move rows in 16-byte pieces: rnn_size and input_encoding_size must be '
+                             'multiples of 4 (got %d, %d)' % (R, E))
+        self.pre2 = z(T, N, 2 * R) if dec == 'AoA' else None
+        if dec == 'LSTM':                    # the logic LSTM: h = self.out (state[0][1]), c = state[1][1], its activated gates
+            self.c_log, self.gates_l = torch.zeros(T + 1, N, R, device=dev), z(T, N, 4 * R)
         self.p_dec = z(T, N, h, 1, K)
         self.it_all = torch.empty(T, N, dtype=torch.long, device=dev)
         # the dropout masks of ALL T steps in two launches ([T, ...] arrays; step t uses slice t)
-        self.m_xt_all, self.m_ctx_all, self.m_out_all = self.d_lm.many([(T, N, E), (T, N, R), (T, N, R)])
+        if v.ctx_drop:
+            self.m_xt_all, self.m_ctx_all, self.m_out_all = self.d_lm.many([(T, N, E), (T, N, R), (T, N, R)])
+        else:                                # ctx_drop 0: no mask is drawn and no launch reads one (AoAModel.py:160-161)
+            (self.m_xt_all, self.m_out_all), self.m_ctx_all = self.d_lm.many([(T, N, E), (T, N, R)]), None
         self.m_patt_all = self.d_att(T, N, h, 1, K)
         unb = lambda a: [None] * T if a is None else list(a.unbind(0))       # noqa: E731
         self.m_xt, self.m_ctx, self.m_out, self.m_patt = unb(self.m_xt_all), unb(self.m_ctx_all), unb(self.m_out_all), unb(self.m_patt_all)
@@ -218,7 +274,11 @@ class AoAGraph:
         st = stream_ptr()
         a_n, b_n = P['core.attention.norm.a_2'], P['core.attention.norm.b_2']
         Wq, bq = P['core.attention.linears.0.weight'], P['core.attention.linears.0.bias']
-        Wc, bc = P['core.att2ctx.0.weight'], P['core.att2ctx.0.bias']
+        if dec == 'LSTM':
+            Wc, Wc_hh, bc, bc_hh = (P['core.att2ctx.' + k] for k in ('weight_ih', 'weight_hh', 'bias_ih', 'bias_hh'))
+        else:
+            Wc, bc = P['core.att2ctx.0.weight'], P['core.att2ctx.0.bias']
+        G = {'AoA': 2, 'LSTM': 4, 'base': 1}[dec]
         # r3: the step's GEMM operands as producer-written bf16x3 planes (N <= 64 rows: the loader / consumer GEMM stages them by
         # LDS-DMA) and ONE launch behind the att2ctx GEMM -- capmi_glu_fwd_fused finishes its slabs, applies the GLU and writes
         # out, out_drop (+ planes: the logit GEMM's operand) and the NEXT step's dropped context input (+ planes): 14 -> 11 launches
@@ -231,6 +291,8 @@ class AoAGraph:
             pl_xt = ops.planes_scratch(dev, ('aoa_xt', E), nbE)
             pl_ctx, pl_h, pl_od = (ops.planes_scratch(dev, ('aoa_' + k, R), nbR) for k in ('ctx', 'h', 'od'))
             pl_zero = ops.zero_planes(dev, max(nbR, nbE) // 12288)
+        fused = use_pl or not plain          # the step's last launch also writes the next step's context input
+        if fused:
             self.ctx_in[0].zero_()                               # out_0 = 0 (AoAModel.py:127-129)
         # r5: a free-running rollout gets the embedding of step t+1 from the select launch of step t (capmi_next_embed, as the UpDown
         # driver does): one launch fewer per step; a teacher-forced one knows its tokens and keeps the per-step launch -- unless it
@@ -247,6 +309,7 @@ class AoAGraph:
             else:
                 check(lib.capmi_embed_fwd(tok_src[0], tok_src[1], ptr(self.it_all[t]), ptr(P['embed.0.weight']), ptr(m_xt),
                                           ptr(self.xt[t]), N, E, 1, st), 'embed_fwd')
+            if not fused:
                 ctx_prev = self.out[t]
                 if m_ctx is None:
                     self.ctx_in[t].copy_(ctx_prev)
@@ -278,7 +341,29 @@ class AoAGraph:
                 check(lib.capmi_mha_fwd(ptr(self.q[t]), self.p_att.data_ptr() + 4 * R, ptr(self.p_att), K * 2 * R, 2 * R, ptr(self.smask),
                                         1, 0, 0, 0, ptr(m_p), ptr(self.att_o[t]), ptr(self.p_dec[t]), N, n, 1, K, h, R // h, st), 'mha_fwd')
             c_segs = [(self.att_o[t], R, Wc, 2 * R, R, 1), (self.h_att[t + 1], R, (Wc, R), 2 * R, R, 1)]
-            if use_pl:
+            if not plain:
+                # one launch behind the att2ctx GEMM for every decoder type: GLU / ReLU over [att | h_att] Wc, or the logic LSTM's
+                # cell over [att | h_att] W_ih + h_logic W_hh; out_res = h_att added to the logit operand only
+                if dec == 'LSTM':
+                    c_segs.append((self.out[t], R, Wc_hh, R, R, 1))
+                sp2 = ops.gemm(c_segs, N, G * R, ws.buf, ws=ws, defer_reduce=True)
+                nxt = t + 1 < T
+                cs = _lib.CtxStep()
+                cs.kind = {'AoA': _lib.CTX_GLU, 'LSTM': _lib.CTX_LSTM, 'base': _lib.CTX_RELU}[dec]
+                cs.slabs, cs.splits, cs.stride, cs.M, cs.R = ws.slabs.data_ptr(), sp2, N * G * R, N, R
+                cs.bias = ptr(bc)
+                if dec == 'LSTM':
+                    cs.bias2, cs.pre, cs.c_prev, cs.c = ptr(bc_hh), ptr(self.gates_l[t]), ptr(self.c_log[t]), ptr(self.c_log[t + 1])
+                elif dec == 'AoA':
+                    cs.pre = ptr(self.pre2[t])
+                cs.out = ptr(self.out[t + 1])
+                cs.resid = ptr(self.h_att[t + 1]) if v.out_res else None
+                cs.mask_a, cs.out_a, cs.planes_a = ptr(m_out), ptr(self.out_drop[t]), ptr(pl_od) if use_pl else None
+                if nxt:
+                    cs.mask_b, cs.out_b = ptr(self.m_ctx[t + 1]), ptr(self.ctx_in[t + 1])
+                    cs.planes_b = ptr(pl_ctx) if use_pl else None
+                check(lib.capmi_ctx_fwd_fused(C.byref(cs), st), 'ctx_fwd_fused')
+            elif use_pl:
                 sp2 = ops.gemm(c_segs, N, 2 * R, ws.buf, ws=ws, defer_reduce=True)
                 nxt = t + 1 < T
                 check(lib.capmi_glu_fwd_fused(ws.slabs.data_ptr(), sp2, N * 2 * R, ptr(bc), ptr(self.pre2[t]), ptr(self.out[t + 1]),
@@ -319,6 +404,8 @@ class AoAGraph:
             self._backward(g_logp, sparse)
         if self._bias_hh_copy:               # (the bias_ih column sums ride in the grouped launch that leaving the block issued)
             self.g['core.att_lstm.bias_hh'].copy_(self.g['core.att_lstm.bias_ih'])
+            if self.v.decoder == 'LSTM':
+                self.g['core.att2ctx.bias_hh'].copy_(self.g['core.att2ctx.bias_ih'])
 
     def _backward(self, g_logp, sparse=None):
         P, g, h, B, K, R, n, N, T, L = self.P, self.g, self.h, self.B, self.K, self.R, self.n, self.N, self.T, self.L
@@ -335,9 +422,14 @@ class AoAGraph:
         d_outdrop = d_outdrop.view(T, N, R)
         W_ih, W_hh = P['core.att_lstm.weight_ih'], P['core.att_lstm.weight_hh']
         ld_ih = E + R
-        Wq, Wc = P['core.attention.linears.0.weight'], P['core.att2ctx.0.weight']
+        v, plain, dec = self.v, self.plain, self.v.decoder
+        Wq = P['core.attention.linears.0.weight']
+        Wc = P['core.att2ctx.weight_ih' if dec == 'LSTM' else 'core.att2ctx.0.weight']
         a_n = P['core.attention.norm.a_2']
-        d_pre2_all, dq_all, dg_all, ln_g, ln_dy = z(T, N, 2 * R), z(T, N, R), z(T, N, 4 * R), z(T, N, R), z(T, N, R)
+        dq_all, dg_all, ln_g, ln_dy = z(T, N, R), z(T, N, 4 * R), z(T, N, R), z(T, N, R)
+        # the gradient at att2ctx's GEMM output: d_pre [.., 2R] (GLU), [.., R] (ReLU) or the logic LSTM's d_gates [.., 4R]
+        Gc = {'AoA': 2, 'LSTM': 4, 'base': 1}[dec] * R
+        d_pre2_all = z(T, N, Gc)
         d_p_att = torch.zeros(B * K, 2 * R, dtype=_f32, device=dev)
         dc_next = None
         d_out_all = mul_mask(d_outdrop, self.m_out_all)              # the out_drop Jacobian of all steps in one launch
@@ -353,19 +445,44 @@ class AoAGraph:
         dh_slabs, dh_splits = None, 0
         # (capmi_layernorm_bwd_slabs moves rows in 16-byte pieces of at most 2 048 columns; other sizes take the r4 route)
         fuse = SLAB_CONSUMERS and R % 4 == 0 and R <= 2048
+        if not plain and not fuse:
+            raise CapmiError('the AoA ablation decoders run on the slab-consuming backward (CAPMI_AOA_SLABS=1, rnn_size %% 4 == 0, '
+                             'rnn_size <= 2048)')
         ws, ws3, ws4 = ops.default_workspace(dev), _dh_workspace(dev, 'ctx'), _dh_workspace(dev, 'dqn')
         ctx_splits = 0
+        if dec == 'LSTM':                    # second recurrent chain: d_gates_logic W_hh as slabs between two steps, dc of the logic cell
+            ws5, hl_splits, dcl_next = _dh_workspace(dev, 'dhl'), 0, None
+            # under ctx_drop the context gradient needs its mask before the cell sums it: that GEMM finishes its product itself
+            d_ctx_m = z(N, R) if self.m_ctx_all is not None else None
         for t in range(T - 1, -1, -1):
             # out_{t+1}: from the logit (through out_drop) and -- accumulated by step t+1 -- from its ctx input
             dq = dq_all[t]                                               # [N,R] = [N,1,R], written in place
             if fuse:
                 # the ctx-input gradient of step t+1 is still the slabs of its GEMM: this launch finishes them (mask, + d_out)
-                check(lib.capmi_glu_bwd_add(ptr(d_out_all[t]), None, ws3.slabs.data_ptr() if ctx_splits else None, ctx_splits, N * R,
-                                            ptr(self.m_ctx[t + 1]) if ctx_splits else None, ptr(self.pre2[t]), ptr(d_pre2_all[t]), N, R, st),
-                      'glu_bwd_add')
+                if dec == 'AoA':
+                    check(lib.capmi_glu_bwd_add(ptr(d_out_all[t]), None, ws3.slabs.data_ptr() if ctx_splits else None, ctx_splits, N * R,
+                                                ptr(self.m_ctx[t + 1]) if ctx_splits else None, ptr(self.pre2[t]), ptr(d_pre2_all[t]), N, R, st),
+                          'glu_bwd_add')
+                elif dec == 'base':          # the ReLU mask from the saved output
+                    check(lib.capmi_relu_bwd_add(ptr(d_out_all[t]), ws3.slabs.data_ptr() if ctx_splits else None, ctx_splits, N * R,
+                                                 ptr(self.m_ctx[t + 1]) if ctx_splits else None, ptr(self.out[t + 1]), ptr(d_pre2_all[t]),
+                                                 N, R, st), 'relu_bwd_add')
+                else:
+                    # the logic cell: dh = logit path + d_gates_logic(t+1) W_hh (slabs) + the context gradient of step t+1 (slabs, or
+                    # the masked product); d_out_all[t] itself is left alone -- out_res hands it to the attention LSTM below
+                    dcl_prev = z(N, R)
+                    if ctx_splits and d_ctx_m is not None:
+                        dh_c, c_sp = d_ctx_m.data_ptr(), 1
+                    else:
+                        dh_c, c_sp = (ws3.slabs.data_ptr(), ctx_splits) if ctx_splits else (None, 1)
+                    check(lib.capmi_lstm_cell_bwd_partial(ptr(d_out_all[t]), R, None, ws5.slabs.data_ptr() if hl_splits else None, R,
+                                                          max(hl_splits, 1), N * R, dh_c, R, c_sp, N * R, ptr(dcl_next),
+                                                          ptr(self.gates_l[t]), ptr(self.c_log[t]), ptr(self.c_log[t + 1]),
+                                                          ptr(d_pre2_all[t]), ptr(dcl_prev), N, R, st), 'lstm_cell_bwd_partial')
+                    dcl_next = dcl_prev
                 # [d_att | d_h_att] = d_pre2 Wc stays K-slice slabs of pitch 2R: the attention backward sums the first half while
                 # staging d_o, the LayerNorm backward the second as the gradient it adds its own term to
-                sp = ops.gemm([(d_pre2_all[t], 2 * R, Wc, 2 * R, 2 * R, 1)], N, 2 * R, ws.buf, a_layout=0, b_layout=1, ws=ws, defer_reduce=True)
+                sp = ops.gemm([(d_pre2_all[t], Gc, Wc, 2 * R, Gc, 1)], N, 2 * R, ws.buf, a_layout=0, b_layout=1, ws=ws, defer_reduce=True)
                 check(lib.capmi_mha_bwd_slabs(ws.slabs.data_ptr(), sp, N * 2 * R, 2 * R, ptr(self.q[t]), 0, self.p_att.data_ptr() + 4 * R,
                                               ptr(self.p_att), K * 2 * R, 2 * R, ptr(self.p_dec[t]), ptr(self.m_patt[t]), ptr(dq), 0,
                                               d_p_att.data_ptr() + 4 * R, ptr(d_p_att), K * 2 * R, 2 * R, 1, N, n, 1, K, h, R // h, st),
@@ -388,18 +505,26 @@ class AoAGraph:
             # LSTM cell: dh = (att2ctx + query path) + the slabs of d_gates(t+1) W_hh
             dc_prev = z(N, R)
             dh_b = None if dh_slabs is None else dh_slabs.data_ptr()
+            res = ptr(d_out_all[t]) if v.out_res else None     # out_res: the logit-path gradient also reaches h_att (AoAModel.py:183)
             if use_pl:
-                check(lib.capmi_lstm_cell_bwd_partial_pl(ptr(dh), R, None, dh_b, R, max(dh_splits, 1), N * R, None, R, 1, 0,
+                check(lib.capmi_lstm_cell_bwd_partial_pl(ptr(dh), R, None, dh_b, R, max(dh_splits, 1), N * R, res, R, 1, 0,
                                                          ptr(dc_next), ptr(self.gates[t]), ptr(self.c_att[t]), ptr(self.c_att[t + 1]),
                                                          ptr(dg_all[t]), ptr(dc_prev), N, R, ptr(pl_dg), st), 'lstm_cell_bwd_partial_pl')
             else:
-                check(lib.capmi_lstm_cell_bwd_partial(ptr(dh), R, None, dh_b, R, max(dh_splits, 1), N * R, None, R, 1, 0,
+                check(lib.capmi_lstm_cell_bwd_partial(ptr(dh), R, None, dh_b, R, max(dh_splits, 1), N * R, res, R, 1, 0,
                                                       ptr(dc_next), ptr(self.gates[t]), ptr(self.c_att[t]), ptr(self.c_att[t + 1]),
                                                       ptr(dg_all[t]), ptr(dc_prev), N, R, st), 'lstm_cell_bwd_partial')
             dc_next = dc_prev
             if t > 0:
                 pl = [pl_dg] if use_pl else None
-                if fuse:
+                if dec == 'LSTM':
+                    hl_splits = ops.gemm([(d_pre2_all[t], 4 * R, P['core.att2ctx.weight_hh'], R, 4 * R, 1)], N, R, ws5.buf, a_layout=0,
+                                         b_layout=1, ws=ws5, defer_reduce=True)
+                if dec == 'LSTM' and d_ctx_m is not None:
+                    ops.gemm([(dg_all[t], 4 * R, (W_ih, E), ld_ih, 4 * R, 1)], N, R, d_ctx_m, a_layout=0, b_layout=1,
+                             mul_mask=self.m_ctx[t], a_planes=pl)
+                    ctx_splits = 1
+                elif fuse:
                     ctx_splits = ops.gemm([(dg_all[t], 4 * R, (W_ih, E), ld_ih, 4 * R, 1)], N, R, ws3.buf, a_layout=0, b_layout=1, ws=ws3,
                                           defer_reduce=True, a_planes=pl)
                 else:
@@ -436,24 +561,37 @@ class AoAGraph:
         _colsum(ln_g.view(TN, R), g['core.attention.norm.a_2'])
         _colsum(ln_dy.view(TN, R), g['core.attention.norm.b_2'])
         # att2ctx
-        gWc = g['core.att2ctx.0.weight']
-        dp2 = d_pre2_all.view(TN, 2 * R)
-        _dw(dp2, self.att_o.view(TN, R), gWc, ldc=2 * R, bias=g['core.att2ctx.0.bias'])
+        gWc = g['core.att2ctx.weight_ih' if dec == 'LSTM' else 'core.att2ctx.0.weight']
+        dp2 = d_pre2_all.view(TN, Gc)
+        _dw(dp2, self.att_o.view(TN, R), gWc, ldc=2 * R, bias=g['core.att2ctx.bias_ih' if dec == 'LSTM' else 'core.att2ctx.0.bias'])
         _dw(dp2, self.h_att[1:].reshape(TN, R), gWc, ldc=2 * R, off=R)
+        if dec == 'LSTM':                    # (bias_hh: copied behind the grouped launch, like the attention LSTM's)
+            _dw(dp2, self.out[:T].reshape(TN, R), g['core.att2ctx.weight_hh'])
         # ---- prefill backward
         d_att = self.ctx2att.bwd(d_p_att)                                              # [B*K,R]
-        check(lib.capmi_meanpool_bwd(ptr(d_mean), ptr(self.att_masks), ptr(d_att), 1, B, K, R, st), 'meanpool_bwd')
+        if v.mean_feats:
+            check(lib.capmi_meanpool_bwd(ptr(d_mean), ptr(self.att_masks), ptr(d_att), 1, B, K, R, st), 'meanpool_bwd')
+        else:
+            self.fc_lin.bwd(d_mean, need_dx=False, fresh=True)
+        if not v.refine:
+            self.embed.bwd(d_att, need_dx=False)
+            return
         dx = torch.zeros(B * K, R, dtype=_f32, device=dev)
         self.ref_norm.bwd(d_att, dx)
         for lay in reversed(self.ref):
             pre = lay['pre']
-            d_pre = glu_bwd(dx, lay['m_res'], lay['pre_act'])                          # residual path stays in dx
-            W = P[pre + '.self_attn.aoa_layer.0.weight']
-            gW2 = g[pre + '.self_attn.aoa_layer.0.weight']
             BK = B * K
-            _dw(d_pre, lay['od'], gW2, ldc=2 * R, bias=g[pre + '.self_attn.aoa_layer.0.bias'])
-            _dw(d_pre, lay['yd'], gW2, ldc=2 * R, off=R)
-            d_o, d_y = dcat_halves(d_pre, W, BK, R, lay['m_o'], lay['m_y'])            # [d_od | d_yd] of [BK,2R] = d_pre W
+            if v.use_ff:                                                               # x2 = x1 + Drop(FFN(LN x1))
+                lay['n1'].bwd(lay['ff'].bwd(dx), dx)
+            if v.refine_aoa:
+                d_pre = glu_bwd(dx, lay['m_res'], lay['pre_act'])                      # residual path stays in dx
+                W = P[pre + '.self_attn.aoa_layer.0.weight']
+                gW2 = g[pre + '.self_attn.aoa_layer.0.weight']
+                _dw(d_pre, lay['od'], gW2, ldc=2 * R, bias=g[pre + '.self_attn.aoa_layer.0.bias'])
+                _dw(d_pre, lay['yd'], gW2, ldc=2 * R, off=R)
+                d_o, d_y = dcat_halves(d_pre, W, BK, R, lay['m_o'], lay['m_y'])        # [d_od | d_yd] of [BK,2R] = d_pre W
+            else:
+                d_o, d_y = lay['lo'].bwd(dx), 0.0                                      # (the query reaches the output through q only)
             if lay['lqkv'] is not None:
                 dqkv = torch.empty(BK, 3 * R, dtype=_f32, device=dev)
                 mha_bwd(d_o.view(B, K, R), lay['q'], lay['k'], lay['v'], K * 3 * R, lay['p'], lay['dp'], B, 1, K, K, h, kstride=3 * R,
@@ -484,7 +622,8 @@ class BeamDecoder:
         self.V1, self.E = P['embed.0.weight'].shape
         z = lambda *s: torch.empty(*s, dtype=_f32, device=dev)       # noqa: E731
         self.z = z
-        self.state = torch.zeros(3, N, R, dtype=_f32, device=dev)   # h_att, c_att, out (ctx of the previous step)
+        # h_att, c_att, out (ctx of the previous step) and -- decoder_type LSTM -- c_logic (state[1][1]): a reorder carries all of them
+        self.state = torch.zeros(4 if g.v.decoder == 'LSTM' else 3, N, R, dtype=_f32, device=dev)
         self.state_alt = torch.empty_like(self.state)
         W_ih = P['core.att_lstm.weight_ih']
         self.mean_gates = z(B, 4 * R)                                # mean-feature term of the gates, once per image
@@ -517,12 +656,28 @@ class BeamDecoder:
         # keys = second half of p_att rows, values = first half (AoAModel.py:168); per image, stride 2R
         check(lib.capmi_mha_fwd(ptr(q), g.p_att.data_ptr() + 4 * R, ptr(g.p_att), K * 2 * R, 2 * R, ptr(g.smask), 1, 0, 0, 0, None,
                                 ptr(att_o), None, rows, rows_per_image, 1, K, h, R // h, st), 'mha_fwd')
-        Wc = P['core.att2ctx.0.weight']
-        pre2 = z(rows, 2 * R)
-        ops.gemm([(att_o, R, Wc, 2 * R, R, 1), (h_new, R, (Wc, R), 2 * R, R, 1)], rows, 2 * R, pre2, bias=P['core.att2ctx.0.bias'])
-        check(lib.capmi_glu_fwd(ptr(pre2), None, None, ptr(new[2]), rows, R, st), 'glu_fwd')
+        dec, pre2 = g.v.decoder, None
+        if dec == 'LSTM':                  # the logic LSTM over [att | h_att] and (state[0][1], state[1][1]), AoAModel.py:173-175
+            Wc, Wc_hh = P['core.att2ctx.weight_ih'], P['core.att2ctx.weight_hh']
+            sp = ops.gemm([(att_o, R, Wc, 2 * R, R, 1), (h_new, R, (Wc, R), 2 * R, R, 1), (ctx_prev, R, Wc_hh, R, R, 1)], rows, 4 * R,
+                          ws.buf, ws=ws, defer_reduce=True)
+            check(lib.capmi_lstm_cell_fwd(ws.slabs.data_ptr(), sp, ptr(P['core.att2ctx.bias_ih']), ptr(P['core.att2ctx.bias_hh']), None,
+                                          1, None, ptr(self.state[3]), ptr(new[2]), ptr(new[3]), None, None, None, rows, R, st),
+                  'lstm_cell_fwd')
+        else:
+            Wc = P['core.att2ctx.0.weight']
+            c_segs = [(att_o, R, Wc, 2 * R, R, 1), (h_new, R, (Wc, R), 2 * R, R, 1)]
+            if dec == 'AoA':
+                pre2 = z(rows, 2 * R)
+                ops.gemm(c_segs, rows, 2 * R, pre2, bias=P['core.att2ctx.0.bias'])
+                check(lib.capmi_glu_fwd(ptr(pre2), None, None, ptr(new[2]), rows, R, st), 'glu_fwd')
+            else:                          # Linear -> ReLU in the GEMM's epilogue
+                ops.gemm(c_segs, rows, R, new[2], bias=P['core.att2ctx.0.bias'], relu=True)
         logits = self.logits[:rows]
-        ops.gemm([(new[2, :rows], R, P['logit.weight'], R, R, 1)], rows, V1, logits, bias=P['logit.bias'])
+        l_segs = [(new[2, :rows], R, P['logit.weight'], R, R, 1)]
+        if g.v.out_res:                    # logit(output + h_att): a second K segment over the same weight, the carried context stays
+            l_segs.append((h_new, R, P['logit.weight'], R, R, 1))
+        ops.gemm(l_segs, rows, V1, logits, bias=P['logit.bias'])
         self.state, self.state_alt = new, self.state
         self._keep = (xt, qn, mu, inv, q, att_o, pre2)           # scratch stays alive until the stream has used it
         return logits
@@ -533,9 +688,9 @@ class BeamDecoder:
         self.state, self.state_alt = self.state_alt, self.state
 
 
-def sample_beam(model, P, att_feats, att_masks, h, L, opt):
+def sample_beam(model, P, att_feats, att_masks, h, L, opt, fc_feats=None):
     from . import beam
-    g = AoAGraph(P, {}, h, 0.0, 0.0, False, 0)
-    g.prepare(att_feats, att_masks)               # refined features are shared by every decoder (diverse groups)
+    g = AoAGraph(P, {}, h, 0.0, 0.0, False, 0, variant=getattr(model, 'variant', None))
+    g.prepare(att_feats, att_masks, fc_feats)     # refined features are shared by every decoder (diverse groups)
     return beam.beam_search_steps(model, lambda rows: BeamDecoder(g, rows), g.B, P['embed.0.weight'].shape[0], L, opt,
                                   att_feats.device)

@@ -1,41 +1,49 @@
 """AoAModel (reference captioning/models/AoAModel.py:188-226) on the HIP backend -- BASELINE configs[4]
-(configs/aoa.yml switches: refine 1, refine_aoa 1, use_ff 0, decoder_type AoA, use_multi_head 2, mean_feats 1).
-Parameter tree = the reference's; arithmetic = aoa_engine.py + csrc kernels."""
+(configs/aoa.yml switches: refine 1, refine_aoa 1, use_ff 0, decoder_type AoA, use_multi_head 2, mean_feats 1) and the ablation
+switches of AoAModel.py:100-226: decoder_type AoA / LSTM / base, out_res, ctx_drop, mean_feats, refine, refine_aoa, use_ff.
+Parameter tree = the reference's for every variant; arithmetic = aoa_engine.py + csrc kernels."""
 import copy
 
 import torch
 import torch.nn as nn
 
 from .CaptionModel import CaptionModel
-from .TransformerModel import _LayerNorm, _Sublayer, _clones
+from .TransformerModel import _FF, _LayerNorm, _Sublayer, _clones
 from imagecaptioning.pytorch_amd import aoa_engine as engine
 from imagecaptioning.pytorch_amd._lib import CapmiError
 from imagecaptioning.pytorch_amd.ops import clip_len
 
 
+FF_HIDDEN = 2048         # PositionwiseFeedForward(rnn_size, 2048, 0.1): constants of the reference (AoAModel.py:119)
+
+
 class _MHDot(nn.Module):
     """MultiHeadedDotAttention parameter holder (AoAModel.py:17-55)."""
 
-    def __init__(self, d, project_k_v, do_aoa, norm_q):
+    def __init__(self, d, project_k_v, do_aoa, norm_q, use_output_layer=1):
         super().__init__()
         if norm_q:
             self.norm = _LayerNorm(d)
         self.linears = _clones(nn.Linear(d, d), 1 + 2 * project_k_v)
+        if use_output_layer and not do_aoa:         # (AoAModel.py:36,48-51: deleted again when the AoA block follows)
+            self.output_layer = nn.Linear(d, d)
         if do_aoa:
             self.aoa_layer = nn.Sequential(nn.Linear(2 * d, 2 * d), nn.GLU())
 
 
 class _RefLayer(nn.Module):
-    def __init__(self, d):
+    def __init__(self, d, refine_aoa, use_ff):
         super().__init__()
-        self.self_attn = _MHDot(d, 1, 1, 0)
-        self.sublayer = _clones(_Sublayer(d), 1)
+        self.self_attn = _MHDot(d, 1, refine_aoa, 0)
+        if use_ff:
+            self.feed_forward = _FF(d, FF_HIDDEN)
+        self.sublayer = _clones(_Sublayer(d), 1 + use_ff)
 
 
 class _Refiner(nn.Module):
-    def __init__(self, d):
+    def __init__(self, d, refine_aoa=1, use_ff=0):
         super().__init__()
-        self.layers = _clones(_RefLayer(d), 6)
+        self.layers = _clones(_RefLayer(d, refine_aoa, use_ff), 6)
         self.norm = _LayerNorm(d)
 
 
@@ -43,20 +51,27 @@ class _Core(nn.Module):
     def __init__(self, opt):
         super().__init__()
         R = opt.rnn_size
+        kind = getattr(opt, 'decoder_type', 'AoA')
         self.att_lstm = nn.LSTMCell(opt.input_encoding_size + R, R)
-        self.att2ctx = nn.Sequential(nn.Linear(2 * R, 2 * R), nn.GLU())
-        self.attention = _MHDot(R, 0, 0, 1)
+        if kind == 'AoA':
+            self.att2ctx = nn.Sequential(nn.Linear(2 * R, 2 * R), nn.GLU())
+        elif kind == 'LSTM':
+            self.att2ctx = nn.LSTMCell(2 * R, R)
+        else:
+            self.att2ctx = nn.Sequential(nn.Linear(2 * R, R), nn.ReLU())
+        self.attention = _MHDot(R, 0, 0, 1, use_output_layer=0)
 
 
 class _Fn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, model, cfg, att_feats, att_masks, *params):
+    def forward(ctx, model, cfg, fc_feats, att_feats, att_masks, *params):
         P = dict(zip(model._param_names, [p.detach() for p in params]))
         ctx.sink = cfg.pop('_sink', None)
         ctx.set_materialize_grads(False)        # the dense log-prob gradient may be undefined (sparse route)
         grads = model._flat.grad_views if model._flat is not None else {k: torch.empty_like(v) for k, v in P.items()}
-        g = engine.AoAGraph(P, grads, model.num_heads, model.drop_prob_lm, model.dropout_aoa, model.training, model._next_seed())
-        g.prepare(att_feats, att_masks)
+        g = engine.AoAGraph(P, grads, model.num_heads, model.drop_prob_lm, model.dropout_aoa, model.training, model._next_seed(),
+                            variant=model.variant)
+        g.prepare(att_feats, att_masks, fc_feats)
         seq, logp = g.rollout(**cfg)
         ctx.g, ctx.model, ctx.grads = g, model, grads
         ctx.mark_non_differentiable(seq)
@@ -75,8 +90,8 @@ class _Fn(torch.autograd.Function):
         ctx.g.backward(g_logp, sparse=sparse)
         if flat is not None:
             flat.end_backward(stash)
-            return (None,) * (4 + len(ctx.model._param_names))
-        return (None, None, None, None) + tuple(ctx.grads[k] for k in ctx.model._param_names)
+            return (None,) * (5 + len(ctx.model._param_names))
+        return (None, None, None, None, None) + tuple(ctx.grads[k] for k in ctx.model._param_names)
 
 
 class AoAModel(CaptionModel):
@@ -84,13 +99,17 @@ class AoAModel(CaptionModel):
 
     def __init__(self, opt):
         super().__init__()
-        for k, want in (('refine', 1), ('refine_aoa', 1), ('use_ff', 0), ('use_multi_head', 2), ('multi_head_scale', 1)):
+        for k, want in (('use_multi_head', 2), ('multi_head_scale', 1)):
             if getattr(opt, k, want) != want:
                 raise NotImplementedError('AoA option %s=%r is outside configs/aoa.yml' % (k, getattr(opt, k)))
-        if getattr(opt, 'decoder_type', 'AoA') != 'AoA' or not getattr(opt, 'mean_feats', 1):
-            raise NotImplementedError('only decoder_type AoA with mean_feats 1 (configs/aoa.yml) is accelerated')
-        if not getattr(opt, 'ctx_drop', 0):
-            pass       # ctx_drop 0 == identity mask: handled by drop_prob in eval; train-mode ctx_drop=0 not in aoa.yml
+        kind = getattr(opt, 'decoder_type', 'AoA')
+        # the ablation switches with the reference's own defaults (getattr sites of AoAModel.py:135-137,193; opt.refine, opt.refine_aoa
+        # and opt.use_ff are read without one there: configs/aoa.yml's values stand in)
+        self.variant = engine.Variant(decoder=kind if kind in ('AoA', 'LSTM') else 'base', out_res=int(bool(getattr(opt, 'out_res', 0))),
+                                      ctx_drop=int(bool(getattr(opt, 'ctx_drop', 0))), mean_feats=int(bool(getattr(opt, 'mean_feats', 1))),
+                                      refine=int(bool(getattr(opt, 'refine', 1))), refine_aoa=int(bool(getattr(opt, 'refine_aoa', 1))),
+                                      use_ff=int(bool(getattr(opt, 'use_ff', 0))))
+        v = self.variant
         self.vocab_size = opt.vocab_size
         self.rnn_size = opt.rnn_size
         self.input_encoding_size = opt.input_encoding_size
@@ -104,10 +123,13 @@ class AoAModel(CaptionModel):
         R = self.rnn_size
         self.embed = nn.Sequential(nn.Embedding(self.vocab_size + 1, self.input_encoding_size), nn.ReLU(),
                                    nn.Dropout(self.drop_prob_lm))
+        if not v.mean_feats:                 # (AoAModel.py:198-199: deleted when the mean of the regions stands in)
+            self.fc_embed = nn.Sequential(nn.Linear(opt.fc_feat_size, R), nn.ReLU(), nn.Dropout(self.drop_prob_lm))
         self.att_embed = nn.Sequential(nn.Linear(opt.att_feat_size, R), nn.ReLU(), nn.Dropout(self.drop_prob_lm))
         self.logit = nn.Linear(R, self.vocab_size + 1)
         self.ctx2att = nn.Linear(R, 2 * R)
-        self.refiner = _Refiner(R)
+        if v.refine:
+            self.refiner = _Refiner(R, v.refine_aoa, v.use_ff)
         self.core = _Core(opt)
 
     def _flat_groups(self):
@@ -116,7 +138,7 @@ class AoAModel(CaptionModel):
         blocks = sorted({n[:n.index('.self_attn.') + len('.self_attn')] for n in names if n.startswith('refiner.') and '.self_attn.linears.' in n})
         return [['%s.linears.%d.%s' % (b, i, kind) for i in range(3)] for b in blocks for kind in ('weight', 'bias')]
 
-    def _run(self, cfg, att_feats, att_masks, clipped=False):
+    def _run(self, cfg, att_feats, att_masks, clipped=False, fc_feats=None):
         if not att_feats.is_cuda:
             raise CapmiError('the capmi backend runs on a HIP device only; there is no CPU path')
         if att_masks is not None and not clipped:
@@ -126,8 +148,16 @@ class AoAModel(CaptionModel):
         from imagecaptioning.pytorch_amd import sparse_logp
         cfg = dict(cfg)
         cfg['_sink'] = sink = sparse_logp.LogpSink()
-        seq, logp = _Fn.apply(self, cfg, att_feats.float().contiguous(), att_masks, *params)
+        seq, logp = _Fn.apply(self, cfg, self._fc(fc_feats), att_feats.float().contiguous(), att_masks, *params)
         return seq, sparse_logp.attach(logp, sink)
+
+    def _fc(self, fc_feats):
+        """the fc features the engine reads (mean_feats 0, AoAModel.py:221), or None"""
+        if self.variant.mean_feats:
+            return None
+        if fc_feats is None:
+            raise CapmiError('mean_feats 0 reads fc_feats (AoAModel.py:221): none were given')
+        return fc_feats.float().contiguous()
 
     def _forward(self, fc_feats, att_feats, seq, att_masks=None):
         B = att_feats.size(0)
@@ -146,7 +176,7 @@ class AoAModel(CaptionModel):
             cfg['seed'] = self._next_seed()
             if getattr(self, '_ss_gumbel', None) is not None:
                 cfg['gumbel'] = self._ss_gumbel
-        _, logp = self._run(cfg, att_feats, att_masks)
+        _, logp = self._run(cfg, att_feats, att_masks, fc_feats=fc_feats)
         return logp
 
     def _decode_stepper(self, fc_feats, att_feats, att_masks, L):
@@ -159,10 +189,11 @@ class AoAModel(CaptionModel):
             att_feats, att_masks = att_feats[:, :ml], att_masks[:, :ml].float().contiguous()
         P = dict(zip(self._param_names, [p.detach() for p in self._param_list()]))
         att_feats = att_feats.float().contiguous()
+        fc = self._fc(fc_feats)
 
         def make(rows):
-            g = engine.AoAGraph(P, {}, self.num_heads, 0.0, 0.0, False, 0)
-            g.prepare(att_feats, att_masks)
+            g = engine.AoAGraph(P, {}, self.num_heads, 0.0, 0.0, False, 0, variant=self.variant)
+            g.prepare(att_feats, att_masks, fc)
             return engine.BeamDecoder(g, rows)
         return make
 
@@ -186,7 +217,8 @@ class AoAModel(CaptionModel):
                 att_feats, att_masks = att_feats[:, :ml], att_masks[:, :ml].float().contiguous()
             with torch.no_grad():
                 P = dict(zip(self._param_names, [p.detach() for p in self._param_list()]))
-                return engine.sample_beam(self, P, att_feats.float().contiguous(), att_masks, self.num_heads, self.seq_length, opt)
+                return engine.sample_beam(self, P, att_feats.float().contiguous(), att_masks, self.num_heads, self.seq_length, opt,
+                                          self._fc(fc_feats))
         from .utils import parse_sample_method
         if decode.wants_options(opt):
             if not att_feats.is_cuda:
@@ -197,8 +229,8 @@ class AoAModel(CaptionModel):
             P = dict(zip(self._param_names, [p.detach() for p in self._param_list()]))
 
             def make(rows):
-                g = engine.AoAGraph(P, {}, self.num_heads, 0.0, 0.0, False, 0)
-                g.prepare(att_feats.float().contiguous(), att_masks)
+                g = engine.AoAGraph(P, {}, self.num_heads, 0.0, 0.0, False, 0, variant=self.variant)
+                g.prepare(att_feats.float().contiguous(), att_masks, self._fc(fc_feats))
                 return engine.BeamDecoder(g, rows)
             return self._sample_with_options(make, att_feats.size(0), opt)
         mode, temperature, top_k, top_p = parse_sample_method(method, opt.get('temperature', 1.0))
@@ -216,6 +248,10 @@ class AoAModel(CaptionModel):
             if att_masks is not None:                 # the data-dependent clip (a host sync) stays outside the graph
                 ml = clip_len(att_masks)
                 att_feats, att_masks = att_feats[:, :ml], att_masks[:, :ml].float().contiguous()
-            return self._graphs(('greedy', cfg['n'], L, raw), lambda a, m: self._run(gcfg, a, m, clipped=True),
-                                (att_feats.float().contiguous(), att_masks))
-        return self._run(cfg, att_feats, att_masks)
+            fc = self._fc(fc_feats)
+            if fc is None:
+                return self._graphs(('greedy', cfg['n'], L, raw), lambda a, m: self._run(gcfg, a, m, clipped=True),
+                                    (att_feats.float().contiguous(), att_masks))
+            return self._graphs(('greedy', cfg['n'], L, raw), lambda a, m, f: self._run(gcfg, a, m, clipped=True, fc_feats=f),
+                                (att_feats.float().contiguous(), att_masks, fc))
+        return self._run(cfg, att_feats, att_masks, fc_feats=fc_feats)

@@ -21,7 +21,7 @@ DEFAULTS = dict(
     checkpoint_path='log_capmi', id='capmi', save_checkpoint_every=0, losses_log_every=10, start_from=None, seed=1234,
     # transformer / aoa
     N_enc=6, N_dec=6, d_model=512, d_ff=2048, num_att_heads=8, dropout=0.1, refine=1, refine_aoa=1, use_ff=0, decoder_type='AoA',
-    use_multi_head=2, num_heads=8, multi_head_scale=1, mean_feats=1, ctx_drop=1, dropout_aoa=0.3,
+    use_multi_head=2, num_heads=8, multi_head_scale=1, mean_feats=1, ctx_drop=1, dropout_aoa=0.3, out_res=0,
     # eval
     beam_size=1, sample_method='greedy', temperature=1.0, suppress_UNK=1, length_penalty='', num_images=20, device='cuda',
     group_size=1, diversity_lambda=0.5, decoding_constraint=0, block_trigrams=0, remove_bad_endings=0, sample_n=1,

@@ -944,6 +944,43 @@ int capmi_glu_fwd(const float *pre, const float *mask, const float *residual, fl
 int capmi_glu_fwd_fused(const float *slabs, int splits, int64_t stride, const float *bias, float *pre, float *out,
                         const float *mask_a, float *out_a, void *planes_a, const float *mask_b, float *out_b, void *planes_b,
                         int M, int R, void *stream);
+/* The att2ctx stage of one AoA decode step for every decoder_type (AoAModel.py:141-149, 172-185): siblings of
+ * capmi_glu_fwd_fused that read the same slab layout (slabs [splits][M, G*R], `stride` floats apart, summed in order from 0.f,
+ * then bias + bias2) and write the same outputs and planes.
+ *   CAPMI_CTX_GLU  (G = 2)  out = a * sigmoid(g), pre [M,2R] kept for capmi_glu_bwd_add
+ *   CAPMI_CTX_RELU (G = 1)  out = max(pre, 0); the backward takes its mask from `out` (capmi_relu_bwd_add), pre is not written
+ *   CAPMI_CTX_LSTM (G = 4)  an nn.LSTMCell over the gate slabs of [att, h_att] W_ih + h_logic W_hh: bias = b_ih, bias2 = b_hh,
+ *                           c = f * c_prev + i * g, out = o * tanh(c); pre (may be NULL) receives the ACTIVATED gates [M,4R] in the
+ *                           layout capmi_lstm_cell_bwd_partial reads
+ * out_a = mask_a * (out + resid): the logit GEMM's input; resid (NULL = none) is h_att under out_res, added before the dropout.
+ * out_b = mask_b * out: the context input of the NEXT step (never with the residual).  A NULL mask is a plain copy -- the mask
+ * is not read, nothing is multiplied (ctx_drop 0).  out_a / out_b NULL = not wanted; planes as in capmi_glu_fwd_fused (M <= 64).
+ * R % 4 == 0, 16-byte aligned operands. */
+#define CAPMI_CTX_GLU 0
+#define CAPMI_CTX_RELU 1
+#define CAPMI_CTX_LSTM 2
+typedef struct {
+    const float *slabs;
+    const float *bias, *bias2;
+    float *pre;
+    const float *c_prev;
+    float *c;
+    float *out;
+    const float *resid;
+    const float *mask_a;
+    float *out_a;
+    void *planes_a;
+    const float *mask_b;
+    float *out_b;
+    void *planes_b;
+    int64_t stride;
+    int kind, splits, M, R;
+} capmi_ctx_step;
+int capmi_ctx_fwd_fused(const capmi_ctx_step *s, void *stream);
+/* d_pre [M,R] = (out > 0) * (d_out + add_mask * sum_s add_slabs[s]): the backward of CAPMI_CTX_RELU with the second gradient
+ * source of capmi_glu_bwd_add (same order of additions); `out` is the saved forward output. */
+int capmi_relu_bwd_add(const float *d_out, const float *add_slabs, int add_splits, int64_t add_stride, const float *add_mask,
+                       const float *out, float *d_pre, int M, int R, void *stream);
 /* d_pre [M,2R] from d_out [M,R] (mask applied first) */
 int capmi_glu_bwd(const float *d_out, const float *mask, const float *pre, float *d_pre, int M, int R, void *stream);
 /* r5: the same with a second gradient source that is still K-slice slabs: g = mask * d_out + add_mask * sum_s add_slabs[s]
