@@ -871,18 +871,21 @@ __global__ void attn_dpatt_kernel(const float *__restrict__ att_h_all, const flo
     }
 }
 
-__global__ void sum_all_kernel(const float *__restrict__ in, size_t count, float *__restrict__ out) {
+// sum over the first `live` values of each of T slabs (`slab` values apart): the time-batched pass owns rows 0 .. B*n-1 of a time slab,
+// the rows behind them belong to another rollout and are not read.  slab == live is the dense walk, element order unchanged.
+__global__ void sum_all_kernel(const float *__restrict__ in, size_t live, size_t slab, size_t count, float *__restrict__ out) {
     // one workgroup (deterministic order); 8 independent loads in flight per thread -- a plain strided loop is one dependent
     // round trip per element (57 us for the 240 000 values of a bs64 XE step)
     __shared__ float scratch[32];
     float s = 0.f;
     const size_t stride = blockDim.x;
+    const bool dense = slab == live;
     for (size_t i0 = threadIdx.x; i0 < count; i0 += 8 * stride) {
         float v[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const size_t i = i0 + u * stride;
-            v[u] = i < count ? in[i] : 0.f;
+            v[u] = i < count ? in[dense ? i : (i / live) * slab + i % live] : 0.f;
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) s += v[u];
@@ -1069,7 +1072,8 @@ int capmi_attention_bwd_batched_ws(const float *d_ctx_all, int ld_dctx, const fl
         hipLaunchKernelGGL(attn_dpatt_kernel<1>, dim3(B * K), dim3(A >= 512 ? 512 : 256), 0, st, att_h_all, d_e_all, p_att, w,
                            d_p_att, d_w, dw_partial, T, N, n, K, A);
     CAPMI_CHECK_LAUNCH();
-    hipLaunchKernelGGL(sum_all_kernel, dim3(1), dim3(1024), 0, st, d_e_all, (size_t)T * N * K, d_b);
+    hipLaunchKernelGGL(sum_all_kernel, dim3(1), dim3(1024), 0, st, d_e_all, (size_t)B * n * K, (size_t)N * K,
+                       (size_t)T * B * n * K, d_b);      // rows >= B * n of a slab are not the pass's
     CAPMI_CHECK_LAUNCH();
     return 0;
 }
@@ -1624,7 +1628,8 @@ int capmi_sentinel_attention_bwd_batched(const float *d_ctx, const float *fre, c
     hipLaunchKernelGGL(sentinel_dpatt_kernel, dim3(B * (K + 1)), dim3(A >= 512 ? 512 : 256), 0, st, fre, hoe, d_e, p_att, w, td,
                        capmi::rng_epoch(), d_p_att, d_w, dw_partial, T, N, n, K, A);
     CAPMI_CHECK_LAUNCH();
-    hipLaunchKernelGGL(sum_all_kernel, dim3(1), dim3(1024), 0, st, d_e, (size_t)T * N * (K + 1), d_b);
+    hipLaunchKernelGGL(sum_all_kernel, dim3(1), dim3(1024), 0, st, d_e, (size_t)T * N * (K + 1), (size_t)T * N * (K + 1),
+                       (size_t)T * N * (K + 1), d_b);
     CAPMI_CHECK_LAUNCH();
     return 0;
 }

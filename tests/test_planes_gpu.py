@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from oracle import planes as PL
+import step_kernels_ref64 as S64
 
 pytestmark = pytest.mark.gpu
 
@@ -105,11 +106,18 @@ def test_producers_write_the_planes_of_their_outputs(dev):
     _lib.check(lib.capmi_lstm_cell_fwd_pl(slabs.data_ptr(), 3, b1.data_ptr(), b2.data_ptr(), None, 1, None, cp.data_ptr(),
                                           h.data_ptr(), c.data_ptr(), ga.data_ptr(), mask.data_ptr(), hd.data_ptr(), N, R,
                                           pl_h.data_ptr(), pl_hd.data_ptr(), sp()), 'cell_pl')
-    _lib.check(lib.capmi_lstm_cell_fwd(slabs.data_ptr(), 3, b1.data_ptr(), b2.data_ptr(), None, 1, None, cp.data_ptr(),
+    cp1 = torch.empty(N * R + 1, device=dev)[1:].view(N, R).copy_(cp)       # one float off a 16-byte boundary: the scalar cell
+    _lib.check(lib.capmi_lstm_cell_fwd(slabs.data_ptr(), 3, b1.data_ptr(), b2.data_ptr(), None, 1, None, cp1.data_ptr(),
                                        h0.data_ptr(), c0.data_ptr(), ga0.data_ptr(), mask.data_ptr(), hd0.data_ptr(), N, R,
                                        sp()), 'cell')
     for a, b in ((h, h0), (c, c0), (ga, ga0), (hd, hd0)):    # the 16-byte cell vs the scalar cell (fma contraction may differ)
         assert float((a - b).abs().max()) < 1e-6
+    # ... and both against the float64 restatement of the cell
+    pre = S64.presum(N, 4 * R, [(slabs.cpu(), 0)], biases=[(b1.cpu(), 0), (b2.cpu(), 0)])
+    h_ref, c_ref, ga_ref = S64.lstm_point(pre, cp.cpu().double())
+    for outs in ((h, c, ga, hd), (h0, c0, ga0, hd0)):
+        for got, ref in zip(outs, (h_ref, c_ref, ga_ref, h_ref * mask.cpu().double())):
+            assert float((got.cpu().double() - ref).abs().max() / ref.abs().max()) < 2e-6
     same(pl_h, h); same(pl_hd, hd)
 
     # embedding
@@ -143,7 +151,8 @@ def test_producers_write_the_planes_of_their_outputs(dev):
     gates = torch.rand(Nb, 4 * R, generator=g).to(dev)
     cprev, cnew = torch.randn(Nb, R, generator=g).to(dev), torch.randn(Nb, R, generator=g).to(dev)
     dg, dcp, pl_dg = z(Nb, 4 * R), z(Nb, R), zb(4 * R)
-    _lib.check(lib.capmi_lstm_cell_bwd_partial_pl(dh.data_ptr(), R, None, None, 0, 1, 0, None, 0, 1, 0, None, gates.data_ptr(),
+    dhb = torch.randn(3, Nb, R, generator=g).to(dev)         # a dX product left as three K-slice slabs
+    _lib.check(lib.capmi_lstm_cell_bwd_partial_pl(dh.data_ptr(), R, None, dhb.data_ptr(), R, 3, Nb * R, None, 0, 1, 0, None, gates.data_ptr(),
                                                   cprev.data_ptr(), cnew.data_ptr(), dg.data_ptr(), dcp.data_ptr(), Nb, R,
                                                   pl_dg.data_ptr(), sp()), 'cell_bwd_pl')
     same(pl_dg, dg)
