@@ -109,7 +109,11 @@ __device__ __forceinline__ void r2s(const f32x4 (&r)[ROWS * BK / 4 / NT], float 
     }
 }
 
-template <int BM, int BN, int WM, int WN, bool AKC, bool BKC, int PF>
+// FLUSH > 0 (the 64 x 128 configuration: >= 64 K tiles by its dispatch rule): blocked summation -- every FLUSH K tiles of a slice the
+// MFMA accumulators are added into a second set and restarted, so no fp32 chain is longer than FLUSH * 32 products.  With one chain
+// over a whole 2017-long K an output element carried 3 x the error of a blocked fp32 GEMM (tests/test_gemm_routes_gpu.py,
+// t64w_full_acc: 2.2e-7 of the magnitude sum against 0.7e-7).
+template <int BM, int BN, int WM, int WN, bool AKC, bool BKC, int PF, int FLUSH = 0>
 __global__ __launch_bounds__(NT) void gemm_kernel(const KArgs a) {
     constexpr int TM = BM / WM / 32;
     constexpr int TN = BN / WN / 32;
@@ -141,6 +145,15 @@ __global__ __launch_bounds__(NT) void gemm_kernel(const KArgs a) {
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    f32x16 tot[FLUSH > 0 ? TM : 1][FLUSH > 0 ? TN : 1];
+    if (FLUSH > 0) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) tot[i][j][r] = 0.f;
+    }
 
     // PF register sets keep PF K-tiles in flight from HBM while one tile is consumed from LDS: at decode
     // sizes the loop is HBM-latency bound (one 16 KB tile per ~2 us round trip per workgroup otherwise).
@@ -201,10 +214,26 @@ __global__ __launch_bounds__(NT) void gemm_kernel(const KArgs a) {
                             for (int j = 0; j < TN; ++j)
                                 acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i][e], bv[j][e], acc[i][j], 0, 0, 0);
                 }
+                if (FLUSH > 0 && (t - t_begin) % FLUSH == FLUSH - 1) {
+#pragma unroll
+                    for (int i = 0; i < TM; ++i)
+#pragma unroll
+                        for (int j = 0; j < TN; ++j)
+#pragma unroll
+                            for (int r = 0; r < 16; ++r) { tot[i][j][r] += acc[i][j][r]; acc[i][j][r] = 0.f; }
+                }
             }
         }
     }
 
+    if (FLUSH > 0) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[i][j][r] += tot[i][j][r];
+    }
     // ---- epilogue: C/D layout of 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
     const bool to_partial = a.to_partial != 0;
     const size_t MN = (size_t)a.M * a.N;
@@ -384,12 +413,12 @@ void launch_one(K kernel, dim3 grid, hipStream_t st, const KArgs &a, const ProfI
     else
         hipLaunchKernelGGL(kernel, grid, dim3(NT), 0, st, a);
 }
-template <int BM, int BN, int WM, int WN, int PF>
+template <int BM, int BN, int WM, int WN, int PF, int FLUSH = 0>
 int launch_cfg(const KArgs &a, int al, int bl, dim3 grid, hipStream_t st, const ProfInfo &pi) {
-    if (al == 0 && bl == 0) launch_one(gemm_kernel<BM, BN, WM, WN, true, true, PF>, grid, st, a, pi);
-    else if (al == 0 && bl == 1) launch_one(gemm_kernel<BM, BN, WM, WN, true, false, PF>, grid, st, a, pi);
-    else if (al == 1 && bl == 1) launch_one(gemm_kernel<BM, BN, WM, WN, false, false, PF>, grid, st, a, pi);
-    else launch_one(gemm_kernel<BM, BN, WM, WN, false, true, PF>, grid, st, a, pi);
+    if (al == 0 && bl == 0) launch_one(gemm_kernel<BM, BN, WM, WN, true, true, PF, FLUSH>, grid, st, a, pi);
+    else if (al == 0 && bl == 1) launch_one(gemm_kernel<BM, BN, WM, WN, true, false, PF, FLUSH>, grid, st, a, pi);
+    else if (al == 1 && bl == 1) launch_one(gemm_kernel<BM, BN, WM, WN, false, false, PF, FLUSH>, grid, st, a, pi);
+    else launch_one(gemm_kernel<BM, BN, WM, WN, false, true, PF, FLUSH>, grid, st, a, pi);
     CAPMI_CHECK_LAUNCH();
     return 0;
 }
@@ -439,6 +468,16 @@ static std::atomic<int> g_wide_deferred{0};
 
 extern "C" int capmi_gemm_set_policy(int allow_wide_deferred) {
     return g_wide_deferred.exchange(allow_wide_deferred ? 1 : 0);
+}
+
+// CAPMI_GEMM_LOG=1: one census line on stderr per successful call -- the shape, the plan, the kernel that ran it (route) and where its
+// epilogue was applied (kernel: inside the launch, reduce: splitk_reduce_kernel, slabs: left to a fused consumer)
+static void gemm_census(const capmi_gemm_desc *d, int tiles, int x3, int wide, int splits, const char *route, int in_launch = 0) {
+    static const int env_log = capmi::knob("CAPMI_GEMM_LOG", 0);
+    if (!env_log) return;
+    fprintf(stderr, "capmi_gemm M=%d N=%d tiles=%d al=%d bl=%d x3=%d wide=%d splits=%d defer=%d acc=%d route=%s epi=%s\n", d->M, d->N, tiles,
+            d->a_layout, d->b_layout, x3, wide, splits, d->defer_reduce, d->accumulate, route,
+            d->defer_reduce ? "slabs" : (splits > 1 && !in_launch) ? "reduce" : "kernel");
 }
 
 extern "C" int capmi_gemm_f32(capmi_gemm_desc *d, void *stream) {
@@ -541,9 +580,10 @@ extern "C" int capmi_gemm_f32(capmi_gemm_desc *d, void *stream) {
                 int rc = launch_lc(a, d->b_layout, st, pcls, bytes, flops);
                 if (rc) return rc;
                 if (splits > 1 && !d->defer_reduce)
-                    return splitk_reduce_addend(a.partial, splits, d->C, d->ldc, d->M, d->N, d->bias, d->bias2, d->row_bias,
-                                               a.row_bias_div, d->mul_mask, d->relu, d->accumulate, d->addend, stream);
-                return 0;
+                    rc = splitk_reduce_addend(a.partial, splits, d->C, d->ldc, d->M, d->N, d->bias, d->bias2, d->row_bias,
+                                              a.row_bias_div, d->mul_mask, d->relu, d->accumulate, d->addend, stream);
+                if (rc == 0) gemm_census(d, tiles, 0, 0, splits, "lc");
+                return rc;
             }
         }
     }
@@ -590,9 +630,10 @@ extern "C" int capmi_gemm_f32(capmi_gemm_desc *d, void *stream) {
             int rc = launch_ares(a, d->b_layout, ts_max, use_x3, st, pcls, bytes, flops);
             if (rc) return rc;
             if (splits > 1 && !d->defer_reduce)
-                return splitk_reduce_addend(a.partial, splits, d->C, d->ldc, d->M, d->N, d->bias, d->bias2, d->row_bias,
-                                           a.row_bias_div, d->mul_mask, d->relu, d->accumulate, d->addend, stream);
-            return 0;
+                rc = splitk_reduce_addend(a.partial, splits, d->C, d->ldc, d->M, d->N, d->bias, d->bias2, d->row_bias,
+                                          a.row_bias_div, d->mul_mask, d->relu, d->accumulate, d->addend, stream);
+            if (rc == 0) gemm_census(d, tiles, 0, 0, splits, !use_x3 ? "ares_f32" : ts_cap == 3 ? "ares_x3_half" : "ares_x3");
+            return rc;
         }
     }
 
@@ -682,10 +723,8 @@ extern "C" int capmi_gemm_f32(capmi_gemm_desc *d, void *stream) {
     if (x3_ok) a.self_reduce = 0;      // the persistent kernel always leaves plain slabs
     if (a.to_partial && (!d->partial || (int64_t)splits * d->M * d->N > slab_cap)) return CAPMI_EINVAL;
     d->splits_used = splits;
-    static const int env_log = capmi::knob("CAPMI_GEMM_LOG", 0);   // shape census on stderr (profiling)
-    if (env_log)
-        fprintf(stderr, "capmi_gemm M=%d N=%d tiles=%d al=%d bl=%d x3=%d wide=%d splits=%d defer=%d acc=%d\n", d->M, d->N, tiles,
-                d->a_layout, d->b_layout, (int)x3_ok, x3_ok ? tiling : 0, splits, d->defer_reduce, d->accumulate);
+    const char *route = x3_ok ? (tiling == 1 ? "x3w" : tiling == 2 ? "x3w_swap" : "x3")
+                              : BM == 32 ? "t32x128" : BM == 128 ? "t128" : BN == 64 ? "t64x64" : "t64x128";
     dim3 grid(gn, gm, splits);
     const ProfInfo pi{pcls, bytes, flops};
     int rc;
@@ -704,13 +743,15 @@ extern "C" int capmi_gemm_f32(capmi_gemm_desc *d, void *stream) {
     } else if (x3_ok) rc = launch_x3(a, d->a_layout, d->b_layout, grid, st, pcls, bytes, flops);
     else if (BM == 32 && BN == 128) rc = launch_cfg<32, 128, 1, 4, 3>(a, d->a_layout, d->b_layout, grid, st, pi);
     else if (BM == 64 && BN == 64) rc = launch_cfg<64, 64, 2, 2, 3>(a, d->a_layout, d->b_layout, grid, st, pi);
-        else if (BM == 64 && BN == 128) rc = launch_cfg<64, 128, 1, 4, 2>(a, d->a_layout, d->b_layout, grid, st, pi);
+    else if (BM == 64 && BN == 128) rc = launch_cfg<64, 128, 1, 4, 2, 16>(a, d->a_layout, d->b_layout, grid, st, pi);
     else rc = launch_cfg<128, 128, 2, 2, 2>(a, d->a_layout, d->b_layout, grid, st, pi);
     if (rc) return rc;
     if (splits > 1 && !d->defer_reduce && !a.self_reduce)
-        return splitk_reduce_addend(a.partial, splits, d->C, d->ldc, d->M, d->N, d->bias, d->bias2, d->row_bias,
-                                   a.row_bias_div, d->mul_mask, d->relu, d->accumulate, d->addend, stream);
-    return 0;
+        rc = splitk_reduce_addend(a.partial, splits, d->C, d->ldc, d->M, d->N, d->bias, d->bias2, d->row_bias,
+                                  a.row_bias_div, d->mul_mask, d->relu, d->accumulate, d->addend, stream);
+    // (a.self_reduce, a research switch: the last-arriving workgroup applied the epilogue inside the launch)
+    if (rc == 0) gemm_census(d, tiles, (int)x3_ok, x3_ok ? tiling : 0, splits, route, a.self_reduce);
+    return rc;
 }
 
 // ---- r6: grouped weight-gradient GEMMs (capmi.h capmi_gemm_group_tn; kernel in gemm_x3w.hip) -------------------------------------
