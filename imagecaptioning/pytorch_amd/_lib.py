@@ -271,6 +271,7 @@ SIGNATURES = {
     'capmi_version': [],
     'capmi_arch': [],
     'capmi_gemm_f32': [C.POINTER(GemmDesc), _P],
+    'capmi_gemm_plan': [C.POINTER(GemmDesc), C.POINTER(C.c_char_p), C.POINTER(_I), C.POINTER(C.c_char_p)],
     'capmi_planes_bytes': [_I],
     'capmi_planes_from_f32': [_P, _I, _I, _I, _P, _P],
     'capmi_updown_planes_bytes': [_I, _I],
@@ -356,7 +357,6 @@ SIGNATURES = {
     'capmi_layernorm_bwd_slabs': [_P, _I, _I64, _P, _P, _P, _P, _P, _P, _I, _I64, _I, _P, _P, _I, _I, _F, _P],
     'capmi_mha_fwd_qslabs': [_P, _I, _I, _I64, _P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     'capmi_mha_bwd_slabs': [_P, _I, _I64, _I, _P, _I, _P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    'capmi_gemm_set_policy': [_I],
     'capmi_gemm_group_tn': [_P, _I, _P, _I64, _P],
     'capmi_split_halves': [_P, _I, _I64, _P, _P, _P, _P, _I, _I, _P],
     'capmi_meanpool_fwd': [_P, _P, _P, _I, _I, _I, _P],

@@ -77,23 +77,44 @@ __device__ __forceinline__ void locate(const KArgs &a, int tile, int &s, int &k0
 int ares_plan(int N, int tiles, int want_blocks, int ts_cap, int *splits);
 int ares_ts_cap(int M, int x3);
 int launch_ares(const KArgs &a, int b_layout, int ts_max, int x3, hipStream_t st, int pcls, double bytes, double flops);
-// r4: a caller that wants to run the loader / consumer GEMM INSIDE another launch (sampler.hip: select + GEMM in one grid) sets this
-// pointer around capmi_gemm_f32(); launch_lc() then stores its arguments here instead of launching.  filled stays false when the
-// dispatcher took another path (that GEMM was launched normally).
-struct LcCapture {
-    KArgs a;
-    int b_layout, grid_x, grid_y, tm;
-    bool filled;
-};
-extern thread_local LcCapture *g_lc_capture;
-// loader / consumer kernel on A planes (gemm_lc.hip): lc_plan picks a.sl and a.splits
+// loader / consumer kernel on A planes (gemm_lc.hip): lc_plan picks a.sl and a.splits; lc_grid_x is the launch's column blocks (its
+// grid is lc_grid_x x a.splits -- sampler.hip runs the same body behind the select rows of its own grid)
 int lc_plan(int N, int tiles, int want_blocks, int *splits);
+int lc_grid_x(const KArgs &a);
 int launch_lc(const KArgs &a, int b_layout, hipStream_t st, int pcls, double bytes, double flops);
 
 // fat GEMMs through the bf16 pipe by exact 3-way operand splitting; defined in gemm_x3.hip
 int launch_x3(const KArgs &a, int a_layout, int b_layout, dim3 grid, hipStream_t st, int pcls, double bytes, double flops);
 // ... on 256 x 128 tiles (gemm_x3w.hip, r5); grid = (gn, gm of the 256-row tiling, splits)
 int launch_x3w(const KArgs &a, int a_layout, int b_layout, dim3 grid, hipStream_t st, int pcls, double bytes, double flops);
+
+// ---- the dispatcher of capmi_gemm_f32 (gemm_f32.hip): gemm_plan decides, gemm_run launches ----
+// one value per kernel configuration a call can end on; ROUTE_NAMES are the census strings (CAPMI_GEMM_LOG, tests/gemm_ref64.py ROUTES)
+enum Route {
+    ROUTE_LC, ROUTE_ARES_X3, ROUTE_ARES_X3_HALF, ROUTE_ARES_F32, ROUTE_T32X128, ROUTE_T64X64, ROUTE_T64X128, ROUTE_T128,
+    ROUTE_X3, ROUTE_X3W, ROUTE_X3W_SWAP, ROUTE_COUNT
+};
+// where the epilogue is applied: inside the launch, by splitk_reduce_kernel, or left to a fused consumer of the slabs (defer_reduce)
+enum Epi { EPI_KERNEL, EPI_REDUCE, EPI_SLABS };
+extern const char *const ROUTE_NAMES[ROUTE_COUNT], *const EPI_NAMES[3];
+struct Plan {
+    KArgs a;             // what the route's kernel takes (x3w_swap: the swapped product, KArgs.transposed); a.sl: loader / consumer slice
+    Route route;
+    Epi epi;
+    int splits;
+    int gx, gy;          // tiled / bf16x3 kernels: the grid is (gx, gy, splits) tiles of the route's tiling
+    int ts_max;          // A-resident kernel: K chunks per wave
+    int tiles;           // K tiles of the whole call
+    int pcls;            // profiling class and the algorithmic traffic accounted to it
+    double bytes, flops;
+};
+// validates and plans *d: host arithmetic only -- no HIP call, no stream, *d is not written.  CAPMI_EINVAL for a descriptor that no
+// kernel can serve (malformed, or K-slice slabs that the workspace cannot hold)
+int gemm_plan(const capmi_gemm_desc *d, Plan *p);
+// launches a plan made from *d (+ the reduce launch where p.epi == EPI_REDUCE) and writes its census line (CAPMI_GEMM_LOG=1), which
+// a caller that ran p.a in a grid of its own writes itself
+int gemm_run(const Plan &p, const capmi_gemm_desc *d, hipStream_t st);
+void gemm_census(const capmi_gemm_desc *d, const Plan &p);
 
 // ---- r6: grouped launch of independent weight-gradient GEMMs C_i = A_i^T B_i ([K][M] x [K][N] operands) on the 256 x 128 kernel ----
 // One table entry = a run of output tiles of one GEMM (row-major tile order of its 256 x 128 tiling).  Entries with splits == 1 write

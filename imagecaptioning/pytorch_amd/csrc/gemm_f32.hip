@@ -22,7 +22,6 @@
 #include "host_common.h"
 #include "profile.h"
 #include "gemm_common.h"
-#include <atomic>
 #include <stdio.h>
 #include <stdlib.h>
 #include <hip/hip_ext.h>
@@ -401,24 +400,20 @@ __global__ __launch_bounds__(256) void splitk_reduce_batch_kernel(const capmi_re
     }
 }
 
-struct ProfInfo {
-    int cls;
-    double bytes, flops;
-};
 template <typename K>
-void launch_one(K kernel, dim3 grid, hipStream_t st, const KArgs &a, const ProfInfo &pi) {
+void launch_one(K kernel, dim3 grid, hipStream_t st, const Plan &p) {
     hipEvent_t e0, e1;
-    if (capmi_prof::take_events(pi.cls, &e0, &e1, pi.bytes, pi.flops))
-        hipExtLaunchKernelGGL(kernel, grid, dim3(NT), 0, st, e0, e1, 0, a);
+    if (capmi_prof::take_events(p.pcls, &e0, &e1, p.bytes, p.flops))
+        hipExtLaunchKernelGGL(kernel, grid, dim3(NT), 0, st, e0, e1, 0, p.a);
     else
-        hipLaunchKernelGGL(kernel, grid, dim3(NT), 0, st, a);
+        hipLaunchKernelGGL(kernel, grid, dim3(NT), 0, st, p.a);
 }
 template <int BM, int BN, int WM, int WN, int PF, int FLUSH = 0>
-int launch_cfg(const KArgs &a, int al, int bl, dim3 grid, hipStream_t st, const ProfInfo &pi) {
-    if (al == 0 && bl == 0) launch_one(gemm_kernel<BM, BN, WM, WN, true, true, PF, FLUSH>, grid, st, a, pi);
-    else if (al == 0 && bl == 1) launch_one(gemm_kernel<BM, BN, WM, WN, true, false, PF, FLUSH>, grid, st, a, pi);
-    else if (al == 1 && bl == 1) launch_one(gemm_kernel<BM, BN, WM, WN, false, false, PF, FLUSH>, grid, st, a, pi);
-    else launch_one(gemm_kernel<BM, BN, WM, WN, false, true, PF, FLUSH>, grid, st, a, pi);
+int launch_cfg(const Plan &p, int al, int bl, dim3 grid, hipStream_t st) {
+    if (al == 0 && bl == 0) launch_one(gemm_kernel<BM, BN, WM, WN, true, true, PF, FLUSH>, grid, st, p);
+    else if (al == 0 && bl == 1) launch_one(gemm_kernel<BM, BN, WM, WN, true, false, PF, FLUSH>, grid, st, p);
+    else if (al == 1 && bl == 1) launch_one(gemm_kernel<BM, BN, WM, WN, false, false, PF, FLUSH>, grid, st, p);
+    else launch_one(gemm_kernel<BM, BN, WM, WN, false, true, PF, FLUSH>, grid, st, p);
     CAPMI_CHECK_LAUNCH();
     return 0;
 }
@@ -462,28 +457,23 @@ extern "C" int capmi_splitk_reduce_batch(const capmi_reduce_item *items, int n_i
     return 0;
 }
 
-// r5: a wide (256 x 128) fat-GEMM workgroup owns its CU; planned for deferred-reduction GEMMs only when the caller says that no
-// other stream runs beside them (capmi_gemm_set_policy)
-static std::atomic<int> g_wide_deferred{0};
+// ---- the dispatcher: gemm_plan (descriptor -> Plan; host arithmetic only) and gemm_run (Plan -> launches) ------------------------------
+const char *const capmi_gemm::ROUTE_NAMES[ROUTE_COUNT] = {"lc", "ares_x3", "ares_x3_half", "ares_f32", "t32x128", "t64x64", "t64x128",
+                                                          "t128", "x3", "x3w", "x3w_swap"};
+const char *const capmi_gemm::EPI_NAMES[3] = {"kernel", "reduce", "slabs"};
 
-extern "C" int capmi_gemm_set_policy(int allow_wide_deferred) {
-    return g_wide_deferred.exchange(allow_wide_deferred ? 1 : 0);
-}
+namespace {
 
-// CAPMI_GEMM_LOG=1: one census line on stderr per successful call -- the shape, the plan, the kernel that ran it (route) and where its
-// epilogue was applied (kernel: inside the launch, reduce: splitk_reduce_kernel, slabs: left to a fused consumer)
-static void gemm_census(const capmi_gemm_desc *d, int tiles, int x3, int wide, int splits, const char *route, int in_launch = 0) {
-    static const int env_log = capmi::knob("CAPMI_GEMM_LOG", 0);
-    if (!env_log) return;
-    fprintf(stderr, "capmi_gemm M=%d N=%d tiles=%d al=%d bl=%d x3=%d wide=%d splits=%d defer=%d acc=%d route=%s epi=%s\n", d->M, d->N, tiles,
-            d->a_layout, d->b_layout, x3, wide, splits, d->defer_reduce, d->accumulate, route,
-            d->defer_reduce ? "slabs" : (splits > 1 && !in_launch) ? "reduce" : "kernel");
-}
+// workspace layout: [CAPMI_WS_COUNTER_FLOATS ints of tile tickets (zero between launches)][K-slice slabs]
+int64_t slab_cap(const capmi_gemm_desc *d) { return d->partial ? d->partial_capacity - CAPMI_WS_COUNTER_FLOATS : 0; }
+bool slabs_fit(const capmi_gemm_desc *d, int splits) { return (int64_t)splits * d->M * d->N <= slab_cap(d); }
 
-extern "C" int capmi_gemm_f32(capmi_gemm_desc *d, void *stream) {
+// descriptor -> KArgs (everything but the K split), K tiles, profiling class and traffic
+int plan_args(const capmi_gemm_desc *d, Plan *p) {
     if (!d || d->nseg < 1 || d->nseg > CAPMI_MAX_SEG || d->M <= 0 || d->N <= 0 || !d->C) return CAPMI_EINVAL;
     if (d->a_layout < 0 || d->a_layout > 1 || d->b_layout < 0 || d->b_layout > 1) return CAPMI_EINVAL;
-    KArgs a{};
+    *p = Plan{};
+    KArgs &a = p->a;
     a.nseg = d->nseg;
     // r7: B as column segments read in place (loader / consumer kernel only)
     static_assert(CAPMI_MAX_BCOL == MAX_BCOL, "column segments of the descriptor and of the kernel arguments");
@@ -523,7 +513,7 @@ extern "C" int capmi_gemm_f32(capmi_gemm_desc *d, void *stream) {
         a.seg[s] = a.seg[0];
         a.seg[s].tstart = 0x7fffffff;
     }
-    a.tiles_total = tiles;
+    a.tiles_total = p->tiles = tiles;
     static const int env_ablate = capmi::ablate_env("CAPMI_GEMM_ABLATE");   // (variants builds only)
     a.ablate = env_ablate;
     a.M = d->M; a.N = d->N; a.C = d->C; a.ldc = d->ldc;
@@ -531,117 +521,95 @@ extern "C" int capmi_gemm_f32(capmi_gemm_desc *d, void *stream) {
     a.row_bias_div = d->row_bias_div > 0 ? d->row_bias_div : 1;
     a.mul_mask = d->mul_mask; a.relu = d->relu; a.accumulate = d->accumulate;
     a.addend = d->addend ? d->addend : d->C;
-    // workspace layout: [CAPMI_WS_COUNTER_FLOATS ints of tile tickets (zero between launches)][K-slice slabs]
-    const int64_t slab_cap = d->partial ? d->partial_capacity - CAPMI_WS_COUNTER_FLOATS : 0;
     a.partial = d->partial ? d->partial + CAPMI_WS_COUNTER_FLOATS : nullptr;
     a.counters = reinterpret_cast<int *>(d->partial);
-    hipStream_t st = (hipStream_t)stream;
     double ksum = 0, abytes = 0;   // algorithmic traffic of this launch: every operand element once + the output once
     for (int s = 0; s < d->nseg; ++s) {
         ksum += d->seg[s].K;
         abytes += (double)d->seg[s].K * ((double)d->M / a.seg[s].a_row_div);
     }
-    const double bytes = 4.0 * (abytes + ksum * d->N + (double)d->M * d->N);
-    const double flops = 2.0 * d->M * (double)d->N * ksum;
-    int pcls = (d->M <= 64 && d->a_layout == 0) ? (d->b_layout == 0 ? CAPMI_PROF_GEMM_DECODE : CAPMI_PROF_GEMM_BPTT)
-                                                 : CAPMI_PROF_GEMM_FAT;
+    p->bytes = 4.0 * (abytes + ksum * d->N + (double)d->M * d->N);
+    p->flops = 2.0 * d->M * (double)d->N * ksum;
+    p->pcls = (d->M <= 64 && d->a_layout == 0) ? (d->b_layout == 0 ? CAPMI_PROF_GEMM_DECODE : CAPMI_PROF_GEMM_BPTT)
+                                               : CAPMI_PROF_GEMM_FAT;
     // (r4: >= 24 MB.  The 17-MB token-embedding segment that is left of the attention-LSTM gate GEMM when its other two segments ride in
     //  the select launch is a short, latency-dominated launch: it is accounted with the small decode GEMMs, class 0)
-    if (pcls == CAPMI_PROF_GEMM_DECODE && bytes >= 24e6) pcls = CAPMI_PROF_GEMM_DECODE_STREAM;
+    if (p->pcls == CAPMI_PROF_GEMM_DECODE && p->bytes >= 24e6) p->pcls = CAPMI_PROF_GEMM_DECODE_STREAM;
+    return 0;
+}
 
-    static const int env_path = capmi::research("CAPMI_GEMM_PATH", 0);
-    static const int env_blocks = capmi::research("CAPMI_GEMM_BLOCKS", 512);
-    bool ares_ok = d->a_layout == 0 && d->M <= 64 && BK == 32;
-    for (int s = 0; s < d->nseg && ares_ok; ++s)     // branch-free 16-byte operand fetch: aligned, K % 4 == 0
-        ares_ok = a.seg[s].vecA && (a.seg[s].K % 4 == 0) && (d->b_layout == 1 || a.seg[s].vecB);
-    // ---- loader / consumer kernel (gemm_lc.hip) when every segment is also delivered as A planes ----
-    // CAPMI_LC=0 (documented knob): the A-resident kernel below serves those GEMMs too (tests/test_planes_gpu.py compares the two)
+// ---- loader / consumer kernel (gemm_lc.hip) when every segment is also delivered as A planes ----
+// CAPMI_LC=0 (documented knob): the A-resident kernel serves those GEMMs too (tests/test_planes_gpu.py compares the two)
+bool plan_lc(const capmi_gemm_desc *d, Plan *p) {
     static const int env_lc = capmi::knob("CAPMI_LC", 1);
-    {
-        bool lc_ok = env_lc && env_path != 3 && ares_ok && d->M <= 64;
-        for (int s = 0; s < d->nseg && lc_ok; ++s)
-            lc_ok = d->a_planes[s] != nullptr && a.seg[s].a_row_div == 1 && a.seg[s].vecB;
-        if (lc_ok && d->b_layout == 1) lc_ok = d->N % 4 == 0 && d->N >= 4;
-        if (lc_ok) {
-            static const int env_ab = capmi::research("CAPMI_ARES_BLOCKS", 256);
-            static const int env_opt = capmi::research("CAPMI_LC_OPT", 1);
-            const int want = d->splits > 0 ? ((d->N + 127) / 128) * d->splits : env_ab;
-            int splits = 0;
-            // (column segments: the plan is that of the packed matrix -- same K slices, same summation order -- and the grid has one
-            //  column block more per ragged segment end that a packed block would have straddled)
-            a.sl = lc_plan(d->N, tiles, want, &splits);
-            const bool partial = splits > 1 || d->defer_reduce;
-            if (!partial || (d->partial && (int64_t)splits * d->M * d->N <= slab_cap)) {
-                a.splits = splits;
-                a.to_partial = partial ? 1 : 0;
-                a.self_reduce = 0;
-                a.ablate = env_opt;              // bit 0: XCD-aware workgroup map
-                d->splits_used = splits;
-                int rc = launch_lc(a, d->b_layout, st, pcls, bytes, flops);
-                if (rc) return rc;
-                if (splits > 1 && !d->defer_reduce)
-                    rc = splitk_reduce_addend(a.partial, splits, d->C, d->ldc, d->M, d->N, d->bias, d->bias2, d->row_bias,
-                                              a.row_bias_div, d->mul_mask, d->relu, d->accumulate, d->addend, stream);
-                if (rc == 0) gemm_census(d, tiles, 0, 0, splits, "lc");
-                return rc;
-            }
-        }
-    }
-    if (a.nbcol) return CAPMI_EINVAL;   // column segments: no other kernel reads them
-    if (env_path != 3 && ares_ok) {     // CAPMI_GEMM_PATH=3 forces the LDS-tiled kernel
-        // ---- A-resident path (gemm_ares.hip): activations stay in LDS, weights stream straight to VGPRs ----
-        static const int env_ab = capmi::research("CAPMI_ARES_BLOCKS", 256);
-        // bf16x3 split (see gemm_x3.hip) for the decode GEMMs too: activations split once when staged, weights split in
-        // registers by the wave that streams them.  Gate GEMM 24.9 -> 19.9 us; greedy decodes stay token-exact on
-        // the reference fixtures.  CAPMI_ARES_X3=0 restores the exact-fp32 MFMA.
-        static const int env_ax3 = capmi::knob("CAPMI_ARES_X3", 1);
-        int use_x3 = env_ax3;
-        const int want = d->splits > 0 ? ((d->N + 127) / 128) * d->splits : env_ab;
-        int splits = 0;
-        int ts_cap = ares_ts_cap(d->M, use_x3);
-        int ts_max = ares_plan(d->N, tiles, want, ts_cap, &splits);
-        if (use_x3 && ((d->N + 127) / 128) * splits > want) {
-            // the bf16 planes of 64 rows cap a slice at 12 chunks; when that pushes the grid past one workgroup per CU
-            // (a second, mostly empty round), first try HALF-size slices with two workgroups resident per CU (<= 6
-            // chunks = 77 KB of LDS each, everything in one round: 21.0 vs 27.8 us for dX = dG [W_ih | W_hh] with
-            // N = 3000), else the exact-fp32 image with its longer slices (26.3 us)
-            const int nblk = (d->N + 127) / 128;
-            int splits2 = 0;
-            const int ts2 = ares_plan(d->N, tiles, 2 * want, 3, &splits2);
-            if (nblk * splits2 <= 2 * want && (int64_t)splits2 * d->M * d->N <= slab_cap) {
-                ts_cap = 3; ts_max = ts2; splits = splits2;
-            } else {
-                int splits32 = 0;
-                const int ts32 = ares_plan(d->N, tiles, want, ares_ts_cap(d->M, 0), &splits32);
-                if (nblk * splits32 <= want) {
-                    use_x3 = 0; ts_cap = ares_ts_cap(d->M, 0); ts_max = ts32; splits = splits32;
-                }
-            }
-        }
-        if ((splits > 1 || d->defer_reduce) && (int64_t)splits * d->M * d->N > slab_cap) ts_max = 99;   // slabs do not fit
-        if (ts_max <= ts_cap) {
-            a.splits = splits;
-            a.to_partial = (splits > 1 || d->defer_reduce) ? 1 : 0;
-            a.self_reduce = 0;
-            static const int env_aopt = capmi::research("CAPMI_ARES_OPT", 2);
-            a.ablate = env_aopt;             // speed-only switches of the A-resident kernel (see gemm_ares.hip)
-            if (a.to_partial && (!d->partial || (int64_t)splits * d->M * d->N > slab_cap)) return CAPMI_EINVAL;
-            d->splits_used = splits;
-            int rc = launch_ares(a, d->b_layout, ts_max, use_x3, st, pcls, bytes, flops);
-            if (rc) return rc;
-            if (splits > 1 && !d->defer_reduce)
-                rc = splitk_reduce_addend(a.partial, splits, d->C, d->ldc, d->M, d->N, d->bias, d->bias2, d->row_bias,
-                                          a.row_bias_div, d->mul_mask, d->relu, d->accumulate, d->addend, stream);
-            if (rc == 0) gemm_census(d, tiles, 0, 0, splits, !use_x3 ? "ares_f32" : ts_cap == 3 ? "ares_x3_half" : "ares_x3");
-            return rc;
-        }
-    }
+    KArgs &a = p->a;
+    bool ok = env_lc != 0;
+    for (int s = 0; s < d->nseg && ok; ++s)
+        ok = d->a_planes[s] != nullptr && a.seg[s].a_row_div == 1 && a.seg[s].vecB;
+    if (ok && d->b_layout == 1) ok = d->N % 4 == 0 && d->N >= 4;
+    if (!ok) return false;
+    static const int env_ab = capmi::research("CAPMI_ARES_BLOCKS", 256);
+    static const int env_opt = capmi::research("CAPMI_LC_OPT", 1);
+    const int want = d->splits > 0 ? ((d->N + 127) / 128) * d->splits : env_ab;
+    int splits = 0;
+    // (column segments: the plan is that of the packed matrix -- same K slices, same summation order -- and the grid has one
+    //  column block more per ragged segment end that a packed block would have straddled)
+    const int sl = lc_plan(d->N, p->tiles, want, &splits);
+    if ((splits > 1 || d->defer_reduce) && !slabs_fit(d, splits)) return false;
+    a.sl = sl;
+    a.ablate = env_opt;              // bit 0: XCD-aware workgroup map
+    p->route = ROUTE_LC;
+    p->splits = splits;
+    return true;
+}
 
+// ---- A-resident kernel (gemm_ares.hip): activations stay in LDS, weights stream straight to VGPRs ----
+bool plan_ares(const capmi_gemm_desc *d, Plan *p) {
+    static const int env_ab = capmi::research("CAPMI_ARES_BLOCKS", 256);
+    // bf16x3 split (see gemm_x3.hip) for the decode GEMMs too: activations split once when staged, weights split in
+    // registers by the wave that streams them.  Gate GEMM 24.9 -> 19.9 us; greedy decodes stay token-exact on
+    // the reference fixtures.  CAPMI_ARES_X3=0 restores the exact-fp32 MFMA.
+    static const int env_ax3 = capmi::knob("CAPMI_ARES_X3", 1);
+    const int tiles = p->tiles, nblk = (d->N + 127) / 128;
+    const int want = d->splits > 0 ? nblk * d->splits : env_ab;
+    Route route = env_ax3 ? ROUTE_ARES_X3 : ROUTE_ARES_F32;
+    int splits = 0;
+    int ts_max = ares_plan(d->N, tiles, want, ares_ts_cap(d->M, env_ax3), &splits);
+    if (env_ax3 && nblk * splits > want) {
+        // the bf16 planes of 64 rows cap a slice at 12 chunks; when that pushes the grid past one workgroup per CU
+        // (a second, mostly empty round), first try HALF-size slices with two workgroups resident per CU (<= 6
+        // chunks = 77 KB of LDS each, everything in one round: 21.0 vs 27.8 us for dX = dG [W_ih | W_hh] with
+        // N = 3000), else the exact-fp32 image with its longer slices (26.3 us)
+        int splits2 = 0;
+        const int ts2 = ares_plan(d->N, tiles, 2 * want, 3, &splits2);
+        if (nblk * splits2 <= 2 * want && slabs_fit(d, splits2)) {
+            route = ROUTE_ARES_X3_HALF; ts_max = ts2; splits = splits2;
+        } else {
+            int splits32 = 0;
+            const int ts32 = ares_plan(d->N, tiles, want, ares_ts_cap(d->M, 0), &splits32);
+            if (nblk * splits32 <= want) {
+                route = ROUTE_ARES_F32; ts_max = ts32; splits = splits32;
+            }
+        }
+    }
+    if ((splits > 1 || d->defer_reduce) && !slabs_fit(d, splits)) return false;
+    static const int env_aopt = capmi::research("CAPMI_ARES_OPT", 2);
+    p->a.ablate = env_aopt;          // speed-only switches of the A-resident kernel (see gemm_ares.hip)
+    p->route = route;
+    p->splits = splits;
+    p->ts_max = ts_max;
+    return true;
+}
+
+// ---- LDS-tiled fp32 MFMA kernel (above) and the persistent bf16x3 kernels (gemm_x3.hip, gemm_x3w.hip) ----
+void plan_tiled(const capmi_gemm_desc *d, Plan *p) {
+    const KArgs &a = p->a;
+    const int tiles = p->tiles;
+    static const int env_blocks = capmi::research("CAPMI_GEMM_BLOCKS", 512);
     // tile shape by M: decode batches are skinny.  Every configuration gives each wave >= 2 independent
     // accumulator chains (a lone dependent v_mfma_f32_32x32x2 chain loses ~40 % to issue gaps).
     static const int env_cfg = capmi::research("CAPMI_GEMM_CFG", 1);
     int BM, BN;
-    (void)env_cfg;
     if (d->M <= 32) { BM = 32; BN = 128; }
     else if (d->M <= 64 || (long long)d->M * d->N < 256LL * 1024) {
         BM = 64;
@@ -684,7 +652,8 @@ extern "C" int capmi_gemm_f32(capmi_gemm_desc *d, void *stream) {
             // owns its CU -- and a persistent grid of them beside another stream's kernels starved both (Transformer XE 14.3 ->
             // 36.5 ms); the 128 x 128 kernel leaves room for the chain's small kernels.  (Re-measured at the end of r5 with the final
             // kernels, scripts/r5_ab7.sh: wide deferred GEMMs 13.44-13.71 ms vs 13.31-13.35 -- still a loss, with 4 or 8 staging waves.)
-            if (w == 1 && env_tile != 256 && d->defer_reduce && !d->allow_wide_deferred && !g_wide_deferred.load(std::memory_order_relaxed)) continue;
+            // The caller that knows that nothing runs beside this GEMM says so per call: allow_wide_deferred.
+            if (w == 1 && env_tile != 256 && d->defer_reduce && !d->allow_wide_deferred) continue;
             // w == 2: SKINNY products (few rows, many columns: the per-step gate / dX GEMMs of a teacher-forced XE step at bs64,
             // [320 x 4000]) on the wide kernel with the operands SWAPPED -- the 256-row side of the tile runs along the WEIGHTS, the
             // activations are the 128-row operand, the epilogue writes C^T back as C in 16-byte pieces (x3_epilogue_t).  Row-major
@@ -693,7 +662,7 @@ extern "C" int capmi_gemm_f32(capmi_gemm_desc *d, void *stream) {
             const int out_tiles = w == 0 ? gm * gn : w == 1 ? gmw * gn : gnw * gm;
             const double step = w ? env_wcost / 100.0 : 1.0;
             for (int sp = sp_lo; sp <= sp_hi && sp <= tiles; ++sp) {
-                if (splits == 0 && sp > 1 && (!d->partial || (int64_t)sp * d->M * d->N > slab_cap)) break;
+                if (splits == 0 && sp > 1 && !slabs_fit(d, sp)) break;
                 const double rounds = (double)((out_tiles * sp + 255) / 256);
                 const double slab_us = sp > 1 ? (2.0 * sp + 1.0) * d->M * (double)d->N * 4.0 / 4.0e6 : 0.0;
                 const double cost = rounds * ((tiles + sp - 1) / sp) * step + slab_us / 1.5;
@@ -710,48 +679,110 @@ extern "C" int capmi_gemm_f32(capmi_gemm_desc *d, void *stream) {
             if (splits > tiles / 4) splits = tiles / 4;
             if (splits > 64) splits = 64;
             if (splits < 1) splits = 1;
-            while (splits > 1 && (int64_t)splits * d->M * d->N > slab_cap) --splits;
+            while (splits > 1 && !slabs_fit(d, splits)) --splits;
         }
     }
     if (splits > tiles) splits = tiles;
-    a.splits = splits;
-    a.to_partial = (splits > 1 || d->defer_reduce) ? 1 : 0;
     // in-launch last-arriver reduction is implemented (G16 recipe) but measured SLOWER than the follow-up reduce
     // kernel at decode sizes (logit 33.5 vs 27.9 us, dX 34.2 vs 27-31 us): opt-in via CAPMI_GEMM_SELF_REDUCE=1.
+    // (the persistent bf16x3 kernels always leave plain slabs)
     static const int env_self = capmi::research("CAPMI_GEMM_SELF_REDUCE", 0);
-    a.self_reduce = (env_self && splits > 1 && !d->defer_reduce && gn * gm <= CAPMI_WS_COUNTER_FLOATS) ? 1 : 0;
-    if (x3_ok) a.self_reduce = 0;      // the persistent kernel always leaves plain slabs
-    if (a.to_partial && (!d->partial || (int64_t)splits * d->M * d->N > slab_cap)) return CAPMI_EINVAL;
-    d->splits_used = splits;
-    const char *route = x3_ok ? (tiling == 1 ? "x3w" : tiling == 2 ? "x3w_swap" : "x3")
-                              : BM == 32 ? "t32x128" : BM == 128 ? "t128" : BN == 64 ? "t64x64" : "t64x128";
-    dim3 grid(gn, gm, splits);
-    const ProfInfo pi{pcls, bytes, flops};
-    int rc;
-    if (x3_ok && tiling == 1) rc = launch_x3w(a, d->a_layout, d->b_layout, dim3(gn, gmw, splits), st, pcls, bytes, flops);
-    else if (x3_ok && tiling == 2) {
-        KArgs t = a;                                     // C^T = B A^T: operands, shapes and layouts swapped; C, its pitch and
-        for (int s2 = 0; s2 < CAPMI_MAX_SEG; ++s2) {     // the epilogue operands keep C's orientation (KArgs.transposed)
-            t.seg[s2].A = a.seg[s2].B; t.seg[s2].B = a.seg[s2].A;
-            t.seg[s2].lda = a.seg[s2].ldb; t.seg[s2].ldb = a.seg[s2].lda;
-            t.seg[s2].vecA = a.seg[s2].vecB; t.seg[s2].vecB = a.seg[s2].vecA;
-            t.seg[s2].Apl = nullptr;
-        }
-        t.M = a.N; t.N = a.M;
-        t.transposed = 1;
-        rc = launch_x3w(t, d->b_layout, d->a_layout, dim3(gm, gnw, splits), st, pcls, bytes, flops);
-    } else if (x3_ok) rc = launch_x3(a, d->a_layout, d->b_layout, grid, st, pcls, bytes, flops);
-    else if (BM == 32 && BN == 128) rc = launch_cfg<32, 128, 1, 4, 3>(a, d->a_layout, d->b_layout, grid, st, pi);
-    else if (BM == 64 && BN == 64) rc = launch_cfg<64, 64, 2, 2, 3>(a, d->a_layout, d->b_layout, grid, st, pi);
-    else if (BM == 64 && BN == 128) rc = launch_cfg<64, 128, 1, 4, 2, 16>(a, d->a_layout, d->b_layout, grid, st, pi);
-    else rc = launch_cfg<128, 128, 2, 2, 2>(a, d->a_layout, d->b_layout, grid, st, pi);
+    p->a.self_reduce = (env_self && !x3_ok && splits > 1 && !d->defer_reduce && gn * gm <= CAPMI_WS_COUNTER_FLOATS) ? 1 : 0;
+    p->splits = splits;
+    p->route = x3_ok ? (tiling == 1 ? ROUTE_X3W : tiling == 2 ? ROUTE_X3W_SWAP : ROUTE_X3)
+                     : BM == 32 ? ROUTE_T32X128 : BM == 128 ? ROUTE_T128 : BN == 64 ? ROUTE_T64X64 : ROUTE_T64X128;
+    // the grid in tiles of the route's tiling: 256-row tiles for x3w; x3w_swap runs C^T, 256-column tiles of C along y
+    p->gx = p->route == ROUTE_X3W_SWAP ? gm : gn;
+    p->gy = p->route == ROUTE_X3W ? gmw : p->route == ROUTE_X3W_SWAP ? gnw : gm;
+}
+
+}  // namespace
+
+// CAPMI_GEMM_LOG=1: one census line on stderr per successful call -- the shape, the plan, the kernel that ran it (route) and where its
+// epilogue was applied (kernel: inside the launch, reduce: splitk_reduce_kernel, slabs: left to a fused consumer)
+void capmi_gemm::gemm_census(const capmi_gemm_desc *d, const Plan &p) {
+    static const int env_log = capmi::knob("CAPMI_GEMM_LOG", 0);
+    if (!env_log) return;
+    fprintf(stderr, "capmi_gemm M=%d N=%d tiles=%d al=%d bl=%d x3=%d wide=%d splits=%d defer=%d acc=%d route=%s epi=%s\n", d->M, d->N,
+            p.tiles, d->a_layout, d->b_layout, p.route >= ROUTE_X3, p.route == ROUTE_X3W ? 1 : p.route == ROUTE_X3W_SWAP ? 2 : 0,
+            p.splits, d->defer_reduce, d->accumulate, ROUTE_NAMES[p.route], EPI_NAMES[p.epi]);
+}
+
+// The route table (tests/gemm_ref64.py walks it row by row).  A skinny plan whose slabs the workspace cannot hold falls through.
+int capmi_gemm::gemm_plan(const capmi_gemm_desc *d, Plan *p) {
+    const int rc = plan_args(d, p);
     if (rc) return rc;
-    if (splits > 1 && !d->defer_reduce && !a.self_reduce)
-        rc = splitk_reduce_addend(a.partial, splits, d->C, d->ldc, d->M, d->N, d->bias, d->bias2, d->row_bias,
-                                  a.row_bias_div, d->mul_mask, d->relu, d->accumulate, d->addend, stream);
-    // (a.self_reduce, a research switch: the last-arriving workgroup applied the epilogue inside the launch)
-    if (rc == 0) gemm_census(d, tiles, (int)x3_ok, x3_ok ? tiling : 0, splits, route, a.self_reduce);
+    KArgs &a = p->a;
+    // the skinny kernels (loader / consumer, A-resident): M <= 64 row-major activations, branch-free 16-byte operand fetch
+    static const int env_path = capmi::research("CAPMI_GEMM_PATH", 0);      // 3 forces the LDS-tiled kernel
+    bool skinny = env_path != 3 && d->a_layout == 0 && d->M <= 64 && BK == 32;
+    for (int s = 0; s < d->nseg && skinny; ++s)      // aligned, K % 4 == 0
+        skinny = a.seg[s].vecA && (a.seg[s].K % 4 == 0) && (d->b_layout == 1 || a.seg[s].vecB);
+    if (skinny && plan_lc(d, p)) {
+    } else if (a.nbcol) {
+        return CAPMI_EINVAL;             // column segments: no other kernel reads them
+    } else if (!(skinny && plan_ares(d, p))) {
+        plan_tiled(d, p);
+    }
+    a.splits = p->splits;
+    a.to_partial = (p->splits > 1 || d->defer_reduce) ? 1 : 0;
+    if (a.to_partial && !slabs_fit(d, p->splits)) return CAPMI_EINVAL;
+    // (a.self_reduce, a research switch of the tiled kernel: its last-arriving workgroup applies the epilogue inside the launch)
+    p->epi = d->defer_reduce ? EPI_SLABS : (p->splits > 1 && !a.self_reduce) ? EPI_REDUCE : EPI_KERNEL;
+    if (p->route == ROUTE_X3W_SWAP) {                    // C^T = B A^T: operands, shapes and layouts swapped; C, its pitch and
+        for (int s = 0; s < CAPMI_MAX_SEG; ++s) {        // the epilogue operands keep C's orientation (KArgs.transposed)
+            Seg &g = a.seg[s];
+            const Seg o = g;
+            g.A = o.B; g.B = o.A; g.lda = o.ldb; g.ldb = o.lda; g.vecA = o.vecB; g.vecB = o.vecA;
+            g.Apl = nullptr;
+        }
+        a.M = d->N; a.N = d->M;
+        a.transposed = 1;
+    }
+    return 0;
+}
+
+int capmi_gemm::gemm_run(const Plan &p, const capmi_gemm_desc *d, hipStream_t st) {
+    const KArgs &a = p.a;
+    const int al = d->a_layout, bl = d->b_layout;
+    const dim3 grid(p.gx, p.gy, p.splits);
+    int rc = CAPMI_EINVAL;
+    switch (p.route) {
+    case ROUTE_LC: rc = launch_lc(a, bl, st, p.pcls, p.bytes, p.flops); break;
+    case ROUTE_ARES_X3: case ROUTE_ARES_X3_HALF: case ROUTE_ARES_F32:
+        rc = launch_ares(a, bl, p.ts_max, p.route != ROUTE_ARES_F32, st, p.pcls, p.bytes, p.flops); break;
+    case ROUTE_T32X128: rc = launch_cfg<32, 128, 1, 4, 3>(p, al, bl, grid, st); break;
+    case ROUTE_T64X64: rc = launch_cfg<64, 64, 2, 2, 3>(p, al, bl, grid, st); break;
+    case ROUTE_T64X128: rc = launch_cfg<64, 128, 1, 4, 2, 16>(p, al, bl, grid, st); break;
+    case ROUTE_T128: rc = launch_cfg<128, 128, 2, 2, 2>(p, al, bl, grid, st); break;
+    case ROUTE_X3: rc = launch_x3(a, al, bl, grid, st, p.pcls, p.bytes, p.flops); break;
+    case ROUTE_X3W: rc = launch_x3w(a, al, bl, grid, st, p.pcls, p.bytes, p.flops); break;
+    case ROUTE_X3W_SWAP: rc = launch_x3w(a, bl, al, grid, st, p.pcls, p.bytes, p.flops); break;
+    case ROUTE_COUNT: break;
+    }
+    if (rc == 0 && p.epi == EPI_REDUCE)
+        rc = splitk_reduce_addend(a.partial, p.splits, d->C, d->ldc, d->M, d->N, d->bias, d->bias2, d->row_bias, a.row_bias_div,
+                                  d->mul_mask, d->relu, d->accumulate, d->addend, st);
+    if (rc == 0) gemm_census(d, p);
     return rc;
+}
+
+extern "C" int capmi_gemm_f32(capmi_gemm_desc *d, void *stream) {
+    Plan p;
+    const int rc = gemm_plan(d, &p);
+    if (rc) return rc;
+    d->splits_used = p.splits;
+    return gemm_run(p, d, (hipStream_t)stream);
+}
+
+extern "C" int capmi_gemm_plan(const capmi_gemm_desc *d, const char **route, int *splits, const char **epi) {
+    Plan p;
+    const int rc = gemm_plan(d, &p);
+    if (rc) return rc;
+    if (route) *route = ROUTE_NAMES[p.route];
+    if (splits) *splits = p.splits;
+    if (epi) *epi = EPI_NAMES[p.epi];
+    return 0;
 }
 
 // ---- r6: grouped weight-gradient GEMMs (capmi.h capmi_gemm_group_tn; kernel in gemm_x3w.hip) -------------------------------------

@@ -638,19 +638,17 @@ int capmi_logsoftmax_select_partial_gemm(const float *partial, int splits, int64
                       reinterpret_cast<uintptr_t>(seq_logp)) & 15) == 0 && (slab_stride % 4 == 0);
     const bool reg_path = partial && splits >= 1 && N > 0 && al && V1 > 0 && V1 % 4 == 0 && V1 <= 3 * 4 * SEL_THREADS &&
                           (!next || !next->x || (next->E && next->Edim > 0 && !(next->x_planes && N > 64)));
-    capmi_gemm::LcCapture cap{};
-    capmi_gemm::g_lc_capture = &cap;
-    const int rc = capmi_gemm_f32(ahead, stream);          // plans the GEMM; launches it only if it is not a loader / consumer GEMM
-    capmi_gemm::g_lc_capture = nullptr;
+    capmi_gemm::Plan p;
+    int rc = capmi_gemm::gemm_plan(ahead, &p);
     if (rc) return rc;
-    const bool fuse = cap.filled && reg_path && cap.tm == 2 && cap.b_layout == 0 && N + cap.grid_x * cap.grid_y <= 256 &&
+    ahead->splits_used = p.splits;
+    // a loader / consumer GEMM (64-row image, [N][K] weights) whose workgroups fit the select grid runs inside the select launch
+    const int gx = capmi_gemm::lc_grid_x(p.a), gy = p.splits;
+    const bool fuse = p.route == capmi_gemm::ROUTE_LC && reg_path && p.a.M > 32 && ahead->b_layout == 0 && N + gx * gy <= 256 &&
                       step >= 0 && step < L && seq && it_next && (no_finish_mask || unfinished) && !(mode == 2 && !forced) &&
                       !(mode == 1 && !(temperature > 0.f)) && top_k >= 0 && top_p >= 0.f && top_p < 1.f && !(top_k > 0 && top_p > 0.f);
     if (!fuse) {
-        if (cap.filled) {                                   // planned but not fusable here: launch it the ordinary way
-            const int rc2 = capmi_gemm_f32(ahead, stream);
-            if (rc2) return rc2;
-        }
+        if ((rc = capmi_gemm::gemm_run(p, ahead, (hipStream_t)stream)) != 0) return rc;
         return capmi_logsoftmax_select_partial(partial, splits, slab_stride, bias, N, V1, step, L, mode_in, row_mode, temperature, gumbel,
                                                seed, forced, forced_ld, no_finish_mask, seq, seq_ld, it_next, unfinished, seq_logp,
                                                sel_logp, live, next, filter, stream);
@@ -663,7 +661,7 @@ int capmi_logsoftmax_select_partial_gemm(const float *partial, int splits, int64
     const SelArgs sa{partial, splits, (size_t)slab_stride, bias, V1, step, L, mode, row_mode, temperature, gumbel, seed, forced,
                      forced_ld, no_finish_mask, seq, seq_ld, it_next, unfinished, seq_logp, sel_logp, live, ne, top_k, top_p, 0, raw_out, capmi::rng_epoch()};
     const size_t lds = (size_t)capmi_gemm::LC_NS * capmi_gemm::LC_STAGE + 512;
-    const dim3 grid(N + cap.grid_x * cap.grid_y);
+    const dim3 grid(N + gx * gy);
 #define CAPMI_FUSED(NQ)                                                                                                     \
     do {                                                                                                                    \
         static bool set = false;                                                                                            \
@@ -672,14 +670,14 @@ int capmi_logsoftmax_select_partial_gemm(const float *partial, int splits, int64
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                              \
             set = true;                                                                                                     \
         }                                                                                                                   \
-        hipLaunchKernelGGL(select_gemm_kernel<NQ>, grid, dim3(SEL_THREADS), lds, (hipStream_t)stream, sa, cap.a, N, cap.grid_x, \
-                           cap.grid_y);                                                                                     \
+        hipLaunchKernelGGL(select_gemm_kernel<NQ>, grid, dim3(SEL_THREADS), lds, (hipStream_t)stream, sa, p.a, N, gx, gy);   \
     } while (0)
     if (V1 <= 4 * SEL_THREADS) CAPMI_FUSED(1);
     else if (V1 <= 8 * SEL_THREADS) CAPMI_FUSED(2);
     else CAPMI_FUSED(3);
 #undef CAPMI_FUSED
     CAPMI_CHECK_LAUNCH();
+    capmi_gemm::gemm_census(ahead, p);
     return 0;
 }
 

@@ -52,14 +52,14 @@ def default_workspace(device):
 
 def gemm(segs, M, N, out, ldc=None, a_layout=0, b_layout=0, bias=None, bias2=None, row_bias=None, row_bias_div=1,
          mul_mask=None, relu=False, accumulate=False, ws=None, splits=0, defer_reduce=False, a_planes=None, addend=None, stream=None,
-         allow_wide=False, b_cols=None):
+         allow_wide=False, b_cols=None, desc_only=False):
     """segs: list of (A, lda, B, ldb, K, a_row_div) with tensors (or (tensor, element_offset) pairs).
     b_cols: optional list of up to 3 (B, ldb, ncol) column segments of a [K][N] B that stay where they are (capmi_gemm_desc.n_bcol;
     one K segment with A planes, M <= 64); the segment's own B may then be None.
     a_planes: optional list (one uint8 tensor per segment, see planes_from_f32) -- the activations also delivered pre-split,
     staged by LDS-DMA in the M <= 64 decode kernel.
     addend: out = addend + epilogue(...) (a residual stream added without copying it into `out` first; row pitch ldc).
-    Returns splits_used."""
+    Returns splits_used; desc_only: nothing is called, returns the filled capmi_gemm_desc (what gemm_plan takes)."""
     d = _lib.GemmDesc()
     d.nseg = len(segs)
     if a_planes is not None:
@@ -87,8 +87,18 @@ def gemm(segs, M, N, out, ldc=None, a_layout=0, b_layout=0, bias=None, bias2=Non
         d.n_bcol = len(b_cols)
         for i, (B, ldb, ncol) in enumerate(b_cols):
             d.bcol_B[i], d.bcol_ldb[i], d.bcol_n[i] = _addr(B), ldb, ncol
+    if desc_only:
+        return d
     check(lib.capmi_gemm_f32(C.byref(d), stream_ptr() if stream is None else stream), 'capmi_gemm_f32')
     return d.splits_used
+
+
+def gemm_plan(d):
+    """(route, splits, epi) that capmi_gemm_f32 would take for the descriptor d (capmi.h capmi_gemm_plan): nothing is launched and no
+    device is needed"""
+    route, epi, splits = C.c_char_p(), C.c_char_p(), C.c_int()
+    check(lib.capmi_gemm_plan(C.byref(d), C.byref(route), C.byref(splits), C.byref(epi)), 'capmi_gemm_plan')
+    return route.value.decode(), splits.value, epi.value.decode()
 
 
 _zero_planes = {}
@@ -305,8 +315,7 @@ class DeferredGrads:
                 self.state['events'] = []
             self.side, self.ev_pool, self.ev_used = self.state['side'], self.state['events'], 0
         # nothing runs beside the deferred GEMMs when there is no side stream: the planner may give them 256 x 128 tiles too -- said
-        # per call (capmi_gemm_desc.allow_wide_deferred; r5 flipped the process-wide capmi_gemm_set_policy flag here, which two live
-        # instances could leave stuck: ADVICE r5)
+        # per call (capmi_gemm_desc.allow_wide_deferred; a process-wide switch could be left stuck by two live instances: ADVICE r5)
         # r6: without a side stream the weight-gradient GEMMs are only RECORDED and go out at flush() as one grouped persistent launch
         # (capmi_gemm_group_tn); CAPMI_DW_GROUP=0 keeps one launch + deferred reduction per GEMM
         self.group = [] if (self.side is None and os.environ.get('CAPMI_DW_GROUP', '1') != '0') else None

@@ -95,8 +95,10 @@ typedef struct capmi_gemm_desc {
      * into C first.  Same row pitch as C; may not overlap C. */
     const float *addend;
     /* r6: with defer_reduce, the caller states PER CALL that nothing runs beside this GEMM on another stream, so the planner may give
-     * it 256 x 128 tiles (a wide workgroup owns its CU; see capmi_gemm_set_policy, whose process-wide flag this replaces for callers
-     * that know -- ops.DeferredGrads without its side stream).  0: the process-wide policy decides. */
+     * it 256 x 128 tiles (ops.DeferredGrads without its side stream).  The fat GEMMs (bf16x3) run on 128 x 128 or 256 x 128 tiles,
+     * whichever the planner costs lower; a 256 x 128 workgroup (16 waves, 144 KB of LDS) owns its CU, so GEMMs whose reduction is
+     * DEFERRED -- the weight gradients a trainer may run on a side stream beside its backward chain (train.py:193 `loss.backward()`
+     * has no such notion: autograd runs them in line) -- are kept on 128 x 128 tiles while this is 0. */
     int allow_wide_deferred;
     /* r7 (b_layout 1, nseg 1, M <= 64 with A planes: the dX GEMMs of a BPTT step): B delivered as n_bcol column segments that stay
      * where they are -- output columns [sum of bcol_n[0..i), + bcol_n[i]) are A [K][bcol_B[i] with row stride bcol_ldb[i]] -- instead
@@ -111,12 +113,12 @@ typedef struct capmi_gemm_desc {
 } capmi_gemm_desc;
 
 int capmi_gemm_f32(capmi_gemm_desc *d, void *stream);
-/* r5 planner policy.  The fat GEMMs (bf16x3) run on 128 x 128 or 256 x 128 tiles, whichever the planner costs lower; a 256 x 128
- * workgroup (16 waves, 144 KB of LDS) owns its CU, so GEMMs whose reduction is DEFERRED -- the weight gradients a trainer may run on
- * a side stream beside its backward chain (train.py:193 `loss.backward()` has no such notion: autograd runs them in line) -- are
- * kept on 128 x 128 tiles unless the caller states that nothing runs beside them: allow_wide_deferred != 0.  Process-wide, returns
- * the previous setting; default 0. */
-int capmi_gemm_set_policy(int allow_wide_deferred);
+/* What capmi_gemm_f32 would do with *d, without doing it: the kernel configuration (*route, one of the CAPMI_GEMM_LOG census names:
+ * lc, ares_x3, ares_x3_half, ares_f32, t32x128, t64x64, t64x128, t128, x3, x3w, x3w_swap), the K split it would report in splits_used
+ * and where the epilogue would be applied (*epi: kernel, reduce or slabs).  Static strings; any out pointer may be NULL.  Host
+ * arithmetic over the descriptor only: nothing is launched, no pointer of *d is dereferenced, *d is not written and no device is
+ * needed.  CAPMI_EINVAL for exactly the descriptors capmi_gemm_f32 refuses. */
+int capmi_gemm_plan(const capmi_gemm_desc *d, const char **route, int *splits, const char **epi);
 
 /* r6: n INDEPENDENT weight-gradient GEMMs in one launch,
  *     C_i [M_i, N_i] (row pitch ldc) (+)= A_i^T B_i,   A_i [K_i, M_i] (pitch lda), B_i [K_i, N_i] (pitch ldb)

@@ -1,6 +1,6 @@
 """float64 restatement of capmi_gemm_f32 (include/capmi.h, "fp32 MFMA GEMM") and the case table that walks every route of its
 dispatcher (csrc/gemm_f32.hip).  Shared by tests/test_gemm_routes_host.py (no GPU), tests/test_gemm_routes_gpu.py and
-tests/gemm_routes_child.py.  Importing this module needs torch only; the package is imported by run_case().
+tests/gemm_routes_child.py.  Importing this module needs torch only; the package is imported by descriptor() and run().
 
 The contract restated by evaluate():
 
@@ -10,7 +10,9 @@ The contract restated by evaluate():
     v = acc + bias[n] + bias2[n] + row_bias[(m // row_bias_div) * N + n];  relu;  v *= mul_mask[m * N + n];
     v += addend[m * ldc + n]   or, with accumulate and no addend, the previous content of C[m * ldc + n]
 
-How the rows reach their routes (restated from the dispatcher; the census test in test_gemm_routes_gpu.py holds them to it).
+How the rows reach their routes: the rules of gemm_plan (csrc/gemm_f32.hip: skinny_ok, plan_lc, plan_ares, plan_tiled), worked out
+for this table.  tests/test_gemm_routes_host.py asks capmi_gemm_plan for every row's route without a GPU; the census test in
+test_gemm_routes_gpu.py holds the launches to it.
 T = sum over segments of ceil(K_s / 32) K tiles, nblk = ceil(N / 128), S = the descriptor's `splits`:
 
   lc        planes for every segment, M <= 64, a_layout 0, every operand 16-byte aligned, K_s % 4 == 0, a_row_div 1 (b_layout 1:
@@ -285,20 +287,55 @@ def measure(out, ref, mag):
     return float(ratio.max())
 
 
-def run_case(c, t, ws):
-    """the call itself, on device tensors t (t['C'] is written).  Returns splits_used."""
+def descriptor(c, buf, planes, ws):
+    """the capmi_gemm_desc of a row, filled by ops.gemm.  buf(key, s=None): the flat buffer of draw()'s t[key] (t[key][s] for the
+    per-segment lists) -- a device tensor, or anything else with a data_ptr(): the planner reads the descriptor only, so an address
+    that nothing dereferences will do; planes: one per segment, or None; ws: an ops.Workspace (or its .buf / .capacity)."""
     from imagecaptioning.pytorch_amd import ops
     M, N, al, bl, e = c['M'], c['N'], c['al'], c['bl'], c['eoff']
-    segs, planes = [], []
+    segs = []
     for s, (K, div) in enumerate(zip(c['Ks'], c['divs'])):
         lda = (K if al == 0 else M) + c['lda_pad']
         ldb = (K if bl == 0 else N) + c['ldb_pad']
-        segs.append(((t['A'][s], c['a_off']), lda, None if c['bcols'] else t['B'][s], ldb, K, div))
-        if c['planes']:
-            planes.append(ops.planes_from_f32(_view(t['A'][s], c['a_off'], M, K, lda)))
-    sl = lambda key, n: t[key][e:e + n] if key in t else None                       # noqa: E731
-    return ops.gemm(segs, M, N, (t['C'], c['c_off']), ldc=c['ldc'], a_layout=al, b_layout=bl, bias=sl('bias', N), bias2=sl('bias2', N),
-                    row_bias=t['row_bias'][e:] if 'row_bias' in t else None, row_bias_div=c['row_bias'] or 1,
-                    mul_mask=sl('mask', M * N), relu=c['relu'], accumulate=c['acc'] == 'C', addend=sl('addend', M * c['ldc']),
-                    ws=ws, splits=c['splits'], defer_reduce=c['defer'], a_planes=planes or None, allow_wide=c['allow_wide'],
-                    b_cols=[(b, n + 4, n) for b, n in zip(t['Bc'], c['bcols'])] if c['bcols'] else None)
+        segs.append(((buf('A', s), c['a_off']), lda, None if c['bcols'] else buf('B', s), ldb, K, div))
+    epi = lambda key, on: Shifted(buf(key), e) if on else None                      # noqa: E731
+    return ops.gemm(segs, M, N, (buf('C'), c['c_off']), ldc=c['ldc'], a_layout=al, b_layout=bl, bias=epi('bias', c['bias']),
+                    bias2=epi('bias2', c['bias2']), row_bias=epi('row_bias', c['row_bias']), row_bias_div=c['row_bias'] or 1,
+                    mul_mask=epi('mask', c['mask']), relu=c['relu'], accumulate=c['acc'] == 'C',
+                    addend=epi('addend', c['acc'] == 'addend'), ws=ws, splits=c['splits'], defer_reduce=c['defer'],
+                    a_planes=planes, allow_wide=c['allow_wide'],
+                    b_cols=[(buf('Bc', i), n + 4, n) for i, n in enumerate(c['bcols'])] if c['bcols'] else None, desc_only=True)
+
+
+class Shifted:
+    """a buffer from its element `off` on (what buf[off:] is for a tensor), for buffers that only have a data_ptr()"""
+
+    def __init__(self, buf, off):
+        self.addr = buf.data_ptr() + 4 * off
+
+    def data_ptr(self):
+        return self.addr
+
+
+def device_descriptor(c, t, ws):
+    """descriptor() on device tensors t, with A planes made from the activations where the row asks for them"""
+    from imagecaptioning.pytorch_amd import ops
+    planes = None
+    if c['planes']:
+        planes = [ops.planes_from_f32(_view(t['A'][s], c['a_off'], c['M'], K, K + c['lda_pad'])) for s, K in enumerate(c['Ks'])]
+    d = descriptor(c, lambda key, s=None: t[key] if s is None else t[key][s], planes, ws)
+    d.keep = planes                   # (the descriptor holds addresses only)
+    return d
+
+
+def run(d):
+    """capmi_gemm_f32 on the current stream (t['C'] is written).  Returns splits_used."""
+    import ctypes
+    from imagecaptioning.pytorch_amd import _lib
+    _lib.check(_lib.lib.capmi_gemm_f32(ctypes.byref(d), _lib.stream_ptr()), 'capmi_gemm_f32')
+    return d.splits_used
+
+
+def run_case(c, t, ws):
+    """the call itself, on device tensors t.  Returns splits_used."""
+    return run(device_descriptor(c, t, ws))

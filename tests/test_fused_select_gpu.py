@@ -120,6 +120,51 @@ def test_fused_launch_is_bit_identical_to_the_two_launches(mode, top_k, top_p):
     assert int(a[0].max()) > 0
 
 
+def test_fused_call_with_a_gemm_that_is_not_loader_consumer_is_the_two_launches():
+    """capmi_logsoftmax_select_partial_gemm with an `ahead` GEMM that has no A planes: the planner gives it the A-resident kernel, the
+    call launches that plan and then the stand-alone select.  Tokens, log-probs and the GEMM's K-slice slabs are the same bits as
+    capmi_gemm_f32 followed by capmi_logsoftmax_select_partial, and splits_used is the same."""
+    import ctypes as C
+    from imagecaptioning.pytorch_amd import ops, _lib
+    from imagecaptioning.pytorch_amd._lib import lib, stream_ptr, check
+    dev = torch.device('cuda:0')
+    g = torch.Generator().manual_seed(5)
+    M, N, K, V1, L, step = 33, 132, 100, 1000, 6, 2
+    logit_slabs = (torch.randn(2, M, V1, generator=g) * 0.7).to(dev)
+    bias = torch.randn(V1, generator=g).to(dev)
+    A, W = torch.randn(M, K, generator=g).to(dev), (torch.randn(N, K, generator=g) * 0.1).to(dev)
+
+    def run(fused):
+        ws = ops.Workspace(dev, floats=4 * M * N)
+        seq = torch.zeros(M, L, dtype=torch.long, device=dev)
+        it = torch.zeros(M, dtype=torch.long, device=dev)
+        unf = torch.ones(M, dtype=torch.uint8, device=dev)
+        slp = torch.zeros(M, L, V1, device=dev)
+        sel = torch.zeros(M, L, device=dev)
+        live = torch.zeros(M, L, dtype=torch.uint8, device=dev)
+        d = ops.gemm([(A, K, W, K, K, 1)], M, N, ws.buf, ws=ws, splits=2, defer_reduce=True, desc_only=True)
+        assert ops.gemm_plan(d) == ('ares_x3', 2, 'slabs')
+        sel_args = (logit_slabs.data_ptr(), 2, M * V1, bias.data_ptr(), M, V1, step, L, 1, None, 1.0, None, 1234, None, 0, 0,
+                    seq.data_ptr(), L, it.data_ptr(), unf.data_ptr(), slp.data_ptr(), sel.data_ptr(), live.data_ptr(), None, None)
+        if fused:
+            check(lib.capmi_logsoftmax_select_partial_gemm(*sel_args, C.byref(d), stream_ptr()), 'fused')
+        else:
+            check(lib.capmi_gemm_f32(C.byref(d), stream_ptr()), 'gemm')
+            check(lib.capmi_logsoftmax_select_partial(*sel_args, stream_ptr()), 'select')
+        torch.cuda.synchronize()
+        sp = int(d.splits_used)
+        return sp, seq[:, step].clone(), slp[:, step].clone(), sel[:, step].clone(), it.clone(), ws.slabs[:sp * M * N].clone()
+
+    a, b = run(True), run(False)
+    assert a[0] == b[0] == 2
+    for x, y in zip(a[1:], b[1:]):
+        assert torch.equal(x, y)
+    assert int(a[1].max()) > 0 and float(a[5].abs().max()) > 0
+    # the slabs sum to the product
+    ref = A.double() @ W.double().t()
+    assert float((a[5].view(2, M, N).double().sum(0) - ref).abs().max()) < 1e-4
+
+
 def test_raw_logit_rollouts_and_a_margin_structure_loss_vs_oracle():
     """VERDICT r3 missing #7 -- AttModel._sample(output_logsoftmax=0) (AttModel.py:171-175, 265; loss_wrapper.py:31-37): the rollout
     stores the LOGITS (CAPMI_SELECT_RAW) and its backward takes the loss gradient as d(logits).  Against oracle/att_lstm.py with the

@@ -47,9 +47,14 @@ def test_gemm_route_vs_float64(dev, ws, name):
     slabs = c['epi'] == 'slabs'
     ref, mag = R.evaluate(c, t, torch.float64, raw=slabs)
     f32, _ = R.evaluate(c, t, torch.float32, raw=slabs)
-    splits = R.run_case(c, t, ws)
+    from imagecaptioning.pytorch_amd import ops
+    d = R.device_descriptor(c, t, ws)
+    plan = ops.gemm_plan(d)
+    splits = R.run(d)
     torch.cuda.synchronize()
     assert 1 <= splits <= R.k_tiles(c)
+    # the planner, asked alone about the same descriptor, says what the call did
+    assert plan == (c['route'], splits, c['epi'])
     # the ticket words in front of the slabs are zero again
     assert int(_bits(ws.buf[:R.COUNTER_FLOATS]).abs().max()) == 0
     after = t['C']

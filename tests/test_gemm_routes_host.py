@@ -1,5 +1,6 @@
 """No GPU: the float64 restatement of capmi_gemm_f32 (tests/gemm_ref64.py) anchored to torch's own float64 linear algebra, the shape
-of the case table, and the descriptors the entry point has to refuse before any launch."""
+of the case table, the descriptors the entry point has to refuse before any launch, and the route the planner (capmi_gemm_plan)
+gives every row of the table."""
 import ctypes as C
 import os
 
@@ -195,8 +196,18 @@ def _bcol_desc(_lib, n_bcol=1, B=FAKE, ldb=8, n=8, **over):
     return d
 
 
+def _plan(_lib, d):
+    """(rc, route, splits, epi) of capmi_gemm_plan"""
+    route, epi, splits = C.c_char_p(), C.c_char_p(), C.c_int(-1)
+    rc = _lib.lib.capmi_gemm_plan(C.byref(d), C.byref(route), C.byref(splits), C.byref(epi))
+    return rc, route.value and route.value.decode(), splits.value, epi.value and epi.value.decode()
+
+
 def _refused(_lib, d):
-    return _lib.lib.capmi_gemm_f32(C.byref(d), None) == _lib.EINVAL
+    """by the call and by the planner alike, and the planner leaves the descriptor as it was"""
+    before = bytes(d)
+    return _plan(_lib, d) == (_lib.EINVAL, None, -1, None) and bytes(d) == before and \
+        _lib.lib.capmi_gemm_f32(C.byref(d), None) == _lib.EINVAL
 
 
 def test_gemm_refuses_bad_descriptors(capmi):
@@ -241,3 +252,46 @@ def test_gemm_refuses_a_deferred_call_whose_slabs_do_not_fit(capmi):
     d = _desc(L, splits=2, defer_reduce=1, partial=FAKE, partial_capacity=R.COUNTER_FLOATS + 8 * 8 - 1)
     assert _refused(L, d)
     assert _refused(L, _desc(L, splits=2, defer_reduce=1))      # no workspace at all
+
+
+# ---- the planner: every row's route, K split and epilogue place from the descriptor alone ---------------------------------------------
+_BUFS = ('A', 'B', 'Bc', 'C', 'bias', 'bias2', 'row_bias', 'mask', 'addend', 'planes', 'ws')
+
+
+class _Fake:
+    """stands where a device tensor would: a 16-byte aligned address per buffer, 16 MB apart, never dereferenced"""
+
+    def __init__(self, key, s=None):
+        self.addr = FAKE + ((_BUFS.index(key) * R.MAX_SEG + (s or 0)) << 24)
+        self.buf, self.capacity = self, R.COUNTER_FLOATS + R.WS_FLOATS          # (as a workspace)
+
+    def data_ptr(self):
+        return self.addr
+
+
+def _fake_desc(c):
+    planes = [_Fake('planes', s) for s in range(len(c['Ks']))] if c['planes'] else None
+    return R.descriptor(c, _Fake, planes, _Fake('ws'))
+
+
+@pytest.mark.parametrize('name', [c['name'] for c in R.CASES])
+def test_plan_gives_every_row_its_route(capmi, name):
+    c = R.BY_NAME[name]
+    d = _fake_desc(c)
+    assert (d.splits, d.defer_reduce, d.allow_wide_deferred) == (c['splits'], int(c['defer']), int(c['allow_wide']))
+    assert all(bool(d.a_planes[s]) == c['planes'] for s in range(d.nseg)) and d.n_bcol == len(c['bcols'] or ())
+    rc, route, splits, epi = _plan(capmi, d)
+    assert rc == 0
+    assert (route, epi) == (c['route'], c['epi'])
+    assert 1 <= splits <= R.k_tiles(c)
+
+
+def test_plan_does_not_write_the_descriptor(capmi):
+    for c in R.CASES:
+        d = _fake_desc(c)
+        d.splits_used = -7
+        before = bytes(d)
+        assert _plan(capmi, d)[0] == 0
+        assert bytes(d) == before and d.splits_used == -7, c['name']
+    # out pointers are optional
+    assert capmi.lib.capmi_gemm_plan(C.byref(d), None, None, None) == 0
