@@ -106,6 +106,9 @@ __global__ __launch_bounds__(SEL_THREADS) void logsoftmax_select_kernel(
 
     // choose
     int token;
+    // prenorm 2 stores what sample_next_word gathers (CaptionModel.py:372, 406): greedy the row's entry, the sampling branches the
+    // TEMPERED entry (x * sel_scale), nucleus the log of the renormalised truncated distribution (:396-398; - sel_shift)
+    float sel_scale = 1.f, sel_shift = 0.f;
     if (my_mode == 2) {
         token = (int)forced[(size_t)r * forced_ld + step];
     } else {
@@ -114,6 +117,7 @@ __global__ __launch_bounds__(SEL_THREADS) void logsoftmax_select_kernel(
             for (int v = threadIdx.x; v < V1; v += blockDim.x) best = better(best, ArgMax{x[v], v});
         } else {
             const float invT = 1.f / temperature;
+            sel_scale = invT;
             // top-k / nucleus threshold: same radix descent as the register-resident kernel (see there)
             uint32_t thr_key = 0;
             if (top_k > 0 || top_p > 0.f) {
@@ -140,6 +144,15 @@ __global__ __launch_bounds__(SEL_THREADS) void logsoftmax_select_kernel(
                     if (top_k > 0 ? acc >= (float)top_k : acc >= top_p) cur = cand;
                 }
                 thr_key = top_k > 0 ? cur : cur + 1;
+                if (prenorm == 2 && top_p > 0.f) {     // log of the kept mass: the truncated distribution's normaliser
+                    float km = 0.f;
+                    for (int v = threadIdx.x; v < V1; v += blockDim.x) {
+                        const float xt_ = (x[v] - lse) * invT;
+                        if (order_key(xt_) >= thr_key) km += __expf(xt_ - lse_t);
+                    }
+                    km = block_sum(km, s_f);
+                    sel_shift = lse_t + __logf(km);
+                }
             }
             if (gumbel) {
                 const float *g = gumbel + (size_t)r * V1;
@@ -198,7 +211,7 @@ __global__ __launch_bounds__(SEL_THREADS) void logsoftmax_select_kernel(
         it_next[r] = token;
         // prenorm 2 (AttModel._diverse_sample, AttModel.py:436-447): the log-prob of the token the sampler picked, also
         // for rows that had already finished (their token is overwritten by the pad, the stored value is not)
-        if (sel_logp) sel_logp[(size_t)r * L + step] = prenorm == 2 ? x[chosen] : keep * (x[token] - lse);
+        if (sel_logp) sel_logp[(size_t)r * L + step] = prenorm == 2 ? (x[chosen] - lse) * sel_scale - sel_shift : keep * (x[token] - lse);
         if (live) live[(size_t)r * L + step] = was_unf ? 1 : 0;
         if (!no_finish_mask) unfinished[r] = (was_unf && token != 0) ? 1 : 0;
         // early exit (AttModel.py:349-350): a row that goes on tells the host so (a word of pinned host memory, only ever set)

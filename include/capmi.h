@@ -857,8 +857,10 @@ int capmi_column_penalty(float *logp, int N, int V1, const int64_t *tokens, int 
  * stored as they are times the unfinished flag (AttModel.py:333-347; -inf * 0 = NaN like there).  mode 0 arg-max,
  * 1 Categorical(logits = logp / temperature) with the optional top-k / nucleus filter.  sel_logp [N,L] (optional):
  * the picked token's log-prob times the unfinished flag, or -- sel_unmasked != 0, AttModel._diverse_sample
- * (AttModel.py:436-447) -- the log-prob of the token the sampler picked even for rows that had finished.  Other
- * arguments as in capmi_logsoftmax_select_partial. */
+ * (AttModel.py:436-447) -- sample_next_word's sampleLogprobs of the token the sampler picked, even for rows that had
+ * finished: the row's entry (mode 0), the entry / temperature (mode 1, also under top-k), or under the nucleus filter
+ * the log-prob of the renormalised truncated distribution (CaptionModel.py:396-398, 406).  Other arguments as in
+ * capmi_logsoftmax_select_partial. */
 int capmi_select_logp(const float *logp, int N, int V1, int step, int L, int mode, float temperature, const float *gumbel,
                       uint64_t seed, int64_t *seq, int seq_ld, int64_t *it_next, uint8_t *unfinished, float *seq_logp,
                       float *sel_logp, int sel_unmasked, const capmi_sample_filter *filter, void *stream);
