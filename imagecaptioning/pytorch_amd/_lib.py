@@ -261,6 +261,17 @@ class DivEval(C.Structure):
                                     'self_cider', 'oracle_scores', 'seen', 'err', 'vocab_bits')])
 
 
+SENTSET_NCOUNT, SENTSET_NOUT = 5, 9      # capmi.h CAPMI_SENTSET_*
+
+
+class SentSet(C.Structure):
+    """capmi_sentset (include/capmi.h): the training and the generated sentences as sets in HBM, the counters of sentstats.py"""
+    _fields_ = ([(k, C.c_int) for k in ('n_train', 'train_w', 'train_elem', 'unk_id')] + [('train_rows', c_f), ('train_table', c_f),
+                ('train_cap', C.c_uint32), ('gen_capacity', C.c_int), ('gen_rows', c_f), ('gen_table', c_f), ('gen_cap', C.c_uint32),
+                ('V1', C.c_int), ('vocab_bits', c_f), ('bad', c_f), ('n_bad', C.c_int), ('counts', c_f), ('sums', c_f), ('err', c_f),
+                ('hash_mask', C.c_uint64)])
+
+
 _I, _F, _P, _U64, _I64 = C.c_int, C.c_float, C.c_void_p, C.c_uint64, C.c_int64
 DECODE_NO_REPEAT, DECODE_NO_BAD_ENDING, DECODE_BLOCK_TRIGRAMS = 1, 2, 4      # capmi.h CAPMI_DECODE_*
 SELECT_RAW = 256       # capmi.h CAPMI_SELECT_RAW: OR into the select `mode` -- the stored rows are the logits, not the log-probabilities
@@ -393,6 +404,10 @@ SIGNATURES = {
     'capmi_langeval_reduce': [C.POINTER(LangEval), _P, _P, _P],
     'capmi_diveval_add': [C.POINTER(DivEval), _P, _I, _I, _P, _P],
     'capmi_diveval_reduce': [C.POINTER(DivEval), _P, _P, _P],
+    'capmi_sentset_build': [C.POINTER(SentSet), _P],
+    'capmi_sentset_add': [C.POINTER(SentSet), _P, _I, _I, _I, _P],
+    'capmi_sentset_add_first': [C.POINTER(SentSet), _P, _I, _I, _P, _P, _P],
+    'capmi_sentset_reduce': [C.POINTER(SentSet), _P, _P],
     'capmi_updown_rollout_fwd': [C.POINTER(UpDownWeights), C.POINTER(UpDownRollout), _P],
     'capmi_updown_rollout_bwd': [C.POINTER(UpDownWeights), C.POINTER(UpDownRollout), _P, C.POINTER(UpDownBwdScratch),
                                  C.POINTER(UpDownGrads), _P],

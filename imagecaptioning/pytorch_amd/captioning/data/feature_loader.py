@@ -184,6 +184,14 @@ class FeatureLoader:
         rows = (np.concatenate(parts) if parts else np.zeros((0, self.seq_length))).astype(np.int64)
         return rows, off, ixs
 
+    def training_captions(self):
+        """label rows [M, L] (the file's dtype) of every image whose split is not val / test -- the training sentences of
+        eval_utils.language_eval (eval_utils.py:60): restval is training, whatever train_only says; an image without a split
+        counts too"""
+        parts = [self.label[int(self.label_start_ix[ix]) - 1: int(self.label_end_ix[ix])]
+                 for ix, img in enumerate(self.info['images']) if img.get('split') not in ('val', 'test')]
+        return np.concatenate(parts) if parts else np.zeros((0, self.seq_length), dtype=self.label.dtype)
+
     # ---- one image
     def _image(self, ix):
         return decode_image(self.att_dir, self.fc_dir, self.info['images'][ix]['id'], self.use_fc, self.norm_att_feat)

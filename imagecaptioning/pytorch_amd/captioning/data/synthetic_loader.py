@@ -46,6 +46,11 @@ class SyntheticLoader:
         rows = np.concatenate(self.refs).astype(np.int64)
         return rows, np.arange(n_img + 1, dtype=np.int64) * 5, list(range(n_img))
 
+    def training_captions(self):
+        """rows [M, L] of the training sentences for novel_sentences (eval_utils.py:60): the references of the train images --
+        every split of the synthetic corpus holds the same images, so all of them"""
+        return np.concatenate(self.refs)
+
     def reset_iterator(self, split):
         """DataLoader.reset_iterator (dataloader.py:356-358)"""
         self.pos[split] = 0

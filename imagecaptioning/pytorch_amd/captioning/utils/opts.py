@@ -32,6 +32,9 @@ DEFAULTS = dict(
     language_eval=0, eval_results_dir='eval_results',
     # opts.py:331 eval_oracle: with language_eval and sample_n > 1, also oracle_X / avg_X over the sample_n captions (diveval.py)
     eval_oracle=1,
+    # eval_utils.py:27-36, 55-68, 79-80, 121: with language_eval, also bad_count_rate and the mean perplexity / entropy and, with
+    # sample_n > 1, novel_sentences and vocab_size, counted on the device (imagecaptioning/pytorch_amd/sentstats.py)
+    sentence_stats=0,
     # data (synthetic only: the reference's h5/lmdb loaders are outside the hot path)
     input_synthetic=1, vocab_size=9487, synthetic_regions=36, synthetic_images=200,
     # real precomputed features (captioning/data/feature_loader.py; opts.py:23-37 of the reference)

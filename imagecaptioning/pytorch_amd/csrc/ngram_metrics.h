@@ -76,12 +76,14 @@ __device__ __forceinline__ int caption_len(int t, int w, int lane) {
 }
 
 // The token conventions.  load: one token of a row (0 beyond its width); KEEP_EOS: see caption_len.
-// Evaluation: int64 rows; an id the 16-bit key fields cannot hold is reported in *err and ends the caption.
+// Evaluation: int64 rows (the label file's uint32 for the training captions of sentset.hip); an id the 16-bit key fields cannot
+// hold is reported in *err and ends the caption.
 struct EvalTokens {
     static constexpr bool KEEP_EOS = false;
     int32_t *err;
-    __device__ __forceinline__ int load(const int64_t *row, int w, int lane) const {
-        const int64_t t = lane < w ? row[lane] : 0;
+    template <typename T>
+    __device__ __forceinline__ int load(const T *row, int w, int lane) const {
+        const int64_t t = lane < w ? (int64_t)row[lane] : 0;
         if (t < 0 || t >= 65535) {
             atomicOr(err, CAPMI_LANGEVAL_E_TOKEN);
             return 0;

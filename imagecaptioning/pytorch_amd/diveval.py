@@ -2,7 +2,7 @@
 
 Replaces captioning/utils/eval_multi.py behind eval_utils.language_eval (eval_utils.py:104-119): eval_div_stats (Div1, Div2, gDiv1
 of div_utils.py, mBLeu_1..4), eval_self_cider (Wang & Chan 2019) and eval_oracle (oracle_X / avg_X for the Java-free X).  AllSPICE
-needs Java and is absent; novel_sentences needs the training captions as strings and is absent.  div_utils.py is pinned by
+needs Java and is absent; novel_sentences and vocab_size are sentstats.py's.  div_utils.py is pinned by
 tests/golden/diveval_ref.npz; the mBLEU and self-CIDEr arithmetic is PARITY UNPINNED, as langeval.py: coco-caption and the cider
 submodule are not part of the reference checkout, the formulas are restated in tests/diveval_ref64.py.  Captions are compared as
 the label vocabulary's ids, a caption being the ids of its row before the first 0.

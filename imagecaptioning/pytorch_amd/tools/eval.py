@@ -7,7 +7,10 @@ CIDEr, BLEU-1..4 and ROUGE-L of the single-caption pass, scored on the device ov
 and written to <eval_results_dir>/<id>_<split>.json as {'overall', 'imgToEval'}; METEOR and SPICE need Java and are absent.
 With --sample_n N > 1 the N captions per image are also scored for diversity on the device (captioning/utils/eval_multi.py ->
 imagecaptioning/pytorch_amd/diveval.py): Div1, Div2, gDiv1, mBLeu_1..4, self_cider and, with --eval_oracle 1, oracle_X / avg_X; they
-join lang_stats and are written to <id>_<split>_n.json.  AllSPICE (Java) and novel_sentences (training captions as strings) are absent.
+join lang_stats and are written to <id>_<split>_n.json.  AllSPICE needs Java and is absent.
+--sentence_stats 1 adds the counting numbers of eval_utils.language_eval (:27-36, 55-68, 79-80, 121) to lang_stats and to
+<id>_<split>.json: bad_count_rate and the mean perplexity / entropy of the first captions and, with --sample_n N > 1, novel_sentences
+and vocab_size of the N captions per image against the training captions of the label file (imagecaptioning/pytorch_amd/sentstats.py).
 
     python -m imagecaptioning.pytorch_amd.tools.eval --caption_model updown --beam_size 5 --num_images 20 [--start_from DIR]
 """
@@ -91,6 +94,10 @@ def eval_split(model, crit, loader, opt):
     if lang is not None and opt.sample_n > 1:
         from imagecaptioning.pytorch_amd.diveval import DiversityEval
         div = DiversityEval(lang, opt.sample_n, oracle=bool(getattr(opt, 'eval_oracle', 0)))
+    sent = None
+    if lang is not None and getattr(opt, 'sentence_stats', 0):
+        from imagecaptioning.pytorch_amd.sentstats import SentenceStats
+        sent = SentenceStats.for_loader(loader, split, dev, model, opt.sample_n)
     if hasattr(loader, 'reset_iterator'):
         loader.reset_iterator(split)                                                                           # eval_utils.py:145
     num_images = opt.num_images
@@ -129,6 +136,8 @@ def eval_split(model, crit, loader, opt):
             # stay on the device, nothing is read back before lang.compute()
             keep = max(0, min(len(data['infos']), num_images - n))
             lang.add_batch(data['infos'][:keep], seq[::rows_per_image][:keep])
+            if sent is not None:
+                sent.add_first(seq[::rows_per_image][:keep], perplexity[::rows_per_image][:keep], entropy[::rows_per_image][:keep])
         for k, s in enumerate(sents):
             preds.append({'image_id': data['infos'][k // rows_per_image]['id'], 'caption': s, 'perplexity': perplexity[k].item(),
                           'entropy': entropy[k].item()})
@@ -137,6 +146,8 @@ def eval_split(model, crit, loader, opt):
             rows = eval_split_n(model, n_preds, fc, att, att_masks, data, opt)                                # :198
             if div is not None:          # the same cut at num_images as the single-caption pass; the rows stay on the device
                 div.add_batch(data['infos'][:keep], rows[:keep])
+                if sent is not None:
+                    sent.add(rows[:keep])
                 groups += [(data['infos'][k]['id'], n_preds[first + k * opt.sample_n:first + (k + 1) * opt.sample_n])
                            for k in range(keep)]
         n += len(data['infos'])
@@ -146,17 +157,20 @@ def eval_split(model, crit, loader, opt):
     model.train()                                                                                              # :224-225
     preds = preds[:num_images * max(1, len(preds) // max(n, 1))]
     if lang is not None:
-        lang_stats = language_eval(lang, preds, opt, split)
+        lang_stats = language_eval(lang, preds, opt, split, sent)
         if div is not None:
             lang_stats.update(language_eval_n(div, groups, opt, split))
         return loss_sum / max(loss_n, 1), preds, lang_stats
     return loss_sum / max(loss_n, 1), preds
 
 
-def language_eval(lang, preds, opt, split):
+def language_eval(lang, preds, opt, split, sent=None):
     """eval_utils.language_eval (:47-125) for the Java-free scorers: lang_stats = {'Bleu_1'..'Bleu_4', 'ROUGE_L', 'CIDEr'}, written
-    with the per-image CIDEr and caption as {'overall', 'imgToEval'} to <eval_results_dir>/<id>_<split>.json (:122-124)."""
+    with the per-image CIDEr and caption as {'overall', 'imgToEval'} to <eval_results_dir>/<id>_<split>.json (:122-124).  sent: a
+    sentstats.SentenceStats of the same rows; its numbers join lang_stats before the file is written."""
     lang_stats, img_cider = lang.compute()
+    if sent is not None:
+        lang_stats.update(sent.compute())
     img_to_eval = {}
     for p in preds:                                            # one entry per image: the first caption, the one that was scored
         pos = lang.pos_of_id.get(p['image_id'])

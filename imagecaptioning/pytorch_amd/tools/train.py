@@ -21,14 +21,15 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))           # so that `captioning` resolves to the mirror package
 
 
-def validation_loss(lw_model, loader, opt, dev, world=1, lang=None):
+def validation_loss(lw_model, loader, opt, dev, world=1, lang=None, sent=None):
     """XE loss over `val_images` images of the val split, teacher forced, eval mode (eval_utils.py:150-160).  With `world`
     data-parallel ranks the val split is partitioned like the train split: each rank scores at most its share
     (val_images / world, never more than its partition holds) and returns (sum of per-image losses, images) so that the caller
     can all-reduce BOTH and every image counts once, whatever the partition sizes.  A rank whose partition is empty (val split
     smaller than world) contributes (0, 0).
     lang: a langeval.LanguageEval of the val split -- every batch is also decoded with the command line's sampler options (the
-    reference hands vars(opt) to eval_split, tools/train.py:246-250) and its rows are scored where they are, on the device."""
+    reference hands vars(opt) to eval_split, tools/train.py:246-250) and its rows are scored where they are, on the device.
+    sent: a sentstats.SentenceStats -- the same rows also count for bad_count_rate and the mean perplexity / entropy."""
     from captioning.data.feature_loader import EmptySplit
     model = lw_model.model
     model.eval()
@@ -56,8 +57,16 @@ def validation_loss(lw_model, loader, opt, dev, world=1, lang=None):
                 from imagecaptioning.pytorch_amd.tools.eval import eval_kwargs_of
                 kw = eval_kwargs_of(opt)
                 kw['sample_n'] = 1                          # eval_utils.py:169-170
-                seq, _ = model(fc, att, att_masks, mode='sample', opt=kw)
-                lang.add_batch(data['infos'], seq[::max(1, seq.shape[0] // len(data['infos']))])
+                seq, seq_logp = model(fc, att, att_masks, mode='sample', opt=kw)
+                step = max(1, seq.shape[0] // len(data['infos']))
+                lang.add_batch(data['infos'], seq[::step])
+                if sent is not None:
+                    if seq_logp.dim() == 3:                 # eval_utils.py:173-174, as tools/eval.py
+                        from imagecaptioning.pytorch_amd import ops
+                        entropy, perplexity = ops.caption_stats(seq_logp.contiguous(), seq.contiguous())
+                    else:
+                        entropy = perplexity = torch.full((seq.shape[0],), float('nan'))
+                    sent.add_first(seq[::step], perplexity[::step], entropy[::step])
     model.train()
     return tot, n
 
@@ -173,7 +182,7 @@ def train(opt):
 
     # language_eval (tools/train.py:246-266): rank 0 decodes and scores ITS part of the val split; the references -- hence the
     # document frequencies -- are the whole split's.  Built at the first validation.
-    lang = None
+    lang = sent = None
     iter_times = []
     loss_slots = [(torch.empty(1, dtype=torch.float32, pin_memory=True), torch.cuda.Event()) for _ in range(2)]
     prev_slot = None
@@ -267,9 +276,15 @@ def train(opt):
                 from imagecaptioning.pytorch_amd.langeval import LanguageEval
                 lang = lang or LanguageEval.for_loader(loader, 'val', dev)
                 lang.reset()
-            val_sum, val_n = validation_loss(lw_model, loader, opt, dev, world, lang)  # eval_utils.eval_split's loss half (:228-256)
+                if getattr(opt, 'sentence_stats', 0):    # the single-caption numbers of eval_utils.language_eval (:79-80, 121)
+                    from imagecaptioning.pytorch_amd.sentstats import SentenceStats
+                    sent = sent or SentenceStats.for_loader(loader, 'val', dev, model, 1)
+                    sent.reset()
+            val_sum, val_n = validation_loss(lw_model, loader, opt, dev, world, lang, sent)  # eval_utils.eval_split's loss half (:228-256)
             if lang is not None:
                 lang_stats = lang.compute()[0]
+                if sent is not None:
+                    lang_stats.update(sent.compute())
             if world > 1 and getattr(opt, 'language_eval', 0):
                 # no collective of its own: rank 0's CIDEr rides in the reduction of the loss (the other ranks add 0), so that every
                 # rank steps the plateau schedule on the same number

@@ -1466,6 +1466,65 @@ typedef struct capmi_diveval {
 int capmi_diveval_add(const capmi_diveval *d, const int64_t *hyp, int B, int L, const int64_t *img_idx, void *stream);
 int capmi_diveval_reduce(const capmi_diveval *d, double *out, int64_t *totals, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Sentence statistics of eval_utils.language_eval (eval_utils.py:27-36, 55-68, 79-80, 121): novel_sentences, vocab_size,
+ * bad_count_rate and the mean perplexity / entropy, counted over token-id rows.  A SENTENCE is the tokens of a row before its
+ * first 0 (all of them when it holds none); what follows the first 0 is ignored.  Rows are at most CAPMI_LANGEVAL_LMAX wide, ids
+ * below 65535 (and, for generated rows, below V1).
+ *
+ * Two sets of sentences live in HBM as open-addressing tables of 64-bit words: the low 32 bits name a row (index + 1; 0 = empty
+ * slot), the high 32 bits are the high half of the sentence's hash.  Membership is exact: a probe that meets an equal hash half
+ * compares the tokens of the named row and goes on probing when they differ.  One wave per row, lane i holds token i.
+ * hash = mix64(sum_i mix64((i + 1) << 16 | (token_i + 1)) + length) & hash_mask; hash_mask is ~0 in production (a test narrows
+ * it to make unequal sentences collide).
+ *
+ * capmi_sentset_build: one launch, once per run.  train_rows [n_train, train_w] (int64 when train_elem == 8, uint32 when 4,
+ *   zero-padded); every sentence that does not contain unk_id (unk_id <= 0: none is skipped) is inserted into train_table
+ *   [train_cap] (zeroed by the caller, a power of two).  A duplicate finds its twin and takes no slot.
+ * capmi_sentset_add: two launches.  seqs [rows, L] int64 on the device, the captions of one decoded batch; base_row: where the
+ *   batch goes in gen_rows [gen_capacity, CAPMI_LANGEVAL_LMAX] (uint16, canonical: zero from the end of the sentence on).
+ *   (1) stores the canonical rows and sets the bits of their tokens in vocab_bits [(V1 + 31) / 32] (token 0 excluded).
+ *   (2) inserts every row into gen_table [gen_cap] with atomicCAS on the slot word: of equal sentences in flight exactly one
+ *   wave sees the empty slot (the CAS returns 0) and counts; the others read the winner's word, find the winner's tokens in
+ *   gen_rows -- stored by launch (1), hence in memory -- and leave.  The winner looks the sentence up in train_table; it is novel
+ *   when it is missing there or contains unk_id.  counts [CAPMI_SENTSET_NCOUNT] (uint64): rows seen, distinct generated
+ *   sentences, distinct generated sentences that are novel, rows of the single-caption pass, those that end in a bad ending.
+ *   None depends on the order of arrival.
+ * capmi_sentset_add_first: one launch, one workgroup, the single-caption pass: seq [rows, L] int64; counts the rows and the
+ *   rows whose last token is in bad [n_bad] (an empty row counts 0); adds perplexity [rows] / entropy [rows] (float32, device) to
+ *   sums [2] in double: thread t sums rows t, t + 256, ..., then the 256 partial sums in index order.
+ * capmi_sentset_reduce: one launch: out [CAPMI_SENTSET_NOUT] = the five counts, popcount of vocab_bits, sum of perplexity, sum
+ *   of entropy, error bits.
+ * err [1] collects CAPMI_LANGEVAL_E_TABLE_FULL (either table) and CAPMI_LANGEVAL_E_TOKEN.  Calls only enqueue.  CAPMI_EINVAL: a
+ * NULL pointer, a width outside 1..CAPMI_LANGEVAL_LMAX, a table size that is no power of two, train_elem not 4 or 8, V1 outside
+ * 1..65536, rows beyond gen_capacity.  rows == 0: success, nothing launched.
+ * ------------------------------------------------------------------------------------------- */
+#define CAPMI_SENTSET_NCOUNT 5
+#define CAPMI_SENTSET_NOUT 9
+typedef struct capmi_sentset {
+    int n_train, train_w, train_elem, unk_id;
+    const void *train_rows;                  /* [n_train, train_w]; may be NULL when n_train == 0 */
+    uint64_t *train_table;                   /* [train_cap] */
+    uint32_t train_cap;
+    int gen_capacity;
+    uint16_t *gen_rows;                      /* [gen_capacity, CAPMI_LANGEVAL_LMAX]; may be NULL when gen_capacity == 0 */
+    uint64_t *gen_table;                     /* [gen_cap] */
+    uint32_t gen_cap;
+    int V1;
+    uint32_t *vocab_bits;                    /* [(V1 + 31) / 32] */
+    const int64_t *bad;                      /* [n_bad]; may be NULL when n_bad == 0 */
+    int n_bad;
+    uint64_t *counts;                        /* [CAPMI_SENTSET_NCOUNT] */
+    double *sums;                            /* [2] perplexity, entropy */
+    int32_t *err;                            /* [1] */
+    uint64_t hash_mask;
+} capmi_sentset;
+int capmi_sentset_build(const capmi_sentset *s, void *stream);
+int capmi_sentset_add(const capmi_sentset *s, const int64_t *seqs, int rows, int L, int base_row, void *stream);
+int capmi_sentset_add_first(const capmi_sentset *s, const int64_t *seq, int rows, int L, const float *perplexity,
+                            const float *entropy, void *stream);
+int capmi_sentset_reduce(const capmi_sentset *s, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
