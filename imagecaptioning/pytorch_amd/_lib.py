@@ -147,6 +147,15 @@ class StepState(C.Structure):
                 ('reserved', C.c_float * 2)]
 
 
+class OptimHp(C.Structure):
+    """capmi_optim_hp (include/capmi.h): rule and hyper-parameters of capmi_optim_step / capmi_optim_step_dyn"""
+    _fields_ = [('rule', C.c_int32), ('alpha', C.c_float), ('beta', C.c_float), ('eps', C.c_float), ('weight_decay', C.c_float),
+                ('clip', C.c_float), ('grad_scale', C.c_float)]
+
+
+OPTIM_RMSPROP, OPTIM_ADAGRAD, OPTIM_SGDM, OPTIM_SGDMOM, OPTIM_ADAMW = 1, 2, 3, 4, 5        # capmi.h CAPMI_OPTIM_*
+
+
 class NewFCBwdScratch(C.Structure):
     _fields_ = ([(k, c_f) for k in ('dlogits', 'd_hdrop', 'd_sums', 'dh_prev', 'dc', 'd_x_all', 'd_ximg', 'partial')] +
                 [('partial_capacity', C.c_int64), ('sparse', C.POINTER(SparseLogpGrad))])
@@ -328,6 +337,8 @@ SIGNATURES = {
     'capmi_step_set_lr': [_P, _F, _P],
     'capmi_rng_bind_epoch': [_P, _P],
     'capmi_adam_step_dyn': [_P, _P, _P, _P, _I64, _P, _F, _F, _F, _F, _F, _F, _P],
+    'capmi_optim_step': [C.POINTER(OptimHp), _P, _P, _P, _P, _I64, _F, _I, _P],
+    'capmi_optim_step_dyn': [C.POINTER(OptimHp), _P, _P, _P, _P, _I64, _P, _P],
     'capmi_ciderd_score': [_P, _I, _I, _P, _P, _P, _I, _I, _P, _P, C.c_uint32, C.c_double, _P, _P],
     'capmi_ciderd_cook_refs': [_P, _P, _I, _I, _I, _P, _P, C.c_uint32, C.c_double, _P, _P],
     'capmi_ciderd_score_cooked': [_P, _I, _I, _P, _P, _P, _I, _P, _P, C.c_uint32, C.c_double, _P, _P],

@@ -73,10 +73,10 @@ class CaptionModel(nn.Module):
     def _params(self):
         return {k: v.detach() for k, v in self._named_param_list()}
 
-    def flatten_parameters_(self):
-        """Move all parameters into one flat buffer (+ flat grads, Adam state).  Call after .cuda()."""
+    def flatten_parameters_(self, rule='adam'):
+        """Move all parameters into one flat buffer (+ flat grads, the optimizer state of `rule`).  Call after .cuda()."""
         from imagecaptioning.pytorch_amd.flat import FlatParams
-        self._flat = FlatParams(self)
+        self._flat = FlatParams(self, rule)
         return self._flat
 
     def _grad_targets(self, P):

@@ -66,8 +66,31 @@ def load_optimizer_state(start_from):
     return torch.load(path, map_location='cpu', weights_only=False) if os.path.isfile(path) else None
 
 
+def build_optimizer(opt):
+    """misc.py:114-130 build_optimizer for the fused flat-buffer step: which rule `opt.optim` names and which of the command line's
+    numbers that rule receives, exactly as the reference hands them to the torch.optim constructors.  Returns
+    {'rule', 'betas', 'eps', 'weight_decay'} -- `rule` for flat.FlatParams, the rest for its step methods; `betas` is
+    (optim_alpha, optim_beta): alpha is RMSprop's smoothing constant and SGD's momentum, Adam / AdamW take both.
+      rmsprop  RMSprop(lr, alpha=optim_alpha, eps=optim_epsilon, weight_decay)
+      adagrad  Adagrad(lr, weight_decay)                       -- torch's default eps 1e-10, optim_epsilon is NOT passed
+      sgdm     SGD(lr, momentum=optim_alpha, weight_decay)
+      sgdmom   SGD(lr, momentum=optim_alpha, weight_decay, nesterov=True)
+      adam     Adam(lr, (optim_alpha, optim_beta), optim_epsilon, weight_decay)
+      adamw    AdamW(lr, (optim_alpha, optim_beta), optim_epsilon, weight_decay)
+    Plain `sgd` (no momentum, no state) has no fused kernel and raises NotImplementedError; any other name is the reference's error."""
+    name = getattr(opt, 'optim', 'adam')
+    if name == 'sgd':
+        raise NotImplementedError("optim 'sgd': plain SGD without momentum is not implemented on the fused flat-buffer step "
+                                  "(rmsprop, adagrad, sgdm, sgdmom, adam and adamw are)")
+    if name not in ('rmsprop', 'adagrad', 'sgdm', 'sgdmom', 'adam', 'adamw'):
+        raise Exception('bad option opt.optim: {}'.format(name))
+    alpha, beta = getattr(opt, 'optim_alpha', 0.9), getattr(opt, 'optim_beta', 0.999)
+    eps = 1e-10 if name == 'adagrad' else getattr(opt, 'optim_epsilon', 1e-8)
+    return {'rule': name, 'betas': (alpha, beta), 'eps': eps, 'weight_decay': getattr(opt, 'weight_decay', 0.0)}
+
+
 class LRSchedule:
-    """Host-side learning-rate policy of the reference's training loop, for the fused clip+Adam step on the flat buffer
+    """Host-side learning-rate policy of the reference's training loop, for the fused clip+update step on the flat buffer
     (which takes the rate as a launch argument, so no torch optimizer object is involved):
       * epoch-wise exponential decay            tools/train.py:134-141  (learning_rate_decay_start/every/rate)
       * linear warm-up                          tools/train.py:171-173  (use_warmup, noamopt_warmup)

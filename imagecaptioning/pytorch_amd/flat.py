@@ -1,7 +1,8 @@
 """Flat parameter / gradient storage.
 
 All parameters of a model live in ONE contiguous fp32 device buffer and all gradients in another:
-  * the optimizer step is one fused clip+Adam launch over the flat buffer (capmi_adam_step);
+  * the optimizer step is one fused clip+update launch over the flat buffer (capmi_adam_step; capmi_optim_step for the other
+    rules of misc.build_optimizer);
   * data-parallel training moves the gradient with a SINGLE RCCL all-reduce per step,
     instead of nn.DataParallel's per-step parameter broadcast + gradient reduce (train.py:86-88);
   * the BPTT kernels write gradients straight into views of the flat buffer.
@@ -11,9 +12,19 @@ import torch
 
 from . import ops
 
+# the state buffers of every rule, under the key names the matching torch.optim class uses in its state_dict
+STATE_KEYS = {'adam': ('exp_avg', 'exp_avg_sq'), 'adamw': ('exp_avg', 'exp_avg_sq'), 'rmsprop': ('square_avg',), 'adagrad': ('sum',),
+              'sgdm': ('momentum_buffer',), 'sgdmom': ('momentum_buffer',)}
+
 
 class FlatParams:
-    def __init__(self, module):
+    def __init__(self, module, rule='adam'):
+        """rule: the update the step methods run -- 'adam' (capmi_adam_step) or one of capmi_optim_step's: 'rmsprop', 'adagrad',
+        'sgdm', 'sgdmom', 'adamw'.  Every state buffer is an attribute named like torch.optim's state key (STATE_KEYS)."""
+        if rule not in STATE_KEYS:
+            raise ValueError('no fused flat-buffer step for optimizer %r (one of %s)' % (rule, sorted(STATE_KEYS)))
+        self.rule = rule
+        self.state_keys = STATE_KEYS[rule]
         params = [(n, p) for n, p in module.named_parameters()]
         if not params:
             raise ValueError('module has no parameters')
@@ -55,8 +66,8 @@ class FlatParams:
             p.data = view
             self.grad_views[n] = self.grad[o:o + p.numel()].view_as(p)
         self._view_ptrs = [self.grad_views[n].data_ptr() for n in self.names]       # (collect_grads)
-        self.exp_avg = torch.zeros_like(self.flat)
-        self.exp_avg_sq = torch.zeros_like(self.flat)
+        for k in self.state_keys:                    # one buffer for the one-state rules: Adam's second one is never allocated
+            setattr(self, k, torch.zeros_like(self.flat))
         self.step_count = 0
         self.on_grads_ready = None      # set by begin_overlap(); native backwards call it per finished bucket
         self._bw_expected, self._bw_seen = 1, 0
@@ -71,34 +82,39 @@ class FlatParams:
         return out
 
     def state_dict(self):
-        return {'exp_avg': self.exp_avg.detach().cpu().clone(), 'exp_avg_sq': self.exp_avg_sq.detach().cpu().clone(),
-                'step_count': int(self.step_count), 'total': int(self.total),
-                'offsets': {n: int(o) for n, o in zip(self.names, self.offsets)}}      # r4: the layout the moments were saved in
+        sd = {k: getattr(self, k).detach().cpu().clone() for k in self.state_keys}
+        sd.update({'rule': self.rule, 'step_count': int(self.step_count), 'total': int(self.total),
+                   'offsets': {n: int(o) for n, o in zip(self.names, self.offsets)}})  # r4: the layout the moments were saved in
+        return sd
 
     def load_state_dict(self, sd):
+        theirs_rule = sd.get('rule', 'adam')                        # (no rule: written before the other rules existed)
+        if theirs_rule != self.rule:
+            raise ValueError('optimizer state was saved under optimizer %r, this run uses %r: resume with --optim %s or start '
+                             'without the optimizer state' % (theirs_rule, self.rule, theirs_rule))
         if int(sd['total']) != self.total:
             raise ValueError('optimizer state is for %d flat elements, the model has %d' % (int(sd['total']), self.total))
         mine = {n: int(o) for n, o in zip(self.names, self.offsets)}
         theirs = sd.get('offsets') or self._natural_offsets()       # (no table: a checkpoint of rounds 1-3, natural order)
         if theirs == mine:
-            self.exp_avg.copy_(sd['exp_avg'])
-            self.exp_avg_sq.copy_(sd['exp_avg_sq'])
+            for key in self.state_keys:
+                getattr(self, key).copy_(sd[key])
         else:
             # the buffer layout changed (r4 lays out a model's _flat_groups() back to back): move every parameter's moments by NAME
             if set(theirs) != set(mine):
                 raise ValueError('optimizer state names do not match this model: %s' % sorted(set(theirs) ^ set(mine))[:4])
-            ea, es = sd['exp_avg'], sd['exp_avg_sq']
             for n, p in zip(self.names, self.params):
                 k, a, b = p.numel(), theirs[n], mine[n]
-                self.exp_avg[b:b + k].copy_(ea[a:a + k])
-                self.exp_avg_sq[b:b + k].copy_(es[a:a + k])
+                for key in self.state_keys:
+                    getattr(self, key)[b:b + k].copy_(sd[key][a:a + k])
         self.step_count = int(sd['step_count'])
 
     def load_torch_adam_state(self, sd):
         """The reference's optimizer.pth is ``torch.optim.Adam(model.parameters()).state_dict()`` (misc.py:87-102, :112-130):
         {'state': {index: {'step', 'exp_avg', 'exp_avg_sq'}}, 'param_groups': [{'params': [index, ...], ...}]}, indices in the
-        order of ``model.parameters()`` -- the order of this buffer's segments.  Returns False (nothing loaded) when the state
-        does not fit this model."""
+        order of ``model.parameters()`` -- the order of this buffer's segments.  Under another rule the state keys are that torch
+        class's (STATE_KEYS; torch.optim.SGD keeps no 'step': any momentum buffer means the first step is over).  Returns False
+        (nothing loaded) when the state does not fit this model or this rule."""
         try:
             order = [i for g in sd['param_groups'] for i in g['params']]
             state = sd['state']
@@ -111,15 +127,15 @@ class FlatParams:
             st = state.get(i)
             if st is None:                         # a parameter that never received a gradient
                 continue
-            if tuple(st['exp_avg'].shape) != tuple(p.shape):
+            if any(k not in st or tuple(st[k].shape) != tuple(p.shape) for k in self.state_keys):
                 return False
         for i, p, o in zip(order, self.params, self.offsets):
             st = state.get(i)
             if st is None:
                 continue
-            self.exp_avg[o:o + p.numel()].view_as(p).copy_(st['exp_avg'])
-            self.exp_avg_sq[o:o + p.numel()].view_as(p).copy_(st['exp_avg_sq'])
-            steps.append(int(st['step']))
+            for k in self.state_keys:
+                getattr(self, k)[o:o + p.numel()].view_as(p).copy_(st[k])
+            steps.append(int(st['step']) if 'step' in st else 1)
         self.step_count = max(steps) if steps else 0
         return True
 
@@ -232,8 +248,7 @@ class FlatParams:
         ranges = ov['done'][:len(ov['works'])]
         for w, (lo, hi) in zip(ov['works'], ranges):
             w.wait()                                   # stream-side: the compute stream waits for this bucket only
-            ops.adam_step(self.flat[lo:hi], self.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], lr, betas[0],
-                          betas[1], eps, weight_decay, clip_value, scale, self.step_count)
+            self._update(lo, hi, lr, betas, eps, weight_decay, clip_value, scale)
         self.last_collectives = len(ov['works'])
         ov['works'], ov['done'] = [], []
         return scale
@@ -251,7 +266,7 @@ class FlatParams:
         on that shard only (1/G of the 28 B/parameter the optimizer streams), and the updated parameter shards are all-gathered.
         Same wire bytes as a ring all-reduce, but the 0.27 ms Adam pass shrinks by G and no rank ever holds -- or clips --
         anything but averaged gradients.  Elementwise update => identical to all_reduce() + adam_step().
-        `adam`: test hook replacing ops.adam_step (CPU tests have no HIP device)."""
+        `adam`: test hook replacing ops.adam_step -- ops.optim_step under another rule -- (CPU tests have no HIP device)."""
         import torch.distributed as dist
         ws, rank = dist.get_world_size(group), dist.get_rank(group)
         if self.total % (4 * ws):
@@ -263,19 +278,34 @@ class FlatParams:
         except (RuntimeError, NotImplementedError):        # gloo has no reduce-scatter: same result through an all-reduce
             dist.all_reduce(self.grad, op=dist.ReduceOp.SUM, group=group)
         self.step_count += 1
-        (adam or ops.adam_step)(self.flat[lo:hi], self.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], lr, betas[0],
-                                betas[1], eps, weight_decay, clip_value, 1.0 / ws, self.step_count)
+        self._update(lo, hi, lr, betas, eps, weight_decay, clip_value, 1.0 / ws, fn=adam)      # the rank's slice of every state buffer
         try:
             dist.all_gather_into_tensor(self.flat, self.flat[lo:hi], group=group)
         except (RuntimeError, NotImplementedError):
             dist.all_gather([self.flat[r * shard:(r + 1) * shard] for r in range(ws)], self.flat[lo:hi].clone(), group=group)
         return 1.0 / ws
 
+    def _update(self, lo, hi, lr, betas, eps, weight_decay, clip_value, grad_scale, fn=None):
+        """the chosen rule on [lo, hi) of the flat buffer (lo None: all of it), step number self.step_count.  betas: (optim_alpha,
+        optim_beta) as misc.build_optimizer hands them to the rule -- the smoothing constant of rmsprop, the momentum of sgdm /
+        sgdmom, Adam's and AdamW's betas"""
+        bufs = [self.flat, self.grad] + [getattr(self, k) for k in self.state_keys]
+        if lo is not None:
+            bufs = [b[lo:hi] for b in bufs]
+        if self.rule == 'adam':
+            (fn or ops.adam_step)(bufs[0], bufs[1], bufs[2], bufs[3], lr, betas[0], betas[1], eps, weight_decay, clip_value, grad_scale,
+                                  self.step_count)
+        else:
+            (fn or ops.optim_step)(self.rule, bufs[0], bufs[1], bufs[2], bufs[3] if len(bufs) > 3 else None, lr, betas[0], betas[1], eps,
+                                   weight_decay, clip_value, grad_scale, self.step_count)
+
     def adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_value=0.0, grad_scale=1.0):
-        """clip_grad_value_ (train.py:194-195) + Adam (misc.py:125-126) fused, one launch."""
+        """clip_grad_value_ (train.py:194-195) + the optimizer's update (misc.py:114-130; Adam unless the buffer was built with
+        another rule) fused, one launch."""
         self.step_count += 1
-        ops.adam_step(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, lr, betas[0], betas[1], eps, weight_decay,
-                      clip_value, grad_scale, self.step_count)
+        self._update(None, None, lr, betas, eps, weight_decay, clip_value, grad_scale)
+
+    step = adam_step
 
     def zero_grad(self):
         self._bw_seen = 0

@@ -8,7 +8,8 @@ graph costs the host one call and runs the device back to back.
 What a graph would freeze is read from device memory instead (ops.StepState, capmi.h capmi_step_state):
   * the dropout / sampling random streams: every seed-taking kernel offsets its seed argument by the record's `epoch` word while
     the record is bound (capmi_rng_bind_epoch); the model's per-iteration seed sequence restarts at every step, the epoch moves on;
-  * Adam's step count, bias corrections and learning rate (capmi_adam_step_dyn; capmi_step_set_lr when the schedule moves).
+  * Adam's step count, bias corrections and learning rate (capmi_adam_step_dyn; capmi_step_set_lr when the schedule moves) -- for
+    the other optimizers of misc.build_optimizer the same words feed capmi_optim_step_dyn.
 `capmi_step_advance` is the first launch of every iteration.  The STEPPED path of this class runs exactly the same launches under
 the same record, so stepped and captured training produce the same numbers bit for bit (tests/test_graph_step_gpu.py) -- the
 captured path is an issue-side optimisation, not a different computation.
@@ -25,7 +26,7 @@ import sys
 import torch
 
 from . import ops
-from .captioning.utils import rewards
+from .captioning.utils import misc, rewards
 
 TENSOR_KEYS = ('fc_feats', 'att_feats', 'labels', 'masks', 'att_masks')
 
@@ -62,8 +63,17 @@ class TrainStep:
     def _adam(self, scale):
         o = self.opt
         clip = o.grad_clip_value if getattr(o, 'grad_clip_mode', 'value') == 'value' else 0.0
-        ops.adam_step_dyn(self.flat.flat, self.flat.grad, self.flat.exp_avg, self.flat.exp_avg_sq, self.state, o.optim_alpha,
-                          o.optim_beta, o.optim_epsilon, o.weight_decay, clip, scale)
+        f = self.flat
+        if f.rule == 'adam':
+            ops.adam_step_dyn(f.flat, f.grad, f.exp_avg, f.exp_avg_sq, self.state, o.optim_alpha, o.optim_beta, o.optim_epsilon,
+                              o.weight_decay, clip, scale)
+        else:       # the other rules of misc.build_optimizer: the same record carries their rate and step number (capmi_optim_step_dyn)
+            hp = misc.build_optimizer(o)
+            if hp['rule'] != f.rule:
+                raise ValueError('the options name optimizer %r, the flat buffer was built for %r' % (hp['rule'], f.rule))
+            bufs = [getattr(f, k) for k in f.state_keys]
+            ops.optim_step_dyn(f.rule, f.flat, f.grad, bufs[0], bufs[1] if len(bufs) > 1 else None, self.state, hp['betas'][0],
+                               hp['betas'][1], hp['eps'], hp['weight_decay'], clip, scale)
 
     def _body(self, t, sc_flag, struc_flag, with_adam):
         """advance the step record, forward + loss + backward into the flat gradient buffer (+ clip/Adam when no collective follows)"""

@@ -665,6 +665,31 @@ def adam_step_dyn(p, g, m, v, state, beta1, beta2, eps, weight_decay, clip, grad
                                   clip, grad_scale, stream_ptr()), 'capmi_adam_step_dyn')
 
 
+OPTIM_RULES = {'rmsprop': _lib.OPTIM_RMSPROP, 'adagrad': _lib.OPTIM_ADAGRAD, 'sgdm': _lib.OPTIM_SGDM, 'sgdmom': _lib.OPTIM_SGDMOM,
+               'adamw': _lib.OPTIM_ADAMW}
+
+
+def _optim_hp(rule, alpha, beta, eps, weight_decay, clip, grad_scale):
+    if rule not in OPTIM_RULES:
+        raise _lib.CapmiError('capmi_optim_step has no rule %r (one of %s; Adam is adam_step)' % (rule, sorted(OPTIM_RULES)))
+    return _lib.OptimHp(rule=OPTIM_RULES[rule], alpha=alpha, beta=beta, eps=eps, weight_decay=weight_decay, clip=clip,
+                        grad_scale=grad_scale)
+
+
+def optim_step(rule, p, g, s1, s2, lr, alpha, beta, eps, weight_decay, clip, grad_scale, step):
+    """fused clip + `rule` ('rmsprop', 'adagrad', 'sgdm', 'sgdmom', 'adamw') on a flat fp32 range; s2: AdamW's second moment, None for
+    the one-state rules (capmi.h capmi_optim_step)"""
+    hp = _optim_hp(rule, alpha, beta, eps, weight_decay, clip, grad_scale)
+    check(lib.capmi_optim_step(C.byref(hp), ptr(p), ptr(g), ptr(s1), ptr(s2), p.numel(), lr, step, stream_ptr()), 'capmi_optim_step')
+
+
+def optim_step_dyn(rule, p, g, s1, s2, state, alpha, beta, eps, weight_decay, clip, grad_scale):
+    """optim_step with the learning rate, the step number and AdamW's bias corrections read from the device record `state`"""
+    hp = _optim_hp(rule, alpha, beta, eps, weight_decay, clip, grad_scale)
+    check(lib.capmi_optim_step_dyn(C.byref(hp), ptr(p), ptr(g), ptr(s1), ptr(s2), p.numel(), state.buf.data_ptr(), stream_ptr()),
+          'capmi_optim_step_dyn')
+
+
 def logsoftmax_bwd(g_dense, sparse, seq_logp, live, dlogits, N, L, T, V1, raw=False):
     """d(logits) [T,N,V1] from the loss gradient w.r.t. the dense log-probs: dense (`g_dense` [N,L,V1]), sparse
     (`sparse`, a _lib.SparseLogpGrad from sparse_logp.split_grad) or both.

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Training entrypoint on the MI355X backend -- the control flow of the reference's tools/train.py:32-292 for the
 hot path: learning-rate decay / warm-up / Noam / reduce-on-plateau (:94-102, :132-141, :171-173, :253-256), XE /
-self-critical / new-self-critical scheduling (:144-161), LossWrapper call (:185), backward, value clip + Adam
-(:193-196), `time/batch` print (:198-208), periodic validation loss and checkpoint (:228-285), bucketed flat-gradient
+self-critical / new-self-critical scheduling (:144-161), LossWrapper call (:185), backward, value clip + the optimizer
+of --optim (:193-196; every name of misc.build_optimizer but plain sgd), `time/batch` print (:198-208), periodic validation loss and checkpoint (:228-285), bucketed flat-gradient
 RCCL all-reduce overlapped with the backward when launched with torch.distributed.run.  With language_eval 1 the validation
 pass also decodes and scores corpus CIDEr / BLEU / ROUGE-L on the device: CIDEr decides best_val_score, model-best.pth and the
 plateau schedule (:252-266, :284-286).
@@ -90,12 +90,12 @@ def train(opt):
     if world > 1:
         dist.init_process_group('nccl', rank=rank, world_size=world)
         dist.barrier(device_ids=[local])              # RCCL communicator created on the main thread, before any backward
-    if opt.optim != 'adam':
-        raise NotImplementedError("optim %r: the fused flat-buffer step implements Adam (misc.py:125-126, every BASELINE "
-                                  "config); other optimizers of misc.build_optimizer are out of scope" % opt.optim)
+    # misc.py:114-130 build_optimizer: rmsprop, adagrad, sgdm, sgdmom, adam, adamw -- each a fused kernel over the flat buffer; plain
+    # `sgd` raises NotImplementedError
+    optim = misc.build_optimizer(opt)
     if opt.grad_clip_mode not in ('value',) and opt.grad_clip_value > 0:
         raise NotImplementedError("grad_clip_mode %r: only clip_grad_value_ (train.py:194-195, the default) is fused into the "
-                                  "Adam kernel" % opt.grad_clip_mode)
+                                  "optimizer kernels" % opt.grad_clip_mode)
     # Every rank draws its own images -- as a PARTITION of one shuffled pass: the loaders share `seed` and take
     # every world-th element of the permutation (tools/train_pl.py:60-73 + Lightning's DistributedSampler; per-GPU batch :459-460)
     if opt.input_json:                                # precomputed bottom-up features + labels (variable region counts)
@@ -119,7 +119,7 @@ def train(opt):
     if opt.start_from:
         model.load_state_dict(torch.load(os.path.join(opt.start_from, 'model.pth'), map_location=dev))
         infos = misc.load_infos(opt.start_from, opt.id)                          # tools/train.py:50-66
-    flat = model.flatten_parameters_()
+    flat = model.flatten_parameters_(optim['rule'])
     overlap = world > 1 and os.environ.get('CAPMI_DDP_OVERLAP', '0') == '1'      # default: ONE all-reduce per step
     if overlap:
         flat.begin_overlap()
@@ -133,15 +133,16 @@ def train(opt):
         # and the loader position
         osd = misc.load_optimizer_state(opt.start_from)
         if osd is not None and 'flat' in osd:                                    # a checkpoint of this trainer
-            flat.load_state_dict(osd['flat'])
+            flat.load_state_dict(osd['flat'])                                    # (raises when it was written under another --optim)
             sched.load_state_dict(osd['sched'])
         elif osd is not None:
-            # a checkpoint of the REFERENCE trainer: torch.optim.Adam's state_dict (misc.py:125, tools/train.py:112-119) -> the flat
-            # moment buffers; the rate schedule restarts from the iteration / epoch counters of infos
+            # a checkpoint of the REFERENCE trainer: the torch optimizer's state_dict (misc.py:114-130, tools/train.py:112-119) -> the
+            # flat state buffers; the rate schedule restarts from the iteration / epoch counters of infos
             if flat.load_torch_adam_state(osd):
-                print('optimizer.pth: torch Adam state converted to the flat moment buffers (step %d)' % flat.step_count)
+                print('optimizer.pth: torch %s state converted to the flat state buffers (step %d)' % (optim['rule'], flat.step_count))
             else:
-                print('optimizer.pth does not match this model (not a torch Adam state of its parameters): optimizer starts fresh')
+                print('optimizer.pth does not match this model (not a torch %s state of its parameters): optimizer starts fresh'
+                      % optim['rule'])
         base = getattr(loader, 'loader', loader)                                 # under the prefetcher (nothing is prefetched yet)
         base = getattr(base, 'loader', base)                                     # ... and the resident feature store
         # the reference saves its sampler's index_list / iter_counter (dataloader.py:376-405): the shuffled order of the epoch
@@ -225,8 +226,7 @@ def train(opt):
             flat.collect_grads()
             clip = opt.grad_clip_value if opt.grad_clip_mode == 'value' else 0.0
             # buckets finished by the backward are already in flight; clip+Adam follows each as it lands
-            flat.finish_overlap_and_step(opt.current_lr, (opt.optim_alpha, opt.optim_beta), opt.optim_epsilon, opt.weight_decay,
-                                         clip_value=clip)
+            flat.finish_overlap_and_step(opt.current_lr, optim['betas'], optim['eps'], optim['weight_decay'], clip_value=clip)
         # The reference reads the loss back right here (train.py:197), leaving the GPU idle while the host prepares the next
         # iteration.  Same values, one iteration later: the loss goes to a pinned buffer asynchronously and the host waits for the
         # PREVIOUS iteration's copy, so one iteration is always queued behind the running one (never more: the host stays at most

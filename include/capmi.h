@@ -490,6 +490,44 @@ int capmi_adam_step_dyn(float *p, const float *g, float *m, float *v, int64_t co
                         void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The other rules of misc.build_optimizer (misc.py:114-130) on the flat fp32 buffer, fused with the same pre-processing as
+ * capmi_adam_step: g = clamp(g * grad_scale, -clip, clip) (clip <= 0: none).  One launch, every stream read and written once.
+ *   CAPMI_OPTIM_RMSPROP  torch.optim.RMSprop(lr, alpha, eps, weight_decay): g += wd p; s1 = alpha s1 + (1 - alpha) g^2;
+ *                        p -= lr g / (sqrt(s1) + eps)                                                    s1 = 'square_avg'
+ *   CAPMI_OPTIM_ADAGRAD  torch.optim.Adagrad(lr, weight_decay), lr_decay 0: g += wd p; s1 += g^2;
+ *                        p -= lr g / (sqrt(s1) + eps)   (the caller passes torch's default eps, 1e-10)   s1 = 'sum'
+ *   CAPMI_OPTIM_SGDM     torch.optim.SGD(lr, momentum = alpha, weight_decay): g += wd p; s1 = step == 1 ? g : alpha s1 + g;
+ *                        p -= lr s1                                                                      s1 = 'momentum_buffer'
+ *   CAPMI_OPTIM_SGDMOM   the same with nesterov=True: p -= lr (g + alpha s1)
+ *   CAPMI_OPTIM_ADAMW    torch.optim.AdamW(lr, (alpha, beta), eps, weight_decay): p *= 1 - lr wd; then Adam's update with no L2
+ *                        term in g                                                    s1 = 'exp_avg', s2 = 'exp_avg_sq'
+ * s2 is read and written by CAPMI_OPTIM_ADAMW only; the other rules never touch it (pass NULL).  p, g, s1 (and s2) need 4-byte
+ * alignment only: a range that starts off a 16-byte boundary (a shard of the flat buffer) gets a scalar head and tail.
+ *   capmi_optim_step      lr and the 1-based step number by value.
+ *   capmi_optim_step_dyn  lr, the step number (capmi_step_state.adam_step, for the first-step rule) and AdamW's bias corrections
+ *                         from the device record: capmi_step_advance(state, alpha, beta) and capmi_step_set_lr serve every rule.
+ * CAPMI_EINVAL: a NULL hp / p / g / s1 / state (s2 for AdamW), count <= 0, step < 1, an unknown rule, a pointer off 4 bytes.
+ * ------------------------------------------------------------------------------------------- */
+#define CAPMI_OPTIM_RMSPROP 1
+#define CAPMI_OPTIM_ADAGRAD 2
+#define CAPMI_OPTIM_SGDM 3
+#define CAPMI_OPTIM_SGDMOM 4
+#define CAPMI_OPTIM_ADAMW 5
+typedef struct capmi_optim_hp {
+    int32_t rule;           /* CAPMI_OPTIM_* */
+    float alpha;            /* rmsprop: smoothing constant; sgdm / sgdmom: momentum; adamw: beta1 */
+    float beta;             /* adamw: beta2 */
+    float eps;
+    float weight_decay;
+    float clip;
+    float grad_scale;
+} capmi_optim_hp;
+int capmi_optim_step(const capmi_optim_hp *hp, float *p, const float *g, float *s1, float *s2, int64_t count, float lr,
+                     int step, void *stream);
+int capmi_optim_step_dyn(const capmi_optim_hp *hp, float *p, const float *g, float *s1, float *s2, int64_t count,
+                         const capmi_step_state *state, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * CIDEr-D reward (external pyciderevalcap.ciderD -- see oracle/ciderd.py for the provenance note;
  * call sites rewards.py:41-81, 83-114).  float64 arithmetic on device.
  *   table: open-addressing hash of the document-frequency pickle; keys = n-gram of <= 4 token ids
