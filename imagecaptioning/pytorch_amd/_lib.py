@@ -424,6 +424,7 @@ SIGNATURES = {
                                  C.POINTER(UpDownGrads), _P],
     'capmi_updown_rollout_bwd_phases': [C.POINTER(UpDownWeights), C.POINTER(UpDownRollout), _P, C.POINTER(UpDownBwdScratch),
                                  C.POINTER(UpDownGrads), _I, _P],
+    'capmi_region_rows_build': [_P, _P, _P, _P, _I, _I, _P, _I64, _I, _I, _I, _P],
 }
 
 

@@ -10,6 +10,11 @@ Inputs (same options as the reference, ``opts.py:23-37``):
   input_fc_dir    ``<id>.npy`` pooled features [F] (optional: mean of the regions when missing, dataloader.py:295-298)
   input_att_dir   ``<id>.npz`` with key ``feat`` (or ``z``, dataloader.py:40) [K_i, F], K_i variable (10..100 for adaptive
                   bottom-up features) -- or ``<id>.npy``
+  input_box_dir   with ``use_box 1``: ``<id>.npy`` (or ``<id>.npz``) boxes [K_i, 4] = x1, y1, x2, y2 in pixels; ``height`` / ``width`` of
+                  every image come from input_json.  Five geometry columns are appended to each region row (``norm_box_feat``: over
+                  their L2 norm) and the rows re-ordered by the last one, descending, stable (dataloader.py:272-282): att_feats are
+                  [B, Kmax, F + 5] and att_feat_size is the user's to set, as in the reference.  (Boxes are cast to float32: the
+                  reference would carry a float64 box file's precision into float64 att_feats.)
 
 ``get_batch(split)`` returns CPU tensors: ``fc_feats [B,F]``, ``att_feats [B,Kmax,F]`` zero padded, ``att_masks [B,Kmax]`` or
 None when every image of the batch has Kmax regions (:240-241), ``labels [B,n,L+2]`` int64 with BOS/EOS columns 0, ``masks``
@@ -48,21 +53,66 @@ def load_labels(path):
             return {k: f[k][:] for k in keys}
 
 
-def decode_image(att_dir, fc_dir, img_id, use_fc, norm_att_feat):
-    """(fc [F] or [0], att [K_i, F]) of one image from its files (dataloader.py:186-229, 295-298)"""
-    p = os.path.join(att_dir, str(img_id) + '.npz')
+def _load_rows(directory, img_id, what):
+    """the 2-D float32 array of one image from ``<id>.npz`` (key ``feat``, or ``z``, dataloader.py:40) or ``<id>.npy``"""
+    p = os.path.join(directory, str(img_id) + '.npz')
     if os.path.exists(p):
         z = np.load(p)
         a = z['feat'] if 'feat' in z else z['z']
     else:
-        a = np.load(os.path.join(att_dir, str(img_id) + '.npy'))
-    a = np.asarray(a, dtype=np.float32).reshape(-1, a.shape[-1])
+        p = os.path.join(directory, str(img_id) + '.npy')
+        if not os.path.exists(p):
+            raise FileNotFoundError('no %s file for image %s: neither %s.npz nor %s.npy in %s' % (what, img_id, img_id, img_id, directory))
+        a = np.load(p)
+    return np.asarray(a, dtype=np.float32).reshape(-1, a.shape[-1])
+
+
+def box_columns(boxes, height, width, norm_box_feat=False):
+    """[K, 5] float32 geometry of use_box (dataloader.py:275-279): x1/w, y1/h, x2/w, y2/h, (x2-x1)*(y2-y1)/(w*h), every operation
+    rounded to float32 on its own (w, h and the integer w*h converted to float32 first), then optionally each 5-vector over its L2
+    norm.  capmi_region_rows_build computes the same columns on the device, bit for bit without the norm."""
+    b = np.asarray(boxes, dtype=np.float32)
+    x1, y1, x2, y2 = np.hsplit(b, 4)
+    w, h, wh = np.float32(width), np.float32(height), np.float32(int(width) * int(height))
+    box = np.hstack((x1 / w, y1 / h, x2 / w, y2 / h, (x2 - x1) * (y2 - y1) / wh))
+    if norm_box_feat:
+        box = box / np.linalg.norm(box, 2, 1, keepdims=True)
+    return box
+
+
+def append_boxes(att, boxes, height, width, norm_box_feat=False):
+    """[K, D + 5]: the geometry columns appended and the rows re-ordered by the last one, descending, ties in file order
+    (dataloader.py:280-282: Python's stable ``sorted(..., reverse=True)``).  NaN keys go last, in file order, as on the device."""
+    rows = np.hstack([att, box_columns(boxes, height, width, norm_box_feat)])
+    key = rows[:, -1]
+    order = sorted(range(rows.shape[0]), key=lambda i: (1, 0.0) if key[i] != key[i] else (0, -key[i]))
+    return np.ascontiguousarray(rows[order])
+
+
+def decode_image(att_dir, fc_dir, img_id, use_fc, norm_att_feat, box=None, raw=False):
+    """(fc [F] or [0], att [K_i, F]) of one image from its files (dataloader.py:186-229, 266-298).
+    box: None, or (input_box_dir, height, width, norm_box_feat) of use_box.
+    raw: for a store that builds its rows on the device (resident.py): (fc, att as the file holds it, boxes [K_i, 4] or None); fc is
+    None where it is the mean of the BUILT rows (no fc file), which the store then takes from them."""
+    a = _load_rows(att_dir, img_id, 'feature')
+    boxes = None
+    if box is not None:
+        boxes = _load_rows(box[0], img_id, 'box')
+        if boxes.shape[1] != 4 or boxes.shape[0] != a.shape[0]:
+            raise ValueError('image %s: the box file holds %s boxes (x1, y1, x2, y2 per row expected), the feature file %d regions'
+                             % (img_id, tuple(boxes.shape), a.shape[0]))
+    p = os.path.join(fc_dir, str(img_id) + '.npy') if fc_dir else None
+    fc_file = use_fc and p and os.path.exists(p)
+    if raw:
+        fc = np.load(p).astype(np.float32) if fc_file else (None if use_fc else np.zeros((0,), dtype=np.float32))
+        return fc, a, boxes
     if norm_att_feat:
         a = a / np.linalg.norm(a, 2, 1, keepdims=True)
+    if box is not None:
+        a = append_boxes(a, boxes, box[1], box[2], box[3])
     if not use_fc:
         return np.zeros((0,), dtype=np.float32), a
-    p = os.path.join(fc_dir, str(img_id) + '.npy') if fc_dir else None
-    fc = np.load(p).astype(np.float32) if p and os.path.exists(p) else a.mean(0)          # dataloader.py:295-298
+    fc = np.load(p).astype(np.float32) if fc_file else a.mean(0)          # dataloader.py:295-298
     return fc, a
 
 
@@ -88,6 +138,19 @@ class FeatureLoader:
         self.fc_dir, self.att_dir = getattr(opt, 'input_fc_dir', None), opt.input_att_dir
         self.use_fc = bool(getattr(opt, 'use_fc', True))
         self.norm_att_feat = bool(getattr(opt, 'norm_att_feat', 0))
+        # use_box (dataloader.py:103-105, 272-282): five box-geometry columns behind every region row, rows re-ordered by the last one
+        self.use_box = bool(getattr(opt, 'use_box', 0))
+        self.norm_box_feat = bool(getattr(opt, 'norm_box_feat', 0))
+        self.box_dir = getattr(opt, 'input_box_dir', None)
+        if self.use_box:
+            if not self.box_dir or not os.path.isdir(self.box_dir):
+                raise ValueError('use_box 1 needs the boxes: input_box_dir %r is not a directory' % (self.box_dir,))
+            for img in self.info['images']:
+                for k in ('height', 'width'):
+                    v = img.get(k)
+                    if v is None or int(v) != v or int(v) <= 0:
+                        raise ValueError('use_box 1 needs a positive integer %r of every image in %s: image %s has %r'
+                                         % (k, opt.input_json, img.get('id'), v))
         self.split_ix = {'train': [], 'val': [], 'test': []}
         for ix, img in enumerate(self.info['images']):        # dataloader.py:143-156
             sp = img.get('split')
@@ -193,15 +256,45 @@ class FeatureLoader:
         return np.concatenate(parts) if parts else np.zeros((0, self.seq_length), dtype=self.label.dtype)
 
     # ---- one image
-    def _image(self, ix):
-        return decode_image(self.att_dir, self.fc_dir, self.info['images'][ix]['id'], self.use_fc, self.norm_att_feat)
+    def _box(self, ix):
+        """decode_image's `box` argument of image `ix`"""
+        if not self.use_box:
+            return None
+        im = self.info['images'][ix]
+        return self.box_dir, int(im['height']), int(im['width']), self.norm_box_feat
 
-    def submit_image(self, ix):
-        """future of (fc, att) of image `ix` on the decode pool (threads, or worker processes: a pure function of paths)"""
+    def _image(self, ix, raw=False):
+        return decode_image(self.att_dir, self.fc_dir, self.info['images'][ix]['id'], self.use_fc, self.norm_att_feat, self._box(ix),
+                            raw)
+
+    def submit_image(self, ix, raw=False):
+        """future of (fc, att) of image `ix` on the decode pool (threads, or worker processes: a pure function of paths).
+        raw: (fc or None, unprocessed att, boxes or None), see decode_image"""
         if self.processes:
             return self.pool.submit(decode_image, self.att_dir, self.fc_dir, self.info['images'][ix]['id'], self.use_fc,
-                                    self.norm_att_feat)
-        return self.pool.submit(self._image, ix)
+                                    self.norm_att_feat, self._box(ix), raw)
+        return self.pool.submit(self._image, ix, raw)
+
+    def finish_image(self, ix, fc, att, boxes):
+        """(fc, att) as get_batch hands them out, from what a raw decode returned: the host path of norm_att_feat / use_box"""
+        if self.norm_att_feat:
+            att = att / np.linalg.norm(att, 2, 1, keepdims=True)
+        if self.use_box:
+            _, h, w, nb = self._box(ix)
+            att = append_boxes(att, boxes, h, w, nb)
+        return (att.mean(0) if fc is None else fc), att
+
+    def att_feat_width(self):
+        """width of the region rows this loader hands out (the first image's D, + 5 with use_box): what att_feat_size must be"""
+        return int(self._image(0)[1].shape[1])
+
+    def check_att_feat_size(self, att_feat_size):
+        """start-up check of tools/train.py and tools/eval.py: with use_box the rows are 5 wider than the feature files, and
+        att_feat_size is the user's to set (as in the reference); a wrong one would otherwise surface as a shape error in att_embed"""
+        if self.use_box and self.att_feat_width() != int(att_feat_size):
+            w = self.att_feat_width()
+            raise ValueError('use_box 1: the loader hands out region rows of width %d (%d features + 5 box columns) but att_feat_size '
+                             'is %d -- pass --att_feat_size %d' % (w, w - 5, int(att_feat_size), w))
 
     def _captions(self, ix, rng):
         """dataloader.py:165-184: seq_per_img consecutive captions from a random start, or sampling with replacement"""

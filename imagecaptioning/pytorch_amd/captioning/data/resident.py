@@ -9,6 +9,12 @@ Wraps a ``FeatureLoader`` and keeps its batch contract; ``fc_feats`` / ``att_fea
 (``DevicePrefetcher`` passes them through), everything else as the wrapped loader returns it.  Images beyond ``budget_bytes`` are
 streamed like before.  Storage is ragged ([rows, F] + per-image (offset, K)), so adaptive 10..100-region features cost what
 they hold; row 0 is a zero row used as padding.
+
+``norm_att_feat`` and ``use_box`` / ``norm_box_feat`` of a store on a HIP device are applied by the device: the decode pool hands
+over the rows as the files hold them, one host-to-device copy carries the rows, the boxes and the per-image table of all newly
+drawn images, and one launch of ``capmi_region_rows_build`` (csrc/region_rows.hip) normalises, appends the five geometry columns
+and writes every image's rows into the store in the reference's order (by the last column, descending, stable).  The host does
+no arithmetic per row; streamed images (beyond the budget) and a store on the CPU keep the loader's numpy path.
 """
 import numpy as np
 import torch
@@ -29,6 +35,8 @@ class ResidentFeatures:
         self.n_images = len(loader.info['images'])
         self._pending = {}
         self.hits = self.misses = self.streamed = 0
+        # rows built by the device from raw files (module docstring); otherwise the loader's decode has already finished them
+        self.device_build = self.dev.type == 'cuda' and bool(getattr(loader, 'norm_att_feat', False) or getattr(loader, 'use_box', False))
 
     def __getattr__(self, name):       # vocabulary, pos, order, document_frequency(), ... of the wrapped loader
         return getattr(self.loader, name)
@@ -54,8 +62,57 @@ class ResidentFeatures:
         self.rows = grown
         return True
 
+    def _build_many(self, new):
+        """_insert_many for raw images [(ix, fc or None, att as in the file, boxes or None)]: one copy (rows | boxes | table), one
+        launch into self.rows; the ones that did not fit come back finished by the loader's host path as (ix, fc, att)"""
+        from imagecaptioning.pytorch_amd import ops
+        ld = self.loader
+        box = bool(ld.use_box)
+        fit, loose, k_tot = [], [], 0
+        for ix, fc, att, boxes in new:
+            if self._room(k_tot + att.shape[0], att.shape[1] + 5 * box):
+                fit.append((ix, fc, att, boxes))
+                k_tot += att.shape[0]
+            else:
+                loose.append((ix,) + ld.finish_image(ix, fc, att, boxes))
+        if fit:
+            D = fit[0][2].shape[1]
+            table = np.zeros((len(fit), 4), dtype=np.int32)
+            r = 0
+            for i, (ix, _, att, _) in enumerate(fit):
+                im = ld.info['images'][ix]
+                table[i] = (r, att.shape[0], int(im['height']), int(im['width'])) if box else (r, att.shape[0], 0, 0)
+                r += att.shape[0]
+            pad = lambda n: (n + 3) & ~3                           # noqa: E731  (every part starts on 16 bytes)
+            o_box = pad(k_tot * D)
+            o_tab = o_box + pad(k_tot * 4 * box)
+            host = np.zeros(o_tab + table.size, dtype=np.float32)
+            host[:k_tot * D] = np.concatenate([a for _, _, a, _ in fit], 0).reshape(-1)
+            if box:
+                host[o_box:o_box + k_tot * 4] = np.concatenate([b for _, _, _, b in fit], 0).reshape(-1)
+            host[o_tab:].view(np.int32)[:] = table.reshape(-1)
+            stage = torch.from_numpy(host).to(self.dev)
+            ops.region_rows_build(stage[:k_tot * D].view(k_tot, D), stage[o_box:o_box + k_tot * 4].view(k_tot, 4) if box else None,
+                                  table, stage[o_tab:].view(torch.int32), self.rows[self.used:self.used + k_tot],
+                                  ld.norm_att_feat, box, ld.norm_box_feat)
+            F = self.rows.shape[1]
+            if self.fc is None:
+                self.fc = torch.zeros(self.n_images, F if fit[0][1] is None else fit[0][1].shape[0], dtype=torch.float32, device=self.dev)
+            if self.fc.shape[1]:
+                ixs = torch.tensor([ix for ix, _, _, _ in fit], dtype=torch.int64).to(self.dev)
+                zero = np.zeros(self.fc.shape[1], dtype=np.float32)
+                self.fc.index_copy_(0, ixs, torch.from_numpy(np.stack([zero if f is None else f for _, f, _, _ in fit])).to(self.dev))
+            for ix, fc, att, _ in fit:
+                self.slot[ix] = (self.used, att.shape[0])
+                if fc is None and self.fc.shape[1]:                # no fc file: the mean of the built rows (dataloader.py:295-298)
+                    self.fc[ix] = self.rows[self.used:self.used + att.shape[0]].mean(0)
+                self.used += att.shape[0]
+        return loose
+
     def _insert_many(self, new):
         """new: [(ix, fc, att)] -> the ones that did not fit; ONE host-to-device copy for all region rows, one for the fc rows"""
+        if self.device_build:
+            return self._build_many(new)
         fit, loose, k_tot = [], [], 0
         for ix, fc, att in new:
             if self._room(k_tot + att.shape[0], att.shape[1]):
@@ -89,7 +146,8 @@ class ResidentFeatures:
     # ---- batches
     def _schedule(self, split, B):
         idx, wrapped = self.loader._next_indices(split, B)
-        futs = {ix: self.loader.submit_image(ix) for ix in set(idx) if ix not in self.slot}
+        raw = (True,) if self.device_build else ()
+        futs = {ix: self.loader.submit_image(ix, *raw) for ix in set(idx) if ix not in self.slot}
         return idx, wrapped, self.loader.pos[split], futs, self.loader._snap[split], self.loader.rng.getstate()
 
     def get_batch(self, split, batch_size=None):
@@ -107,8 +165,7 @@ class ResidentFeatures:
                 self.hits += 1
             elif ix not in seen:
                 seen.add(ix)
-                fc, att = futs[ix].result() if ix in futs else ld._image(ix)
-                new.append((ix, fc, att))
+                new.append((ix,) + tuple(futs[ix].result() if ix in futs else ld._image(ix, *((True,) if self.device_build else ()))))
                 self.misses += 1
         loose = {ix: (fc, att) for ix, fc, att in self._insert_many(new)}      # images the budget has no room for: streamed
         self.streamed += len(loose)

@@ -896,3 +896,42 @@ def clip_len(att_masks, width=None):
         except Exception:
             pass
     return k
+
+
+REGION_KMAX = 1024                 # capmi.h CAPMI_REGION_KMAX
+region_rows_build_calls = 0        # launches so far (tests: a second pass over a resident store launches none)
+
+
+def region_rows_build(src, boxes, table_host, table, dst, norm_att, use_box, norm_box):
+    """Store rows of a block of images from their raw region rows (capmi.h capmi_region_rows_build): norm_att_feat, the five
+    box-geometry columns, norm_box_feat and the stable descending re-ordering by the last column, one launch.
+    src [R, D] and boxes [R, 4] (None without use_box) float32 contiguous; table_host: numpy int32 [n, 4] (first row, K, height,
+    width), table: the same words as an int32 device tensor; dst: a 2-D float32 view of unit column stride, D + 5 * use_box wide,
+    whose rows first .. first + K - 1 are written (its row stride is the leading dimension)."""
+    global region_rows_build_calls
+    import numpy as np
+    use_box = bool(use_box)
+    n = int(table_host.shape[0]) if table_host.ndim == 2 else 0
+    if table_host.dtype != np.int32 or table_host.ndim != 2 or table_host.shape[1] != 4 or not table_host.flags['C_CONTIGUOUS']:
+        raise _lib.CapmiError('region_rows_build: table_host must be a contiguous int32 [n, 4] array')
+    if table.dtype != torch.int32 or table.numel() != 4 * n or not table.is_contiguous() or table.device != src.device:
+        raise _lib.CapmiError('region_rows_build: table must hold the %d int32 words of table_host on the device' % (4 * n))
+    if src.dtype != _f32 or src.dim() != 2 or not src.is_contiguous():
+        raise _lib.CapmiError('region_rows_build: src must be a contiguous float32 [rows, D] tensor')
+    R, D = src.shape
+    W = D + (5 if use_box else 0)
+    if use_box and (boxes is None or boxes.dtype != _f32 or tuple(boxes.shape) != (R, 4) or not boxes.is_contiguous()
+                    or boxes.device != src.device):
+        raise _lib.CapmiError('region_rows_build: boxes must be a contiguous float32 [%d, 4] tensor' % R)
+    if dst.dtype != _f32 or dst.dim() != 2 or dst.shape[1] != W or (dst.shape[0] > 1 and dst.stride(0) < W) or dst.stride(1) != 1 \
+            or dst.device != src.device:
+        raise _lib.CapmiError('region_rows_build: dst must be a float32 [rows, %d] view with unit column stride' % W)
+    if n:                              # the rows the kernel reads and writes lie inside src / dst, no two images share one
+        order = np.argsort(table_host[:, 0], kind='stable')
+        first, K = table_host[order, 0].astype(np.int64), table_host[order, 1].astype(np.int64)
+        if first[0] < 0 or (K <= 0).any() or (first[:-1] + K[:-1] > first[1:]).any() or first[-1] + K[-1] > min(R, dst.shape[0]):
+            raise _lib.CapmiError('region_rows_build: the images\' rows overlap or leave src %s / dst %s' % (tuple(src.shape), tuple(dst.shape)))
+    check(lib.capmi_region_rows_build(ptr(src), ptr(boxes) if use_box else None, table_host.ctypes.data, ptr(table), n, D, ptr(dst),
+                                      dst.stride(0) if dst.shape[0] > 1 else W, int(bool(norm_att)), int(use_box), int(bool(norm_box)),
+                                      stream_ptr()), 'capmi_region_rows_build')
+    region_rows_build_calls += 1

@@ -227,6 +227,7 @@ def build_loader(opt, dev):
     if getattr(opt, 'input_json', ''):
         from captioning.data.feature_loader import FeatureLoader
         loader = FeatureLoader(opt)
+        loader.check_att_feat_size(getattr(opt, 'att_feat_size', 0))     # use_box: rows are 5 wider than the feature files
         opt.vocab_size, opt.seq_length = loader.vocab_size, loader.seq_length
         if not getattr(opt, 'max_length', None) or opt.max_length > opt.seq_length:
             opt.max_length = opt.seq_length

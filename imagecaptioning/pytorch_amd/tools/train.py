@@ -101,6 +101,7 @@ def train(opt):
     if opt.input_json:                                # precomputed bottom-up features + labels (variable region counts)
         from captioning.data.feature_loader import FeatureLoader
         loader = FeatureLoader(opt, rank=rank, world=world)
+        loader.check_att_feat_size(opt.att_feat_size)     # use_box: rows are 5 wider than the feature files
         opt.vocab_size, opt.seq_length = loader.vocab_size, loader.seq_length
         if not getattr(opt, 'max_length', None) or opt.max_length > opt.seq_length:
             opt.max_length = opt.seq_length

@@ -1563,6 +1563,30 @@ int capmi_sentset_add_first(const capmi_sentset *s, const int64_t *seq, int rows
                             const float *entropy, void *stream);
 int capmi_sentset_reduce(const capmi_sentset *s, double *out, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Store rows of a block of images, built on the device (region_rows.hip): norm_att_feat, the box-geometry columns of use_box,
+ * norm_box_feat and the re-ordering of an image's rows by the last column (captioning/data/dataloader.py:266-282).  One launch,
+ * one workgroup per image.
+ *   src    [sum K, D] float32, the region rows as the feature files hold them; image i owns rows first_i .. first_i + K_i - 1
+ *   boxes  [sum K, 4] float32 x1, y1, x2, y2 of the same rows (read with use_box only; may be NULL without it)
+ *   table  [n_images, 4] int32 on the DEVICE: first row, K, height, width; table_host: the same words in host memory -- the
+ *          arguments are checked there, the kernel reads the device copy
+ *   dst    rows of D + 5 * use_box floats, leading dimension ldd (in floats): image i's rows go to dst rows first_i .. first_i + K_i - 1,
+ *          nothing else is written (the ldd - row elements between two rows are left alone).  No alignment beyond 4 bytes is asked of
+ *          src, boxes or dst.
+ *   norm_att: every row of src is divided by its L2 norm over D.
+ *   use_box:  the columns x1 / w, y1 / h, x2 / w, y2 / h, ((x2 - x1) * (y2 - y1)) / (w * h) are appended, in float32 with correctly
+ *          rounded, non-contracted operations in that order (w, h and the integer w * h converted to float first): bit for bit
+ *          what numpy computes in float32.  norm_box divides the five columns by their L2 norm.  The K rows are then written in the
+ *          order of the last column, descending, equal keys in file order (Python's stable sorted(..., reverse=True)).  NaN keys go
+ *          behind every other key, in file order; they are not refused (that would take a device-to-host wait).
+ * CAPMI_EINVAL, before anything is launched: a NULL src / table_host / table / dst (boxes with use_box), n_images <= 0, D <= 0,
+ * a first row < 0 or K <= 0, with use_box K > CAPMI_REGION_KMAX or height / width <= 0, ldd < D + 5 * use_box, a pointer off 4 bytes.
+ * ------------------------------------------------------------------------------------------- */
+#define CAPMI_REGION_KMAX 1024
+int capmi_region_rows_build(const float *src, const float *boxes, const int32_t *table_host, const int32_t *table, int n_images,
+                            int D, float *dst, int64_t ldd, int norm_att, int use_box, int norm_box, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
