@@ -425,6 +425,14 @@ SIGNATURES = {
     'capmi_updown_rollout_bwd_phases': [C.POINTER(UpDownWeights), C.POINTER(UpDownRollout), _P, C.POINTER(UpDownBwdScratch),
                                  C.POINTER(UpDownGrads), _I, _P],
     'capmi_region_rows_build': [_P, _P, _P, _P, _I, _I, _P, _I64, _I, _I, _I, _P],
+    'capmi_bn_row_blocks': [_I],
+    'capmi_bn_stats': [_P, _P, _I, _I, _P, _P],
+    'capmi_bn_finalize': [_P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P],
+    'capmi_bn_apply': [_P] * 7 + [_I, _I, _P],
+    'capmi_bn_bwd_partial': [_P] * 5 + [_I, _I, _P, _P],
+    'capmi_bn_colsum_parts': [_P, _I, _I, _P, _P, _P],
+    'capmi_bn_bwd_dx': [_P] * 9 + [_I, _P, _I, _I, _P],
+    'capmi_bn_linear_bwd': [_P] * 7 + [_I, _I, _P, _P],
 }
 
 

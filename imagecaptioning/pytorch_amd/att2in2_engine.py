@@ -23,10 +23,10 @@ def weights_struct(P):
     return fill_struct(_lib.Att2in2Weights(), _W, P)
 
 
-def prepare(P, att_feats, att_masks=None, drop_att=None, ws=None):
+def prepare(P, att_feats, att_masks=None, drop_att=None, ws=None, bn=None):
     """att' = drop(relu(att_embed(att))) with padded regions zeroed (pack_wrapper, AttModel.py:44-49), p_att = ctx2att(att').
-    drop_att: [B,K,R] keep mask of the att_embed dropout (train mode) or None."""
-    return engine_common.prepare(P, None, att_feats, att_masks, None, drop_att, ws=ws)
+    drop_att: [B,K,R] keep mask of the att_embed dropout (train mode) or None.  bn: engine_common.RegionBN of a use_bn model."""
+    return engine_common.prepare(P, None, att_feats, att_masks, None, drop_att, ws=ws, bn=bn)
 
 
 def prepare_backward(P, pr, d_att, d_p_att, grads, ws=None):

@@ -35,7 +35,7 @@ def sample_beam(model, fc_feats, att_feats, att_masks, opt):
     model._device_check(fc_feats)
     P = {k: v.detach() for k, v in model.named_parameters()}
     pr = engine.prepare(P, fc_feats.float().contiguous(), att_feats.float().contiguous(),
-                        None if att_masks is None else att_masks.float())
+                        None if att_masks is None else att_masks.float(), bn=model._region_bn(False))      # an eval-mode prefill
     dev = fc_feats.device
     if group_size != 1 or opt.get('decoding_constraint', 0) or opt.get('remove_bad_endings', 0):
         # diverse groups / decoding constraints: same kernels, host-stepped (the one-call search below has no hooks)
@@ -184,6 +184,10 @@ def check_train_beam_options(opt):
 def updown_beam_train(model, fc_feats, att_feats, att_masks, opt):
     """AttModel._sample_beam called in train() mode with gradients (loss_wrapper.py with train_beam_size > 1): returns
     (seq [B*sample_n, L], seqLogprobs [B*sample_n, L, V1] attached to the forced rollout's autograd function)."""
+    if getattr(model, 'use_bn', 0):
+        # the search and its forced replay would each run a train-mode prefill: two updates of the running statistics per step
+        raise NotImplementedError('train_beam_size > 1 does not support use_bn=%d: the search-then-replay would update the BatchNorm '
+                                  'running statistics more than once per step' % model.use_bn)
     check_train_beam_options(opt)
     bd, sample_n = opt.get('beam_size', 10), opt.get('sample_n', 10)
     fc_feats, att_feats = fc_feats.float().contiguous(), att_feats.float().contiguous()

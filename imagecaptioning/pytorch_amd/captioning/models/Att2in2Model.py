@@ -26,6 +26,8 @@ class Att2in2Core(nn.Module):
 
 
 class Att2in2Model(StepAPI, RecurrentModel):
+    _use_bn_refusal = None
+
     def __init__(self, opt):
         super().__init__()
         self.vocab_size = opt.vocab_size
@@ -40,7 +42,7 @@ class Att2in2Model(StepAPI, RecurrentModel):
         self._check_supported_opt(opt)
         self.embed = nn.Sequential(nn.Embedding(self.vocab_size + 1, self.input_encoding_size), nn.ReLU(),
                                    nn.Dropout(self.drop_prob_lm))
-        self.att_embed = nn.Sequential(nn.Linear(self.att_feat_size, self.rnn_size), nn.ReLU(), nn.Dropout(self.drop_prob_lm))
+        self.att_embed = self._att_embed_modules(opt)
         self.logit = nn.Linear(self.rnn_size, self.vocab_size + 1)
         self.ctx2att = nn.Linear(self.rnn_size, self.att_hid_size)
         self.core = Att2in2Core(opt)
@@ -68,18 +70,20 @@ class Att2in2Model(StepAPI, RecurrentModel):
         return dict(drop_att=att, drop_xt=xt, drop_out=out)
 
     def _make_rollout(self, P, cfg, att_feats, att_masks):
-        pr = engine.prepare(P, att_feats, att_masks, cfg.pop('drop_att', None))
+        pr = engine.prepare(P, att_feats, att_masks, cfg.pop('drop_att', None), bn=self._region_bn(self.training))
         return engine.Rollout(P, pr, **cfg), None
 
     def _prepare_feature(self, fc_feats, att_feats, att_masks):
         """AttModel.py:114-124 (eval numerics): (fc_feats unchanged, att', p_att, clipped masks)."""
-        pr = engine.prepare(self._params(), att_feats.float().contiguous(), None if att_masks is None else att_masks.float())
+        pr = engine.prepare(self._params(), att_feats.float().contiguous(), None if att_masks is None else att_masks.float(),
+                            bn=self._region_bn(False))
         return fc_feats, pr.att, pr.p_att, pr.att_masks
 
     def _stepper(self, att_feats, att_masks):
         from imagecaptioning.pytorch_amd.step import Att2in2Stepper
         P = self._params()
-        pr = engine.prepare(P, att_feats.float().contiguous(), None if att_masks is None else att_masks.float())
+        pr = engine.prepare(P, att_feats.float().contiguous(), None if att_masks is None else att_masks.float(),
+                            bn=self._region_bn(False))
         return lambda rows: Att2in2Stepper(P, pr, rows)
 
     def _row_stepper(self, P, pr, fc_feats):

@@ -76,6 +76,8 @@ class UpDownCore(nn.Module):
 
 
 class AttModel(StepAPI, RecurrentModel):
+    _use_bn_refusal = None
+
     def __init__(self, opt):
         super().__init__()
         self.vocab_size = opt.vocab_size
@@ -95,8 +97,7 @@ class AttModel(StepAPI, RecurrentModel):
         self.embed = nn.Sequential(nn.Embedding(self.vocab_size + 1, self.input_encoding_size), nn.ReLU(),
                                    nn.Dropout(self.drop_prob_lm))
         self.fc_embed = nn.Sequential(nn.Linear(self.fc_feat_size, self.rnn_size), nn.ReLU(), nn.Dropout(self.drop_prob_lm))
-        self.att_embed = nn.Sequential(nn.Linear(self.att_feat_size, self.rnn_size), nn.ReLU(),
-                                       nn.Dropout(self.drop_prob_lm))
+        self.att_embed = self._att_embed_modules(opt)
         self.logit = nn.Linear(self.rnn_size, self.vocab_size + 1)
         self.ctx2att = nn.Linear(self.rnn_size, self.att_hid_size)
         self.vocab = opt.vocab
@@ -130,13 +131,22 @@ class AttModel(StepAPI, RecurrentModel):
             pr_run.fc = torch.empty(2 * B, R, dtype=torch.float32, device=dev)
             pr_run.att = torch.empty(2 * B, K, R, dtype=torch.float32, device=dev)
             pr_run.p_att = torch.empty(2 * B, K, A, dtype=torch.float32, device=dev)
+            bn = self._region_bn(True)
+            greedy = lambda: engine.prepare(P, fc_feats, att_feats, att_masks, out=(pr_run.fc[B:], pr_run.att[B:], pr_run.p_att[B:]),      # noqa: E731
+                                            bn=None if bn is None else bn.eval())
+            if bn is not None:
+                # loss_wrapper.py:57-68: the greedy baseline runs first, in eval mode, on the running statistics from BEFORE this
+                # step's update; the sampled half then normalises with the batch statistics and updates them (stream order)
+                greedy()
             pr = engine.prepare(P, fc_feats, att_feats, att_masks, cfg.get('drop_fc'), cfg.get('drop_att'),
-                                out=(pr_run.fc[:B], pr_run.att[:B], pr_run.p_att[:B]))
-            engine.prepare(P, fc_feats, att_feats, att_masks, out=(pr_run.fc[B:], pr_run.att[B:], pr_run.p_att[B:]))
+                                out=(pr_run.fc[:B], pr_run.att[:B], pr_run.p_att[:B]), bn=bn)
+            if bn is None:
+                greedy()
             pr_run.att_masks = None if pr.att_masks is None else torch.cat([pr.att_masks, pr.att_masks], 0)
             extra = dict(row_img=cfg['row_img'], B_grad=B)
         else:
-            pr = engine.prepare(P, fc_feats, att_feats, att_masks, cfg.get('drop_fc'), cfg.get('drop_att'))
+            pr = engine.prepare(P, fc_feats, att_feats, att_masks, cfg.get('drop_fc'), cfg.get('drop_att'),
+                                bn=self._region_bn(self.training))
             pr_run, extra = pr, {}
         ro = engine.Rollout(P, pr_run, n=cfg['n'], T=cfg['T'], L=cfg['L'], mode=cfg['mode'],
                             temperature=cfg.get('temperature', 1.0), drop_xt=cfg.get('drop_xt'),
@@ -159,7 +169,7 @@ class AttModel(StepAPI, RecurrentModel):
         from imagecaptioning.pytorch_amd.step import UpDownStepper
         P = self._params()
         pr = engine.prepare(P, fc_feats.float().contiguous(), att_feats.float().contiguous(),
-                            None if att_masks is None else att_masks.float())
+                            None if att_masks is None else att_masks.float(), bn=self._region_bn(False))
         return lambda rows: UpDownStepper(P, pr, rows)
 
     def _row_stepper(self, P, pr, fc_feats):
@@ -171,7 +181,7 @@ class AttModel(StepAPI, RecurrentModel):
     def _prepare_feature(self, fc_feats, att_feats, att_masks):
         """AttModel.py:114-124 (eval-mode numerics; training dropout is applied inside the rollouts)."""
         pr = engine.prepare(self._params(), fc_feats.float().contiguous(), att_feats.float().contiguous(),
-                            None if att_masks is None else att_masks.float())
+                            None if att_masks is None else att_masks.float(), bn=self._region_bn(False))
         return pr.fc, pr.att, pr.p_att, pr.att_masks
 
     def _sample(self, fc_feats, att_feats, att_masks=None, opt={}):

@@ -20,7 +20,7 @@ import torch
 from .CaptionModel import CaptionModel
 from .utils import parse_sample_method, clip_len
 from imagecaptioning.pytorch_amd import _lib, sparse_logp
-from imagecaptioning.pytorch_amd.engine_common import Prepared
+from imagecaptioning.pytorch_amd.engine_common import Prepared, RegionBN
 
 
 class _RolloutFn(torch.autograd.Function):
@@ -62,14 +62,34 @@ class _RolloutFn(torch.autograd.Function):
 class RecurrentModel(CaptionModel):
     ss_prob = 0.0
 
-    @staticmethod
-    def _check_supported_opt(opt):
+    # why a family refuses use_bn (None: it runs it).  models.setup gives the same reasons for the families outside this base.
+    _use_bn_refusal = 'its prefill has no BatchNorm path (UpDown and Att2in2 have)'
+
+    def _check_supported_opt(self, opt):
         if (getattr(opt, 'bos_idx', 0), getattr(opt, 'eos_idx', 0), getattr(opt, 'pad_idx', 0)) != (0, 0, 0):
             raise NotImplementedError('capmi kernels assume bos=eos=pad=0 (the reference default, AttModel.py:65-67)')
         if getattr(opt, 'use_bn', 0):
-            raise NotImplementedError('use_bn is outside the shipped configs')
+            if self._use_bn_refusal is not None:
+                raise NotImplementedError('use_bn is not supported for %s: %s' % (type(self).__name__, self._use_bn_refusal))
+            if opt.use_bn not in (1, 2):
+                raise NotImplementedError('use_bn is 0, 1 or 2 (AttModel.py:80-85), got %r' % (opt.use_bn,))
         if getattr(opt, 'logit_layers', 1) != 1:
             raise NotImplementedError('logit_layers > 1 is broken in the reference itself (AttModel.py:92)')
+
+    use_bn = 0              # UpDown / Att2in2 set it from opt; the other families refuse it (models.setup)
+
+    def _att_embed_modules(self, opt):
+        """att_embed of AttModel.py:80-85: (BatchNorm1d(att_feat_size),) Linear, ReLU, Dropout (, BatchNorm1d(rnn_size))"""
+        import torch.nn as nn
+        self.use_bn = int(getattr(opt, 'use_bn', 0) or 0)
+        return nn.Sequential(*(((nn.BatchNorm1d(opt.att_feat_size),) if self.use_bn else ()) +
+                               (nn.Linear(opt.att_feat_size, opt.rnn_size), nn.ReLU(), nn.Dropout(opt.drop_prob_lm)) +
+                               ((nn.BatchNorm1d(opt.rnn_size),) if self.use_bn == 2 else ())))
+
+    def _region_bn(self, train):
+        """the BatchNorm state of one prefill (None without use_bn).  train: batch statistics and ONE update of the running buffers;
+        steppers, _prepare_feature, beam search, get_logprobs_state and ensemble members are eval-mode prefills."""
+        return RegionBN.of_module(self.att_embed, self.use_bn, train) if self.use_bn else None
 
     def _device_check(self, t):
         if not t.is_cuda:

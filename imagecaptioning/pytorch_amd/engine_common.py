@@ -3,6 +3,7 @@
   fill_struct()                  parameter / gradient tensors -> pointer fields of a capmi.h struct
   Prepared, prepare(), prepare_backward()
                                  AttModel._prepare_feature (AttModel.py:114-124) and its backward; fc_embed optional
+  att_linear(), RegionBN         use_bn: the name of att_embed's Linear, the BatchNorm layers' buffers and mode
   RolloutBase                    the select-side buffers, the sampling / forcing fields of capmi_*_rollout, run(), and the struct
                                  filling of backward()
 
@@ -33,7 +34,7 @@ def fill_struct(struct, fields, tensors, validate=True):
 
 class Prepared:
     """fc' [B,R], att' [B,K,R], p_att [B,K,A] (+ what the backward of the prefill needs)."""
-    __slots__ = ('fc', 'att', 'p_att', 'att_masks', 'fc_in', 'att_in', 'drop_fc', 'drop_att', 'K')
+    __slots__ = ('fc', 'att', 'p_att', 'att_masks', 'fc_in', 'att_in', 'drop_fc', 'drop_att', 'K', 'bn', 'bn1', 'bn2', 'att_pre', 'bn_keep')
 
     @classmethod
     def of_features(cls, att, p_att, att_masks):
@@ -47,10 +48,52 @@ class Prepared:
         return pr
 
 
-def prepare(P, fc_feats, att_feats, att_masks=None, drop_fc=None, drop_att=None, ws=None, out=None):
+ATT_BN1, ATT_BN2 = 'att_embed.0', 'att_embed.4'      # the BatchNorm1d layers of use_bn (AttModel.py:80-85); gamma / beta live in P
+
+
+def att_linear(P):
+    """name of att_embed's Linear: index 0 of the Sequential, index 1 behind the BatchNorm1d of use_bn (AttModel.py:80-85).  The one
+    place that knows; without use_bn index 1 is the ReLU and has no parameters."""
+    return 'att_embed.1' if 'att_embed.1.weight' in P else 'att_embed.0'
+
+
+class RegionBN:
+    """The state of att_embed's BatchNorm layers for one prefill: train (batch statistics over the valid region rows, running
+    buffers updated once, in place, on the stream) or eval (running statistics, nothing written), and per layer the buffers
+    (running_mean, running_var, num_batches_tracked).  bn2 is None unless use_bn == 2."""
+    __slots__ = ('train', 'bn1', 'bn2')
+
+    def __init__(self, train, bn1, bn2=None):
+        self.train, self.bn1, self.bn2 = bool(train), tuple(bn1), None if bn2 is None else tuple(bn2)
+
+    @classmethod
+    def of_module(cls, att_embed, use_bn, train):
+        """att_embed: the nn.Sequential of AttModel.py:80-85 -> its state (None without use_bn)"""
+        if not use_bn:
+            return None
+        bufs = lambda m: (m.running_mean, m.running_var, m.num_batches_tracked)      # noqa: E731
+        return cls(train, bufs(att_embed[0]), bufs(att_embed[4]) if use_bn == 2 else None)
+
+    def eval(self):
+        return RegionBN(False, self.bn1, self.bn2)
+
+
+def _check_bn(P, bn):
+    has = att_linear(P) == 'att_embed.1'
+    if has and bn is None:
+        raise _lib.CapmiError('these parameters have BatchNorm layers around att_embed (use_bn): the prefill needs their running '
+                              'buffers (engine_common.RegionBN)')
+    if bn is not None and (not has or ((ATT_BN2 + '.weight') in P) != (bn.bn2 is not None)):
+        raise _lib.CapmiError('the BatchNorm state does not match the parameters (use_bn)')
+
+
+def prepare(P, fc_feats, att_feats, att_masks=None, drop_fc=None, drop_att=None, ws=None, out=None, bn=None):
     """AttModel._prepare_feature (AttModel.py:114-124): MFMA GEMMs with fused bias/ReLU/dropout epilogues.  Padded regions
     (att_masks == 0) are zeroed like pad_packed_sequence does (44-49).  fc_feats None: the family has no fc_embed (Att2in2).
-    out: optional (fc [B,R], att [B,K,R], p_att [B,K,A]) contiguous targets (slices of a caller's larger buffers)."""
+    out: optional (fc [B,R], att [B,K,R], p_att [B,K,A]) contiguous targets (slices of a caller's larger buffers).
+    bn: the RegionBN of a use_bn model -- BatchNorm1d in front of the Linear, with use_bn 2 another behind the dropout, both over
+    the valid region rows only (pack_wrapper); att_masks None counts all B * K rows."""
+    _check_bn(P, bn)
     if att_masks is not None:
         max_len = clip_len(att_masks)          # clip_att, AttModel.py:106-112
         att_feats = att_feats[:, :max_len].contiguous()
@@ -58,9 +101,11 @@ def prepare(P, fc_feats, att_feats, att_masks=None, drop_fc=None, drop_att=None,
         if drop_att is not None:
             drop_att = drop_att[:, :max_len].contiguous()
     B, K = att_feats.shape[:2]
-    R = P['att_embed.0.weight'].shape[0]
+    lin = att_linear(P)
+    R = P[lin + '.weight'].shape[0]
     pr = Prepared()
     pr.K = K
+    pr.bn, pr.bn1, pr.bn2, pr.att_pre, pr.bn_keep = bn, None, None, None, None
     pr.att_in, pr.drop_fc = att_feats.contiguous(), drop_fc
     o_fc, o_att, o_patt = out if out is not None else (None, None, None)
     pr.fc_in = pr.fc = None
@@ -72,9 +117,21 @@ def prepare(P, fc_feats, att_feats, att_masks=None, drop_fc=None, drop_att=None,
         m = att_masks.unsqueeze(-1).expand(B, K, R)
         att_mask_full = (m if drop_att is None else m * drop_att).contiguous()
     pr.drop_att = att_mask_full
-    att2d = ops.linear(pr.att_in.view(B * K, -1), P['att_embed.0.weight'], P['att_embed.0.bias'], relu=True,
-                       mul_mask=None if att_mask_full is None else att_mask_full.view(B * K, R), ws=ws,
-                       out=None if o_att is None else o_att.view(B * K, R))
+    x2d = pr.att_in.view(B * K, -1)
+    o_att2d = None if o_att is None else o_att.view(B * K, R)
+    rows = None if att_masks is None else att_masks.view(B * K)
+    if bn is not None:
+        # BatchNorm1d(att_feat_size): the normalised rows are written once and feed the GEMM ("Batch normalization")
+        pr.bn1 = ops.bn_stats(x2d, rows, bn.train, *bn.bn1)
+        x2d = ops.bn_apply(x2d, rows, pr.bn1[3], pr.bn1[1], P[ATT_BN1 + '.weight'], P[ATT_BN1 + '.bias'])
+    two = bn is not None and bn.bn2 is not None
+    att2d = ops.linear(x2d, P[lin + '.weight'], P[lin + '.bias'], relu=True,
+                       mul_mask=None if att_mask_full is None else att_mask_full.view(B * K, R), ws=ws, out=None if two else o_att2d)
+    if two:
+        # BatchNorm1d(rnn_size) behind ReLU / dropout; the padded rows of its output are zero (pad_packed_sequence)
+        pr.att_pre = att2d
+        pr.bn2 = ops.bn_stats(att2d, rows, bn.train, *bn.bn2)
+        att2d = ops.bn_apply(att2d, rows, pr.bn2[3], pr.bn2[1], P[ATT_BN2 + '.weight'], P[ATT_BN2 + '.bias'], out=o_att2d)
     pr.att = att2d.view(B, K, R)
     pr.p_att = ops.linear(att2d, P['ctx2att.weight'], P['ctx2att.bias'], ws=ws,
                           out=None if o_patt is None else o_patt.view(B * K, -1)).view(B, K, -1)
@@ -112,14 +169,29 @@ def prepare_backward(P, pr, d_fc, d_att, d_p_att, grads, ws=None, group=True, ca
     ops.gemm([(dp, A, P['ctx2att.weight'], R, A, 1)], B * K, R, d_att_total, a_layout=0, b_layout=1, accumulate=True, ws=ws)
     # att_embed: att = drop(relu(x W^T + b)).  relu gate: pre-activation > 0  <=>  relu output > 0; with dropout the saved output
     # may be zero for kept units only if relu clipped, and for dropped units the mask already zeroes the gradient.
-    d_pre = relu_drop_bwd(d_att_total, att2d, None if pr.drop_att is None else pr.drop_att.view(B * K, R))
-    dw(d_pre, pr.att_in.view(B * K, -1), 'att_embed.0.weight', 'att_embed.0.bias')
+    bn = getattr(pr, 'bn', None)
+    lin = att_linear(P)
+    rows = None if pr.att_masks is None else pr.att_masks.view(B * K)
+    d_h, y_saved = d_att_total, att2d
+    if bn is not None and bn.bn2 is not None:
+        # the second BatchNorm: its full Jacobian over the valid rows; the ReLU gate reads the saved pre-BN activation
+        mean2, rstd2, count2, _ = pr.bn2
+        y_saved = pr.att_pre
+        d_h = ops.bn_backward(d_att_total, y_saved, rows, mean2, rstd2, P[ATT_BN2 + '.weight'], count2, bn.train,
+                              grads[ATT_BN2 + '.weight'], grads[ATT_BN2 + '.bias'], dx=d_att_total)
+    d_pre = relu_drop_bwd(d_h, y_saved, None if pr.drop_att is None else pr.drop_att.view(B * K, R))
+    # with use_bn the weight-gradient item still reads the RAW rows: ops.bn_linear_bwd below turns G0 = d_pre^T x into the
+    # gradients of the Linear and of the BatchNorm in front of it
+    dw(d_pre, pr.att_in.view(B * K, -1), lin + '.weight', lin + '.bias')
     d_pre_fc = None
     if pr.fc is not None:
         d_pre_fc = relu_drop_bwd(d_fc, pr.fc, pr.drop_fc)
         dw(d_pre_fc, pr.fc_in, 'fc_embed.0.weight', 'fc_embed.0.bias')
     if items:
         ops.gemm_group_tn(items, ws=ws, cache_key=cache_key)
+    if bn is not None:
+        pr.bn_keep = ops.bn_linear_bwd(grads[lin + '.weight'], grads[lin + '.bias'], P[lin + '.weight'], pr.bn1[0], pr.bn1[1],
+                                 P[ATT_BN1 + '.weight'], P[ATT_BN1 + '.bias'], grads[ATT_BN1 + '.weight'], grads[ATT_BN1 + '.bias'])
     return d_pre, d_pre_fc, dp
 
 

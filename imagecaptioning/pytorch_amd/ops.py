@@ -935,3 +935,78 @@ def region_rows_build(src, boxes, table_host, table, dst, norm_att, use_box, nor
                                       dst.stride(0) if dst.shape[0] > 1 else W, int(bool(norm_att)), int(use_box), int(bool(norm_box)),
                                       stream_ptr()), 'capmi_region_rows_build')
     region_rows_build_calls += 1
+
+
+# ---- BatchNorm1d over the valid region rows (use_bn; capmi.h capmi_bn_*, region_norm.hip) ----------------------------------------
+BN_EPS, BN_MOMENTUM = 1e-5, 0.1         # nn.BatchNorm1d's defaults, the reference's (AttModel.py:80-85)
+
+
+def _bn_partial(rows, D, dev, counts=True):
+    nrb = int(lib.capmi_bn_row_blocks(rows))
+    return torch.empty(nrb * (2 * D + (1 if counts else 0)), dtype=_f32, device=dev), nrb
+
+
+def bn_stats(x, mask, train, running_mean=None, running_var=None, num_batches_tracked=None, eps=BN_EPS, momentum=BN_MOMENTUM):
+    """x [rows, D], mask [rows] floats (0 = padded row) or None -> (mean [D], rstd [D], count [1], shift [2, D]: the mean as the
+    pair (pivot, mean - pivot) bn_apply subtracts).
+    train: batch statistics over the valid rows (biased variance); the running buffers (unbiased variance, momentum) and
+    num_batches_tracked (int64 [] / [1]) are updated in place on the stream when given.  Eval: the running statistics, nothing is
+    updated.  No host read either way."""
+    _chk(x, mask, running_mean, running_var)
+    rows, D = x.shape
+    mean, rstd = torch.empty(D, dtype=_f32, device=x.device), torch.empty(D, dtype=_f32, device=x.device)
+    count = torch.empty(1, dtype=_f32, device=x.device)
+    shift = torch.empty(2, D, dtype=_f32, device=x.device)
+    partial = None
+    if train:
+        if mask is not None and mask.numel() != rows:
+            raise _lib.CapmiError('bn_stats: mask must hold one float per row')
+        if num_batches_tracked is not None and not (num_batches_tracked.is_cuda and num_batches_tracked.dtype == torch.long):
+            raise _lib.CapmiError('bn_stats: num_batches_tracked must be an int64 device tensor')
+        partial, _ = _bn_partial(rows, D, x.device)
+        check(lib.capmi_bn_stats(ptr(x), ptr(mask), rows, D, ptr(partial), stream_ptr()), 'capmi_bn_stats')
+    elif running_mean is None or running_var is None:
+        raise _lib.CapmiError('bn_stats: eval mode needs the running statistics')
+    check(lib.capmi_bn_finalize(ptr(partial), ptr(x), ptr(mask), rows, D, int(bool(train)), float(eps), float(momentum), ptr(running_mean),
+                                ptr(running_var), ptr(num_batches_tracked), ptr(mean), ptr(rstd), ptr(count), ptr(shift),
+                                stream_ptr()), 'capmi_bn_finalize')
+    return mean, rstd, count, shift
+
+
+def bn_apply(x, mask, shift, rstd, gamma, beta, out=None):
+    """y = (x - mean) * rstd * gamma + beta on valid rows, 0 on padded rows; shift: bn_stats' fourth result"""
+    _chk(x, mask, shift, rstd, gamma, beta, out)
+    rows, D = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    check(lib.capmi_bn_apply(ptr(x), ptr(mask), ptr(shift), ptr(rstd), ptr(gamma), ptr(beta), ptr(out), rows, D, stream_ptr()),
+          'capmi_bn_apply')
+    return out
+
+
+def bn_backward(dy, x, mask, mean, rstd, gamma, count, train, dgamma, dbeta, dx=None):
+    """Backward of bn_apply(bn_stats(x)) over the valid rows: dgamma / dbeta [D] are overwritten, -> dx (0 on padded rows; may be dy).
+    train: the full BatchNorm Jacobian (batch statistics); eval: the statistics are constants."""
+    _chk(dy, x, mask, mean, rstd, gamma, dgamma, dbeta, dx)
+    rows, D = x.shape
+    partial, nrb = _bn_partial(rows, D, x.device, counts=False)
+    check(lib.capmi_bn_bwd_partial(ptr(dy), ptr(x), ptr(mask), ptr(mean), ptr(rstd), rows, D, ptr(partial), stream_ptr()),
+          'capmi_bn_bwd_partial')
+    check(lib.capmi_bn_colsum_parts(ptr(partial), nrb, D, ptr(dbeta), ptr(dgamma), stream_ptr()), 'capmi_bn_colsum_parts')
+    if dx is None:
+        dx = torch.empty_like(dy)
+    check(lib.capmi_bn_bwd_dx(ptr(dy), ptr(x), ptr(mask), ptr(mean), ptr(rstd), ptr(gamma), ptr(dgamma), ptr(dbeta), ptr(count),
+                              int(bool(train)), ptr(dx), rows, D, stream_ptr()), 'capmi_bn_bwd_dx')
+    return dx
+
+
+def bn_linear_bwd(G, db, W, mean, rstd, gamma, beta, dgamma, dbeta):
+    """BatchNorm in front of a Linear whose input needs no gradient: G [R, D] holds d_pre^T x on the RAW input and becomes the
+    Linear's weight gradient; dgamma / dbeta [D] are overwritten (capmi.h capmi_bn_linear_bwd)."""
+    _chk(G, db, W, mean, rstd, gamma, beta, dgamma, dbeta)
+    R, D = W.shape
+    partial, nrb = _bn_partial(R, D, W.device, counts=False)
+    check(lib.capmi_bn_linear_bwd(ptr(G), ptr(db), ptr(W), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), R, D, ptr(partial),
+                                  stream_ptr()), 'capmi_bn_linear_bwd')
+    check(lib.capmi_bn_colsum_parts(ptr(partial), nrb, D, ptr(dgamma), ptr(dbeta), stream_ptr()), 'capmi_bn_colsum_parts')
+    return partial

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib, ops, engine_common
 from ._lib import lib, ptr, check, stream_ptr
-from .engine_common import Prepared, RolloutBase, fill_struct, prepare          # noqa: F401  (Prepared, prepare: this module's API)
+from .engine_common import Prepared, RegionBN, RolloutBase, fill_struct, prepare          # noqa: F401  (Prepared, RegionBN, prepare: this module's API)
 
 _f32 = torch.float32
 
@@ -25,6 +25,7 @@ PARAM_KEYS = ('embed.0.weight', 'fc_embed.0.weight', 'fc_embed.0.bias', 'att_emb
               'core.lang_lstm.bias_ih', 'core.lang_lstm.bias_hh', 'core.attention.h2att.weight',
               'core.attention.h2att.bias', 'core.attention.alpha_net.weight', 'core.attention.alpha_net.bias',
               'logit.weight', 'logit.bias')
+
 
 _W_FIELDS = (('embed', 'embed.0.weight'), ('att_w_ih', 'core.att_lstm.weight_ih'), ('att_w_hh', 'core.att_lstm.weight_hh'),
              ('att_b_ih', 'core.att_lstm.bias_ih'), ('att_b_hh', 'core.att_lstm.bias_hh'),

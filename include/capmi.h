@@ -1587,6 +1587,48 @@ int capmi_sentset_reduce(const capmi_sentset *s, double *out, void *stream);
 int capmi_region_rows_build(const float *src, const float *boxes, const int32_t *table_host, const int32_t *table, int n_images,
                             int D, float *dst, int64_t ldd, int norm_att, int use_box, int norm_box, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * BatchNorm1d over the valid region rows (region_norm.hip; use_bn, AttModel.py:80-85 under pack_wrapper :44-49).
+ *   x / y / dy / dx  [rows, D] float32, rows = B * K; mask: one float per row, 0 = padded region (NULL: every row is valid)
+ *   M, the number of valid rows, is counted on the device; nothing here waits for the device.
+ * capmi_bn_row_blocks(rows): row blocks nrb of the statistics / backward partials.
+ * capmi_bn_stats:    partial [nrb][2][D] (mean minus the pivot -- the column's value in the first valid row --, sum of squared deviations
+ *                    of the block's valid rows), then nrb valid-row counts: nrb * (2 * D + 1) floats.  One read of x, no atomics.
+ * capmi_bn_finalize: x / mask / rows: those of capmi_bn_stats (the pivot row is read again; x may be NULL with train == 0).
+ *                    train != 0: merges the blocks in block order (Chan et al.) -> mean [D], rstd [D] = 1 / sqrt(biased var + eps),
+ *                    count [1] = M; running_mean / running_var (unbiased variance, `momentum`) and num_batches_tracked (+1) are
+ *                    updated in place (NULL: not kept).  M < 2: mean / rstd are those of the M rows (variance 0), the running buffers
+ *                    and the counter are left alone.  train == 0: mean = running_mean, rstd = 1 / sqrt(running_var + eps), count = 0,
+ *                    partial is not read, nothing is updated.
+ *                    Either way shift [2][D] receives the mean as a pair: the pivot (0 in eval mode) and the mean minus the pivot.
+ * capmi_bn_apply:    y = ((x - shift[0]) - shift[1]) * rstd * gamma + beta on valid rows, 0 on padded rows.  y may be x.
+ * capmi_bn_bwd_partial: partial [nrb][2][D]: per row block sum dy and sum dy * xhat over the valid rows.
+ * capmi_bn_colsum_parts: out0 / out1 [D] (either may be NULL) = the sums of partial[p][0] / partial[p][1] over p < nparts, in order.
+ * capmi_bn_bwd_dx:   train: dx = gamma * rstd * (dy - (dbeta + xhat * dgamma) / count) on valid rows; eval: gamma * rstd * dy; 0 on
+ *                    padded rows.  dx may be dy.
+ * capmi_bn_linear_bwd: BatchNorm in front of a Linear (weight W [R, D]) whose input needs no gradient.  G holds G0 = d_pre^T x
+ *                    (the Linear's weight gradient on the RAW input) and receives dW = (G0 - db mean^T) diag(rstd * gamma) + db beta^T;
+ *                    partial [capmi_bn_row_blocks(R)][2][D] receives per 16 rows of W the sums of W * (G0 - db mean^T) diag(rstd)
+ *                    (d gamma) and of W * db (d beta) for capmi_bn_colsum_parts.
+ * The 16-byte path is used where D % 4 == 0 and the matrices are 16-byte aligned, dword accesses otherwise (D = 2053).
+ * CAPMI_EINVAL, before anything is launched: a NULL required pointer, rows / D / R <= 0, more than 65535 row blocks, a float pointer
+ * off 4 bytes, num_batches_tracked off 8.
+ * ------------------------------------------------------------------------------------------- */
+int capmi_bn_row_blocks(int rows);
+int capmi_bn_stats(const float *x, const float *mask, int rows, int D, float *partial, void *stream);
+int capmi_bn_finalize(const float *partial, const float *x, const float *mask, int rows, int D, int train, float eps, float momentum,
+                      float *running_mean, float *running_var, int64_t *num_batches_tracked, float *mean, float *rstd, float *count,
+                      float *shift, void *stream);
+int capmi_bn_apply(const float *x, const float *mask, const float *shift, const float *rstd, const float *gamma, const float *beta,
+                   float *y, int rows, int D, void *stream);
+int capmi_bn_bwd_partial(const float *dy, const float *x, const float *mask, const float *mean, const float *rstd, int rows, int D,
+                         float *partial, void *stream);
+int capmi_bn_colsum_parts(const float *partial, int nparts, int D, float *out0, float *out1, void *stream);
+int capmi_bn_bwd_dx(const float *dy, const float *x, const float *mask, const float *mean, const float *rstd, const float *gamma,
+                    const float *dgamma, const float *dbeta, const float *count, int train, float *dx, int rows, int D, void *stream);
+int capmi_bn_linear_bwd(float *G, const float *db, const float *W, const float *mean, const float *rstd, const float *gamma,
+                        const float *beta, int R, int D, float *partial, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
