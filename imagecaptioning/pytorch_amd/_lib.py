@@ -247,6 +247,12 @@ class Ppo(C.Structure):
                 [(k, c_f) for k in ('lp_new', 'lp_old', 'seq', 'scores', 'row_stats', 'msum', 'out', 'loss_rows', 'g_out', 'grad')])
 
 
+class XeLoss(C.Structure):
+    """capmi_xe_loss (include/capmi.h): LanguageModelCriterion / LabelSmoothing of one teacher-forced pass, forward and backward"""
+    _fields_ = ([(k, C.c_int) for k in ('N', 'T', 'V1', 'tok_ld', 'mask_ld', 'per_row')] + [('smoothing', C.c_double)] +
+                [(k, c_f) for k in ('logp', 'tok', 'mask', 'pos', 'msum', 'loss', 'g_out', 'g_sel', 'g_sum')])
+
+
 LANGEVAL_LMAX = 64     # capmi.h CAPMI_LANGEVAL_LMAX
 CIDERD_COOKED_BYTES = 4392     # capmi.h CAPMI_CIDERD_COOKED_BYTES
 SELF_CIDER_NMAX = 32   # capmi.h CAPMI_SELF_CIDER_NMAX
@@ -410,6 +416,8 @@ SIGNATURES = {
     'capmi_ensemble_logprobs': [C.POINTER(Ensemble), _P],
     'capmi_ppo_loss_fwd': [C.POINTER(Ppo), _P],
     'capmi_ppo_loss_bwd': [C.POINTER(Ppo), _P],
+    'capmi_xe_loss_fwd': [C.POINTER(XeLoss), _P],
+    'capmi_xe_loss_bwd': [C.POINTER(XeLoss), _P],
     'capmi_langeval_build': [C.POINTER(LangEval), _P],
     'capmi_langeval_add': [C.POINTER(LangEval), _P, _I, _I, _P, _P],
     'capmi_langeval_reduce': [C.POINTER(LangEval), _P, _P, _P],

@@ -11,7 +11,7 @@ import torch.nn as nn
 
 from ..utils.rewards import get_scores, get_self_cider_scores
 from imagecaptioning.pytorch_amd.ciderd import nsc_advantage
-from imagecaptioning.pytorch_amd.sparse_logp import select_logp, sum_logp, fused_reward_criterion
+from imagecaptioning.pytorch_amd.sparse_logp import select_logp, sum_logp, fused_reward_criterion, fused_xe_criterion
 
 
 def _shifted_mask(seq, like):
@@ -43,6 +43,10 @@ class LanguageModelCriterion(nn.Module):
         if target.ndim == 3:
             target = target.reshape(-1, target.shape[2])
             mask = mask.reshape(-1, mask.shape[2])
+        # device float32 log-probs: capmi_xe_loss_fwd / _bwd read the uncut labels and masks through their row pitch
+        fused = fused_xe_criterion(input, target, mask, 0.0, per_row=(reduction == 'none'))
+        if fused is not None:
+            return fused
         T = input.size(1)
         target = target[:, :T]
         mask = mask[:, :T].to(input)
@@ -64,6 +68,11 @@ class LabelSmoothing(nn.Module):
         if target.ndim == 3:
             target = target.reshape(-1, target.shape[2])
             mask = mask.reshape(-1, mask.shape[2])
+        if 0.0 < self.smoothing < 1.0:
+            # device float32 log-probs: every dense row is read once by capmi_xe_loss_fwd, nothing dense goes through ATen
+            fused = fused_xe_criterion(input, target, mask, self.smoothing, per_row=(reduction == 'none'))
+            if fused is not None:
+                return fused
         N, T, V1 = input.shape
         tgt2 = target[:, :T]
         target = tgt2.reshape(-1)

@@ -880,6 +880,72 @@ def ppo_loss_bwd(lp_old, seq, row_stats, msum, g_out, n, eps=0.2, kl_coef=0.02, 
     return out
 
 
+def _xe_desc(N, T, V1, tok, mask, smoothing, per_row, what):
+    for name, t, dt in (('tok', tok, torch.int64), ('mask', mask, _f32)):
+        if t is None:
+            continue
+        if not t.is_cuda or t.dtype != dt or t.dim() != 2 or t.shape[0] != N:
+            raise _lib.CapmiError('%s: %s [%d, >= T] %s on the device expected (got %s %s %s)'
+                                  % (what, name, N, dt, tuple(t.shape), t.dtype, t.device))
+        if t.shape[1] > 1 and t.stride(1) != 1:
+            raise _lib.CapmiError('%s: the rows of %s must be dense (stride %d)' % (what, name, t.stride(1)))
+    p = _lib.XeLoss()
+    p.N, p.T, p.V1 = int(N), int(T), int(V1)
+    p.per_row = int(bool(per_row))
+    p.smoothing = float(smoothing)
+    # a [N, >= T] buffer is read through its row pitch: the cut views target[:, :T] / mask[:, :T] of the criteria need no copy
+    # (a buffer narrower than T hands its width over as the pitch, which the entry point rejects)
+    def pitch(t):
+        return t.stride(0) if N > 1 and t.shape[1] >= T else t.shape[1]
+    p.mask, p.mask_ld = mask.data_ptr(), pitch(mask)
+    if tok is not None:
+        p.tok, p.tok_ld = tok.data_ptr(), pitch(tok)
+    else:
+        p.tok_ld = p.T
+    return p
+
+
+def xe_loss_fwd(logp, tok, mask, smoothing=0.0, per_row=False):
+    """LanguageModelCriterion (smoothing == 0) / LabelSmoothing (losses.py:204-265) in the two launches of capmi_xe_loss_fwd.
+    logp [N, T, V1] float32 contiguous; tok [N, >= T] int64 and mask [N, >= T] float32 with dense rows (any row pitch: only the
+    first T columns are read).  Returns (loss [1] ('mean') or [N] ('none'), msum [1] or [N], pos [N, T] the per-position
+    values).  All stay on the device."""
+    if logp.dim() != 3 or logp.dtype != _f32:
+        raise _lib.CapmiError('xe_loss_fwd: log-probs [N, T, V1] float32 expected (got %s %s)' % (tuple(logp.shape), logp.dtype))
+    _chk(logp)
+    N, T, V1 = logp.shape
+    p = _xe_desc(N, T, V1, tok, mask, smoothing, per_row, 'xe_loss_fwd')
+    dev = logp.device
+    pos = torch.empty(N, T, dtype=_f32, device=dev)
+    msum = torch.empty(N if per_row else 1, dtype=_f32, device=dev)
+    loss = torch.empty(N if per_row else 1, dtype=_f32, device=dev)
+    p.logp, p.pos, p.msum, p.loss = logp.data_ptr(), pos.data_ptr(), msum.data_ptr(), loss.data_ptr()
+    check(lib.capmi_xe_loss_fwd(C.byref(p), stream_ptr()), 'capmi_xe_loss_fwd')
+    return loss, msum, pos
+
+
+def xe_loss_bwd(mask, msum, T, V1, smoothing=0.0, per_row=False, g_out=None):
+    """the sparse gradient of xe_loss_fwd (capmi_xe_loss_bwd, one launch): mask / smoothing / per_row as given to the forward,
+    msum as it returned it, g_out None (the factor 1: a scalar loss passes its upstream gradient on as the sink's `scale`) or the
+    upstream gradient, [1] / [N] float32 on the device.  Returns (g_sel [N, T], g_sum [N, T] or None without smoothing)."""
+    N = mask.shape[0] if mask.dim() == 2 else -1
+    p = _xe_desc(N, T, V1, None, mask, smoothing, per_row, 'xe_loss_bwd')
+    if msum.dtype != _f32 or msum.numel() != (N if per_row else 1):
+        raise _lib.CapmiError('xe_loss_bwd: msum as returned by xe_loss_fwd expected')
+    if g_out is not None:
+        g_out = g_out.reshape(-1)
+        if g_out.dtype != _f32 or g_out.numel() != (N if per_row else 1):
+            raise _lib.CapmiError('xe_loss_bwd: upstream gradient of %d float32 values expected (got %s %s)'
+                                  % (N if per_row else 1, tuple(g_out.shape), g_out.dtype))
+        g_out = g_out.contiguous()
+    _chk(msum, g_out)
+    g_sel = torch.empty(N, T, dtype=_f32, device=mask.device)
+    g_sum = torch.empty(N, T, dtype=_f32, device=mask.device) if smoothing > 0 else None
+    p.msum, p.g_out, p.g_sel, p.g_sum = msum.data_ptr(), ptr(g_out), g_sel.data_ptr(), ptr(g_sum)
+    check(lib.capmi_xe_loss_bwd(C.byref(p), stream_ptr()), 'capmi_xe_loss_bwd')
+    return g_sel, g_sum
+
+
 def clip_len(att_masks, width=None):
     """Longest valid region count of the batch -- the K that clip_att (AttModel.py:106-112) truncates to.
 

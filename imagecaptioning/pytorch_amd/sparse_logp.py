@@ -155,6 +155,81 @@ def fused_reward_criterion(logp, seq, reward, per_row=False):
     return _FusedReward.apply(full, sink, reward.float(), n_used, per_row)
 
 
+class _FusedXE(torch.autograd.Function):
+    """LanguageModelCriterion / LabelSmoothing on the device (capmi_xe_loss_fwd: two launches; backward = capmi_xe_loss_bwd, one
+    launch that writes the sparse gradient, handed to the sink with the tokens and -- for a scalar loss -- the upstream scalar)."""
+
+    @staticmethod
+    def forward(ctx, logp, sink, tok, mask, smoothing, per_row):
+        from . import ops
+        loss, msum, _ = ops.xe_loss_fwd(logp.detach(), tok, mask, smoothing, per_row)
+        ctx.sink, ctx.tok, ctx.mask, ctx.msum = sink, tok, mask, msum
+        ctx.cfg = (logp.shape[1], logp.shape[2], smoothing, per_row)
+        return loss if per_row else loss.squeeze(0)
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import ops
+        T, V1, smoothing, per_row = ctx.cfg
+        sink = ctx.sink
+        sink.tok = ctx.tok[:, :T].contiguous()         # the kernels read through the pitch; split_grad wants the cut [N, T]
+        if per_row:                                    # one upstream value per row
+            sink.g_sel, sink.g_sum = ops.xe_loss_bwd(ctx.mask, ctx.msum, T, V1, smoothing, True, g.reshape(-1).float())
+        else:                                          # scalar loss: the upstream gradient stays a device scalar
+            sink.g_sel, sink.g_sum = ops.xe_loss_bwd(ctx.mask, ctx.msum, T, V1, smoothing, False)
+            sink.scale = g.reshape(1).float().contiguous()
+        return None, None, None, None, None, None
+
+
+def _rows_ok(t, N, T):
+    """a [N, >= T] buffer whose first T columns capmi_xe_loss_fwd can read through a row pitch"""
+    return (t.ndim == 2 and t.shape[0] == N and t.shape[1] >= T and (t.shape[1] == 1 or t.stride(1) == 1)
+            and (N == 1 or t.stride(0) >= T))
+
+
+def fused_xe_route(input, target, mask, smoothing=0.0):
+    """Which way the XE criteria take on `input` [N, T, V1] with the 2-D `target` / `mask` (cut to T columns or not):
+    None = today's select_logp / sum_logp route; 'forward' = the kernel without a graph (no gradient asked for: validation loss);
+    'sink' = the kernel under _FusedXE, its gradient going to the tensor's LogpSink.  CAPMI_FUSED_XE=0 forces None (A/B runs)."""
+    if _DENSE or os.environ.get('CAPMI_FUSED_XE', '1') == '0':
+        return None
+    if not (input.is_cuda and input.dtype == torch.float32 and input.ndim == 3 and input.is_contiguous()):
+        return None
+    N, T, V1 = input.shape
+    if N < 1 or T < 1 or V1 < (2 if smoothing > 0 else 1) or not (0.0 <= smoothing < 1.0):
+        return None
+    if not (target.dtype == torch.int64 and target.device == input.device and _rows_ok(target, N, T)):
+        return None
+    if not (mask.device == input.device and not mask.requires_grad and mask.ndim == 2 and mask.shape[0] == N and mask.shape[1] >= T):
+        return None
+    if not (input.requires_grad and torch.is_grad_enabled()):
+        return 'forward'
+    sink = getattr(input, '_capmi_sink', None)
+    if sink is None or sink.sel_taken or (smoothing > 0 and sink.sum_taken):
+        return None                                   # no sink (a dense gradient is wanted), or one already gathered from
+    return 'sink'
+
+
+def fused_xe_criterion(input, target, mask, smoothing=0.0, per_row=False):
+    """LanguageModelCriterion (smoothing == 0) / LabelSmoothing of `input` through capmi_xe_loss_fwd / _bwd, or None when the
+    inputs are not eligible (then the caller takes the generic route).  `target` / `mask`: 2-D, at least input.size(1) wide."""
+    route = fused_xe_route(input, target, mask, smoothing)
+    if route is None:
+        return None
+    T = input.shape[1]
+    if mask.dtype != torch.float32 or not _rows_ok(mask, input.shape[0], T):
+        mask = mask[:, :T].to(input).contiguous()     # (the reference's mask[:, :T].to(input))
+    if route == 'forward':
+        from . import ops
+        loss = ops.xe_loss_fwd(input.detach(), target, mask, smoothing, per_row)[0]
+        return loss if per_row else loss.squeeze(0)
+    sink = input._capmi_sink
+    sink.sel_taken = True
+    if smoothing > 0:
+        sink.sum_taken = True
+    return _FusedXE.apply(input, sink, target, mask, float(smoothing), per_row)
+
+
 def split_grad(g_logp, sink, like=None):
     """What a rollout backward receives -> (dense gradient or None, SparseLogpGrad struct or None, keep-alive tuple).
     `like`: the saved dense log-probs, for the (rare) case that no gradient at all arrived."""

@@ -1398,6 +1398,52 @@ int capmi_ppo_loss_fwd(const capmi_ppo *p, void *stream);
 int capmi_ppo_loss_bwd(const capmi_ppo *p, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Cross-entropy criteria of the teacher-forced pass (captioning/modules/losses.py:204-265): LanguageModelCriterion
+ * (smoothing == 0) and LabelSmoothing (0 < smoothing < 1) over the log-probs logp [N, T, V1] (float, contiguous), the targets
+ * tok [N, tok_ld] int64 and the mask [N, mask_ld] float, tok_ld, mask_ld >= T: both criteria cut labels and masks to the T
+ * columns of the input (target[:, :T]); the uncut buffers are read through their row pitch, nothing is copied.
+ * Position (n, t), with s = tok[n, t] and m = mask[n, t]:
+ *   smoothing == 0:  c = -logp[n,t,s] m                                   (one entry gathered; the dense row is not read)
+ *   smoothing  > 0:  c = (ent - off sum_v logp[n,t,v] - (conf - off) logp[n,t,s]) m
+ *                    off = smoothing / (V1 - 1), conf = 1 - smoothing, ent = (V1-1) off ln off + conf ln conf = sum_v q ln q of the
+ *                    smoothed target distribution q (the three are formed in double on the host and passed by value)
+ *   loss = sum c / sum m ([1], 'mean');  per_row ('none', the drop_worst route): loss[n] = sum_t c / sum_t m ([N]).
+ * A position with m == 0 is not read and contributes an exact 0; a mask sum of 0 gives 0 / 0 = NaN as the reference does.  A token
+ * outside [0, V1) is not read and gives NaN.
+ *
+ * capmi_xe_loss_fwd: two launches, no float atomics.  Stage 1 writes c to pos [N*T]: one thread per position without smoothing;
+ *   with it one workgroup per (n, t) row, the row read once (scalar head up to the 16-byte boundary, float4 body, scalar tail:
+ *   V1 is odd in general, so row bases fall off the boundary).  Stage 2, one workgroup, folds pos and the mask in double in a
+ *   fixed order and writes loss and msum (the mask sums the backward needs: [1], or [N] with per_row).  Two runs on the same
+ *   inputs are bit-equal.
+ * capmi_xe_loss_bwd: one launch over [N, T]; writes the gradient in the sparse form of capmi_sparse_logp_grad:
+ *     g_sel[n,t] = -(conf - off) m / msum u      (d loss / d logp[n,t,s])
+ *     g_sum[n,t] = -off m / msum u               (d loss / d sum_v logp[n,t,v]; smoothing > 0 only, else g_sum is not written)
+ *   msum = msum[0] ('mean') or msum[n] (per_row); u = g_out[0] / g_out[n], the upstream gradient on the device, or 1 when g_out
+ *   is NULL (a scalar loss hands its upstream gradient on as capmi_sparse_logp_grad.scale, no host read).  No dense [N, T, V1]
+ *   gradient is produced.
+ * CAPMI_EINVAL: a NULL pointer that the call reads or writes, N, T or V1 <= 0, a pitch below T, smoothing outside [0, 1),
+ * smoothing > 0 with V1 < 2.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct capmi_xe_loss {
+    int N, T, V1;
+    int tok_ld, mask_ld;             /* row pitches of tok / mask, elements, >= T */
+    int per_row;                     /* 0: reduction 'mean', 1: 'none' */
+    double smoothing;                /* 0: LanguageModelCriterion; (0, 1): LabelSmoothing */
+    const float *logp;               /* [N, T, V1] (fwd) */
+    const int64_t *tok;              /* [N, tok_ld] targets (fwd) */
+    const float *mask;               /* [N, mask_ld] */
+    float *pos;                      /* [N*T] scratch: the per-position values (fwd) */
+    float *msum;                     /* [1] or [N] mask sums (written by fwd, read by bwd) */
+    float *loss;                     /* [1] or [N] (fwd) */
+    const float *g_out;              /* NULL, or [1] / [N] upstream gradient (bwd) */
+    float *g_sel;                    /* [N*T] (bwd) */
+    float *g_sum;                    /* [N*T] (bwd, smoothing > 0) */
+} capmi_xe_loss;
+int capmi_xe_loss_fwd(const capmi_xe_loss *p, void *stream);
+int capmi_xe_loss_bwd(const capmi_xe_loss *p, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Corpus language evaluation without Java: coco-caption's Cider, Bleu (option 'closest') and Rouge over token ids, for the
  * validation pass (eval_utils.language_eval -> lang_stats['CIDEr'], 'Bleu_1'..'Bleu_4', 'ROUGE_L').  A caption is the tokens of
  * its int64 row before the first 0 (the whole row when it holds none); ids are below 65535.  Restated from the published
