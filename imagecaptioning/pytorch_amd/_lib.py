@@ -257,6 +257,7 @@ LANGEVAL_LMAX = 64     # capmi.h CAPMI_LANGEVAL_LMAX
 CIDERD_COOKED_BYTES = 4392     # capmi.h CAPMI_CIDERD_COOKED_BYTES
 SELF_CIDER_NMAX = 32   # capmi.h CAPMI_SELF_CIDER_NMAX
 LANGEVAL_E_TABLE_FULL, LANGEVAL_E_TOKEN, LANGEVAL_E_IMAGE = 1, 2, 4      # capmi.h CAPMI_LANGEVAL_E_*
+DF_E_OFFSETS = 8       # capmi.h CAPMI_DF_E_OFFSETS
 
 
 class LangEval(C.Structure):
@@ -427,6 +428,8 @@ SIGNATURES = {
     'capmi_sentset_add': [C.POINTER(SentSet), _P, _I, _I, _I, _P],
     'capmi_sentset_add_first': [C.POINTER(SentSet), _P, _I, _I, _P, _P, _P],
     'capmi_sentset_reduce': [C.POINTER(SentSet), _P, _P],
+    'capmi_df_count': [_P, _I, _I64, _P, _P, _I64, _P, _P, _I, _P, _P, C.c_uint32, _P, _P, _P],
+    'capmi_df_finalize': [_P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P],
     'capmi_updown_rollout_fwd': [C.POINTER(UpDownWeights), C.POINTER(UpDownRollout), _P],
     'capmi_updown_rollout_bwd': [C.POINTER(UpDownWeights), C.POINTER(UpDownRollout), _P, C.POINTER(UpDownBwdScratch),
                                  C.POINTER(UpDownGrads), _P],

@@ -39,11 +39,16 @@ def pack_ngram(tokens):
     return k
 
 
+def table_cap(n, load_factor=0.5):
+    """slots of the table of n distinct n-grams: the power of two (at least 16) that keeps the load at or below load_factor"""
+    return 1 << max(4, int(math.ceil(math.log2(max(1, n) / load_factor))))
+
+
 def build_table(document_frequency, load_factor=0.5):
     """dict {tuple[int|str] -> count} -> (keys uint64[cap], vals float64[cap]); empty slot = key 0.
     Vectorised linear-probing insertion (the COCO table has a few million n-grams)."""
     n = len(document_frequency)
-    cap = 1 << max(4, int(math.ceil(math.log2(max(1, n) / load_factor))))
+    cap = table_cap(n, load_factor)
     keys = np.zeros(cap, dtype=np.uint64)
     vals = np.zeros(cap, dtype=np.float64)
     if n == 0:
@@ -86,6 +91,70 @@ def load_df_image(path):
     return keys, vals, float(z['ref_len'])
 
 
+def save_table_image(keys, vals, ref_len, path):
+    """save_df_image for a table that is already hashed (build_df_image): the same .npz layout, read by load_df_image"""
+    np.savez(path, keys=keys, vals=vals, ref_len=np.float64(ref_len), n=np.int64(np.count_nonzero(keys)))
+    return path if str(path).endswith('.npz') else str(path) + '.npz'
+
+
+_DF_ERRORS = ((_lib.LANGEVAL_E_TABLE_FULL, 'table full: more distinct n-grams than slots'),
+              (_lib.LANGEVAL_E_TOKEN, 'a token id outside [0, 65535)'),
+              (_lib.DF_E_OFFSETS, 'malformed caption / image offsets'))
+
+
+def _df_tables(tok, cap_off, img_off, device, count_cap=None):
+    """The document-frequency image of a ragged corpus, built on the device (capmi_df_count + capmi_df_finalize, csrc/df_build.hip)
+    -> (keys int64 [cap] holding the bits of uint64, vals float64 [cap], ref_len), device tensors.  One host read (error bits and
+    the number of distinct n-grams, which sizes the image) between the two launches."""
+    from . import ops
+    dev = torch.device(device)
+
+    def put(a, keep_int32=False):
+        """-> (int64 device tensor -- int32 where kept --, the host array it came from or None)"""
+        if torch.is_tensor(a) and a.is_cuda:
+            return (a if keep_int32 and a.dtype == torch.int32 else a.to(torch.int64)).contiguous(), None
+        a = a.numpy() if torch.is_tensor(a) else np.asarray(a)
+        a = np.ascontiguousarray(a if keep_int32 and a.dtype == np.int32 else a.astype(np.int64))
+        return torch.from_numpy(a).to(dev), a
+
+    tok_d, _ = put(tok, keep_int32=True)
+    cap_d, cap_h = put(cap_off)
+    img_d, img_h = put(img_off)
+    if tok_d.dim() != 1 or cap_d.dim() != 1 or img_d.dim() != 1 or cap_d.numel() < 1 or img_d.numel() < 1:
+        raise ValueError('a corpus is tok [total_tokens], cap_off [n_caps + 1], img_off [n_img + 1]')
+    # every token starts at most four n-grams: a counting table that the corpus cannot fill beyond one half
+    count_cap = int(count_cap) if count_cap is not None else table_cap(4 * tok_d.numel())
+    if count_cap < 1 or count_cap & (count_cap - 1) or count_cap > 1 << 31:
+        raise ValueError('the counting table needs a power of two of slots, at most 2^31: got %d' % count_cap)
+    ckeys = torch.zeros(count_cap, dtype=torch.int64, device=dev)
+    counts = torch.zeros(count_cap, dtype=torch.int32, device=dev)
+    meta = torch.zeros(2, dtype=torch.int32, device=dev)                 # error bits, distinct n-grams
+    with torch.cuda.device(dev):
+        ops.df_count(tok_d, cap_d, img_d, ckeys, counts, meta, cap_h, img_h)
+        err, n = (int(x) for x in meta.tolist())                         # the one host read
+        if err:
+            raise _lib.CapmiError('capmi_df_count: ' + '; '.join(msg for bit, msg in _DF_ERRORS if err & bit))
+        cap = table_cap(n)
+        keys = torch.zeros(cap, dtype=torch.int64, device=dev)
+        vals = torch.zeros(cap, dtype=torch.float64, device=dev)
+        ops.df_finalize(ckeys, counts, keys, vals, meta)                 # cap >= 2 n: it cannot fill
+    # scripts/prepro_ngrams.py:22 returns len(tmp.crefs), and cook_append adds an entry for every image of the split, one that
+    # owns no caption included: ref_len is the number of images
+    return keys, vals, float(img_d.numel() - 1)
+
+
+def build_df_image(tok, cap_off, img_off, device=None, count_cap=None):
+    """scripts/prepro_ngrams.py's document frequencies on the device -> (keys uint64 [cap], vals float64 [cap], ref_len), the host
+    arrays load_df_image returns and save_table_image writes.  tok: the token ids of every caption back to back, each caption
+    exactly as it counts (the caller appends the <eos> = 0; nothing is cut); cap_off [n_caps + 1]: where each caption starts;
+    img_off [n_img + 1]: the first caption of each image (an image may own none).  Arrays, CPU tensors or device tensors; offsets
+    given on the host are checked there.  cap is the size build_table gives the same number of distinct n-grams; the slots may
+    differ from build_table's, a lookup does not see them."""
+    device = device or torch.device('cuda', torch.cuda.current_device())
+    keys, vals, ref_len = _df_tables(tok, cap_off, img_off, device, count_cap)
+    return keys.cpu().numpy().view(np.uint64), vals.cpu().numpy(), ref_len
+
+
 class PackedRefs(tuple):
     """(refs int32 [B,max_refs,w], n_refs int32 [B]) -- unpacks like the pair it used to be -- plus `.cooked`"""
 
@@ -119,6 +188,16 @@ class DeviceCiderD:
     def from_image(cls, path, device):
         keys, vals, ref_len = load_df_image(path)
         return cls(None, ref_len, device, _table=(keys, vals))
+
+    @classmethod
+    def from_corpus(cls, tok, cap_off, img_off, device, count_cap=None):
+        """the scorer of a ragged caption corpus (build_df_image's arguments), its table built on the device and left there"""
+        self = cls.__new__(cls)
+        self.keys, self.vals, ref_len = _df_tables(tok, cap_off, img_off, device, count_cap)
+        self.cap = int(self.keys.shape[0])
+        self.log_ref_len = math.log(ref_len)
+        self.device = device
+        return self
 
     @classmethod
     def from_pickle(cls, path, device):

@@ -1076,3 +1076,50 @@ def bn_linear_bwd(G, db, W, mean, rstd, gamma, beta, dgamma, dbeta):
                                   stream_ptr()), 'capmi_bn_linear_bwd')
     check(lib.capmi_bn_colsum_parts(ptr(partial), nrb, D, ptr(dgamma), ptr(dbeta), stream_ptr()), 'capmi_bn_colsum_parts')
     return partial
+
+
+# ---- CIDEr-D document frequencies of a caption corpus (tools/prepro_ngrams.py; capmi.h capmi_df_*, df_build.hip) -----------------
+def _host_offsets(off, n):
+    """numpy int64 [n + 1] offsets for the host-side check of capmi_df_count (None: not checked there)"""
+    import numpy as np
+    if off is None:
+        return None
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    if off.shape != (n + 1,):
+        raise _lib.CapmiError('df_count: host offsets must be [%d], got %s' % (n + 1, off.shape))
+    return off
+
+
+def df_count(tok, cap_off, img_off, table_keys, table_counts, meta, cap_off_host=None, img_off_host=None):
+    """One launch (capmi_df_count): every distinct n-gram (n = 1..4) of an image's captions adds 1 to the counting table.
+    tok int32 / int64 [total_tokens]; cap_off int64 [n_caps + 1]; img_off int64 [n_img + 1]; table_keys int64 (the bits of uint64) and
+    table_counts int32 [cap], cap a power of two; meta int32 [2] = error bits, distinct n-grams; tables and meta zeroed by the
+    caller.  cap_off_host / img_off_host: the same offsets on the host (numpy), checked before the launch.  No host sync."""
+    _chk(tok, cap_off, img_off, table_keys, table_counts, meta)
+    if tok.dtype not in (torch.int32, torch.int64) or tok.dim() != 1:
+        raise _lib.CapmiError('df_count: tok must be a 1-D int32 or int64 tensor')
+    if cap_off.dtype != torch.int64 or img_off.dtype != torch.int64 or cap_off.dim() != 1 or img_off.dim() != 1 \
+            or cap_off.numel() < 1 or img_off.numel() < 1:
+        raise _lib.CapmiError('df_count: cap_off and img_off must be 1-D int64 tensors of at least one entry')
+    if table_keys.dtype != torch.int64 or table_counts.dtype != torch.int32 or table_keys.numel() != table_counts.numel():
+        raise _lib.CapmiError('df_count: the counting table is int64 keys and int32 counts of one size')
+    if meta.dtype != torch.int32 or meta.numel() != 2:
+        raise _lib.CapmiError('df_count: meta must be int32 [2]')
+    n_caps, n_img = cap_off.numel() - 1, img_off.numel() - 1
+    ch, ih = _host_offsets(cap_off_host, n_caps), _host_offsets(img_off_host, n_img)
+    check(lib.capmi_df_count(ptr(tok) if tok.numel() else None, tok.element_size(), tok.numel(), ptr(cap_off),
+                             ch.ctypes.data if ch is not None else None, n_caps, ptr(img_off),
+                             ih.ctypes.data if ih is not None else None, n_img, ptr(table_keys), ptr(table_counts),
+                             table_keys.numel(), meta.data_ptr() + 4, ptr(meta), stream_ptr()), 'capmi_df_count')
+
+
+def df_finalize(count_keys, counts, keys, vals, meta):
+    """One launch (capmi_df_finalize): the occupied slots of the counting table re-inserted into the scorer's image, keys int64
+    (the bits of uint64) / vals float64 [cap], zeroed by the caller, cap a power of two.  meta: as df_count."""
+    _chk(count_keys, counts, keys, vals, meta)
+    if count_keys.dtype != torch.int64 or counts.dtype != torch.int32 or count_keys.numel() != counts.numel():
+        raise _lib.CapmiError('df_finalize: the counting table is int64 keys and int32 counts of one size')
+    if keys.dtype != torch.int64 or vals.dtype != torch.float64 or keys.numel() != vals.numel():
+        raise _lib.CapmiError('df_finalize: the image is int64 keys and float64 vals of one size')
+    check(lib.capmi_df_finalize(ptr(count_keys), ptr(counts), count_keys.numel(), ptr(keys), ptr(vals), keys.numel(), ptr(meta),
+                                stream_ptr()), 'capmi_df_finalize')

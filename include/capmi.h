@@ -1610,6 +1610,40 @@ int capmi_sentset_add_first(const capmi_sentset *s, const int64_t *seq, int rows
 int capmi_sentset_reduce(const capmi_sentset *s, double *out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The CIDEr-D document-frequency table of a caption corpus, built on the device (df_build.hip): what scripts/prepro_ngrams.py
+ * computes with CiderScorer.compute_doc_freq and tools/convert_df.py turns into the image capmi_ciderd_score probes.
+ *
+ * The corpus is ragged: tok [total_tokens] (int32 when tok_elem == 4, int64 when 8), cap_off [n_caps + 1] (caption c is
+ * tok[cap_off[c] .. cap_off[c + 1])), img_off [n_img + 1] (image i owns captions img_off[i] .. img_off[i + 1] - 1; it may own
+ * none).  A caption is exactly its tokens, a 0 included: the caller appends the <eos>, nothing here stops at a 0 or adds one,
+ * and no caption is cut at any width.
+ *
+ * capmi_df_count: one launch, one workgroup per image.  For n = 1..4, every n-gram that occurs in any caption of an image adds 1
+ *   to its slot of the counting table (table_keys uint64 / table_counts int32 [table_cap], zeroed by the caller, a power of two),
+ *   once per image however often it occurs there.  Keys and hash are the scorer's (16-bit fields of id + 1, splitmix64); a slot
+ *   is claimed with atomicCAS on its key and linear probing, the count is an integer atomicAdd: the key -> count mapping is the
+ *   same on every run, only the slots are not.  An occurrence counts when no EARLIER token position of the image starts the
+ *   same n-gram; the earlier positions are walked in tiles through LDS, so an image may be of any size (the walk is quadratic
+ *   in the image's tokens).  n_distinct [1] (zeroed by the caller) receives the number of slots claimed.
+ * capmi_df_finalize: one launch.  Every occupied slot of the counting table is inserted into keys uint64 / vals float64 [cap]
+ *   (zeroed by the caller, a power of two), vals = the count converted exactly.
+ * err [1] (zeroed by the caller) collects CAPMI_LANGEVAL_E_TABLE_FULL (either table), CAPMI_LANGEVAL_E_TOKEN (an id outside
+ * [0, 65535); it counts as id 0) and CAPMI_DF_E_OFFSETS (an image whose offsets decrease or leave [0, n_caps] / [0, total_tokens],
+ * or img_off that does not run from 0 to n_caps; the image is skipped).  Nothing is read or written out of range in any of these
+ * cases; the tables are meaningless when err is not 0.
+ * cap_off_host / img_off_host: the same offsets in host memory, or NULL.  Where given they are checked before anything is
+ * launched (the kernel reads the device copies).  Calls only enqueue and never allocate.
+ * CAPMI_EINVAL: a NULL pointer (tok may be NULL when total_tokens == 0), tok_elem not 4 or 8, a negative size, a table size that is
+ * no power of two, host offsets that decrease or do not run from 0 to n_caps / total_tokens.  n_img == 0: success, nothing launched.
+ * ------------------------------------------------------------------------------------------- */
+#define CAPMI_DF_E_OFFSETS 8            /* malformed cap_off / img_off (joins CAPMI_LANGEVAL_E_*) */
+int capmi_df_count(const void *tok, int tok_elem, int64_t total_tokens, const int64_t *cap_off, const int64_t *cap_off_host,
+                   int64_t n_caps, const int64_t *img_off, const int64_t *img_off_host, int n_img, uint64_t *table_keys,
+                   int32_t *table_counts, uint32_t table_cap, uint32_t *n_distinct, int32_t *err, void *stream);
+int capmi_df_finalize(const uint64_t *count_keys, const int32_t *counts, uint32_t count_cap, uint64_t *keys, double *vals,
+                      uint32_t cap, int32_t *err, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Store rows of a block of images, built on the device (region_rows.hip): norm_att_feat, the box-geometry columns of use_box,
  * norm_box_feat and the re-ordering of an image's rows by the last column (captioning/data/dataloader.py:266-282).  One launch,
  * one workgroup per image.
