@@ -290,6 +290,8 @@ class SentSet(C.Structure):
 
 _I, _F, _P, _U64, _I64 = C.c_int, C.c_float, C.c_void_p, C.c_uint64, C.c_int64
 DECODE_NO_REPEAT, DECODE_NO_BAD_ENDING, DECODE_BLOCK_TRIGRAMS = 1, 2, 4      # capmi.h CAPMI_DECODE_*
+ROWS_L2NORM_DMAX = 8192       # capmi.h CAPMI_ROWS_L2NORM_DMAX
+ROWS_F32, ROWS_BF16, ROWS_FP16 = 0, 1, 2      # capmi.h CAPMI_ROWS_*: the element format of the resident store's rows
 SELECT_RAW = 256       # capmi.h CAPMI_SELECT_RAW: OR into the select `mode` -- the stored rows are the logits, not the log-probabilities
 
 # name -> argtypes (restype is always int unless noted).  Must list EVERY symbol of include/capmi.h:
@@ -436,6 +438,9 @@ SIGNATURES = {
     'capmi_updown_rollout_bwd_phases': [C.POINTER(UpDownWeights), C.POINTER(UpDownRollout), _P, C.POINTER(UpDownBwdScratch),
                                  C.POINTER(UpDownGrads), _I, _P],
     'capmi_region_rows_build': [_P, _P, _P, _P, _I, _I, _P, _I64, _I, _I, _I, _P],
+    'capmi_rows_l2norm': [_P, _I64, _I, _P],
+    'capmi_rows_narrow': [_P, _P, _I64, _I, _P],
+    'capmi_resident_gather': [_P, _I, _I, _P, _P, _I, _I, _P, _P, _P],
     'capmi_bn_row_blocks': [_I],
     'capmi_bn_stats': [_P, _P, _I, _I, _P, _P],
     'capmi_bn_finalize': [_P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P],

@@ -34,7 +34,8 @@ def _newest_dep():
 # decode_opts: the edits must round like the reference's separate torch ops (x - count*lambda), so no fma contraction.
 # reward_mix: the reward mix must round like numpy's cw * cider + bw * bleu, likewise.
 # region_rows: the box area is a sort key and must round like numpy's separate float32 operations, likewise.
-EXTRA_FLAGS = {'region_rows.hip': ['-ffp-contract=off'],'gemm_x3.hip': ['-fno-slp-vectorize'], 'gemm_x3w.hip': ['-fno-slp-vectorize'], 'gemm_lc.hip': ['-fno-slp-vectorize'], 'sampler.hip': ['-fno-slp-vectorize'], 'decode_opts.hip': ['-ffp-contract=off'], 'reward_mix.hip': ['-ffp-contract=off']}
+# resident: the row norm of norm_att_feat must round like numpy's x * x followed by its float32 add.reduce, likewise.
+EXTRA_FLAGS = {'region_rows.hip': ['-ffp-contract=off'], 'resident.hip': ['-ffp-contract=off'],'gemm_x3.hip': ['-fno-slp-vectorize'], 'gemm_x3w.hip': ['-fno-slp-vectorize'], 'gemm_lc.hip': ['-fno-slp-vectorize'], 'sampler.hip': ['-fno-slp-vectorize'], 'decode_opts.hip': ['-ffp-contract=off'], 'reward_mix.hip': ['-ffp-contract=off']}
 
 
 def build(force=False, verbose=True):

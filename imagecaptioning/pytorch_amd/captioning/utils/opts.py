@@ -39,9 +39,14 @@ DEFAULTS = dict(
     input_synthetic=1, vocab_size=9487, synthetic_regions=36, synthetic_images=200,
     # real precomputed features (captioning/data/feature_loader.py; opts.py:23-37 of the reference)
     input_json='', input_label_h5='', input_fc_dir='', input_att_dir='', use_fc=1, norm_att_feat=0, train_only=0, resident_features=1, resident_budget_gb=0.0,
+    # the element format of the HBM-resident store's region rows (captioning/data/resident.py): 'fp32', or 'bf16' / 'fp16' -- twice the
+    # images in the same budget, rounded once at insertion
+    resident_dtype='fp32',
     # opts.py:29-37, 103-106: box geometry appended to every region row (att_feat_size grows by 5: the user sets it, as in the reference)
     use_box=0, norm_box_feat=0, input_box_dir='data/cocotalk_box',
 )
+
+RESIDENT_DTYPES = ('fp32', 'bf16', 'fp16')
 
 
 def parse_opt(argv=None):
@@ -60,6 +65,8 @@ def parse_opt(argv=None):
             opt[k] = v
     opt['cfg'] = ns.cfg
     o = argparse.Namespace(**opt)
+    if o.resident_dtype not in RESIDENT_DTYPES:
+        ap.error("--resident_dtype %r: choose one of 'fp32', 'bf16', 'fp16'" % (o.resident_dtype,))
     if o.max_length is None:
         o.max_length = o.seq_length
     return o

@@ -64,7 +64,7 @@ __global__ __launch_bounds__(THREADS) void region_rows_kernel(RowsArgs a) {
                 float s = __fmul_rn(c[0], c[0]);
 #pragma unroll
                 for (int e = 1; e < 5; ++e) s = __fadd_rn(s, __fmul_rn(c[e], c[e]));
-                const float n = __fsqrt_rn(s);
+                const float n = __builtin_sqrtf(s);             // correctly rounded; __fsqrt_rn is the native (approximate) root
 #pragma unroll
                 for (int e = 0; e < 5; ++e) c[e] = __fdiv_rn(c[e], n);
             }

@@ -1003,6 +1003,62 @@ def region_rows_build(src, boxes, table_host, table, dst, norm_att, use_box, nor
     region_rows_build_calls += 1
 
 
+# ---- the compact resident store (capmi.h capmi_rows_narrow / capmi_resident_gather, resident.hip) ---------------------------------
+ROWS_DTYPES = {'fp32': (torch.float32, _lib.ROWS_F32), 'bf16': (torch.bfloat16, _lib.ROWS_BF16), 'fp16': (torch.float16, _lib.ROWS_FP16)}
+_ROWS_CODE = {t: c for t, c in ROWS_DTYPES.values()}
+resident_gather_calls = 0          # launches so far
+
+
+def rows_l2norm(rows):
+    """norm_att_feat on the device, in place: every row of the contiguous float32 [n, D] tensor over its L2 norm, bit for bit what the
+    loader's host path (att / np.linalg.norm(att, 2, 1, keepdims=True)) computes."""
+    if rows.dtype != _f32 or rows.dim() != 2 or not rows.is_contiguous() or not rows.is_cuda:
+        raise _lib.CapmiError('rows_l2norm: rows must be a contiguous float32 [n, D] device tensor')
+    if rows.shape[1] > _lib.ROWS_L2NORM_DMAX:
+        raise _lib.CapmiError('rows_l2norm: rows of %d features; the kernel takes up to %d' % (rows.shape[1], _lib.ROWS_L2NORM_DMAX))
+    if rows.numel():
+        check(lib.capmi_rows_l2norm(ptr(rows), rows.shape[0], rows.shape[1], stream_ptr()), 'capmi_rows_l2norm')
+    return rows
+
+
+def rows_narrow(src, dst):
+    """dst <- src rounded to nearest even, element by element: src float32 contiguous, dst a contiguous bfloat16 / float16 tensor (or
+    view: any 2-byte-aligned place of a store) of the same number of elements on the same device.  The bits of src.to(dst.dtype)."""
+    if src.dtype != _f32 or not src.is_contiguous() or not src.is_cuda:
+        raise _lib.CapmiError('rows_narrow: src must be a contiguous float32 device tensor')
+    if dst.dtype not in (torch.bfloat16, torch.float16) or not dst.is_contiguous() or dst.device != src.device \
+            or dst.numel() != src.numel():
+        raise _lib.CapmiError('rows_narrow: dst must be a contiguous bfloat16 / float16 tensor of %d elements on %s' % (src.numel(), src.device))
+    if src.numel():
+        check(lib.capmi_rows_narrow(ptr(src), ptr(dst), src.numel(), _ROWS_CODE[dst.dtype], stream_ptr()), 'capmi_rows_narrow')
+    return dst
+
+
+def resident_gather(rows, table_host, table, kmax):
+    """One launch from the resident store to a batch: rows [n, F] contiguous float32 / bfloat16 / float16, table_host numpy int32
+    [B, 2] of (first row, K) per image (K = 0: not resident), table the same words as an int32 device tensor
+    -> (att [B, kmax, F] float32: the rows widened, +0.0 from K on; mask [B, kmax] float32: k < K)."""
+    global resident_gather_calls
+    import numpy as np
+    if rows.dtype not in _ROWS_CODE or rows.dim() != 2 or not rows.is_contiguous() or not rows.is_cuda:
+        raise _lib.CapmiError('resident_gather: rows must be a contiguous [n, F] float32 / bfloat16 / float16 device tensor')
+    if table_host.dtype != np.int32 or table_host.ndim != 2 or table_host.shape[1] != 2 or not table_host.flags['C_CONTIGUOUS']:
+        raise _lib.CapmiError('resident_gather: table_host must be a contiguous int32 [B, 2] array')
+    B, kmax = int(table_host.shape[0]), int(kmax)
+    if table.dtype != torch.int32 or table.numel() != 2 * B or not table.is_contiguous() or table.device != rows.device:
+        raise _lib.CapmiError('resident_gather: table must hold the %d int32 words of table_host on the device' % (2 * B))
+    first, K = table_host[:, 0].astype(np.int64), table_host[:, 1].astype(np.int64)
+    if B < 1 or kmax < 1 or (K < 0).any() or (K > kmax).any() or ((K > 0) & ((first < 0) | (first + K > rows.shape[0]))).any():
+        raise _lib.CapmiError('resident_gather: an image\'s rows leave the store %s or its K leaves 0..%d' % (tuple(rows.shape), kmax))
+    F = rows.shape[1]
+    att = torch.empty(B, kmax, F, dtype=_f32, device=rows.device)
+    mask = torch.empty(B, kmax, dtype=_f32, device=rows.device)
+    check(lib.capmi_resident_gather(ptr(rows), _ROWS_CODE[rows.dtype], F, table_host.ctypes.data, ptr(table), B, kmax, ptr(att), ptr(mask),
+                                    stream_ptr()), 'capmi_resident_gather')
+    resident_gather_calls += 1
+    return att, mask
+
+
 # ---- BatchNorm1d over the valid region rows (use_bn; capmi.h capmi_bn_*, region_norm.hip) ----------------------------------------
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1         # nn.BatchNorm1d's defaults, the reference's (AttModel.py:80-85)
 

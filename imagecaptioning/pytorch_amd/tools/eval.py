@@ -235,7 +235,7 @@ def build_loader(opt, dev):
         if getattr(opt, 'resident_features', 1):
             from captioning.data.resident import ResidentFeatures
             budget = int(opt.resident_budget_gb * (1 << 30)) if getattr(opt, 'resident_budget_gb', 0) > 0 else None
-            loader = ResidentFeatures(loader, dev, budget_bytes=budget)
+            loader = ResidentFeatures(loader, dev, budget_bytes=budget, dtype=getattr(opt, 'resident_dtype', 'fp32'))
         return loader, vocab
     from captioning.data.synthetic_loader import SyntheticLoader
     loader = SyntheticLoader(opt)

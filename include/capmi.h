@@ -1668,6 +1668,40 @@ int capmi_region_rows_build(const float *src, const float *boxes, const int32_t 
                             int D, float *dst, int64_t ldd, int norm_att, int use_box, int norm_box, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The compact resident feature store (resident.hip; captioning/data/resident.py): region rows kept in HBM as float32, bfloat16 or
+ * IEEE half, and the launch that turns the store into a batch.
+ * capmi_rows_narrow: dst[i] = src[i] converted to CAPMI_ROWS_BF16 or CAPMI_ROWS_FP16, round to nearest even, i < count.  NaN stays NaN
+ *          (quiet), +-inf stays +-inf; fp16 overflow goes to +-inf and fp16 subnormals are produced: the bits of
+ *          torch.Tensor.to(dtype).  src: 4-byte aligned (the fp32 staging block of an insert), dst: 2-byte aligned -- any row of the
+ *          store: a scalar head up to dst's first 16-byte boundary, 16-byte stores, a scalar tail.
+ *          CAPMI_EINVAL: a NULL pointer, count <= 0, a dtype other than the two, src off 4 bytes, dst off 2.
+ * capmi_resident_gather: one launch, one workgroup per output row.
+ *   rows   the store, [n_rows, F] elements of `dtype` (CAPMI_ROWS_F32: a plain copy), rows packed (leading dimension F)
+ *   table  [B, 2] int32 on the DEVICE: (first row, K) per batch image, K = 0: not resident (first is not read); table_host: the same
+ *          words in host memory -- the arguments are checked there, the kernel reads the device copy (as capmi_region_rows_build)
+ *   att    [B, kmax, F] float32: att[b, k, :] = row first_b + k widened (exact) for k < K_b, +0.0 for k >= K_b
+ *   mask   [B, kmax] float32: 1 for k < K_b, else 0
+ *   No alignment beyond the element size is asked of rows, beyond 4 bytes of att: the 16-byte stores follow each output row, the
+ *   loads take the widest form the source row's address allows, down to single elements (F = 2053: 4106-byte rows at 16 bits).
+ *   The caller guarantees first_b + K_b <= n_rows.
+ *   CAPMI_EINVAL, before anything is launched: a NULL pointer, B / kmax / F <= 0, an unknown dtype, K < 0 or K > kmax, first < 0
+ *   where K > 0, a pointer off its element size.
+ * capmi_rows_l2norm: norm_att_feat for rows on their way into the store, in place: every row of rows [n_rows, D] (packed) over its L2
+ *          norm, the squares summed in the order of numpy's float32 add.reduce (8 strided accumulators per run of up to 128, runs
+ *          split at n / 2 rounded down to 8), every operation a correctly rounded float32 one: the bits of
+ *          att / np.linalg.norm(att, 2, 1, keepdims=True), the loader's host path.  A zero row becomes NaN, as there.
+ *          CAPMI_EINVAL: NULL, n_rows <= 0, D <= 0 or D > CAPMI_ROWS_L2NORM_DMAX, rows off 4 bytes.
+ * ------------------------------------------------------------------------------------------- */
+#define CAPMI_ROWS_F32 0
+#define CAPMI_ROWS_BF16 1
+#define CAPMI_ROWS_FP16 2
+#define CAPMI_ROWS_L2NORM_DMAX 8192
+int capmi_rows_l2norm(float *rows, int64_t n_rows, int D, void *stream);
+int capmi_rows_narrow(const float *src, void *dst, int64_t count, int dtype, void *stream);
+int capmi_resident_gather(const void *rows, int dtype, int F, const int32_t *table_host, const int32_t *table, int B, int kmax,
+                          float *att, float *mask, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * BatchNorm1d over the valid region rows (region_norm.hip; use_bn, AttModel.py:80-85 under pack_wrapper :44-49).
  *   x / y / dy / dx  [rows, D] float32, rows = B * K; mask: one float per row, 0 = padded region (NULL: every row is valid)
  *   M, the number of valid rows, is counted on the device; nothing here waits for the device.
