@@ -449,6 +449,9 @@ SIGNATURES = {
     'capmi_bn_colsum_parts': [_P, _I, _I, _P, _P, _P],
     'capmi_bn_bwd_dx': [_P] * 9 + [_I, _P, _I, _I, _P],
     'capmi_bn_linear_bwd': [_P] * 7 + [_I, _I, _P, _P],
+    'capmi_att_trace_rollout': [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
+    'capmi_att_trace_beam': [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
+    'capmi_att_ground': [_P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
 }
 
 

@@ -90,6 +90,7 @@ class Rollout(RolloutBase):
 
     SCRATCH, GRADS, G_FIELDS = _lib.AdaAttBwdScratch, _lib.AdaAttGrads, _G
     FWD, BWD = 'capmi_adaatt_rollout_fwd', 'capmi_adaatt_rollout_bwd'
+    TRACE = 'pi'                               # [T, N, K + 1]: sentinel, then the regions
     DROPS = ('drop_xt', 'drop_h', 'drop_fake', 'drop_fr', 'drop_ho', 'drop_out', 'drop_tile')
 
     def __init__(self, P, ap, n, T, L=None, mode='greedy', temperature=1.0, gumbel=None, seed=0, forced=None, teacher=False,

@@ -37,8 +37,9 @@ def sample_beam(model, fc_feats, att_feats, att_masks, opt):
     pr = engine.prepare(P, fc_feats.float().contiguous(), att_feats.float().contiguous(),
                         None if att_masks is None else att_masks.float(), bn=model._region_bn(False))      # an eval-mode prefill
     dev = fc_feats.device
-    if group_size != 1 or opt.get('decoding_constraint', 0) or opt.get('remove_bad_endings', 0):
-        # diverse groups / decoding constraints: same kernels, host-stepped (the one-call search below has no hooks)
+    if group_size != 1 or opt.get('decoding_constraint', 0) or opt.get('remove_bad_endings', 0) or model._trace_req is not None:
+        # diverse groups / decoding constraints / return_attention: same kernels, host-stepped (the one-call search below has no
+        # hooks and keeps no per-step weights)
         from .step import UpDownStepper
         return beam_search_steps(model, lambda rows: UpDownStepper(P, pr, rows), pr.att.shape[0], P['embed.0.weight'].shape[0],
                                  model.seq_length, opt, dev)
@@ -346,6 +347,10 @@ def beam_search_steps(model, make_decoder, B, V1, L, opt, dev, tables_only=False
     if int(opt.get('group_size', 1)) != 1:
         return diverse_beam_search_steps(model, make_decoder, B, V1, L, opt, dev)
     assert sample_n == 1 or sample_n == beam_size, 'when beam search, sample_n == 1 or beam search'
+    trace = None if tables_only else getattr(model, '_trace_req', None)
+    if trace is not None:
+        from . import att_trace
+        make_decoder, recs = att_trace.recording(make_decoder, L)
     dec = make_decoder(beam_size)
     step, reorder = dec.step, dec.reorder
     bd = beam_size
@@ -379,6 +384,8 @@ def beam_search_steps(model, make_decoder, B, V1, L, opt, dev, tables_only=False
         cur = bd
     if tables_only:                                                         # the training search finalises on the device
         return parent, token, score, ended, logp_rows
+    if trace is not None:
+        att_trace.from_beam(model, recs[0], parent, token, score, ended, sample_n if sample_n == beam_size else 1, B * sample_n, opt)
     return assemble_done_beams(model, parent, token, score, ended, logp_rows, B, bd, L, V1, sample_n, beam_size, opt)
 
 
@@ -402,7 +409,13 @@ def diverse_beam_search_steps(model, make_decoder, B, V1, L, opt, dev):
     temperature = float(opt.get('temperature', 1))
     unk = unk_column(model, opt, V1)
     flags, bad = _decode_flags(model, opt, dev)
-    decs = [make_decoder(bd) for _ in range(G)]
+    trace = getattr(model, '_trace_req', None)
+    if trace is not None:
+        # the returned caption of an image is the best beam of group 0 (CaptionModel.py:207-208 concatenates the groups in order):
+        # only that group's decoder records
+        from . import att_trace
+        rec_make, recs = att_trace.recording(make_decoder, L)
+    decs = [(rec_make if (trace is not None and g == 0) else make_decoder)(bd) for g in range(G)]
     logp_rows = torch.zeros(L, B * W, V1, dtype=_f32, device=dev)          # rows image-major, then group, then beam
     lparent = torch.zeros(G, L, B, bd, dtype=torch.int32, device=dev)      # per-group tables
     ltoken = torch.zeros(G, L, B, bd, dtype=torch.long, device=dev)
@@ -454,6 +467,8 @@ def diverse_beam_search_steps(model, make_decoder, B, V1, L, opt, dev):
     token = ltoken.permute(1, 2, 0, 3).reshape(L, B, W).contiguous()
     score = lscore.permute(1, 2, 0, 3).reshape(L, B, W).contiguous()
     ended = lended.permute(1, 2, 0, 3).reshape(L, B, W).contiguous()
+    if trace is not None:
+        att_trace.from_beam(model, recs[0], lparent[0], ltoken[0], lscore[0], lended[0], 1, B * sample_n, opt)
     return assemble_done_beams(model, parent, token, score, ended, logp_rows, B, bd, L, V1, sample_n, beam_size, opt, groups=G)
 
 

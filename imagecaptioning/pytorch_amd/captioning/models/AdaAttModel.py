@@ -53,6 +53,9 @@ class AdaAttCore(nn.Module):
 
 class AdaAttModel(StepAPI, RecurrentModel):
     use_maxout = False
+    # return_attention: pi [.., K + 1] of the rollouts / steppers, the visual sentinel in column 0 as AdaAtt_attention puts it
+    # (AttModel.py:581-593: cat([fake_region, conv_feat]); with att_masks the sentinel takes the mask of region 0, then renormalised)
+    _trace_refusal, _trace_col0 = None, 1
 
     def __init__(self, opt):
         super().__init__()

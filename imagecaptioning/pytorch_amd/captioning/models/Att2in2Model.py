@@ -26,6 +26,7 @@ class Att2in2Core(nn.Module):
 
 
 class Att2in2Model(StepAPI, RecurrentModel):
+    _trace_refusal = None           # return_attention: alpha of the rollouts / steppers
     _use_bn_refusal = None
 
     def __init__(self, opt):

@@ -77,6 +77,7 @@ class UpDownCore(nn.Module):
 
 class AttModel(StepAPI, RecurrentModel):
     _use_bn_refusal = None
+    _trace_refusal = None           # return_attention: alpha of the rollouts / steppers
 
     def __init__(self, opt):
         super().__init__()
@@ -195,6 +196,8 @@ class AttModel(StepAPI, RecurrentModel):
         if beam_size > 1 and sample_method in ('greedy', 'beam_search'):
             from imagecaptioning.pytorch_amd import beam
             if beam.wants_train_beam(self, opt):
+                if self._trace_req is not None:
+                    raise NotImplementedError('return_attention is not implemented for the training beam search (train_beam_size > 1)')
                 # train mode with gradients (loss_wrapper.py, train_beam_size > 1): search, finalise on the device, forced replay
                 return beam.updown_beam_train(self, fc_feats, att_feats, att_masks, opt)
             return self._sample_beam(fc_feats, att_feats, att_masks, opt)

@@ -2,6 +2,8 @@
 import torch
 import torch.nn as nn
 
+from imagecaptioning.pytorch_amd import att_trace
+
 BAD_ENDINGS = ['a', 'an', 'the', 'in', 'for', 'at', 'of', 'with', 'before', 'after', 'on', 'upon', 'near', 'to', 'is',
                'are', 'am', 'the']       # AttModel.py:27
 
@@ -10,7 +12,30 @@ class CaptionModel(nn.Module):
     def forward(self, *args, **kwargs):
         """``model(..., mode='forward'|'sample')`` -> ``self._forward`` / ``self._sample``."""
         mode = kwargs.pop('mode', 'forward')
+        if mode == 'sample':
+            return self._sample_entry(*args, **kwargs)
         return getattr(self, '_' + mode)(*args, **kwargs)
+
+    # ---- opt['return_attention'] (imagecaptioning.pytorch_amd.att_trace): the per-word region attention of a sample call
+    last_attention = None       # dict of device tensors (att, top, top_w, entropy[, box]) after a sample call with the option on
+    _trace_req = None           # att_trace.Request while such a call runs
+    _trace_col0 = 0             # leading columns of the trace that are no region (AdaAtt: the sentinel)
+    # why a family has no trace (None: it has one)
+    _trace_refusal = 'the model keeps no per-step weights over the regions'
+
+    def _sample_entry(self, *args, **kwargs):
+        opt = kwargs.get('opt') or (args[3] if len(args) > 3 else None)
+        if self.last_attention is not None:
+            self.last_attention = None
+        if not att_trace.wanted(opt):
+            return self._sample(*args, **kwargs)
+        if self._trace_refusal is not None:
+            att_trace.refuse(self)
+        self._trace_req = att_trace.Request(self, args[1] if len(args) > 1 else kwargs['att_feats'], opt)
+        try:
+            return self._sample(*args, **kwargs)
+        finally:
+            self._trace_req = None
 
     # ---- parameters without a walk of the module tree per step.  nn.Module.named_parameters() recurses through named_modules()
     # building prefixed names and a de-duplication set: 0.5 ms for the Transformer's 260 parameters, and every forward asks twice
@@ -106,9 +131,16 @@ class CaptionModel(nn.Module):
         make_stepper(rows_per_image) -> stepper (imagecaptioning.pytorch_amd.step protocol)."""
         from imagecaptioning.pytorch_amd import decode
         dev = next(self.parameters()).device
+        if self._trace_req is not None:
+            # return_attention: the stepper keeps every step's weights, laid out like a rollout's alpha [L, rows, K]
+            make_stepper, made = att_trace.recording(make_stepper, self.seq_length)
         with torch.no_grad():
             if opt.get('group_size', 1) > 1:
                 st = make_stepper(int(opt['group_size']))
-                return decode.diverse_sample_steps(self, st, B, self.seq_length, opt, dev, seed=self._next_seed())
-            st = make_stepper(int(opt.get('sample_n', 1)))
-            return decode.sample_steps(self, st, B, self.seq_length, opt, dev, seed=self._next_seed())
+                out = decode.diverse_sample_steps(self, st, B, self.seq_length, opt, dev, seed=self._next_seed())
+            else:
+                st = make_stepper(int(opt.get('sample_n', 1)))
+                out = decode.sample_steps(self, st, B, self.seq_length, opt, dev, seed=self._next_seed())
+            if self._trace_req is not None:
+                att_trace.from_steps(self, made[0], out[0])
+            return out

@@ -38,6 +38,9 @@ class _RolloutFn(torch.autograd.Function):
         seq, logp = ro.run()
         ctx.model, ctx.ro, ctx.P, ctx.lead = model, ro, P, 2 + k
         model._publish_rollout(ro, ctx.sink)
+        if model._trace_req is not None:            # return_attention: the trace is read off the rollout's own weight buffer
+            from imagecaptioning.pytorch_amd import att_trace
+            att_trace.from_rollout(model, ro)
         ctx.mark_non_differentiable(seq)
         # (an ALIAS of the engine's tensor is returned: autograd hangs this Function on the returned object, and returning the very
         #  tensor the saved engine holds would close a reference cycle ctx -> engine -> tensor -> grad_fn -> ctx -- every activation

@@ -35,6 +35,9 @@ DEFAULTS = dict(
     # eval_utils.py:27-36, 55-68, 79-80, 121: with language_eval, also bad_count_rate and the mean perplexity / entropy and, with
     # sample_n > 1, novel_sentences and vocab_size, counted on the device (imagecaptioning/pytorch_amd/sentstats.py)
     sentence_stats=0,
+    # tools/eval.py: write every decoded caption's per-word region attention (opt['return_attention'], imagecaptioning/pytorch_amd/
+    # att_trace.py) to <eval_results_dir>/<id>_<split>_att.npz; updown / topdown, att2in2, adaatt, adaattmo
+    dump_attention=0,
     # data (synthetic only: the reference's h5/lmdb loaders are outside the hot path)
     input_synthetic=1, vocab_size=9487, synthetic_regions=36, synthetic_images=200,
     # real precomputed features (captioning/data/feature_loader.py; opts.py:23-37 of the reference)

@@ -204,6 +204,7 @@ class RolloutBase:
     G_FIELDS = ()                             # (capmi_*_grads field, parameter name): gradients written in place
     FWD = BWD = None                          # native entry points, by name
     SELECT_BUFS = ('it_all', 'seq', 'seq_logp', 'sel_logp', 'live', 'it', 'unfinished')
+    TRACE = 'alpha'                           # the activation that holds the per-step region weights [T, N, K] (att_trace.py)
 
     def _bind(self, r, acts, dev, N, T, L, V1, mode, temperature=1.0, gumbel=None, seed=0, forced=None, teacher=False,
               ss_mode=None, raw=False, ws=None, always_zero=False):

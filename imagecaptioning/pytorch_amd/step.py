@@ -49,6 +49,7 @@ class _StructStepper(_Stepper):
     its buffers (by field name; `it` and `logits` are added here) and its entry point."""
 
     STEP = None                       # native entry point, by name
+    TRACE = 'alpha'                   # the buffer that holds the step's region weights [rows, K] (att_trace.Recorder)
 
     def _bind(self, s, bufs, dev):
         logits = torch.empty(self.N, self.V1, dtype=_f32, device=dev)
@@ -205,6 +206,7 @@ class AdaAttStepper(_OneLayerState, _StructStepper):
     undropped h: AdaAtt_lstm returns it beside the copy that goes on to the attention)."""
 
     STEP = 'capmi_adaatt_decode_step'
+    TRACE = 'pi'                      # [rows, K + 1]: sentinel, then the regions
 
     def __init__(self, P, ap, rows_per_image_max):
         from . import adaatt_engine

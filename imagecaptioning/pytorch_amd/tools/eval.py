@@ -11,6 +11,10 @@ join lang_stats and are written to <id>_<split>_n.json.  AllSPICE needs Java and
 --sentence_stats 1 adds the counting numbers of eval_utils.language_eval (:27-36, 55-68, 79-80, 121) to lang_stats and to
 <id>_<split>.json: bad_count_rate and the mean perplexity / entropy of the first captions and, with --sample_n N > 1, novel_sentences
 and vocab_size of the N captions per image against the training captions of the label file (imagecaptioning/pytorch_amd/sentstats.py).
+--dump_attention 1 (updown / topdown, att2in2, adaatt, adaattmo) decodes with opt['return_attention'] and writes, per image id, the
+caption's per-word region attention to <eval_results_dir>/<id>_<split>_att.npz: <image id>/att [L, regions (+ 1 sentinel column in front
+for AdaAtt)], /top, /top_w, /entropy [L], /regions, and -- with the real-file loader and --input_box_dir -- /box (the attention-weighted
+box per word) and /top_box (the top region's own box); one device-to-host transfer per batch (imagecaptioning/pytorch_amd/att_trace.py).
 
     python -m imagecaptioning.pytorch_amd.tools.eval --caption_model updown --beam_size 5 --num_images 20 [--start_from DIR]
 """
@@ -80,6 +84,68 @@ def _pad_stack(seqs):
     return torch.stack([torch.cat([s, s.new_zeros(ln - s.shape[0])]) for s in seqs])
 
 
+def batch_boxes(loader, opt, data, K, dev):
+    """[B, K, 4] float32 boxes (x1, y1, x2, y2 in pixels, zero rows behind an image's regions) of a batch of the real-file loader, in
+    the order of its region rows (use_box re-orders them by area), or None without --input_box_dir / with the synthetic loader"""
+    box_dir = getattr(opt, 'input_box_dir', None)
+    if not getattr(opt, 'input_json', '') or not box_dir or not os.path.isdir(box_dir):
+        return None
+    import numpy as np
+    from captioning.data import feature_loader as fl
+    out = np.zeros((len(data['infos']), K, 4), dtype=np.float32)
+    for i, info in enumerate(data['infos']):
+        b = fl._load_rows(box_dir, info['id'], 'box')
+        if getattr(opt, 'use_box', 0):
+            im = loader.info['images'][info['ix']]
+            b = fl.append_boxes(b, b, int(im['height']), int(im['width']), bool(getattr(opt, 'norm_box_feat', 0)))[:, :4]
+        out[i, :min(K, b.shape[0])] = b[:K]
+    return torch.from_numpy(out).to(dev)
+
+
+class AttentionDump:
+    """--dump_attention: the first caption row of every image of a batch, as ONE device-to-host transfer (every array of
+    model.last_attention packed into one float32 block), kept by image id and written as one .npz"""
+
+    def __init__(self):
+        self.arrays = {}
+
+    def add_batch(self, last, infos, keep, att_masks, boxes, col0):
+        att = last['att']
+        N, L, Kw = att.shape
+        B = len(infos)
+        rows = slice(0, N, max(N // B, 1))                   # the first row of each image: the caption that is reported
+        parts = [att[rows], last['top'][rows].to(att.dtype).unsqueeze(2), last['top_w'][rows].unsqueeze(2),
+                 last['entropy'][rows].unsqueeze(2)]
+        regions = att.new_full((B, L, 1), Kw - col0) if att_masks is None else \
+            att_masks.to(att.dtype).sum(1).view(B, 1, 1).expand(B, L, 1)
+        parts.append(regions)
+        if boxes is not None:
+            # the top region's own box: column top - col0 of the image's boxes (zeros for the sentinel column and on zeroed steps)
+            k = last['top'][rows].long() - col0
+            own = boxes.gather(1, k.clamp(min=0).unsqueeze(2).expand(B, L, 4)) * (k >= 0).unsqueeze(2).to(att.dtype)
+            parts += [last['box'][rows], own]
+        host = torch.cat(parts, 2).cpu().numpy()            # the one transfer
+        for i, info in enumerate(infos[:keep]):              # images past num_images are left out, like their predictions
+            h, key = host[i], str(info['id'])
+            n_reg = int(h[0, Kw + 3])
+            self.arrays[key + '/att'] = h[:, :n_reg + col0].copy()
+            self.arrays[key + '/top'] = h[:, Kw].astype('int32')
+            self.arrays[key + '/top_w'] = h[:, Kw + 1].copy()
+            self.arrays[key + '/entropy'] = h[:, Kw + 2].copy()
+            self.arrays[key + '/regions'] = h[0, Kw + 3].astype('int32')
+            if boxes is not None:
+                self.arrays[key + '/box'] = h[:, Kw + 4:Kw + 8].copy()
+                self.arrays[key + '/top_box'] = h[:, Kw + 8:Kw + 12].copy()
+
+    def write(self, opt, split):
+        import numpy as np
+        out_dir = getattr(opt, 'eval_results_dir', 'eval_results')
+        os.makedirs(out_dir, exist_ok=True)
+        path = os.path.join(out_dir, '%s_%s_att.npz' % (getattr(opt, 'id', 'capmi'), split))
+        np.savez(path, **self.arrays)
+        return path
+
+
 def eval_split(model, crit, loader, opt):
     from captioning.utils import misc
     dev = next(model.parameters()).device
@@ -98,6 +164,7 @@ def eval_split(model, crit, loader, opt):
     if lang is not None and getattr(opt, 'sentence_stats', 0):
         from imagecaptioning.pytorch_amd.sentstats import SentenceStats
         sent = SentenceStats.for_loader(loader, split, dev, model, opt.sample_n)
+    dump = AttentionDump() if getattr(opt, 'dump_attention', 0) else None
     if hasattr(loader, 'reset_iterator'):
         loader.reset_iterator(split)                                                                           # eval_utils.py:145
     num_images = opt.num_images
@@ -112,9 +179,17 @@ def eval_split(model, crit, loader, opt):
         att_masks = None if data.get('att_masks') is None else data['att_masks'].to(dev)
         kw = eval_kwargs_of(opt)
         kw['sample_n'] = 1                                                                                     # :169-170
+        if dump is not None:
+            kw['return_attention'] = 1
+            boxes = batch_boxes(loader, opt, data, att.shape[1], dev)
+            if boxes is not None:
+                kw['boxes'] = boxes
         with torch.no_grad():
             loss = crit(model(fc, att, labels[..., :-1], att_masks), labels[..., 1:], masks[..., 1:]).item()  # eval_utils.py:163
             seq, seq_logp = model(fc, att, att_masks, mode='sample', opt=kw)                                   # :171
+        if dump is not None:
+            dump.add_batch(model.last_attention, data['infos'], max(0, min(len(data['infos']), num_images - n)), att_masks,
+                           kw.get('boxes'), model._trace_col0)
         loss_sum += loss
         loss_n += 1
         if seq_logp.dim() == 3:
@@ -153,6 +228,8 @@ def eval_split(model, crit, loader, opt):
         n += len(data['infos'])
     if n_preds and 'perplexity' in n_preds[0]:
         n_preds = sorted(n_preds, key=lambda x: x['perplexity'])                                               # :217-218
+    if dump is not None:
+        print('attention written to', dump.write(opt, split))
     model.n_predictions = n_preds
     model.train()                                                                                              # :224-225
     preds = preds[:num_images * max(1, len(preds) // max(n, 1))]

@@ -1743,6 +1743,36 @@ int capmi_bn_bwd_dx(const float *dy, const float *x, const float *mask, const fl
 int capmi_bn_linear_bwd(float *G, const float *db, const float *W, const float *mean, const float *rstd, const float *gamma,
                         const float *beta, int R, int D, float *partial, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Per-word region attention of a decoded caption (att_trace.hip; opt['return_attention'], tools/eval.py --dump_attention).
+ * One launch each, one wave per (caption row, step), no atomics, nothing waits for the device.  Weights are copied, not recomputed.
+ * capmi_att_trace_rollout: alpha [T, N, K] as the rollouts keep it (step-major, K = the clipped region count) and seq [N, L]
+ *          -> att [N, L, Kout], caption-major.  Kept steps are those where losses._shifted_mask is 1: step 0 and every step
+ *          l < T whose previous token seq[n, l - 1] is not 0 (the EOS step is kept); every other step, and every column behind
+ *          the source's, is WRITTEN as 0 (no memset needed; alpha is not read there, so steps an early exit left unwritten are
+ *          harmless).  beta (optional, [T, N]): a weight with a column of its own in front of the regions -- column 0 = beta,
+ *          columns 1 .. K = alpha.  (AdaAtt keeps its sentinel weight as column 0 of pi [T, N, K + 1], which is passed as alpha with
+ *          K + 1 columns and no beta.)  T <= L is the number of steps alpha holds.
+ * capmi_att_trace_beam: alpha_rows [L, rows_src, K] by SEARCH row and step, lineage [L, rows] and
+ *          length [rows] of capmi_beam_finalize -> att [rows, L, Kout]: att[i, l] = alpha_rows[l, lineage[l, i]] for l < length[i]
+ *          (and a lineage inside [0, rows_src)), 0 elsewhere.
+ * capmi_att_ground: att [N, L, Kw] -> per (row, step) top (int32: the arg-max column, the lowest index among equal weights, -1 on a
+ *          step without a positive weight), top_w (its weight, 0 there), entropy (-sum a ln a in float32, 0 ln 0 = 0).
+ *          att must be finite (every producer above writes finite weights or 0): a NaN compares false with everything, so a row that
+ *          holds one could be reported as a zeroed step.
+ *          boxes [B, Kb, 4] with box [N, L, 4] (both or neither; 16-byte aligned): box = sum_k att[.., col0 + k] * boxes[r / n, k]
+ *          for caption row r; col0 is the number of leading columns without a box (1 for AdaAtt's sentinel column, else 0).
+ * CAPMI_EINVAL, before anything is launched: a NULL required pointer, a dimension <= 0, T > L, more source columns than Kout,
+ *          N * L (rows * L) above 2^31 - 1, a pointer off its element size, boxes without box or the reverse, B * n < N,
+ *          col0 + Kb > Kw, boxes / box off 16 bytes.
+ * ------------------------------------------------------------------------------------------- */
+int capmi_att_trace_rollout(const float *alpha, const float *beta, const int64_t *seq, int T, int N, int L, int K, int Kout,
+                            float *att, void *stream);
+int capmi_att_trace_beam(const float *alpha_rows, const int32_t *lineage, const int32_t *length, int L, int rows_src, int rows, int K,
+                         int Kout, float *att, void *stream);
+int capmi_att_ground(const float *att, int N, int L, int Kw, const float *boxes, int B, int n, int col0, int Kb, int32_t *top,
+                     float *top_w, float *entropy, float *box, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
