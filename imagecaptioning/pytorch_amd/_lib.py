@@ -348,6 +348,8 @@ SIGNATURES = {
     'capmi_adam_step_dyn': [_P, _P, _P, _P, _I64, _P, _F, _F, _F, _F, _F, _F, _P],
     'capmi_optim_step': [C.POINTER(OptimHp), _P, _P, _P, _P, _I64, _F, _I, _P],
     'capmi_optim_step_dyn': [C.POINTER(OptimHp), _P, _P, _P, _P, _I64, _P, _P],
+    'capmi_ema_step': [_P, _P, _I64, _F, _I, _I, _P],
+    'capmi_ema_step_dyn': [_P, _P, _I64, _P, _F, _I, _P],
     'capmi_ciderd_score': [_P, _I, _I, _P, _P, _P, _I, _I, _P, _P, C.c_uint32, C.c_double, _P, _P],
     'capmi_ciderd_cook_refs': [_P, _P, _I, _I, _I, _P, _P, C.c_uint32, C.c_double, _P, _P],
     'capmi_ciderd_score_cooked': [_P, _I, _I, _P, _P, _P, _I, _P, _P, C.c_uint32, C.c_double, _P, _P],

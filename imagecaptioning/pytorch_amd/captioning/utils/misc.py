@@ -30,12 +30,15 @@ def decode_sequence(ix_to_word, seq):
     return out
 
 
-def save_checkpoint(opt, model, infos, optimizer_state=None, append=''):
-    """misc.py:87-102: model[-suffix].pth (state_dict), infos_{id}[-suffix].pkl."""
+def save_checkpoint(opt, model, infos, optimizer_state=None, append='', ema_state=None):
+    """misc.py:87-102: model[-suffix].pth (state_dict), infos_{id}[-suffix].pkl.  ema_state: the same state dict with the averaged
+    weights (flat.FlatParams.ema_state_dict) -> model_ema[-suffix].pth, written like model.pth."""
     suffix = ('-' + append) if append else ''
     os.makedirs(opt.checkpoint_path, exist_ok=True)
     path = os.path.join(opt.checkpoint_path, 'model%s.pth' % suffix)
     torch.save({k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, path)
+    if ema_state is not None:
+        torch.save({k: v.detach().cpu().clone() for k, v in ema_state.items()}, os.path.join(opt.checkpoint_path, 'model_ema%s.pth' % suffix))
     if optimizer_state is not None:
         torch.save(optimizer_state, os.path.join(opt.checkpoint_path, 'optimizer%s.pth' % suffix))
     with open(os.path.join(opt.checkpoint_path, 'infos_%s%s.pkl' % (opt.id, suffix)), 'wb') as f:

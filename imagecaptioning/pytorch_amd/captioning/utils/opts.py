@@ -18,6 +18,10 @@ DEFAULTS = dict(
     noamopt_factor=1.0, use_warmup=0, reduce_on_plateau=0, reduce_on_plateau_factor=0.5, reduce_on_plateau_patience=3,
     scheduled_sampling_start=-1, scheduled_sampling_increase_every=5, scheduled_sampling_increase_prob=0.05,
     scheduled_sampling_max_prob=0.25, val_every=0, val_images=0,
+    # exponential moving average of the weights (flat.FlatParams.enable_ema; not a flag of the reference).  ema_decay 0: off -- no buffer,
+    # no launch, no file.  ema_warmup: decay = min(ema_decay, (1 + step) / (10 + step)).  ema_eval: validate (and pick "best") on the
+    # averaged weights.  Checkpoints gain model_ema[-best].pth, optimizer.pth carries the average
+    ema_decay=0.0, ema_warmup=1, ema_eval=1,
     checkpoint_path='log_capmi', id='capmi', save_checkpoint_every=0, losses_log_every=10, start_from=None, seed=1234,
     # transformer / aoa
     N_enc=6, N_dec=6, d_model=512, d_ff=2048, num_att_heads=8, dropout=0.1, refine=1, refine_aoa=1, use_ff=0, decoder_type='AoA',
@@ -27,6 +31,7 @@ DEFAULTS = dict(
     group_size=1, diversity_lambda=0.5, decoding_constraint=0, block_trigrams=0, remove_bad_endings=0, sample_n=1,
     sample_n_method='sample', verbose_beam=0,                                # opts.py:288-330 add_eval_sample_opts
     split='test',                                                            # opts.py:314 add_eval_options
+    model='',                                                                # tools/eval.py:25 --model: the state-dict file tools/eval.py loads (else <start_from>/model.pth)
     # opts.py:127 / :311 language_eval: corpus CIDEr / BLEU-1..4 / ROUGE-L on the device (imagecaptioning/pytorch_amd/langeval.py; METEOR
     # and SPICE need Java).  eval_results_dir: where tools/eval.py writes <id>_<split>.json (the reference: always ./eval_results)
     language_eval=0, eval_results_dir='eval_results',

@@ -10,6 +10,10 @@
 //
 // Everything derived from the learning rate and the step number is computed INSIDE the kernel, after the _dyn form has replaced
 // them by the words of the device step record: the stepped and the captured form are the same arithmetic on the same floats.
+//
+// The exponential moving average of the parameters (capmi_ema_step / capmi_ema_step_dyn, --ema_decay) is a pass of its own in the
+// same shape: p read once (plain: the optimizer has just written it and the next forward streams it), ema read and written once,
+// non-temporal -- nothing reads the average before the next step.  12 bytes per element.
 #include "host_common.h"
 
 using namespace capmi;
@@ -152,6 +156,75 @@ bool valid(const capmi_optim_hp *hp, const float *p, const float *g, const float
     return hp->rule != CAPMI_OPTIM_ADAMW || s2 != nullptr;
 }
 
+// ---- exponential moving average of the parameters ----------------------------------------------------------------------------
+struct EmaArgs {
+    float decay;
+    int warmup, step;
+};
+
+// the decay of this step.  warmup: min(decay, (1 + step) / (10 + step)), so that the first steps are not averaged against the initial
+// weights for 1 / (1 - decay) steps
+__device__ __forceinline__ float ema_decay(EmaArgs h, const capmi_step_state *dyn) {
+    const int step = dyn ? dyn->adam_step : h.step;
+    return h.warmup ? fminf(h.decay, (1.f + step) / (10.f + step)) : h.decay;
+}
+
+__device__ __forceinline__ float ema_update(float e, float p, float d, float om) { return fmaf(d, e, om * p); }
+
+// elements [0, head) and [head + 4 * quads, count) scalar, the quads between them 16 bytes at a time (as optim_kernel)
+__global__ void ema_kernel(float *__restrict__ ema, const float *__restrict__ p, size_t head, size_t quads, size_t count, EmaArgs args,
+                           const capmi_step_state *__restrict__ dyn) {
+    const float d = ema_decay(args, dyn);
+    const float om = 1.f - d;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const f32x4 *p4 = reinterpret_cast<const f32x4 *>(p + head);
+    f32x4 *e4 = reinterpret_cast<f32x4 *>(ema + head);
+    for (size_t q0 = tid; q0 < quads; q0 += 2 * stride) {
+        const size_t q1 = q0 + stride;
+        const bool two = q1 < quads;
+        const size_t q1c = two ? q1 : q0;
+        f32x4 ee[2], pp[2];
+        ee[0] = __builtin_nontemporal_load(e4 + q0); ee[1] = __builtin_nontemporal_load(e4 + q1c);
+        pp[0] = p4[q0]; pp[1] = p4[q1c];
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) ee[u][k] = ema_update(ee[u][k], pp[u][k], d, om);
+        __builtin_nontemporal_store(ee[0], e4 + q0);
+        if (two) __builtin_nontemporal_store(ee[1], e4 + q1);
+    }
+    const size_t body_end = head + quads * 4;
+    const size_t scalars = head + (count - body_end);
+    for (size_t t = tid; t < scalars; t += stride) {
+        const size_t i = t < head ? t : body_end + (t - head);
+        ema[i] = ema_update(ema[i], p[i], d, om);
+    }
+}
+
+bool ema_valid(const float *ema, const float *p, int64_t count, float decay) {
+    if (!ema || !p || ema == p || count <= 0) return false;
+    if (!(decay >= 0.f && decay < 1.f)) return false;
+    return ((reinterpret_cast<uintptr_t>(ema) | reinterpret_cast<uintptr_t>(p)) & 3) == 0;
+}
+
+int ema_launch(float *ema, const float *p, int64_t count, float decay, int warmup, int step, const capmi_step_state *dyn, void *stream) {
+    const uintptr_t ue = reinterpret_cast<uintptr_t>(ema), up = reinterpret_cast<uintptr_t>(p);
+    const size_t n = (size_t)count;
+    size_t head = n;                                        // misalignments differ: no common quad grid, scalar throughout
+    if ((ue & 15) == (up & 15)) {
+        head = ((16 - (ue & 15)) & 15) / 4;
+        if (head > n) head = n;
+    }
+    const size_t quads = (n - head) / 4;
+    const size_t scalars = n - quads * 4;
+    const size_t work = quads / 2 + 1 > scalars ? quads / 2 + 1 : scalars;
+    const EmaArgs a{decay, warmup != 0, step};
+    hipLaunchKernelGGL(ema_kernel, dim3(grid_for(work)), dim3(256), 0, (hipStream_t)stream, ema, p, head, quads, n, a, dyn);
+    CAPMI_CHECK_LAUNCH();
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -171,6 +244,16 @@ int capmi_optim_step_dyn(const capmi_optim_hp *hp, float *p, const float *g, flo
                          const capmi_step_state *state, void *stream) {
     if (!valid(hp, p, g, s1, s2, count) || !state) return CAPMI_EINVAL;
     return optim_launch(hp, p, g, s1, s2, count, 0.f, 1.f, 1.f, 0, state, stream);
+}
+
+int capmi_ema_step(float *ema, const float *p, int64_t count, float decay, int warmup, int step, void *stream) {
+    if (!ema_valid(ema, p, count, decay) || step < 1) return CAPMI_EINVAL;
+    return ema_launch(ema, p, count, decay, warmup, step, nullptr, stream);
+}
+
+int capmi_ema_step_dyn(float *ema, const float *p, int64_t count, const capmi_step_state *state, float decay, int warmup, void *stream) {
+    if (!ema_valid(ema, p, count, decay) || !state) return CAPMI_EINVAL;
+    return ema_launch(ema, p, count, decay, warmup, 0, state, stream);
 }
 
 }  // extern "C"

@@ -5,7 +5,8 @@ All parameters of a model live in ONE contiguous fp32 device buffer and all grad
     rules of misc.build_optimizer);
   * data-parallel training moves the gradient with a SINGLE RCCL all-reduce per step,
     instead of nn.DataParallel's per-step parameter broadcast + gradient reduce (train.py:86-88);
-  * the BPTT kernels write gradients straight into views of the flat buffer.
+  * the BPTT kernels write gradients straight into views of the flat buffer;
+  * an exponential moving average of the weights (enable_ema, --ema_decay) is one more flat buffer and one more launch per step.
 ``state_dict()`` is unchanged: every nn.Parameter keeps its name and shape, its storage is a view.
 """
 import torch
@@ -69,8 +70,57 @@ class FlatParams:
         for k in self.state_keys:                    # one buffer for the one-state rules: Adam's second one is never allocated
             setattr(self, k, torch.zeros_like(self.flat))
         self.step_count = 0
+        self.ema, self.ema_decay, self.ema_warmup = None, 0.0, True      # enable_ema(): nothing is allocated before
         self.on_grads_ready = None      # set by begin_overlap(); native backwards call it per finished bucket
         self._bw_expected, self._bw_seen = 1, 0
+
+    # ---- exponential moving average of the parameters (--ema_decay; capmi_ema_step) -------------------------------
+    # Under every gradient-exchange mode (all-reduce, overlap, sharded_step) each rank holds the FULL updated parameters after the
+    # step, so the average runs over the whole buffer on every rank and is identical across ranks: no shard of `ema` exists.
+    def enable_ema(self, decay, warmup=True):
+        """allocate `self.ema`: a flat fp32 buffer in the layout of `self.flat`, starting as a copy of the parameters"""
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:
+            raise ValueError('ema decay %r: must be in [0, 1)' % (decay,))
+        self.ema_decay, self.ema_warmup = decay, bool(warmup)
+        self.ema = self.flat.detach().clone()
+
+    def _need_ema(self):
+        if self.ema is None:
+            raise RuntimeError('no moving average: call enable_ema(decay) first')
+
+    def ema_update(self, step=None):
+        """one launch over the whole buffer, after the optimizer's.  step: the 1-based number of the step just taken (step_count)"""
+        self._need_ema()
+        ops.ema_step(self.ema, self.flat, self.ema_decay, self.ema_warmup, self.step_count if step is None else step)
+
+    def ema_update_dyn(self, state):
+        """ema_update with the step number read from the device record (ops.StepState): the form a captured step replays"""
+        self._need_ema()
+        ops.ema_step_dyn(self.ema, self.flat, state, self.ema_decay, self.ema_warmup)
+
+    def ema_state_dict(self, module):
+        """the module's state dict -- its keys, in its order -- with every parameter taken from the average; buffers (BatchNorm's
+        running statistics) are copied as they are.  What model_ema.pth holds: it loads wherever model.pth does."""
+        self._need_ema()
+        at = {n: (o, p) for n, p, o in zip(self.names, self.params, self.offsets)}
+        out = {}
+        for k, v in module.state_dict().items():
+            if k in at:
+                o, p = at[k]
+                out[k] = self.ema[o:o + p.numel()].view_as(p).clone()
+            else:
+                out[k] = v.detach().clone()
+        return out
+
+    def swap_ema(self):
+        """exchange parameters and average in place (validation on the averaged weights and back; its own inverse, bit for bit).
+        Plain copies: off the hot path, and every pointer a captured step recorded stays valid."""
+        self._need_ema()
+        with torch.no_grad():
+            tmp = self.flat.clone()
+            self.flat.copy_(self.ema)
+            self.ema.copy_(tmp)
 
     # ---- optimizer state (the reference's optimizer.pth, misc.py:87-102 / tools/train.py:112-119) --------------------
     def _natural_offsets(self):
@@ -85,6 +135,8 @@ class FlatParams:
         sd = {k: getattr(self, k).detach().cpu().clone() for k in self.state_keys}
         sd.update({'rule': self.rule, 'step_count': int(self.step_count), 'total': int(self.total),
                    'offsets': {n: int(o) for n, o in zip(self.names, self.offsets)}})  # r4: the layout the moments were saved in
+        if self.ema is not None:                    # the average travels like a state buffer: whole, in the layout of `offsets`
+            sd.update({'ema': self.ema.detach().cpu().clone(), 'ema_decay': float(self.ema_decay), 'ema_warmup': bool(self.ema_warmup)})
         return sd
 
     def load_state_dict(self, sd):
@@ -96,8 +148,11 @@ class FlatParams:
             raise ValueError('optimizer state is for %d flat elements, the model has %d' % (int(sd['total']), self.total))
         mine = {n: int(o) for n, o in zip(self.names, self.offsets)}
         theirs = sd.get('offsets') or self._natural_offsets()       # (no table: a checkpoint of rounds 1-3, natural order)
+        # the average loads like a state buffer when this object keeps one and the file has one; a file's average is ignored by an
+        # object without one; decay and warm-up stay what enable_ema() was given (the command line's, like the learning rate)
+        keys = tuple(self.state_keys) + (('ema',) if self.ema is not None and 'ema' in sd else ())
         if theirs == mine:
-            for key in self.state_keys:
+            for key in keys:
                 getattr(self, key).copy_(sd[key])
         else:
             # the buffer layout changed (r4 lays out a model's _flat_groups() back to back): move every parameter's moments by NAME
@@ -105,8 +160,13 @@ class FlatParams:
                 raise ValueError('optimizer state names do not match this model: %s' % sorted(set(theirs) ^ set(mine))[:4])
             for n, p in zip(self.names, self.params):
                 k, a, b = p.numel(), theirs[n], mine[n]
-                for key in self.state_keys:
+                for key in keys:
                     getattr(self, key)[b:b + k].copy_(sd[key][a:a + k])
+        if self.ema is not None and 'ema' not in sd:
+            self.ema.copy_(self.flat.detach())
+            if not getattr(self, '_ema_note', False):
+                print('optimizer state carries no moving average: it starts from the loaded parameters')
+                self._ema_note = True
         self.step_count = int(sd['step_count'])
 
     def load_torch_adam_state(self, sd):

@@ -9,7 +9,8 @@ What a graph would freeze is read from device memory instead (ops.StepState, cap
   * the dropout / sampling random streams: every seed-taking kernel offsets its seed argument by the record's `epoch` word while
     the record is bound (capmi_rng_bind_epoch); the model's per-iteration seed sequence restarts at every step, the epoch moves on;
   * Adam's step count, bias corrections and learning rate (capmi_adam_step_dyn; capmi_step_set_lr when the schedule moves) -- for
-    the other optimizers of misc.build_optimizer the same words feed capmi_optim_step_dyn.
+    the other optimizers of misc.build_optimizer the same words feed capmi_optim_step_dyn, and the step count the moving average of
+    the parameters (capmi_ema_step_dyn, --ema_decay), launched right after the optimizer.
 `capmi_step_advance` is the first launch of every iteration.  The STEPPED path of this class runs exactly the same launches under
 the same record, so stepped and captured training produce the same numbers bit for bit (tests/test_graph_step_gpu.py) -- the
 captured path is an issue-side optimisation, not a different computation.
@@ -74,6 +75,8 @@ class TrainStep:
             bufs = [getattr(f, k) for k in f.state_keys]
             ops.optim_step_dyn(f.rule, f.flat, f.grad, bufs[0], bufs[1] if len(bufs) > 1 else None, self.state, hp['betas'][0],
                                hp['betas'][1], hp['eps'], hp['weight_decay'], clip, scale)
+        if f.ema is not None:       # --ema_decay: the average follows the update, inside the capture when the update is (a replay advances it)
+            f.ema_update_dyn(self.state)
 
     def _body(self, t, sc_flag, struc_flag, with_adam):
         """advance the step record, forward + loss + backward into the flat gradient buffer (+ clip/Adam when no collective follows)"""

@@ -690,6 +690,18 @@ def optim_step_dyn(rule, p, g, s1, s2, state, alpha, beta, eps, weight_decay, cl
           'capmi_optim_step_dyn')
 
 
+def ema_step(ema, p, decay, warmup, step):
+    """ema = d * ema + (1 - d) * p over a flat fp32 range, d = min(decay, (1 + step) / (10 + step)) with `warmup` else decay.  `step`:
+    the 1-based step number (capmi.h capmi_ema_step)"""
+    check(lib.capmi_ema_step(ptr(ema), ptr(p), p.numel(), decay, int(bool(warmup)), int(step), stream_ptr()), 'capmi_ema_step')
+
+
+def ema_step_dyn(ema, p, state, decay, warmup):
+    """ema_step with the step number read from the device record `state` (after its advance()): the form a captured step replays"""
+    check(lib.capmi_ema_step_dyn(ptr(ema), ptr(p), p.numel(), state.buf.data_ptr(), decay, int(bool(warmup)), stream_ptr()),
+          'capmi_ema_step_dyn')
+
+
 def logsoftmax_bwd(g_dense, sparse, seq_logp, live, dlogits, N, L, T, V1, raw=False):
     """d(logits) [T,N,V1] from the loss gradient w.r.t. the dense log-probs: dense (`g_dense` [N,L,V1]), sparse
     (`sparse`, a _lib.SparseLogpGrad from sparse_logp.split_grad) or both.

@@ -16,7 +16,7 @@ caption's per-word region attention to <eval_results_dir>/<id>_<split>_att.npz: 
 for AdaAtt)], /top, /top_w, /entropy [L], /regions, and -- with the real-file loader and --input_box_dir -- /box (the attention-weighted
 box per word) and /top_box (the top region's own box); one device-to-host transfer per batch (imagecaptioning/pytorch_amd/att_trace.py).
 
-    python -m imagecaptioning.pytorch_amd.tools.eval --caption_model updown --beam_size 5 --num_images 20 [--start_from DIR]
+    python -m imagecaptioning.pytorch_amd.tools.eval --caption_model updown --beam_size 5 --num_images 20 [--start_from DIR | --model FILE]
 """
 import json
 import os
@@ -326,9 +326,11 @@ def main(opt):
     loader, opt.vocab = build_loader(opt, dev)
     torch.manual_seed(1234)
     model = models.setup(opt).to(dev)
-    if opt.start_from:
+    if getattr(opt, 'model', ''):       # tools/eval.py:25, :96 --model: one state-dict file by path (a run's model_ema.pth, model-best.pth, ...)
+        model.load_state_dict(torch.load(opt.model, map_location=dev))
+    elif opt.start_from:
         model.load_state_dict(torch.load(os.path.join(opt.start_from, 'model.pth'), map_location=dev))
-    crit = losses.LabelSmoothing(smoothing=opt.label_smoothing) if opt.label_smoothing > 0 else losses.LanguageModelCriterion()
+    crit =losses.LabelSmoothing(smoothing=opt.label_smoothing) if opt.label_smoothing > 0 else losses.LanguageModelCriterion()
     res = eval_split(model, crit, loader, opt)
     report(res)
     return res

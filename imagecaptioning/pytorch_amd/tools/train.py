@@ -122,6 +122,10 @@ def train(opt):
         model.load_state_dict(torch.load(os.path.join(opt.start_from, 'model.pth'), map_location=dev))
         infos = misc.load_infos(opt.start_from, opt.id)                          # tools/train.py:50-66
     flat = model.flatten_parameters_(optim['rule'])
+    if getattr(opt, 'ema_decay', 0.0):
+        # exponential moving average of the weights: a second flat buffer that starts as the (loaded) parameters; a resumed
+        # optimizer.pth overwrites it below.  Off (0, the default): no buffer, no launch, no model_ema.pth
+        flat.enable_ema(opt.ema_decay, warmup=bool(getattr(opt, 'ema_warmup', 1)))
     overlap = world > 1 and os.environ.get('CAPMI_DDP_OVERLAP', '0') == '1'      # default: ONE all-reduce per step
     if overlap:
         flat.begin_overlap()
@@ -181,7 +185,8 @@ def train(opt):
                                           # (position of the dropout / sampling streams: the step record's epoch word under TrainStep)
                                           'rng_calls': ts.state_dict()['epoch'] if ts is not None else int(getattr(model, '_rng_calls', 0)),
                                           'best_val_score': best_val_score, 'histories': histories, **last_loader},
-                             optimizer_state={'flat': flat.state_dict(), 'sched': sched.state_dict()}, append=append)
+                             optimizer_state={'flat': flat.state_dict(), 'sched': sched.state_dict()}, append=append,
+                             ema_state=flat.ema_state_dict(model) if flat.ema is not None else None)       # -> model_ema[-best].pth
 
     # language_eval (tools/train.py:246-266): rank 0 decodes and scores ITS part of the val split; the references -- hence the
     # document frequencies -- are the whole split's.  Built at the first validation.
@@ -229,6 +234,8 @@ def train(opt):
             clip = opt.grad_clip_value if opt.grad_clip_mode == 'value' else 0.0
             # buckets finished by the backward are already in flight; clip+Adam follows each as it lands
             flat.finish_overlap_and_step(opt.current_lr, optim['betas'], optim['eps'], optim['weight_decay'], clip_value=clip)
+            if flat.ema is not None:                   # (TrainStep launches it behind its own optimizer step)
+                flat.ema_update()
         # The reference reads the loss back right here (train.py:197), leaving the GPU idle while the host prepares the next
         # iteration.  Same values, one iteration later: the loss goes to a pinned buffer asynchronously and the host waits for the
         # PREVIOUS iteration's copy, so one iteration is always queued behind the running one (never more: the host stays at most
@@ -282,7 +289,14 @@ def train(opt):
                     from imagecaptioning.pytorch_amd.sentstats import SentenceStats
                     sent = sent or SentenceStats.for_loader(loader, 'val', dev, model, 1)
                     sent.reset()
-            val_sum, val_n = validation_loss(lw_model, loader, opt, dev, world, lang, sent)  # eval_utils.eval_split's loss half (:228-256)
+            ema_eval = flat.ema is not None and bool(getattr(opt, 'ema_eval', 1))
+            if ema_eval:                 # validate -- and so decide "best" and the plateau schedule -- on the averaged weights
+                flat.swap_ema()
+            try:
+                val_sum, val_n = validation_loss(lw_model, loader, opt, dev, world, lang, sent)  # eval_utils.eval_split's loss half (:228-256)
+            finally:
+                if ema_eval:
+                    flat.swap_ema()
             if lang is not None:
                 lang_stats = lang.compute()[0]
                 if sent is not None:

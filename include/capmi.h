@@ -528,6 +528,23 @@ int capmi_optim_step_dyn(const capmi_optim_hp *hp, float *p, const float *g, flo
                          const capmi_step_state *state, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Exponential moving average of the flat fp32 parameters (--ema_decay), one launch after the optimizer's, under every rule:
+ *   d   = warmup ? min(decay, (1 + step) / (10 + step)) : decay        (float arithmetic, inside the kernel)
+ *   ema = fma(d, ema, (1 - d) * p)
+ * p is read only; ema is read once and written once (non-temporal: nothing reads the average before the next step).  12 bytes
+ * per element.  ema and p need 4-byte alignment only: a range that starts off a 16-byte boundary gets a scalar head and tail,
+ * ranges misaligned differently from each other run scalar.
+ *   capmi_ema_step      the 1-based step number by value.
+ *   capmi_ema_step_dyn  the step number from the device record (capmi_step_state.adam_step, after capmi_step_advance): the
+ *                       form a captured training step replays.  Same arithmetic on the same floats: bit-equal.
+ * CAPMI_EINVAL, before anything is launched: a NULL ema / p / state, count <= 0, step < 1, decay outside [0, 1), a pointer
+ * off 4 bytes, ema == p.
+ * ------------------------------------------------------------------------------------------- */
+int capmi_ema_step(float *ema, const float *p, int64_t count, float decay, int warmup, int step, void *stream);
+int capmi_ema_step_dyn(float *ema, const float *p, int64_t count, const capmi_step_state *state, float decay, int warmup,
+                       void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * CIDEr-D reward (external pyciderevalcap.ciderD -- see oracle/ciderd.py for the provenance note;
  * call sites rewards.py:41-81, 83-114).  float64 arithmetic on device.
  *   table: open-addressing hash of the document-frequency pickle; keys = n-gram of <= 4 token ids
