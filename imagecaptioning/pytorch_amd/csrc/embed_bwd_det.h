@@ -16,7 +16,9 @@
 namespace capmi {
 
 constexpr int EBD_THREADS = 1024, EBD_WAVES = EBD_THREADS / 64;
-constexpr int EBD_MAX_ROWS = 14336;          // 56 KB of list
+// 56 KB of list + 16 KB of partials = 72 KB of dynamic LDS (+ 64 B static).  From 12 273 positions up that is past the 64 KB a
+// kernel may ask for by default: every caller goes through embed_bwd_det_opt_in() first.
+constexpr int EBD_MAX_ROWS = 14336;
 
 // G: float4 g(size_t position, int column) -- the gradient reaching the embedding output at (position, column .. column + 3)
 template <typename G>
@@ -70,5 +72,13 @@ __device__ __forceinline__ void embed_bwd_det_body(const int64_t *__restrict__ t
 }
 
 static inline size_t embed_bwd_det_lds(int rows) { return (size_t)((rows + 3) & ~3) * sizeof(int) + EBD_WAVES * 64 * sizeof(f32x4); }
+
+// the large-LDS opt-in of a kernel built on embed_bwd_det_body, sized for EBD_MAX_ROWS; the caller keeps the result in a function-local
+// static (one call per kernel and process) and returns it when it is not hipSuccess
+template <typename K>
+static inline hipError_t embed_bwd_det_opt_in(K kernel) {
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)embed_bwd_det_lds(EBD_MAX_ROWS));
+}
 
 }  // namespace capmi

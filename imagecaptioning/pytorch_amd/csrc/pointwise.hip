@@ -753,6 +753,8 @@ int capmi_embed_bwd(const int64_t *it, const float *dx, const float *x_saved, co
         ((reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(x_saved) | reinterpret_cast<uintptr_t>(mask) |
           reinterpret_cast<uintptr_t>(dE)) & 15) == 0) {
         // r6: ordered sums instead of atomicAdd -- the same bits on every run (embed_bwd_det.h)
+        static const hipError_t lds_opt_in = embed_bwd_det_opt_in(&embed_bwd_det_kernel);      // up to 72 KB of dynamic LDS
+        HIP_RC(lds_opt_in);
         hipLaunchKernelGGL(embed_bwd_det_kernel, dim3(rows, (Edim + 255) / 256), dim3(EBD_THREADS), embed_bwd_det_lds(rows),
                            (hipStream_t)stream, it, rows, Edim, dE, EmbedGrad{dx, x_saved, mask, Edim, relu});
         CAPMI_CHECK_LAUNCH();

@@ -1297,6 +1297,8 @@ int capmi_embed_pe_bwd(const int64_t *tok, int tok_ld, const float *dx, const fl
     if (det && D % 4 == 0 && (int64_t)N * T <= capmi::EBD_MAX_ROWS &&
         ((reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(drop) | reinterpret_cast<uintptr_t>(dE)) & 15) == 0) {
         // r6: ordered sums instead of atomicAdd -- the same bits on every run (embed_bwd_det.h)
+        static const hipError_t lds_opt_in = capmi::embed_bwd_det_opt_in(&embed_pe_bwd_det_kernel);      // up to 72 KB of dynamic LDS
+        HIP_RC(lds_opt_in);
         hipLaunchKernelGGL(embed_pe_bwd_det_kernel, dim3(N * T, (D + 255) / 256), dim3(capmi::EBD_THREADS),
                            capmi::embed_bwd_det_lds(N * T), (hipStream_t)stream, tok, T, tok_ld, N * T, D, dE,
                            EmbedPeGrad{dx, drop, D, sqrtf((float)D)});
