@@ -253,6 +253,13 @@ class XeLoss(C.Structure):
                 [(k, c_f) for k in ('logp', 'tok', 'mask', 'pos', 'msum', 'loss', 'g_out', 'g_sel', 'g_sum')])
 
 
+class Distill(C.Structure):
+    """capmi_distill (include/capmi.h): hard-label NLL + soft-target KL of one teacher-forced pass, forward and backward"""
+    _fields_ = ([(k, C.c_int) for k in ('N', 'T', 'V1', 'ld_s', 'ld_t', 'ld_grad', 't_rows', 'tok_ld', 'mask_ld', 'per_row')] +
+                [('lambda', C.c_float), ('tau', C.c_float)] +
+                [(k, c_f) for k in ('lp_s', 'lp_t', 'tok', 'mask', 'row_stats', 'msum', 'out', 'loss_rows', 'g_out', 'grad')])
+
+
 LANGEVAL_LMAX = 64     # capmi.h CAPMI_LANGEVAL_LMAX
 CIDERD_COOKED_BYTES = 4392     # capmi.h CAPMI_CIDERD_COOKED_BYTES
 SELF_CIDER_NMAX = 32   # capmi.h CAPMI_SELF_CIDER_NMAX
@@ -423,6 +430,8 @@ SIGNATURES = {
     'capmi_ppo_loss_bwd': [C.POINTER(Ppo), _P],
     'capmi_xe_loss_fwd': [C.POINTER(XeLoss), _P],
     'capmi_xe_loss_bwd': [C.POINTER(XeLoss), _P],
+    'capmi_distill_loss_fwd': [C.POINTER(Distill), _P],
+    'capmi_distill_loss_bwd': [C.POINTER(Distill), _P],
     'capmi_langeval_build': [C.POINTER(LangEval), _P],
     'capmi_langeval_add': [C.POINTER(LangEval), _P, _I, _I, _P, _P],
     'capmi_langeval_reduce': [C.POINTER(LangEval), _P, _P, _P],

@@ -19,6 +19,12 @@ class LossWrapper(torch.nn.Module):
         self.rl_crit = losses.RewardCriterion()
         self.struc_crit = losses.StructureLosses(opt) if getattr(opt, 'structure_loss_type', None) else None
         self.ppo_crit = losses.PPOLoss(opt, model) if getattr(opt, 'use_ppo', 0) else None
+        # distill_weight > 0: the plain XE branch trains against the frozen teacher of distill_from as well (SCST / structure
+        # branches and their lm_loss term keep self.crit).  0, the default: nothing is built, nothing is launched
+        self.distill_crit = self.distill_teacher = None
+        if getattr(opt, 'distill_weight', 0.0) > 0:
+            self.distill_teacher = losses.DistillTeacher(opt, model)          # (not an nn.Module: no parameters of ours)
+            self.distill_crit = losses.DistillCriterion(opt.distill_weight, getattr(opt, 'distill_temperature', 1.0))
 
     def forward(self, fc_feats, att_feats, labels, masks, att_masks, gts, gt_indices, sc_flag, struc_flag,
                 drop_worst_flag):
@@ -67,6 +73,16 @@ class LossWrapper(torch.nn.Module):
                 out['pg_loss'] = struc_loss['pg_loss']
                 out['kl_loss'] = struc_loss['kl_loss']
                 out['clipfrac'] = struc_loss['clipfrac']
+        elif not sc_flag and self.distill_crit is not None:
+            if getattr(self.model, 'ss_prob', 0.0) > 0:
+                raise NotImplementedError('distill_weight > 0 with scheduled sampling: teacher and student would condition on '
+                                          'different prefixes')
+            logp = self.model(fc_feats, att_feats, labels[..., :-1], att_masks)
+            teacher = self.distill_teacher(fc_feats, att_feats, labels[..., :-1], att_masks, logp.size(1))
+            d = self.distill_crit(logp, teacher, labels[..., 1:], masks[..., 1:], reduction=reduction)
+            loss = d['loss']
+            out['lm_loss'] = d['lm_loss']
+            out['kd_loss'] = d['kd_loss']
         elif not sc_flag:
             loss = self.crit(self.model(fc_feats, att_feats, labels[..., :-1], att_masks), labels[..., 1:], masks[..., 1:],
                              reduction=reduction)

@@ -288,3 +288,182 @@ class PPOLoss(nn.Module):
         else:
             out['loss'] = out['pg_loss'] + self.kl_coef * out['kl_loss']
         return out
+
+
+def check_distill_opt(opt):
+    """the start-up refusals of distill_weight > 0 (each with its reason); returns (names, normalised weights)"""
+    from imagecaptioning.pytorch_amd import _lib
+    names = list(getattr(opt, 'distill_from', None) or [])
+    if getattr(opt, 'label_smoothing', 0) > 0:
+        raise NotImplementedError('distill_weight > 0 with label_smoothing > 0: the teacher\'s soft targets replace the smoothed '
+                                  'hard targets; set label_smoothing 0')
+    if getattr(opt, 'scheduled_sampling_start', -1) >= 0 or getattr(opt, 'ss_prob', 0.0) > 0:
+        raise NotImplementedError('distill_weight > 0 with scheduled sampling: the student would condition on its own sampled '
+                                  'prefix and the teacher on the ground truth; set scheduled_sampling_start -1')
+    if not names:
+        raise NotImplementedError('distill_weight > 0 needs at least one teacher: distill_from is empty')
+    if len(names) > _lib.ENSEMBLE_MAX:
+        raise NotImplementedError('distill_from names %d teachers; the mixture kernel takes at most %d (CAPMI_ENSEMBLE_MAX)'
+                                  % (len(names), _lib.ENSEMBLE_MAX))
+    lam, tau = float(opt.distill_weight), float(getattr(opt, 'distill_temperature', 1.0))
+    if not (0.0 < lam <= 1.0) or not (0.0 < tau < float('inf')):
+        raise ValueError('distill_weight must lie in (0, 1] and distill_temperature be positive and finite (got %r, %r)' % (lam, tau))
+    w = list(getattr(opt, 'distill_weights', None) or [1.0] * len(names))
+    if len(w) != len(names) or any(not (x >= 0.0) or x == float('inf') for x in w) or not sum(w) > 0.0:
+        raise ValueError('distill_weights: %d finite weights >= 0 with a positive sum expected (got %r)' % (len(names), w))
+    tot = float(sum(w))
+    return names, [float(x) / tot for x in w]
+
+
+class DistillTeacher:
+    """The frozen teacher of DistillCriterion: the members named by ``distill_from`` (id[-suffix], as tools/eval_ensemble.py --ids
+    names them, under ``distill_log_root``), each built as its own family from its saved infos (models.setup) with its weights, on
+    the student's device, in eval mode.  Members may be of different families; their vocabulary must be the student's.
+
+    Deliberately not an nn.Module: the members are not part of the student's parameters, state_dict, flat optimizer buffer, EMA or
+    checkpoints.  ``members``: already built models instead of saved runs (then nothing is loaded)."""
+
+    def __init__(self, opt, model, members=None):
+        self.names, self.weights = check_distill_opt(opt)
+        if members is None:
+            members = self._load(opt, model)
+        if len(members) != len(self.names):
+            raise ValueError('%d members for the %d names of distill_from' % (len(members), len(self.names)))
+        V = getattr(model, 'vocab_size', None)
+        for name, m in zip(self.names, members):
+            if getattr(m, 'vocab_size', None) != V:
+                raise ValueError('distill_from member %r has another vocabulary than the student (vocab_size %s vs %s)'
+                                 % (name, getattr(m, 'vocab_size', None), V))
+            m.eval()
+            for p in m.parameters():
+                p.requires_grad = False
+        self.members = list(members)
+
+    def _load(self, opt, model):
+        import argparse
+        from .. import models
+        from ..utils import misc
+        from imagecaptioning.pytorch_amd.tools.eval_ensemble import member_paths
+        dev = next(model.parameters()).device
+        out = []
+        for name, (d, id_, suffix, _, model_path) in zip(self.names, member_paths(self.names, getattr(opt, 'distill_log_root', '.'))):
+            inf = misc.load_infos_suffixed(d, id_, suffix)
+            if getattr(opt, 'vocab', None) is not None and inf.get('vocab') is not None and inf['vocab'] != opt.vocab:
+                raise ValueError('distill_from member %r has another vocabulary than the student' % name)
+            mopt = argparse.Namespace(**vars(inf['opt']))
+            mopt.start_from, mopt.vocab = None, inf.get('vocab', getattr(opt, 'vocab', None))
+            m = models.setup(mopt).to(dev)
+            m.load_state_dict(torch.load(model_path, map_location=dev))
+            out.append(m)
+        return out
+
+    def __call__(self, fc_feats, att_feats, seq, att_masks, T):
+        """the teacher's log-probs of one batch, [N, >= T, V1] (only the first T steps are meaningful to the caller): every member's
+        teacher-forced forward on the student's input tokens; M >= 2 members are mixed by capmi_ensemble_logprobs"""
+        lps = []
+        with torch.no_grad():
+            for m in self.members:
+                m.eval()
+                lp = m(fc_feats, att_feats, seq, att_masks)
+                if lp.size(1) < T:
+                    raise RuntimeError('a distillation teacher returned %d steps, the student %d' % (lp.size(1), T))
+                lps.append(lp)
+            if len(lps) == 1:
+                return lps[0]
+            if lps[0].is_cuda and all(lp.dtype == torch.float32 for lp in lps):
+                from imagecaptioning.pytorch_amd import ops
+                cut = [lp if lp.size(1) == T else lp[:, :T].contiguous() for lp in lps]
+                N, _, V1 = cut[0].shape
+                return ops.ensemble_logprobs([lp.contiguous().view(N * T, V1) for lp in cut], self.weights).view(N, T, V1)
+            w = torch.tensor(self.weights, dtype=lps[0].dtype, device=lps[0].device).log().view(-1, 1, 1, 1)
+            return torch.logsumexp(torch.stack([torch.log_softmax(lp[:, :T], 2) for lp in lps]) + w, 0)
+
+
+class _FusedDistill(torch.autograd.Function):
+    """DistillCriterion's arithmetic on the device: forward = capmi_distill_loss_fwd (two launches), backward = capmi_distill_loss_bwd
+    (one launch, the dense [N,T,V1] gradient written once; it reaches the teacher-forced backward as its dense gradient,
+    sparse_logp.split_grad).  `stats` receives the [3] device tensor lm_loss, kd_loss, loss (no host sync)."""
+
+    @staticmethod
+    def forward(ctx, input, lt, tok, mask, lam, tau, per_row, stats):
+        from imagecaptioning.pytorch_amd import ops
+        x = input.detach()
+        out, loss_rows, row_stats, msum = ops.distill_loss_fwd(x, lt, tok, mask, lam, tau, per_row)
+        ctx.save_for_backward(x, lt, tok, mask, row_stats, msum)
+        ctx.cfg = (lam, tau, per_row)
+        stats['out'] = out
+        return loss_rows if per_row else out[2]
+
+    @staticmethod
+    def backward(ctx, g):
+        from imagecaptioning.pytorch_amd import ops
+        x, lt, tok, mask, row_stats, msum = ctx.saved_tensors
+        lam, tau, per_row = ctx.cfg
+        # 'mean': the upstream gradient stays a device scalar
+        grad = ops.distill_loss_bwd(x, lt, tok, mask, row_stats, msum, g.reshape(-1).float(), lam, tau, per_row)
+        return grad, None, None, None, None, None, None, None
+
+
+class DistillCriterion(nn.Module):
+    """Knowledge distillation on the teacher-forced pass: (1 - lambda) NLL(target) + lambda tau^2 KL(softmax(teacher / tau) ||
+    softmax(student / tau)), masked means as LanguageModelCriterion's (the normative formula: include/capmi.h, capmi_distill).
+    Returns {'loss', 'lm_loss' (masked mean NLL), 'kd_loss' (masked mean KL before lambda and tau^2)}.
+
+    Two routes compute the same numbers: device float32 contiguous inputs go through _FusedDistill (every dense row is read once
+    per pass, nothing dense goes through ATen); anything else (CPU tensors, float64) through ``generic``, plain torch."""
+
+    def __init__(self, weight, temperature=1.0):
+        super().__init__()
+        self.weight, self.temperature = float(weight), float(temperature)
+
+    @staticmethod
+    def _dense2d(t, N, T):
+        return t.ndim == 2 and t.shape[0] == N and t.shape[1] >= T and (t.shape[1] == 1 or t.stride(1) == 1) and (N == 1 or t.stride(0) >= T)
+
+    def forward(self, input, teacher, target, mask, reduction='mean'):
+        if target.ndim == 3:
+            target = target.reshape(-1, target.shape[2])
+            mask = mask.reshape(-1, mask.shape[2])
+        N, T, V1 = input.shape
+        fused = (input.is_cuda and input.dtype == torch.float32 and input.is_contiguous() and N > 0 and T > 0
+                 and teacher.is_cuda and teacher.dtype == torch.float32 and teacher.ndim == 3 and teacher.shape[0] == N
+                 and teacher.shape[1] >= T and teacher.shape[2] == V1 and (V1 == 1 or teacher.stride(2) == 1)
+                 and (N == 1 or (teacher.stride(1) > 0 and teacher.stride(0) % teacher.stride(1) == 0
+                                 and teacher.stride(0) // teacher.stride(1) >= teacher.shape[1]))
+                 and not teacher.requires_grad and target.dtype == torch.int64 and target.is_cuda and mask.is_cuda
+                 and not mask.requires_grad and self._dense2d(target, N, T) and mask.ndim == 2 and mask.shape[0] == N
+                 and mask.shape[1] >= T)
+        if not fused:
+            return self.generic(input, teacher, target, mask, reduction)
+        if mask.dtype != torch.float32 or not self._dense2d(mask, N, T):
+            mask = mask[:, :T].float().contiguous()
+        stats = {}
+        loss = _FusedDistill.apply(input, teacher, target, mask, self.weight, self.temperature, reduction == 'none', stats)
+        st = stats['out']
+        return {'loss': loss, 'lm_loss': st[0], 'kd_loss': st[1]}
+
+    def generic(self, input, teacher, target, mask, reduction='mean'):
+        """the formula in plain torch (the route of CPU and float64 tensors)"""
+        if target.ndim == 3:
+            target = target.reshape(-1, target.shape[2])
+            mask = mask.reshape(-1, mask.shape[2])
+        N, T, V1 = input.shape
+        lam, tau = self.weight, self.temperature
+        target = target[:, :T]
+        mask = mask[:, :T].to(input)
+        on = mask != 0
+        zero = torch.zeros((), dtype=input.dtype, device=input.device)
+        ok = (target >= 0) & (target < V1)
+        nll = -input.gather(2, target.clamp(0, V1 - 1).unsqueeze(2)).squeeze(2)
+        nll = torch.where(ok, nll, torch.full_like(nll, float('nan')))
+        lp_s = torch.log_softmax(input / tau, 2)
+        lp_t = torch.log_softmax(teacher[:, :T].detach().to(input) / tau, 2)
+        p_t = lp_t.exp()
+        kl = torch.where(p_t > 0, p_t * (lp_t - lp_s), zero).sum(2)
+        # a masked position is not read: an exact 0, also where it holds an infinity or a NaN
+        nll_m, kl_m = torch.where(on, mask * nll, zero), torch.where(on, mask * kl, zero)
+        c = torch.where(on, mask * ((1.0 - lam) * nll + lam * tau * tau * kl), zero)
+        msum = mask.sum()
+        out = {'lm_loss': nll_m.sum() / msum, 'kd_loss': kl_m.sum() / msum}
+        out['loss'] = c.sum(1) / mask.sum(1) if reduction == 'none' else c.sum() / msum
+        return out

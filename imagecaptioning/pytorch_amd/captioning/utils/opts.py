@@ -22,6 +22,11 @@ DEFAULTS = dict(
     # no launch, no file.  ema_warmup: decay = min(ema_decay, (1 + step) / (10 + step)).  ema_eval: validate (and pick "best") on the
     # averaged weights.  Checkpoints gain model_ema[-best].pth, optimizer.pth carries the average
     ema_decay=0.0, ema_warmup=1, ema_eval=1,
+    # knowledge distillation (losses.DistillCriterion / DistillTeacher; not a flag of the reference).  distill_from: id[-suffix] of saved
+    # runs, named as tools/eval_ensemble.py --ids names them (log_<id>/ under distill_log_root); distill_weights: their mixture weights
+    # (default: equal); distill_weight: lambda of (1 - lambda) NLL + lambda tau^2 KL(teacher || student), 0: off -- no teacher, no launch;
+    # distill_temperature: tau
+    distill_from=[], distill_weights=[], distill_weight=0.0, distill_temperature=1.0, distill_log_root='.',
     checkpoint_path='log_capmi', id='capmi', save_checkpoint_every=0, losses_log_every=10, start_from=None, seed=1234,
     # transformer / aoa
     N_enc=6, N_dec=6, d_model=512, d_ff=2048, num_att_heads=8, dropout=0.1, refine=1, refine_aoa=1, use_ff=0, decoder_type='AoA',
@@ -57,13 +62,24 @@ DEFAULTS = dict(
 RESIDENT_DTYPES = ('fp32', 'bf16', 'fp16')
 
 
+LIST_ELEMENTS = dict(distill_from=str, distill_weights=float)      # the list-valued flags: --flag A B ...
+
+
+def add_flag(ap, k, v):
+    """--k with the type of its default v, default None (= not given on the command line)"""
+    if k in LIST_ELEMENTS:
+        ap.add_argument('--' + k, nargs='*', type=LIST_ELEMENTS[k], default=None)
+    else:
+        ap.add_argument('--' + k, type=(type(v) if v is not None else str), default=None)
+
+
 def parse_opt(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--cfg', type=str, default=None)
     for k, v in DEFAULTS.items():
-        ap.add_argument('--' + k, type=(type(v) if v is not None else str), default=None)
+        add_flag(ap, k, v)
     ns = ap.parse_args(argv)
-    opt = dict(DEFAULTS)
+    opt = {k: (list(v) if isinstance(v, list) else v) for k, v in DEFAULTS.items()}
     if ns.cfg:
         for k, v in config.load(ns.cfg).items():
             opt[k] = v

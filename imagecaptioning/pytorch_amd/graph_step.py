@@ -157,7 +157,9 @@ class TrainStep:
         multi = self.all_reduce is not None
         graphable = self.graph and not force_stepped and self.failed is None and not drop_worst_flag and getattr(self.model, 'ss_prob', 0.0) == 0.0 \
             and self.flat.on_grads_ready is None \
-            and not (struc_flag and getattr(o, 'use_ppo', 0))    # the old model's teacher-forced forward picks its length on the host
+            and not (struc_flag and getattr(o, 'use_ppo', 0)) \
+            and not (getattr(o, 'distill_weight', 0.0) > 0 and not sc_flag and not struc_flag)
+        # (use_ppo's old model and a distillation's teachers pick the length of their teacher-forced forward on the host)
         if (sc_flag or struc_flag) and getattr(o, 'train_beam_size', 1) > 1:
             graphable = False                                     # beam-search SCST runs launch by launch
         ent = None

@@ -958,6 +958,90 @@ def xe_loss_bwd(mask, msum, T, V1, smoothing=0.0, per_row=False, g_out=None):
     return g_sel, g_sum
 
 
+def _distill_desc(lp_t, tok, mask, N, T, V1, lam, tau, per_row, what):
+    """the capmi_distill descriptor of a teacher [N, >= T, V1] (dense rows, any row / sample stride), tok / mask [N, >= T]"""
+    if lp_t.dim() != 3 or lp_t.dtype != _f32 or lp_t.shape[0] != N or lp_t.shape[1] < T or lp_t.shape[2] != V1:
+        raise _lib.CapmiError('%s: teacher log-probs [%d, >= %d, %d] float32 expected (got %s %s)'
+                              % (what, N, T, V1, tuple(lp_t.shape), lp_t.dtype))
+    if V1 > 1 and lp_t.stride(2) != 1:
+        raise _lib.CapmiError('%s: the rows of the teacher must be dense' % what)
+    # row (i, t) at (i * t_rows + t) * ld_t: the sample stride must be a whole number of rows
+    ld_t = lp_t.stride(1) if lp_t.shape[1] > 1 else V1
+    t_rows = lp_t.shape[1]
+    if N > 1:
+        if ld_t <= 0 or lp_t.stride(0) % ld_t or lp_t.stride(0) // ld_t < lp_t.shape[1]:
+            raise _lib.CapmiError('%s: teacher strides %s are not rows of one pitch' % (what, lp_t.stride()))
+        t_rows = lp_t.stride(0) // ld_t
+    for name, t, dt in (('tok', tok, torch.int64), ('mask', mask, _f32)):
+        if t.dtype != dt or t.dim() != 2 or t.shape[0] != N or t.shape[1] < T or (t.shape[1] > 1 and t.stride(1) != 1) \
+                or (N > 1 and t.stride(0) < T):
+            raise _lib.CapmiError('%s: %s [%d, >= %d] %s with dense rows expected (got %s %s)' % (what, name, N, T, dt, tuple(t.shape), t.dtype))
+    for t in (lp_t, tok, mask):
+        if not t.is_cuda:
+            raise _lib.CapmiError('capmi ops need device tensors (got %s)' % t.device)
+    p = _lib.Distill()
+    p.N, p.T, p.V1 = N, T, V1
+    p.ld_s = p.ld_grad = V1
+    p.ld_t, p.t_rows = ld_t, t_rows
+    p.tok_ld = tok.stride(0) if N > 1 else tok.shape[1]
+    p.mask_ld = mask.stride(0) if N > 1 else mask.shape[1]
+    p.per_row = int(bool(per_row))
+    setattr(p, 'lambda', float(lam))
+    p.tau = float(tau)
+    p.lp_t, p.tok, p.mask = lp_t.data_ptr(), tok.data_ptr(), mask.data_ptr()
+    return p
+
+
+def distill_loss_fwd(lp_s, lp_t, tok, mask, lam, tau=1.0, per_row=False):
+    """DistillCriterion's arithmetic (capmi.h capmi_distill_loss_fwd, two launches): lp_s [N, T, V1] float32 contiguous, the student's
+    teacher-forced log-probs; lp_t [N, >= T, V1] float32, the teacher's (dense rows; a [:, :T] cut or a wider row stride is read in
+    place); tok [N, >= T] int64 and mask [N, >= T] float32 read through their row pitch.  Returns (out [3] = lm_loss, kd_loss, loss
+    ('mean'); loss_rows [N] ('none') or None; row_stats [4, N, T] = lseS, lseT, kl, -ls[tok]; msum [1] or [N]), all on the device."""
+    if lp_s.dim() != 3 or lp_s.dtype != _f32 or not lp_s.is_contiguous():
+        raise _lib.CapmiError('distill_loss_fwd: student log-probs [N, T, V1] float32 contiguous expected (got %s %s)'
+                              % (tuple(lp_s.shape), lp_s.dtype))
+    _chk(lp_s)
+    N, T, V1 = lp_s.shape
+    p = _distill_desc(lp_t, tok, mask, N, T, V1, lam, tau, per_row, 'distill_loss_fwd')
+    dev = lp_s.device
+    row_stats = torch.empty(4, N, T, dtype=_f32, device=dev)
+    msum = torch.empty(N if per_row else 1, dtype=_f32, device=dev)
+    out = torch.empty(3, dtype=_f32, device=dev)
+    loss_rows = torch.empty(N, dtype=_f32, device=dev) if per_row else None
+    p.lp_s = lp_s.data_ptr()
+    p.row_stats, p.msum, p.out, p.loss_rows = row_stats.data_ptr(), msum.data_ptr(), out.data_ptr(), ptr(loss_rows)
+    check(lib.capmi_distill_loss_fwd(C.byref(p), stream_ptr()), 'capmi_distill_loss_fwd')
+    return out, loss_rows, row_stats, msum
+
+
+def distill_loss_bwd(lp_s, lp_t, tok, mask, row_stats, msum, g_out, lam, tau=1.0, per_row=False, out=None):
+    """d loss / d lp_s of distill_loss_fwd (capmi_distill_loss_bwd, one launch): the inputs as given to the forward, row_stats and msum
+    as it returned them, g_out the upstream gradient ([1] or 0-dim for 'mean', [N] for 'none', float32 on the device).  Returns the
+    dense [N, T, V1] gradient (masked rows are zeros)."""
+    if lp_s.dim() != 3 or lp_s.dtype != _f32 or not lp_s.is_contiguous():
+        raise _lib.CapmiError('distill_loss_bwd: student log-probs [N, T, V1] float32 contiguous expected (got %s %s)'
+                              % (tuple(lp_s.shape), lp_s.dtype))
+    N, T, V1 = lp_s.shape
+    p = _distill_desc(lp_t, tok, mask, N, T, V1, lam, tau, per_row, 'distill_loss_bwd')
+    g_out = g_out.reshape(-1)
+    if g_out.dtype != _f32 or g_out.numel() != (N if per_row else 1):
+        raise _lib.CapmiError('distill_loss_bwd: upstream gradient of %d float32 values expected (got %s %s)'
+                              % (N if per_row else 1, tuple(g_out.shape), g_out.dtype))
+    if row_stats.dtype != _f32 or tuple(row_stats.shape) != (4, N, T) or not row_stats.is_contiguous() or msum.dtype != _f32 \
+            or msum.numel() != (N if per_row else 1):
+        raise _lib.CapmiError('distill_loss_bwd: row_stats [4, N, T] and msum as returned by distill_loss_fwd expected')
+    if out is None:
+        out = torch.empty(N, T, V1, dtype=_f32, device=lp_s.device)
+    if tuple(out.shape) != (N, T, V1) or out.dtype != _f32 or not out.is_contiguous():
+        raise _lib.CapmiError('distill_loss_bwd: out must be contiguous float32 of shape %s' % ((N, T, V1),))
+    g_out = g_out.contiguous()
+    _chk(lp_s, row_stats, msum, g_out, out)
+    p.lp_s = lp_s.data_ptr()
+    p.row_stats, p.msum, p.g_out, p.grad = row_stats.data_ptr(), msum.data_ptr(), g_out.data_ptr(), out.data_ptr()
+    check(lib.capmi_distill_loss_bwd(C.byref(p), stream_ptr()), 'capmi_distill_loss_bwd')
+    return out
+
+
 def clip_len(att_masks, width=None):
     """Longest valid region count of the batch -- the K that clip_att (AttModel.py:106-112) truncates to.
 

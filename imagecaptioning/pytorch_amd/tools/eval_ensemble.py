@@ -53,7 +53,7 @@ def parse_args(argv=None):
     ap.add_argument('--weights', nargs='+', type=float, default=None, help='one weight per id (default: all equal)')
     ap.add_argument('--log_root', type=str, default='.', help='directory holding the log_<id> directories')
     for k, v in opts.DEFAULTS.items():
-        ap.add_argument('--' + k, type=(type(v) if v is not None else str), default=None)
+        opts.add_flag(ap, k, v)
     ns = ap.parse_args(argv)
     explicit = {k: getattr(ns, k) for k in opts.DEFAULTS if getattr(ns, k) is not None}
     return ns.ids, ns.weights, ns.log_root, explicit

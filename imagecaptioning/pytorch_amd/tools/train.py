@@ -264,7 +264,11 @@ def train(opt):
                     print('iter %d (epoch %d), pg_loss = %.3f, kl_loss = %.3f, clipfrac = %.3f'
                           % (it, epoch, out['pg_loss'].item(), out['kl_loss'].item(), out['clipfrac'].item()))
             elif not sc_flag:
-                print('iter %d (epoch %d), train_loss = %.3f, time/batch = %.3f' % (it, epoch, train_loss, t2 - t1))
+                if 'kd_loss' in out:         # distill_weight > 0
+                    print('iter %d (epoch %d), train_loss = %.3f, lm_loss = %.3f, kd_loss = %.4g, time/batch = %.3f'
+                          % (it, epoch, train_loss, out['lm_loss'].item(), out['kd_loss'].item(), t2 - t1))
+                else:
+                    print('iter %d (epoch %d), train_loss = %.3f, time/batch = %.3f' % (it, epoch, train_loss, t2 - t1))
             else:
                 print('iter %d (epoch %d), avg_reward = %.3f, time/batch = %.3f' % (it, epoch, out['reward'].mean().item(), t2 - t1))
             print('Read data:', t1 - t0)

@@ -1461,6 +1461,55 @@ int capmi_xe_loss_fwd(const capmi_xe_loss *p, void *stream);
 int capmi_xe_loss_bwd(const capmi_xe_loss *p, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Knowledge distillation (distill.hip; losses.DistillCriterion): the hard-label NLL of the teacher-forced pass mixed with the
+ * temperature-softened KL(teacher || student) over the whole vocabulary.  There is no reference counterpart: the formula below is
+ * normative (tests/distill_ref64.py restates it in float64).  Position (i, t), t < T, with the student row ls = lp_s[i, t, :],
+ * the teacher row lt = lp_t[i, t, :], s = tok[i, t], m = mask[i, t], lambda in [0, 1], tau > 0:
+ *   a = ls / tau, b = lt / tau, pS = softmax(a), pT = softmax(b)
+ *   kl   = sum_v pT_v (log pT_v - log pS_v)                       (a term with pT_v == 0 is exactly 0)
+ *   c    = m ((1 - lambda) (-ls_s) + lambda tau^2 kl)
+ *   loss = sum c / sum m ('mean');  per_row ('none', the drop_worst route): loss_rows[i] = sum_t c / sum_t m
+ *   d loss / d ls_v = g m / M (-(1 - lambda) [v == s] + lambda tau (pS_v - pT_v))
+ * A position with m == 0 is not read, contributes an exact 0 and gets a gradient row of zeros; a mask sum of 0 gives 0 / 0 = NaN as
+ * the other criteria do; a token outside [0, V1) gives NaN and is not read (its gradient row has no hard-label term).
+ * Rows are addressed through strides: student row (i, t) at lp_s + (i T + t) ld_s, teacher row at lp_t + (i t_rows + t) ld_t (the
+ * teacher may be the [:, :T] cut of a longer [N, t_rows, .] tensor), gradient row at grad + (i T + t) ld_grad.
+ *
+ * capmi_distill_loss_fwd: two launches, no float atomics; two runs on the same inputs are bit-equal.  (1) one workgroup per (i, t)
+ *   row reads the student and the teacher row once, in one sweep (scalar head up to the 16-byte boundary, float4 body, scalar
+ *   tail where both rows share their alignment mod 16 bytes, else scalar): an online-rescaled running max and sum for both rows
+ *   and the running sum_v e^(b_v - max) (b_v - a_v), so that kl = that / zT - lseT + lseS takes no second pass.  Writes
+ *   row_stats [4][N*T] = {lseS, lseT, kl, -ls_s} (lse of the tempered rows; masked positions: zeros).  (2) one workgroup folds them
+ *   in double in a fixed order: out [3] = {lm_loss = masked mean of -ls_s, kd_loss = masked mean of kl (before lambda and tau^2),
+ *   loss}, msum ([1], or [N] with per_row) and, with per_row, loss_rows [N].
+ * capmi_distill_loss_bwd: one launch, one workgroup per row; reads both rows, row_stats, msum and the upstream gradient g_out ([1]
+ *   for 'mean': a device scalar, no host sync; [N] for per_row) and writes the dense gradient once, with plain stores: the
+ *   teacher-forced backward reads it next.  lambda == 0 reads neither row.
+ * CAPMI_EINVAL: tau <= 0 or not finite, lambda outside [0, 1], a stride below V1, t_rows, tok_ld or mask_ld below T, N < 0, T or
+ * V1 below 1, a NULL pointer that the call reads or writes, a pointer off 4 bytes.  N == 0: success, nothing launched.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct capmi_distill {
+    int N, T, V1;
+    int ld_s, ld_t, ld_grad;         /* row strides, floats, >= V1 */
+    int t_rows;                      /* rows per sample of the teacher tensor, >= T */
+    int tok_ld, mask_ld;             /* row pitches of tok / mask, elements, >= T */
+    int per_row;                     /* 0: reduction 'mean', 1: 'none' */
+    float lambda, tau;               /* distill_weight, distill_temperature */
+    const float *lp_s;               /* [N*T, V1] the student's teacher-forced log-probs */
+    const float *lp_t;               /* [N, t_rows, V1] the teacher's log-probs */
+    const int64_t *tok;              /* [N, tok_ld] targets */
+    const float *mask;               /* [N, mask_ld] */
+    float *row_stats;                /* [4][N*T] lseS, lseT, kl, -ls_s (written by fwd, read by bwd) */
+    float *msum;                     /* [1] or [N] mask sums (written by fwd, read by bwd) */
+    float *out;                      /* [3] lm_loss, kd_loss, loss (fwd) */
+    float *loss_rows;                /* [N] per_row losses (fwd, per_row only) */
+    const float *g_out;              /* [1] or [N] upstream gradient (bwd) */
+    float *grad;                     /* [N*T, V1] d loss / d lp_s (bwd) */
+} capmi_distill;
+int capmi_distill_loss_fwd(const capmi_distill *p, void *stream);
+int capmi_distill_loss_bwd(const capmi_distill *p, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Corpus language evaluation without Java: coco-caption's Cider, Bleu (option 'closest') and Rouge over token ids, for the
  * validation pass (eval_utils.language_eval -> lang_stats['CIDEr'], 'Bleu_1'..'Bleu_4', 'ROUGE_L').  A caption is the tokens of
  * its int64 row before the first 0 (the whole row when it holds none); ids are below 65535.  Restated from the published
