@@ -263,6 +263,7 @@ class Distill(C.Structure):
 LANGEVAL_LMAX = 64     # capmi.h CAPMI_LANGEVAL_LMAX
 CIDERD_COOKED_BYTES = 4392     # capmi.h CAPMI_CIDERD_COOKED_BYTES
 SELF_CIDER_NMAX = 32   # capmi.h CAPMI_SELF_CIDER_NMAX
+MBR_CIDERD, MBR_BLEU4 = 0, 1   # capmi.h CAPMI_MBR_*
 LANGEVAL_E_TABLE_FULL, LANGEVAL_E_TOKEN, LANGEVAL_E_IMAGE = 1, 2, 4      # capmi.h CAPMI_LANGEVAL_E_*
 DF_E_OFFSETS = 8       # capmi.h CAPMI_DF_E_OFFSETS
 
@@ -365,6 +366,8 @@ SIGNATURES = {
     'capmi_reward_bleu4': [_P, _I, _I, _P, _P, _P, _I, _I, _I, _P, C.c_double, C.c_double, _P, _P, _P],
     'capmi_self_cider_reward': [_P, _I, _I, _I, _P, _P, C.c_uint32, C.c_double, _P, _P, _P, _P, _P, _P],
     'capmi_nsc_advantage': [_P, _P, C.c_double, _I, _I, _P, _P, _P],
+    'capmi_mbr_utility': [_P, _I, _I, _I, _I, _P, _P, C.c_uint32, C.c_double, _P, _P, _P],
+    'capmi_mbr_select': [_P, _P, _P, _I, _I, _I, _P, _P, _P],
     'capmi_prof_enable': [_I],
     'capmi_prof_reset': [],
     'capmi_prof_read': [_I, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)],

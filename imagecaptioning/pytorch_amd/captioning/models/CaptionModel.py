@@ -2,7 +2,7 @@
 import torch
 import torch.nn as nn
 
-from imagecaptioning.pytorch_amd import att_trace
+from imagecaptioning.pytorch_amd import att_trace, mbr
 
 BAD_ENDINGS = ['a', 'an', 'the', 'in', 'for', 'at', 'of', 'with', 'before', 'after', 'on', 'upon', 'near', 'to', 'is',
                'are', 'am', 'the']       # AttModel.py:27
@@ -23,7 +23,19 @@ class CaptionModel(nn.Module):
     # why a family has no trace (None: it has one)
     _trace_refusal = 'the model keeps no per-step weights over the regions'
 
+    # ---- opt['rerank'] (imagecaptioning.pytorch_amd.mbr): consensus reranking of the sample_n captions of every image
+    last_rerank = None          # dict of device tensors (choice, expected, utility, candidates, candidate_logp_sum) after such a call
+
     def _sample_entry(self, *args, **kwargs):
+        opt = kwargs.get('opt') or (args[3] if len(args) > 3 else None)
+        if self.last_rerank is not None:
+            self.last_rerank = None
+        if not mbr.wanted(opt):
+            return self._sample_traced(*args, **kwargs)
+        mbr.check_options(self, opt)                        # every refusal, before any device work
+        return mbr.apply(self, opt, self._sample_traced(*args, **kwargs))
+
+    def _sample_traced(self, *args, **kwargs):
         opt = kwargs.get('opt') or (args[3] if len(args) > 3 else None)
         if self.last_attention is not None:
             self.last_attention = None

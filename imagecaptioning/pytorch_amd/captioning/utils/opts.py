@@ -48,6 +48,10 @@ DEFAULTS = dict(
     # tools/eval.py: write every decoded caption's per-word region attention (opt['return_attention'], imagecaptioning/pytorch_amd/
     # att_trace.py) to <eval_results_dir>/<id>_<split>_att.npz; updown / topdown, att2in2, adaatt, adaattmo
     dump_attention=0,
+    # consensus (minimum-Bayes-risk) reranking of the sample_n captions of every image (opt['rerank'], imagecaptioning/pytorch_amd/mbr.py;
+    # not a flag of the reference): '' off, 'mbr_ciderd' / 'mbr_bleu4' keep the caption with the highest expected CIDEr-D / BLEU-4
+    # against the others; rerank_prior: 'uniform', or 'model' -- every candidate weighs as much as the model believes in it
+    rerank='', rerank_prior='uniform',
     # data (synthetic only: the reference's h5/lmdb loaders are outside the hot path)
     input_synthetic=1, vocab_size=9487, synthetic_regions=36, synthetic_images=200,
     # real precomputed features (captioning/data/feature_loader.py; opts.py:23-37 of the reference)

@@ -13,41 +13,14 @@
 // HBM or MFMA roofline to chase, the win is removing the device->host sync from the SCST step.
 //
 // Keys, the token convention (cut after the first 0), the cooking of a row and the per-order norm / dot / cosine are the
-// family's (ngram_metrics.h); this file keeps what is CIDEr-D's own: the cooked blob, the clipped product, the length penalty.
-#include "ngram_metrics.h"
+// family's (ngram_metrics.h); CIDEr-D's own are the cooked blob and the length penalty (ciderd_cooked.h, shared with mbr.hip) and the
+// clipped product here.
+#include "ciderd_cooked.h"
 #include "profile.h"
 
 using namespace capmi;
 
 namespace {
-
-constexpr double SIGMA = 6.0;
-
-struct Cooked {
-    uint64_t key[CT];
-    double vec[CT];      // tf * idf on the FIRST occurrence of each distinct n-gram, else 0
-    uint8_t first[CT];
-    double norm[NG];
-    int len;             // tokens kept (up to and including the first 0)
-};
-
-// all CT threads participate.  row: int64 (hypotheses) or int32 (packed references), w tokens wide; R is scratch.
-template <typename T>
-__device__ void cook(Row &R, const T *row, int w, Cooked &c, const RewardIdf &idf) {
-    const int tid = threadIdx.x;
-    const Lane l = cook_row(R, row, w, RewardTokens());
-    double v = 0.0;
-    if (l.first) v = (double)l.tf * idf(l.key);
-    c.key[tid] = l.key;
-    c.vec[tid] = v;
-    c.first[tid] = l.first ? 1 : 0;
-    if (tid == 0) c.len = R.len;
-    __syncthreads();
-    if (tid < NG) c.norm[tid] = order_norm(c.vec, tid);
-    __syncthreads();
-}
-
-static_assert(sizeof(Cooked) == CAPMI_CIDERD_COOKED_BYTES, "capmi.h CAPMI_CIDERD_COOKED_BYTES must equal sizeof(Cooked)");
 
 // References are cooked ONCE per batch (SURVEY Appendix A "refs pre-cooked per image once"): the scoring kernel below cooked
 // each of an image's references again for every one of its hypotheses (300 cooks instead of 50 at bs10 x (5+1), with their
@@ -112,7 +85,7 @@ __global__ __launch_bounds__(CT) void ciderd_kernel(const int64_t *__restrict__ 
             double s = order_cosine(order_dot(contrib, tid), H.norm[tid], Rf.norm[tid]);
             const int len_r_bi = Rf.len > 0 ? Rf.len - 1 : 0;
             const double delta = (double)(len_h_bi - len_r_bi);
-            s *= exp(-(delta * delta) / (2.0 * SIGMA * SIGMA));
+            s *= exp(-(delta * delta) / (2.0 * CIDERD_SIGMA * CIDERD_SIGMA));
             score[tid] += s;
         }
         __syncthreads();

@@ -16,6 +16,12 @@ caption's per-word region attention to <eval_results_dir>/<id>_<split>_att.npz: 
 for AdaAtt)], /top, /top_w, /entropy [L], /regions, and -- with the real-file loader and --input_box_dir -- /box (the attention-weighted
 box per word) and /top_box (the top region's own box); one device-to-host transfer per batch (imagecaptioning/pytorch_amd/att_trace.py).
 
+--rerank mbr_ciderd | mbr_bleu4 with --sample_n N (2..32) and --sample_n_method sample / gumbel / top<k|p> / bs decodes N captions per
+image and keeps the one with the highest expected CIDEr-D / BLEU-4 against the others (imagecaptioning/pytorch_amd/mbr.py;
+--rerank_prior model weighs them by the model's own probabilities): that caption is the image's prediction, scored and written
+as for --sample_n 1; every prediction gains 'mbr_choice' and 'mbr_expected', and <eval_results_dir>/<id>_<split>_mbr.npz holds
+image_id, choice [images], expected [images, N] and candidates [images, N, L].
+
     python -m imagecaptioning.pytorch_amd.tools.eval --caption_model updown --beam_size 5 --num_images 20 [--start_from DIR | --model FILE]
 """
 import json
@@ -102,6 +108,46 @@ def batch_boxes(loader, opt, data, K, dev):
     return torch.from_numpy(out).to(dev)
 
 
+def rerank_kwargs(opt):
+    """--rerank: the decode options of the single-caption pass -- the sample_n_method decode of eval_split_n with the reranking
+    on top -- or {} without the flag"""
+    kind = getattr(opt, 'rerank', '')
+    if not kind:
+        return {}
+    n, method = opt.sample_n, opt.sample_n_method
+    kw = dict(rerank=kind, rerank_prior=getattr(opt, 'rerank_prior', 'uniform'), sample_n=n)
+    if method == 'bs':
+        kw.update(beam_size=n, group_size=1, sample_method='beam_search')
+    elif method in ('sample', 'gumbel') or method.startswith('top'):
+        kw.update(sample_method=method, beam_size=1)
+    else:
+        raise NotImplementedError('--rerank chooses among the captions of --sample_n_method sample / gumbel / top<k|p> / bs; %r '
+                                  'returns the first beam of every group or one row per group, not sample_n rows of one decode'
+                                  % method)
+    return kw
+
+
+class RerankDump:
+    """--rerank: what the reranking chose, kept on the device per batch and written as one .npz"""
+
+    def __init__(self):
+        self.ids, self.parts = [], []
+
+    def add_batch(self, last, infos, keep):
+        n = last['expected'].shape[1]
+        self.ids += [info['id'] for info in infos[:keep]]
+        self.parts.append((last['choice'][:keep], last['expected'][:keep], last['candidates'].view(-1, n, last['candidates'].shape[1])[:keep]))
+
+    def write(self, opt, split):
+        import numpy as np
+        out_dir = getattr(opt, 'eval_results_dir', 'eval_results')
+        os.makedirs(out_dir, exist_ok=True)
+        path = os.path.join(out_dir, '%s_%s_mbr.npz' % (getattr(opt, 'id', 'capmi'), split))
+        choice, expected, candidates = (torch.cat(p).cpu().numpy() for p in zip(*self.parts))
+        np.savez(path, image_id=np.array(self.ids), choice=choice, expected=expected, candidates=candidates)
+        return path
+
+
 class AttentionDump:
     """--dump_attention: the first caption row of every image of a batch, as ONE device-to-host transfer (every array of
     model.last_attention packed into one float32 block), kept by image id and written as one .npz"""
@@ -156,14 +202,17 @@ def eval_split(model, crit, loader, opt):
     if getattr(opt, 'language_eval', 0):
         from imagecaptioning.pytorch_amd.langeval import LanguageEval
         lang = LanguageEval.for_loader(loader, split, dev)
+    rerank_kw = rerank_kwargs(opt)
+    redump = RerankDump() if rerank_kw else None
+    sample_n = 1 if rerank_kw else opt.sample_n      # --rerank: the sample_n captions become one, the pass is the single-caption one
     div, groups = None, []               # groups: (image_id, the image's n prediction dicts in slot order), before any sorting
-    if lang is not None and opt.sample_n > 1:
+    if lang is not None and sample_n > 1:
         from imagecaptioning.pytorch_amd.diveval import DiversityEval
-        div = DiversityEval(lang, opt.sample_n, oracle=bool(getattr(opt, 'eval_oracle', 0)))
+        div = DiversityEval(lang, sample_n, oracle=bool(getattr(opt, 'eval_oracle', 0)))
     sent = None
     if lang is not None and getattr(opt, 'sentence_stats', 0):
         from imagecaptioning.pytorch_amd.sentstats import SentenceStats
-        sent = SentenceStats.for_loader(loader, split, dev, model, opt.sample_n)
+        sent = SentenceStats.for_loader(loader, split, dev, model, sample_n)
     dump = AttentionDump() if getattr(opt, 'dump_attention', 0) else None
     if hasattr(loader, 'reset_iterator'):
         loader.reset_iterator(split)                                                                           # eval_utils.py:145
@@ -179,6 +228,7 @@ def eval_split(model, crit, loader, opt):
         att_masks = None if data.get('att_masks') is None else data['att_masks'].to(dev)
         kw = eval_kwargs_of(opt)
         kw['sample_n'] = 1                                                                                     # :169-170
+        kw.update(rerank_kw)
         if dump is not None:
             kw['return_attention'] = 1
             boxes = batch_boxes(loader, opt, data, att.shape[1], dev)
@@ -190,6 +240,10 @@ def eval_split(model, crit, loader, opt):
         if dump is not None:
             dump.add_batch(model.last_attention, data['infos'], max(0, min(len(data['infos']), num_images - n)), att_masks,
                            kw.get('boxes'), model._trace_col0)
+        if redump is not None:
+            redump.add_batch(model.last_rerank, data['infos'], max(0, min(len(data['infos']), num_images - n)))
+            mbr_choice = model.last_rerank['choice'].tolist()
+            mbr_expected = model.last_rerank['expected'].gather(1, model.last_rerank['choice'].long().unsqueeze(1)).squeeze(1).tolist()
         loss_sum += loss
         loss_n += 1
         if seq_logp.dim() == 3:
@@ -216,7 +270,9 @@ def eval_split(model, crit, loader, opt):
         for k, s in enumerate(sents):
             preds.append({'image_id': data['infos'][k // rows_per_image]['id'], 'caption': s, 'perplexity': perplexity[k].item(),
                           'entropy': entropy[k].item()})
-        if opt.sample_n > 1:                                                                                   # :199-200
+            if redump is not None:
+                preds[-1].update(mbr_choice=mbr_choice[k], mbr_expected=mbr_expected[k])
+        if sample_n > 1:                                                                                       # :199-200
             first = len(n_preds)
             rows = eval_split_n(model, n_preds, fc, att, att_masks, data, opt)                                # :198
             if div is not None:          # the same cut at num_images as the single-caption pass; the rows stay on the device
@@ -230,6 +286,8 @@ def eval_split(model, crit, loader, opt):
         n_preds = sorted(n_preds, key=lambda x: x['perplexity'])                                               # :217-218
     if dump is not None:
         print('attention written to', dump.write(opt, split))
+    if redump is not None:
+        print('reranking written to', redump.write(opt, split))
     model.n_predictions = n_preds
     model.train()                                                                                              # :224-225
     preds = preds[:num_images * max(1, len(preds) // max(n, 1))]
@@ -330,6 +388,13 @@ def main(opt):
         model.load_state_dict(torch.load(opt.model, map_location=dev))
     elif opt.start_from:
         model.load_state_dict(torch.load(os.path.join(opt.start_from, 'model.pth'), map_location=dev))
+    if getattr(opt, 'rerank', '') == 'mbr_ciderd':
+        # the document frequencies of the CIDEr-D reward, as tools/train.py finds them: the prepro_ngrams pickle (or its converted
+        # image) when it exists, else the same table rebuilt from the training references
+        from captioning.utils import rewards
+        ct = str(opt.cached_tokens)
+        have = any(os.path.exists(p_) for p_ in (ct, os.path.join('data', ct + '.p'), os.path.join('data', ct + '.capmi.npz')))
+        rewards.init_scorer(ct if (opt.input_json and have) else loader.document_frequency(), device=dev)
     crit =losses.LabelSmoothing(smoothing=opt.label_smoothing) if opt.label_smoothing > 0 else losses.LanguageModelCriterion()
     res = eval_split(model, crit, loader, opt)
     report(res)

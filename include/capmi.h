@@ -612,6 +612,38 @@ int capmi_nsc_advantage(const double *scores, const double *add, double add_w, i
                         void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Consensus (minimum-Bayes-risk) reranking of the n candidate captions of an image (opt['rerank'], imagecaptioning/pytorch_amd/
+ * mbr.py; not part of the reference): keep the candidate whose expected utility against the other candidates is highest.  hyp
+ * [B * n, L] int64, rows g*n .. g*n+n-1 the candidates of image g, 2 <= n <= CAPMI_SELF_CIDER_NMAX, L in 1..64.  Token rows follow
+ * the convention of capmi_ciderd_score (cut AFTER the first 0, which is a word); a completely filled row has no end token and, read
+ * as a reference, behaves like a reference ended by a negative entry.  Double throughout; no allocation, no host sync, no
+ * atomics: the same bits on every run.
+ *
+ * capmi_mbr_utility: three launches.  U[g][i][j] = the utility of candidate i, read as the hypothesis, against candidate j read as
+ *   its only reference (not symmetric; the diagonal is written, nothing downstream reads it).
+ *     CAPMI_MBR_CIDERD  the arithmetic of capmi_ciderd_score with n_refs = 1: clipped counts, Gaussian length term, factor 10,
+ *                       weights tf * (log_ref_len - log(max(1, df))) on the table of capmi_ciderd_score.
+ *     CAPMI_MBR_BLEU4   the bleu4 of capmi_reward_bleu4 with that one reference; takes no table (the pointers may be NULL).
+ *   Every candidate is cooked once (n-gram keys, weights, norms, length: the record of capmi_ciderd_cook_refs), then the n * n
+ *   pairs of every image are scored, one workgroup each.  scratch: CAPMI_CIDERD_COOKED_BYTES * B * n bytes, 8-byte aligned.
+ * capmi_mbr_select: one launch.  expected[g][i] = sum_{j != i} w_j U[g][i][j] / sum_{j != i} w_j, j ascending (0 where that
+ *   denominator is 0); w_j = 1 when seq_weight is NULL, else exp(seq_weight[g*n+j] - max over the image), the largest exactly 1
+ *   (seq_weight: a log-prior of each candidate, e.g. the sum of its selected log-probs).  A candidate whose caption (the tokens up
+ *   to and including the first 0) repeats that of an earlier candidate of its image is never chosen but still counts as a
+ *   reference: identical captions have identical rows of U up to the order of the sums, and this rule makes the choice among
+ *   them deterministic.  choice[g] = the lowest index with the largest expected value among the first occurrences; 0 when all
+ *   expected values are 0.
+ * CAPMI_EINVAL, before anything is launched: a NULL pointer (table pointers only for CAPMI_MBR_CIDERD, seq_weight never), B < 1, n
+ *   or L out of range, an unknown kind, a table size that is no power of two, a misaligned scratch.
+ * ------------------------------------------------------------------------------------------- */
+#define CAPMI_MBR_CIDERD 0
+#define CAPMI_MBR_BLEU4 1
+int capmi_mbr_utility(const int64_t *hyp, int B, int n, int L, int kind, const uint64_t *table_keys, const double *table_vals,
+                      uint32_t table_cap, double log_ref_len, void *scratch, double *U, void *stream);
+int capmi_mbr_select(const double *U, const double *seq_weight, const int64_t *hyp, int B, int n, int L, double *expected,
+                     int32_t *choice, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Launch instrumentation (counterpart of the reference's `time/batch` prints, train.py:198-208).
  * capmi_prof_enable(class_mask): launches of the selected kernel classes carry a HIP event pair in the
  * dispatch itself (hipExtLaunchKernelGGL start/stop events on the kernel's own stream: no extra queue
