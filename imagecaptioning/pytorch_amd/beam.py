@@ -389,6 +389,74 @@ def beam_search_steps(model, make_decoder, B, V1, L, opt, dev, tables_only=False
     return assemble_done_beams(model, parent, token, score, ended, logp_rows, B, bd, L, V1, sample_n, beam_size, opt)
 
 
+def stochastic_beam_search_steps(model, make_decoder, B, V1, L, opt, dev):
+    """Stochastic beam search (sbs.py; Kool et al. 2019) for any decoder of the protocol above: opt['sample_n'] = k distinct captions
+    per image, drawn without replacement from the model.  A sibling of beam_search_steps: the decoder step is the callback, the
+    normalisation / constraints / selection (capmi_sbs_select) / reordering / backtrack (capmi_sbs_backtrack) are native, nothing
+    reads the device.
+
+    Sampling semantics: EVERY step's rows are log_softmax(logits / temperature), step 0 included.  suppress_UNK, decoding_constraint
+    and remove_bad_endings edit the rows as in the beam path; the rows are then renormalised, so that the draw is without replacement
+    from the constrained distribution.  Returns (seq [B*k, L], seqLogprobs [B*k, L, V1]) like a sampled rollout with sample_n = k
+    (rows of an image by descending perturbed value) and sets model.last_sbs = {'phi', 'g', 'log_w'} [B, k] (sbs.py).
+    opt['_gumbel'] [L, B*k, V1]: injected noise by search row (test hook; step 0 reads the first B rows)."""
+    from . import sbs
+    k = sbs.check_options(model, opt)
+    if k > V1:
+        raise ValueError("sample_method 'sbs': sample_n = %d captions need a vocabulary of at least as many words (%d)" % (k, V1))
+    trace = getattr(model, '_trace_req', None)
+    if trace is not None:
+        from . import att_trace
+        make_decoder, recs = att_trace.recording(make_decoder, L)
+    dec = make_decoder(k)
+    N = B * k
+    temperature = float(opt.get('temperature', 1))
+    unk = unk_column(model, opt, V1)
+    flags, bad = _decode_flags(model, opt, dev)
+    gumbel = opt.get('_gumbel')
+    seed = model._next_seed()
+    logp_rows = torch.zeros(L, N, V1, dtype=_f32, device=dev)
+    edited = torch.empty(N, V1, dtype=_f32, device=dev) if (flags or unk >= 0) else None
+    parent = torch.zeros(L, B, k, dtype=torch.int32, device=dev)
+    token = torch.zeros(L, B, k, dtype=torch.long, device=dev)
+    alive = torch.zeros(L, B, k, dtype=torch.uint8, device=dev)
+    phi = torch.zeros(2, B, k, dtype=_f32, device=dev)
+    g = torch.zeros(2, B, k, dtype=_f32, device=dev)
+    root, zero = torch.ones(B, 1, dtype=torch.uint8, device=dev), torch.zeros(B, 1, dtype=_f32, device=dev)     # the root: phi 0
+    st = stream_ptr()
+    it, rows, cur = torch.zeros(B, dtype=torch.long, device=dev), B, 1       # BOS
+    for t in range(L):
+        logits = dec.step(t, it, cur)
+        out = logp_rows[t]
+        if edited is None:
+            check(lib.capmi_beam_logsoftmax(ptr(logits), ptr(out), rows, V1, temperature, -1, st), 'beam_logsoftmax')
+        else:
+            check(lib.capmi_beam_logsoftmax(ptr(logits), ptr(edited), rows, V1, temperature, unk, st), 'beam_logsoftmax')
+            if flags and t > 0:
+                check(lib.capmi_decode_constrain(ptr(edited), rows, V1, ptr(token[t - 1]), 1, flags, ptr(bad), bad.numel(), None, 0,
+                                                 t, 0, st), 'decode_constrain')
+            check(lib.capmi_beam_logsoftmax(ptr(edited), ptr(out), rows, V1, 1.0, -1, st), 'beam_logsoftmax')
+        i, o = t & 1, (t + 1) & 1
+        state = (zero, zero, root) if t == 0 else (phi[i], g[i], alive[t - 1])
+        ops.sbs_select(out[:rows], *state, k, step0=t == 0, force_end=t == L - 1,
+                       gumbel=None if gumbel is None else gumbel[t, :rows], seed=seed, offset=t,
+                       out=(parent[t], token[t], phi[o], g[o], alive[t]))
+        if t == L - 1:
+            break
+        dec.reorder(parent[t], cur)
+        it, rows, cur = token[t].reshape(N), N, k
+    seq, length, lineage = ops.sbs_backtrack(parent, token, alive)
+    live = (lineage >= 0).unsqueeze(2)
+    gathered = logp_rows.gather(1, lineage.clamp(min=0).long().unsqueeze(2).expand(L, N, V1))
+    seq_logp = torch.where(live, gathered, gathered.new_zeros(())).permute(1, 0, 2).contiguous()
+    phi_k, g_k = phi[L & 1].clone(), g[L & 1].clone()
+    model.last_sbs = dict(phi=phi_k, g=g_k, log_w=sbs.log_weights(phi_k, g_k))
+    if trace is not None:
+        att = att_trace.beam(recs[0].buf, lineage, length, trace.Kout)
+        att_trace.publish(model, att, k)
+    return seq, seq_logp
+
+
 def diverse_beam_search_steps(model, make_decoder, B, V1, L, opt, dev):
     """Diverse beam search: group_size groups of bdash = beam_size // group_size beams; group g is penalised by
     diversity_lambda for every token the beams of groups < g hold at the same position (CaptionModel.add_diversity, :38-57).

@@ -23,6 +23,8 @@ from imagecaptioning.pytorch_amd._lib import CapmiError
 
 
 class AttEnsemble(CaptionModel):
+    _sbs_refusal = 'it is implemented for the single-model families; decode the members one by one'
+
     def __init__(self, models, weights=None):
         super().__init__()
         models = list(models)

@@ -202,6 +202,8 @@ class AttModel(StepAPI, RecurrentModel):
                 return beam.updown_beam_train(self, fc_feats, att_feats, att_masks, opt)
             return self._sample_beam(fc_feats, att_feats, att_masks, opt)
         from imagecaptioning.pytorch_amd import decode
+        if sample_method == 'sbs':
+            return self._sample_sbs(self._stepper(fc_feats, att_feats, att_masks), fc_feats.size(0), opt)
         if decode.wants_options(opt):
             # _diverse_sample (AttModel.py:270-271) / decoding constraints (:293-330): host-stepped, same kernels
             return self._sample_with_options(self._stepper(fc_feats, att_feats, att_masks), fc_feats.size(0), opt)

@@ -2,7 +2,7 @@
 import torch
 import torch.nn as nn
 
-from imagecaptioning.pytorch_amd import att_trace, mbr
+from imagecaptioning.pytorch_amd import att_trace, mbr, sbs
 
 BAD_ENDINGS = ['a', 'an', 'the', 'in', 'for', 'at', 'of', 'with', 'before', 'after', 'on', 'upon', 'near', 'to', 'is',
                'are', 'am', 'the']       # AttModel.py:27
@@ -26,10 +26,19 @@ class CaptionModel(nn.Module):
     # ---- opt['rerank'] (imagecaptioning.pytorch_amd.mbr): consensus reranking of the sample_n captions of every image
     last_rerank = None          # dict of device tensors (choice, expected, utility, candidates, candidate_logp_sum) after such a call
 
+    # ---- opt['sample_method'] = 'sbs' (imagecaptioning.pytorch_amd.sbs): sample_n distinct captions, drawn without replacement
+    last_sbs = None             # dict of device tensors (phi, g, log_w), each [B, sample_n], after such a call
+    # why a model has no stochastic beam search (None: it has one -- every family that runs beam.beam_search_steps on a stepper)
+    _sbs_refusal = 'the model has no single-step decoder for the beam driver'
+
     def _sample_entry(self, *args, **kwargs):
         opt = kwargs.get('opt') or (args[3] if len(args) > 3 else None)
         if self.last_rerank is not None:
             self.last_rerank = None
+        if self.last_sbs is not None:
+            self.last_sbs = None
+        if sbs.wanted(opt):
+            sbs.check_options(self, opt)                        # every refusal, before any device work
         if not mbr.wanted(opt):
             return self._sample_traced(*args, **kwargs)
         mbr.check_options(self, opt)                        # every refusal, before any device work
@@ -136,6 +145,13 @@ class CaptionModel(nn.Module):
     @bad_endings_ix.setter
     def bad_endings_ix(self, ix):
         self.__dict__['_bad_endings_ix'] = [int(i) for i in ix]
+
+    def _sample_sbs(self, make_stepper, B, opt):
+        """sample_method 'sbs' on the family's single-step decoder (beam.stochastic_beam_search_steps).  Eval numerics, no gradient."""
+        from imagecaptioning.pytorch_amd import beam
+        dev = next(self.parameters()).device
+        with torch.no_grad():
+            return beam.stochastic_beam_search_steps(self, make_stepper, B, self.vocab_size + 1, self.seq_length, opt, dev)
 
     def _sample_with_options(self, make_stepper, B, opt):
         """AttModel._sample's option branches that need per-step hooks (AttModel.py:270-271 _diverse_sample,

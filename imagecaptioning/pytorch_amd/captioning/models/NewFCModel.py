@@ -65,7 +65,7 @@ class NewFCModel(RecurrentModel):
         from imagecaptioning.pytorch_amd import decode, beam
         raw = not opt.get('output_logsoftmax', 1)
         is_beam = opt.get('beam_size', 1) > 1 and method in ('greedy', 'beam_search')
-        mode, temperature, top_k, top_p = (None, 1.0, 0, 0.0) if is_beam else parse_sample_method(method, opt.get('temperature', 1.0))
+        mode, temperature, top_k, top_p = (None, 1.0, 0, 0.0) if (is_beam or method == 'sbs') else parse_sample_method(method, opt.get('temperature', 1.0))
         if raw and (is_beam or decode.wants_options(opt) or top_k or top_p):
             # AttModel.py:171-175: the margin structure losses read raw LOGITS (loss_wrapper.py:31-37 samples them with sample_n and no
             # decode-time option); the one-call rollout stores them (r5, CAPMI_SELECT_RAW), beam search and the host-stepped option
@@ -73,6 +73,8 @@ class NewFCModel(RecurrentModel):
             raise NotImplementedError('output_logsoftmax=0 is implemented for the sampled / greedy rollout; beam search and the '
                                       'decode-time options of %s return log-probabilities' % type(self).__name__)
         self._device_check(fc_feats)
+        if method == 'sbs':
+            return self._sample_sbs(self._stepper(fc_feats), fc_feats.size(0), opt)
         if is_beam and beam.wants_train_beam(self, opt):
             # train mode with gradients (loss_wrapper.py, train_beam_size > 1): search, finalise on the device, forced replay
             return beam.newfc_beam_train(self, fc_feats, opt)

@@ -138,6 +138,7 @@ class _Fn(torch.autograd.Function):
 
 
 class TransformerModel(CaptionModel):
+    _sbs_refusal = None             # sample_method 'sbs': the KV-cached Decoder is a stepper
     graph_step = True      # graph_step.TrainStep captures this family's training iteration into a hipGraph (no host sync in it)
 
     def __init__(self, opt):
@@ -256,10 +257,10 @@ class TransformerModel(CaptionModel):
                 P = self._pdict(self._param_list())
                 return engine.sample_beam(self, P, att_feats, att_masks, self.h, self.N_enc, self.N_dec, self.seq_length, opt)
         from .utils import parse_sample_method
-        if decode.wants_options(opt):
+        if method == 'sbs' or decode.wants_options(opt):
             att_feats, att_masks = self._clip(att_feats, att_masks)
             P = self._pdict(self._param_list())
-            return self._sample_with_options(
+            return (self._sample_sbs if method == 'sbs' else self._sample_with_options)(
                 lambda rows: engine.Decoder(P, att_feats, att_masks, self.h, self.N_enc, self.N_dec, self.seq_length, rows),
                 att_feats.size(0), opt)
         mode, temperature, top_k, top_p = parse_sample_method(method, opt.get('temperature', 1.0))

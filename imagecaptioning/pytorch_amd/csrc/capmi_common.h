@@ -124,6 +124,8 @@ __device__ __forceinline__ uint64_t epoch_seed(uint64_t seed, const uint64_t *__
 }
 // uniform in (0,1): never 0 so log() is finite
 __device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
+// a standard Gumbel variate from one Philox word (the sampling kernels of sampler.hip and the stochastic beam search of sbs.hip)
+__device__ __forceinline__ float gumbel_u32(uint32_t x) { return -__logf(-__logf(u01(x))); }
 
 // Environment switches of the library, all read once per process through these three helpers:
 //  * knob():     the documented product switches: CAPMI_GEMM_X3, CAPMI_ARES_X3, CAPMI_LC, CAPMI_GEMM_LOG and -- r5 --

@@ -170,7 +170,7 @@ __global__ __launch_bounds__(SEL_THREADS) void logsoftmax_select_kernel(
                     for (int k = 0; k < 4; ++k) {
                         const int v = q * 4 + k;
                         if (v < V1) {
-                            const float gn = -__logf(-__logf(u01(o[k])));
+                            const float gn = gumbel_u32(o[k]);
                             const float xt_ = (x[v] - lse) * invT;
                             if (order_key(xt_) >= thr_key) best = better(best, ArgMax{xt_ + gn, v});
                         }
@@ -374,7 +374,7 @@ __device__ __forceinline__ void select_reg_body(const SelArgs &A, const int r, f
                         uint32_t o[4];
                         rng.gen(((uint64_t)step << 32) | (uint32_t)r, (uint64_t)q, o);
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) gn[k] = -__logf(-__logf(u01(o[k])));
+                        for (int k = 0; k < 4; ++k) gn[k] = gumbel_u32(o[k]);
                     }
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {

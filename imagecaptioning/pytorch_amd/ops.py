@@ -1275,3 +1275,50 @@ def df_finalize(count_keys, counts, keys, vals, meta):
         raise _lib.CapmiError('df_finalize: the image is int64 keys and float64 vals of one size')
     check(lib.capmi_df_finalize(ptr(count_keys), ptr(counts), count_keys.numel(), ptr(keys), ptr(vals), keys.numel(), ptr(meta),
                                 stream_ptr()), 'capmi_df_finalize')
+
+
+# ---- stochastic beam search (beam.stochastic_beam_search_steps; capmi.h capmi_sbs_*, sbs.hip) ------------------------------------
+SBS_BD_MAX = 16       # = BD_MAX of beam.hip / sbs.hip
+
+
+def sbs_select(logp, phi, g, alive, bd, step0=False, force_end=False, gumbel=None, seed=0, offset=0, out=None):
+    """One selection step of the stochastic beam search (capmi_sbs_select): logp [B * cur, V1] normalised rows, phi / g float32 and
+    alive uint8 [B, cur]; noise: `gumbel` [B * cur, V1] (injected) or Philox (seed, offset = the step).  Returns (parent int32,
+    token int64, phi_out, g_out, alive_out uint8), each [B, bd], by descending g_out (out: the same five, preallocated)."""
+    _chk(logp, phi, g, alive, gumbel)
+    B, cur = phi.shape
+    V1 = logp.shape[1]
+    if logp.dtype != _f32 or phi.dtype != _f32 or g.dtype != _f32 or alive.dtype != torch.uint8 or logp.shape[0] != B * cur \
+            or g.shape != phi.shape or alive.shape != phi.shape:
+        raise _lib.CapmiError('sbs_select: logp float32 [B * cur, V1], phi / g float32 [B, cur], alive uint8 [B, cur]')
+    if gumbel is not None and (gumbel.dtype != _f32 or gumbel.shape != logp.shape):
+        raise _lib.CapmiError('sbs_select: gumbel must be float32 %s' % (tuple(logp.shape),))
+    dev = logp.device
+    if out is None:
+        out = (torch.empty(B, bd, dtype=torch.int32, device=dev), torch.empty(B, bd, dtype=torch.long, device=dev),
+               torch.empty(B, bd, dtype=_f32, device=dev), torch.empty(B, bd, dtype=_f32, device=dev),
+               torch.empty(B, bd, dtype=torch.uint8, device=dev))
+    _chk(*out)
+    nbytes = max(int(lib.capmi_sbs_scratch_bytes(B, cur, bd, V1)), 4)
+    scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+    check(lib.capmi_sbs_select(ptr(logp), ptr(phi), ptr(g), ptr(alive), ptr(gumbel), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                               int(offset) & 0xFFFFFFFF, B, cur, int(bd), V1, int(bool(step0)), int(bool(force_end)), ptr(scratch),
+                               nbytes, *[ptr(t) for t in out], stream_ptr()), 'capmi_sbs_select')
+    return out
+
+
+def sbs_backtrack(parent, token, alive):
+    """capmi_sbs_backtrack: the tables [L, B, bd] of a finished search -> (seq int64 [B * bd, L], length int32 [B * bd],
+    lineage int32 [L, B * bd]), with the conventions of beam.finalize."""
+    _chk(parent, token, alive)
+    L, B, bd = parent.shape
+    if parent.dtype != torch.int32 or token.dtype != torch.long or alive.dtype != torch.uint8 or token.shape != parent.shape \
+            or alive.shape != parent.shape:
+        raise _lib.CapmiError('sbs_backtrack: parent int32, token int64, alive uint8, all [L, B, bd]')
+    dev = parent.device
+    seq = torch.empty(B * bd, L, dtype=torch.long, device=dev)
+    length = torch.empty(B * bd, dtype=torch.int32, device=dev)
+    lineage = torch.empty(L, B * bd, dtype=torch.int32, device=dev)
+    check(lib.capmi_sbs_backtrack(ptr(parent), ptr(token), ptr(alive), B, bd, L, ptr(seq), ptr(length), ptr(lineage), stream_ptr()),
+          'capmi_sbs_backtrack')
+    return seq, length, lineage

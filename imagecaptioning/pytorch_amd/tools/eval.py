@@ -16,7 +16,11 @@ caption's per-word region attention to <eval_results_dir>/<id>_<split>_att.npz: 
 for AdaAtt)], /top, /top_w, /entropy [L], /regions, and -- with the real-file loader and --input_box_dir -- /box (the attention-weighted
 box per word) and /top_box (the top region's own box); one device-to-host transfer per batch (imagecaptioning/pytorch_amd/att_trace.py).
 
---rerank mbr_ciderd | mbr_bleu4 with --sample_n N (2..32) and --sample_n_method sample / gumbel / top<k|p> / bs decodes N captions per
+--sample_n_method sbs (stochastic beam search, imagecaptioning/pytorch_amd/sbs.py) draws the N <= 16 captions of an image WITHOUT
+replacement in one search: N distinct captions; the predictions carry 'perplexity' and, with --verbose_beam 1, the caption's
+importance weight 'log_w'.
+
+--rerank mbr_ciderd | mbr_bleu4 with --sample_n N (2..32) and --sample_n_method sample / gumbel / top<k|p> / sbs / bs decodes N captions per
 image and keeps the one with the highest expected CIDEr-D / BLEU-4 against the others (imagecaptioning/pytorch_amd/mbr.py;
 --rerank_prior model weighs them by the model's own probabilities): that caption is the image's prediction, scored and written
 as for --sample_n 1; every prediction gains 'mbr_choice' and 'mbr_expected', and <eval_results_dir>/<id>_<split>_mbr.npz holds
@@ -46,7 +50,8 @@ def eval_kwargs_of(opt):
 
 def eval_split_n(model, n_predictions, fc, att, att_masks, data, opt):
     """eval_utils.eval_split_n (eval_utils.py:228-290): sample_n captions per image by beam search ('bs'), sampling
-    ('sample' / 'gumbel' / 'top<k|p>'), diverse beam search ('dbs') or diverse sampling ('d<method>').  Returns the token rows of
+    ('sample' / 'gumbel' / 'top<k|p>'), stochastic beam search ('sbs': distinct captions, drawn without replacement), diverse beam
+    search ('dbs') or diverse sampling ('d<method>').  Returns the token rows of
     what it decoded, int64 [B, sample_n, L] on the device (finished beams padded with 0), in the order of the appended predictions."""
     from captioning.utils import misc
     kw = eval_kwargs_of(opt)
@@ -65,6 +70,18 @@ def eval_split_n(model, n_predictions, fc, att, att_masks, data, opt):
             ppl = -logp.gather(2, seq.unsqueeze(2)).squeeze(2).sum(1) / ((seq > 0).to(logp).sum(1) + 1)
             for k, sent in enumerate(misc.decode_sequence(model.vocab, seq)):
                 n_predictions.append({'image_id': data['infos'][k // sample_n]['id'], 'caption': sent, 'perplexity': ppl[k].item()})
+            rows = seq
+        elif method == 'sbs':
+            # stochastic beam search (imagecaptioning/pytorch_amd/sbs.py; not a method of the reference): sample_n DISTINCT captions,
+            # drawn without replacement in one search
+            kw.update(sample_n=sample_n, sample_method='sbs', beam_size=1, group_size=1)
+            seq, logp = model(fc, att, att_masks, opt=kw, mode='sample')
+            ppl = -logp.gather(2, seq.unsqueeze(2)).squeeze(2).sum(1) / ((seq > 0).to(logp).sum(1) + 1)
+            log_w = model.last_sbs['log_w'].reshape(-1).tolist() if getattr(opt, 'verbose_beam', 0) else None
+            for k, sent in enumerate(misc.decode_sequence(model.vocab, seq)):
+                n_predictions.append({'image_id': data['infos'][k // sample_n]['id'], 'caption': sent, 'perplexity': ppl[k].item()})
+                if log_w is not None:          # the importance weight of the caption among the image's sample_n (-inf: the threshold)
+                    n_predictions[-1]['log_w'] = log_w[k]
             rows = seq
         elif method == 'dbs':                                               # :265-274
             kw.update(beam_size=sample_n * beam_size, group_size=sample_n, sample_method='beam_search', sample_n=1)
@@ -118,10 +135,10 @@ def rerank_kwargs(opt):
     kw = dict(rerank=kind, rerank_prior=getattr(opt, 'rerank_prior', 'uniform'), sample_n=n)
     if method == 'bs':
         kw.update(beam_size=n, group_size=1, sample_method='beam_search')
-    elif method in ('sample', 'gumbel') or method.startswith('top'):
+    elif method in ('sample', 'gumbel', 'sbs') or method.startswith('top'):
         kw.update(sample_method=method, beam_size=1)
     else:
-        raise NotImplementedError('--rerank chooses among the captions of --sample_n_method sample / gumbel / top<k|p> / bs; %r '
+        raise NotImplementedError('--rerank chooses among the captions of --sample_n_method sample / gumbel / top<k|p> / sbs / bs; %r '
                                   'returns the first beam of every group or one row per group, not sample_n rows of one decode'
                                   % method)
     return kw

@@ -1871,6 +1871,36 @@ int capmi_att_trace_beam(const float *alpha_rows, const int32_t *lineage, const 
 int capmi_att_ground(const float *att, int N, int L, int Kw, const float *boxes, int B, int n, int col0, int Kb, int32_t *top,
                      float *top_w, float *entropy, float *box, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Stochastic beam search (sbs.hip; opt['sample_method'] = 'sbs', beam.stochastic_beam_search_steps): sample_n DISTINCT captions per
+ * image, drawn without replacement from the model (Kool, van Hoof and Welling 2019).  Every hypothesis carries its joint log-prob
+ * phi and a perturbed value g; a step keeps the bd children with the largest perturbed values.
+ * capmi_sbs_select: one step.  logp [B * cur, V1] normalised rows, image-major as in capmi_beam_select; phi / g / alive [B, cur]
+ *          (alive uint8: 0 = the hypothesis has ended); noise either gumbel [B * cur, V1] (injected) or, gumbel == NULL, standard
+ *          Gumbel variates from Philox (seed, offset = the step; the stream follows capmi_rng_bind_epoch like every seeded kernel).
+ *          Per row j of an image: s_v = phi_j + logp[j, v] + G_v, Z_j = max_v s_v.  step0 (cur = 1, the root): the candidate's
+ *          value is s_v.  Otherwise u = g_j - s_v + log(1 - exp(s_v - Z_j)), value = g_j - max(0, u) - log1p(exp(-|u|)) -- the
+ *          children's values conditioned on their maximum being g_j -- and exactly g_j at the arg-max.  A row that is not alive has
+ *          one candidate: token 0, phi_j, g_j bit for bit.  -inf entries of logp are never candidates.
+ *          Outputs [B, bd], by descending value, equal values by the lower flat index row * V1 + token: parent (the row j), token,
+ *          phi_out = phi_j + logp[j, token], g_out, alive_out = the parent was alive, token != 0 and !force_end.  An image with
+ *          fewer than bd candidates fills the rest with parent 0, token 0, phi / g -inf, alive 0.
+ *          scratch: capmi_sbs_scratch_bytes(B, cur, bd, V1) bytes, 4-byte aligned (the per-chunk candidate lists).
+ *          Two launches, no atomics, bit-identical from run to run.  CAPMI_EINVAL, before anything is launched: a NULL pointer
+ *          (gumbel excepted), a dimension <= 0, cur > bd, bd > 16, cur * V1 < bd, step0 with cur != 1, a scratch that is too small,
+ *          ceil(V1 / 1024) * bd above 6144.
+ * capmi_sbs_backtrack: the [L][B, bd] tables parent / token / alive_out of L steps (the last one with force_end) ->
+ *          seq [B * bd, L] (0 behind the end), length [B * bd] (the end token's step counts) and lineage [L][B * bd] with the
+ *          conventions of capmi_beam_finalize (capmi_lineage_gather and capmi_att_trace_beam read it as they read that one's).
+ * ------------------------------------------------------------------------------------------- */
+int64_t capmi_sbs_scratch_bytes(int B, int cur, int bd, int V1);
+int capmi_sbs_select(const float *logp, const float *phi, const float *g, const uint8_t *alive, const float *gumbel,
+                     uint64_t seed, uint32_t offset, int B, int cur, int bd, int V1, int step0, int force_end, void *scratch,
+                     int64_t scratch_bytes, int32_t *parent, int64_t *token, float *phi_out, float *g_out, uint8_t *alive_out,
+                     void *stream);
+int capmi_sbs_backtrack(const int32_t *parent, const int64_t *token, const uint8_t *alive, int B, int bd, int L, int64_t *seq,
+                        int32_t *length, int32_t *lineage, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
