@@ -469,6 +469,9 @@ SIGNATURES = {
     'capmi_sbs_scratch_bytes': [_I, _I, _I, _I],
     'capmi_sbs_select': [_P, _P, _P, _P, _P, _U64, C.c_uint32, _I, _I, _I, _I, _I, _I, _P, _I64, _P, _P, _P, _P, _P, _P],
     'capmi_sbs_backtrack': [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    'capmi_cbs_scratch_bytes': [_I, _I, _I, _I],
+    'capmi_cbs_select': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I64, _P, _P, _P, _P, _P, _P, _P],
+    'capmi_cbs_finalize': [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
 }
 
 
@@ -490,7 +493,8 @@ def _load():
         fn.argtypes = argtypes
         fn.restype = (C.c_char_p if name == 'capmi_arch' else
                       C.c_int64 if name in ('capmi_planes_bytes', 'capmi_updown_planes_bytes',
-                                                   'capmi_updown_bwd_planes_bytes', 'capmi_sbs_scratch_bytes')
+                                                   'capmi_updown_bwd_planes_bytes', 'capmi_sbs_scratch_bytes',
+                                                   'capmi_cbs_scratch_bytes')
                       else C.c_int)
     return lib
 

@@ -457,6 +457,71 @@ def stochastic_beam_search_steps(model, make_decoder, B, V1, L, opt, dev):
     return seq, seq_logp
 
 
+def constrained_beam_search_steps(model, make_decoder, B, V1, L, opt, dev):
+    """Constrained beam search (cbs.py; Anderson et al. 2017) for any decoder of the protocol above: opt['constraints'] lists, per
+    image, sets of tokens of which the caption must contain one each.  A sibling of beam_search_steps and everything that is not
+    about states is that function's: the root row at temperature 1, `temperature` afterwards, suppress_UNK, decoding_constraint and
+    remove_bad_endings through the same kernels, ended hypotheses carried on 1000 lower.  The decoder steps S * beam_size rows per
+    image (slot = state * beam_size + j, S = 2^C states of the batch's largest C); capmi_cbs_select keeps the beam_size best per
+    state, capmi_cbs_finalize picks the caption; nothing reads the device.  Returns (seq [B, L], seqLogprobs [B, L, V1]) and sets
+    model.last_cbs = {'state', 'satisfied', 'total', 'score'} [B] (cbs.py)."""
+    from . import cbs
+    req = getattr(model, '_cbs_req', None) or cbs.prepare(model, opt)
+    if req.B != B:
+        raise ValueError("opt['constraints'] lists %d images, the batch holds %d" % (req.B, B))
+    b, S = req.b, req.S
+    SB = S * b
+    if V1 < 2:
+        raise ValueError("opt['constraints'] needs a vocabulary")
+    tables = ops.cbs_tables(req.words, req.ncons, V1, S, dev)
+    trace = getattr(model, '_trace_req', None)
+    if trace is not None:
+        from . import att_trace
+        make_decoder, recs = att_trace.recording(make_decoder, L)
+    dec = make_decoder(SB)
+    N = B * SB
+    temperature = float(opt.get('temperature', 1))
+    unk = unk_column(model, opt, V1)
+    flags, bad = _decode_flags(model, opt, dev)
+    logp_rows = torch.zeros(L, N, V1, dtype=_f32, device=dev)
+    parent = torch.zeros(L, B, SB, dtype=torch.int32, device=dev)
+    token = torch.zeros(L, B, SB, dtype=torch.long, device=dev)
+    score = torch.zeros(L, B, SB, dtype=_f32, device=dev)
+    ended = torch.zeros(L, B, SB, dtype=torch.uint8, device=dev)
+    valid = torch.zeros(L, B, SB, dtype=torch.uint8, device=dev)
+    sums = torch.zeros(2, B, SB, dtype=_f32, device=dev)
+    st = stream_ptr()
+    it = torch.zeros(B, dtype=torch.long, device=dev)                       # BOS
+    logits = dec.step(0, it, 1)
+    check(lib.capmi_beam_logsoftmax(ptr(logits), ptr(logp_rows[0]), B, V1, 1.0, unk, st), 'beam_logsoftmax')
+    rows, cur = B, 1
+    for t in range(L):
+        ops.cbs_select(logp_rows[t, :rows], sums[t & 1], tables, b, S, force_end=t == L - 1,
+                       out=(parent[t], token[t], score[t], sums[(t + 1) & 1], ended[t], valid[t]))
+        if t == L - 1:
+            break
+        dec.reorder(parent[t], cur)
+        logits = dec.step(t + 1, token[t].reshape(N), SB)
+        check(lib.capmi_beam_logsoftmax(ptr(logits), ptr(logp_rows[t + 1]), N, V1, temperature, unk, st), 'beam_logsoftmax')
+        if flags:
+            check(lib.capmi_decode_constrain(ptr(logp_rows[t + 1]), N, V1, ptr(token[t]), 1, flags, ptr(bad), bad.numel(), None, 0,
+                                             t + 1, 0, st), 'decode_constrain')
+        rows, cur = N, SB
+    seq, lineage, length, state, p = ops.cbs_finalize(parent, token, score, ended, valid, tables.ncons, b, S,
+                                                      length_divisors(opt.get('length_penalty', ''), L, dev))
+    live = (lineage >= 0).unsqueeze(2)
+    gathered = logp_rows.gather(1, lineage.clamp(min=0).long().unsqueeze(2).expand(L, B, V1))
+    seq_logp = torch.where(live, gathered, gathered.new_zeros(())).permute(1, 0, 2).contiguous()
+    cbs.publish(model, state, tables.ncons, p)
+    if isinstance(opt.get('_cbs_tables'), dict):                            # test hook: the per-step tables and rows
+        opt['_cbs_tables'].update(parent=parent, token=token, score=score, ended=ended, valid=valid, logp_rows=logp_rows,
+                                  lineage=lineage, length=length, words=req.words, ncons=req.ncons, b=b, S=S)
+    if trace is not None:
+        att = att_trace.beam(recs[0].buf, lineage, length, trace.Kout)
+        att_trace.publish(model, att, 1)
+    return seq, seq_logp
+
+
 def diverse_beam_search_steps(model, make_decoder, B, V1, L, opt, dev):
     """Diverse beam search: group_size groups of bdash = beam_size // group_size beams; group g is penalised by
     diversity_lambda for every token the beams of groups < g hold at the same position (CaptionModel.add_diversity, :38-57).

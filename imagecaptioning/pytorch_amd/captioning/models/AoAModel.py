@@ -96,6 +96,7 @@ class _Fn(torch.autograd.Function):
 
 class AoAModel(CaptionModel):
     _sbs_refusal = None             # sample_method 'sbs': BeamDecoder is a stepper
+    _cbs_refusal = None             # opt['constraints']: likewise
     graph_step = True      # graph_step.TrainStep captures this family's training iteration into a hipGraph (no host sync in it)
 
     def __init__(self, opt):
@@ -208,7 +209,8 @@ class AoAModel(CaptionModel):
             # samplers return log-probabilities -- refuse rather than hand those to a margin loss
             raise NotImplementedError('output_logsoftmax=0 is implemented for the sampled / greedy rollout; beam search and the '
                                       'decode-time options of %s return log-probabilities' % type(self).__name__)
-        if opt.get('beam_size', 1) > 1 and method in ('greedy', 'beam_search'):
+        cbs = self._cbs_req is not None
+        if not cbs and opt.get('beam_size', 1) > 1 and method in ('greedy', 'beam_search'):
             if not att_feats.is_cuda:
                 raise CapmiError('the capmi backend runs on a HIP device only; there is no CPU path')
             from imagecaptioning.pytorch_amd import beam
@@ -221,7 +223,7 @@ class AoAModel(CaptionModel):
                 return engine.sample_beam(self, P, att_feats.float().contiguous(), att_masks, self.num_heads, self.seq_length, opt,
                                           self._fc(fc_feats))
         from .utils import parse_sample_method
-        if method == 'sbs' or decode.wants_options(opt):
+        if cbs or method == 'sbs' or decode.wants_options(opt):
             if not att_feats.is_cuda:
                 raise CapmiError('the capmi backend runs on a HIP device only; there is no CPU path')
             if att_masks is not None:
@@ -233,7 +235,8 @@ class AoAModel(CaptionModel):
                 g = engine.AoAGraph(P, {}, self.num_heads, 0.0, 0.0, False, 0, variant=self.variant)
                 g.prepare(att_feats.float().contiguous(), att_masks, self._fc(fc_feats))
                 return engine.BeamDecoder(g, rows)
-            return (self._sample_sbs if method == 'sbs' else self._sample_with_options)(make, att_feats.size(0), opt)
+            return (self._sample_cbs if cbs else self._sample_sbs if method == 'sbs' else self._sample_with_options)(
+                make, att_feats.size(0), opt)
         mode, temperature, top_k, top_p = parse_sample_method(method, opt.get('temperature', 1.0))
         L = self.seq_length
         cfg = dict(n=int(opt.get('sample_n', 1)), T=L, L=L, mode=mode, temperature=temperature,

@@ -24,6 +24,7 @@ from imagecaptioning.pytorch_amd._lib import CapmiError
 
 class AttEnsemble(CaptionModel):
     _sbs_refusal = 'it is implemented for the single-model families; decode the members one by one'
+    _cbs_refusal = _sbs_refusal
 
     def __init__(self, models, weights=None):
         super().__init__()

@@ -193,6 +193,8 @@ class AttModel(StepAPI, RecurrentModel):
         temperature = opt.get('temperature', 1.0)
         sample_n = int(opt.get('sample_n', 1))
         group_size = opt.get('group_size', 1)
+        if self._cbs_req is not None:
+            return self._sample_cbs(self._stepper(fc_feats, att_feats, att_masks), fc_feats.size(0), opt)
         if beam_size > 1 and sample_method in ('greedy', 'beam_search'):
             from imagecaptioning.pytorch_amd import beam
             if beam.wants_train_beam(self, opt):

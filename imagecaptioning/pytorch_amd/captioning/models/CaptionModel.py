@@ -2,7 +2,7 @@
 import torch
 import torch.nn as nn
 
-from imagecaptioning.pytorch_amd import att_trace, mbr, sbs
+from imagecaptioning.pytorch_amd import att_trace, cbs, mbr, sbs
 
 BAD_ENDINGS = ['a', 'an', 'the', 'in', 'for', 'at', 'of', 'with', 'before', 'after', 'on', 'upon', 'near', 'to', 'is',
                'are', 'am', 'the']       # AttModel.py:27
@@ -31,8 +31,21 @@ class CaptionModel(nn.Module):
     # why a model has no stochastic beam search (None: it has one -- every family that runs beam.beam_search_steps on a stepper)
     _sbs_refusal = 'the model has no single-step decoder for the beam driver'
 
+    # ---- opt['constraints'] (imagecaptioning.pytorch_amd.cbs): constrained beam search, captions that must contain given words
+    last_cbs = None             # dict of device tensors (state, satisfied, total, score), each [B], after such a call
+    _cbs_req = None             # cbs.Request (the checked host tables) while such a call runs
+    _cbs_refusal = 'the model has no single-step decoder for the beam driver'
+
     def _sample_entry(self, *args, **kwargs):
         opt = kwargs.get('opt') or (args[3] if len(args) > 3 else None)
+        if self.last_cbs is not None:
+            self.last_cbs = None
+        if cbs.wanted(opt):
+            self._cbs_req = cbs.prepare(self, opt)              # every refusal, before any device work
+            try:
+                return self._sample_traced(*args, **kwargs)
+            finally:
+                self._cbs_req = None
         if self.last_rerank is not None:
             self.last_rerank = None
         if self.last_sbs is not None:
@@ -152,6 +165,13 @@ class CaptionModel(nn.Module):
         dev = next(self.parameters()).device
         with torch.no_grad():
             return beam.stochastic_beam_search_steps(self, make_stepper, B, self.vocab_size + 1, self.seq_length, opt, dev)
+
+    def _sample_cbs(self, make_stepper, B, opt):
+        """opt['constraints'] on the family's single-step decoder (beam.constrained_beam_search_steps).  Eval numerics, no gradient."""
+        from imagecaptioning.pytorch_amd import beam
+        dev = next(self.parameters()).device
+        with torch.no_grad():
+            return beam.constrained_beam_search_steps(self, make_stepper, B, self.vocab_size + 1, self.seq_length, opt, dev)
 
     def _sample_with_options(self, make_stepper, B, opt):
         """AttModel._sample's option branches that need per-step hooks (AttModel.py:270-271 _diverse_sample,

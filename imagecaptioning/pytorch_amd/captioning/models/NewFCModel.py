@@ -73,8 +73,8 @@ class NewFCModel(RecurrentModel):
             raise NotImplementedError('output_logsoftmax=0 is implemented for the sampled / greedy rollout; beam search and the '
                                       'decode-time options of %s return log-probabilities' % type(self).__name__)
         self._device_check(fc_feats)
-        if method == 'sbs':
-            return self._sample_sbs(self._stepper(fc_feats), fc_feats.size(0), opt)
+        if method == 'sbs' or self._cbs_req is not None:
+            return (self._sample_sbs if method == 'sbs' else self._sample_cbs)(self._stepper(fc_feats), fc_feats.size(0), opt)
         if is_beam and beam.wants_train_beam(self, opt):
             # train mode with gradients (loss_wrapper.py, train_beam_size > 1): search, finalise on the device, forced replay
             return beam.newfc_beam_train(self, fc_feats, opt)

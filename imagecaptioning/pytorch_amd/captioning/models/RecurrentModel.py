@@ -64,6 +64,7 @@ class _RolloutFn(torch.autograd.Function):
 
 class RecurrentModel(CaptionModel):
     _sbs_refusal = None             # sample_method 'sbs': every family here has a stepper
+    _cbs_refusal = None             # opt['constraints']: likewise
     ss_prob = 0.0
 
     # why a family refuses use_bn (None: it runs it).  models.setup gives the same reasons for the families outside this base.
@@ -159,8 +160,9 @@ class RecurrentModel(CaptionModel):
         self._device_check(att_feats)
         beam.refuse_train_beam(self, opt)           # train_beam_size > 1: no log-probs without a graph
         method = opt.get('sample_method', 'greedy')
-        if method == 'sbs':
-            return self._sample_sbs(self._stepper(*self._feeds(fc_feats, att_feats, att_masks)), att_feats.size(0), opt)
+        if method == 'sbs' or self._cbs_req is not None:
+            return (self._sample_sbs if method == 'sbs' else self._sample_cbs)(
+                self._stepper(*self._feeds(fc_feats, att_feats, att_masks)), att_feats.size(0), opt)
         raw = not opt.get('output_logsoftmax', 1)
         is_beam = opt.get('beam_size', 1) > 1 and method in ('greedy', 'beam_search')
         mode, temperature, top_k, top_p = (None, 1.0, 0, 0.0) if is_beam else parse_sample_method(method, opt.get('temperature', 1.0))

@@ -139,6 +139,7 @@ class _Fn(torch.autograd.Function):
 
 class TransformerModel(CaptionModel):
     _sbs_refusal = None             # sample_method 'sbs': the KV-cached Decoder is a stepper
+    _cbs_refusal = None             # opt['constraints']: likewise
     graph_step = True      # graph_step.TrainStep captures this family's training iteration into a hipGraph (no host sync in it)
 
     def __init__(self, opt):
@@ -251,16 +252,17 @@ class TransformerModel(CaptionModel):
             raise CapmiError('the capmi backend runs on a HIP device only; there is no CPU path')
         from imagecaptioning.pytorch_amd import beam
         beam.refuse_train_beam(self, opt)           # train_beam_size > 1: no log-probs without a graph
-        if opt.get('beam_size', 1) > 1 and method in ('greedy', 'beam_search'):
+        cbs = self._cbs_req is not None
+        if not cbs and opt.get('beam_size', 1) > 1 and method in ('greedy', 'beam_search'):
             att_feats, att_masks = self._clip(att_feats, att_masks)
             with torch.no_grad():
                 P = self._pdict(self._param_list())
                 return engine.sample_beam(self, P, att_feats, att_masks, self.h, self.N_enc, self.N_dec, self.seq_length, opt)
         from .utils import parse_sample_method
-        if method == 'sbs' or decode.wants_options(opt):
+        if cbs or method == 'sbs' or decode.wants_options(opt):
             att_feats, att_masks = self._clip(att_feats, att_masks)
             P = self._pdict(self._param_list())
-            return (self._sample_sbs if method == 'sbs' else self._sample_with_options)(
+            return (self._sample_cbs if cbs else self._sample_sbs if method == 'sbs' else self._sample_with_options)(
                 lambda rows: engine.Decoder(P, att_feats, att_masks, self.h, self.N_enc, self.N_dec, self.seq_length, rows),
                 att_feats.size(0), opt)
         mode, temperature, top_k, top_p = parse_sample_method(method, opt.get('temperature', 1.0))

@@ -52,6 +52,10 @@ DEFAULTS = dict(
     # not a flag of the reference): '' off, 'mbr_ciderd' / 'mbr_bleu4' keep the caption with the highest expected CIDEr-D / BLEU-4
     # against the others; rerank_prior: 'uniform', or 'model' -- every candidate weighs as much as the model believes in it
     rerank='', rerank_prior='uniform',
+    # constrained beam search (opt['constraints'], imagecaptioning/pytorch_amd/cbs.py; not a flag of the reference): constraints_json
+    # names a file {"<image id>": [["zebra", "zebras"], ["grass"]], ...} of words the image's caption must contain (one of each
+    # list); constraints_oov: 'error' stops at a word outside the vocabulary, 'drop' leaves such words out
+    constraints_json='', constraints_oov='error',
     # data (synthetic only: the reference's h5/lmdb loaders are outside the hot path)
     input_synthetic=1, vocab_size=9487, synthetic_regions=36, synthetic_images=200,
     # real precomputed features (captioning/data/feature_loader.py; opts.py:23-37 of the reference)

@@ -1322,3 +1322,83 @@ def sbs_backtrack(parent, token, alive):
     check(lib.capmi_sbs_backtrack(ptr(parent), ptr(token), ptr(alive), B, bd, L, ptr(seq), ptr(length), ptr(lineage), stream_ptr()),
           'capmi_sbs_backtrack')
     return seq, length, lineage
+
+
+# ---- constrained beam search (beam.constrained_beam_search_steps; capmi.h capmi_cbs_*, cbs.hip) ----------------------------------
+CBS_C_MAX, CBS_W_MAX, CBS_SLOTS_MAX = 4, 8, 64
+
+
+class CbsTables:
+    """The constraint tables of a batch on the device, checked on the host before the upload (capmi_cbs_select trusts them):
+    words [B, 4, 8] int32 padded with -1, ncons [B] int32, for a vocabulary of V1 columns and S states."""
+
+    def __init__(self, words, ncons, V1, S, dev):
+        words, ncons = torch.as_tensor(words), torch.as_tensor(ncons)
+        if words.is_cuda or ncons.is_cuda:
+            raise _lib.CapmiError('cbs_tables: the tables are checked on the host; pass CPU tensors')
+        if words.dim() != 3 or tuple(words.shape[1:]) != (CBS_C_MAX, CBS_W_MAX) or ncons.shape != (words.shape[0],):
+            raise _lib.CapmiError('cbs_tables: words [B, %d, %d], ncons [B] (EINVAL)' % (CBS_C_MAX, CBS_W_MAX))
+        words, ncons = words.to(torch.int32).contiguous(), ncons.to(torch.int32).contiguous()
+        if bool(((words != -1) & ((words < 1) | (words >= V1))).any()):
+            raise _lib.CapmiError('cbs_tables: a word id outside [1, %d) (EINVAL)' % V1)
+        if bool((ncons < 0).any()) or bool(((1 << ncons.long()) > S).any()):
+            raise _lib.CapmiError('cbs_tables: ncons needs 2^ncons <= S = %d (EINVAL)' % S)
+        self.V1, self.S, self.B = int(V1), int(S), words.shape[0]
+        self.words, self.ncons = words.to(dev), ncons.to(dev)
+
+
+def cbs_tables(words, ncons, V1, S, dev):
+    return CbsTables(words, ncons, V1, S, dev)
+
+
+def cbs_select(logp, sums, tables, b, S, force_end=False, out=None):
+    """One selection step of the constrained beam search (capmi_cbs_select): logp float32 [B * cur, V1] (cur = 1: the root, or S * b),
+    sums float32 [B, S * b] (-inf: an empty slot), tables a CbsTables made for the same V1 and S.  Returns (parent int32, token
+    int64, score, next_sums, ended uint8, valid uint8), each [B, S * b] (out: the same six, preallocated)."""
+    if not isinstance(tables, CbsTables):
+        raise _lib.CapmiError('cbs_select: tables must come from ops.cbs_tables')
+    _chk(logp, sums, tables.words, tables.ncons)
+    B, SB = sums.shape
+    V1 = logp.shape[1]
+    b, S = int(b), int(S)
+    if logp.dtype != _f32 or sums.dtype != _f32 or logp.dim() != 2 or B <= 0 or logp.shape[0] % B:
+        raise _lib.CapmiError('cbs_select: logp float32 [B * cur, V1], sums float32 [B, S * b]')
+    cur = logp.shape[0] // B
+    if tables.V1 != V1 or tables.S != S or tables.B != B:
+        raise _lib.CapmiError('cbs_select: the tables were checked for B = %d, V1 = %d, S = %d (EINVAL)' % (tables.B, tables.V1, tables.S))
+    if S * b != SB:
+        raise _lib.CapmiError('cbs_select: sums must be [B, S * b] (EINVAL)')
+    dev = logp.device
+    if out is None:
+        e = lambda dt: torch.empty(B, SB, dtype=dt, device=dev)      # noqa: E731
+        out = (e(torch.int32), e(torch.long), e(_f32), e(_f32), e(torch.uint8), e(torch.uint8))
+    _chk(*out)
+    nbytes = max(int(lib.capmi_cbs_scratch_bytes(B, cur, b, V1)), 4)
+    scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+    check(lib.capmi_cbs_select(ptr(logp), ptr(sums), ptr(tables.words), ptr(tables.ncons), B, cur, b, S, V1, int(bool(force_end)),
+                               ptr(scratch), nbytes, *[ptr(t) for t in out], stream_ptr()), 'capmi_cbs_select')
+    return out
+
+
+def cbs_finalize(parent, token, score, ended, valid, ncons, b, S, len_div=None):
+    """capmi_cbs_finalize: the tables [L, B, S * b] of a finished search and ncons int32 [B] (device) -> (seq int64 [B, L],
+    lineage int32 [L, B], length int32 [B], state int32 [B], score float32 [B]); len_div float64 [L] or None."""
+    _chk(parent, token, score, ended, valid, ncons, len_div)
+    L, B, SB = parent.shape
+    if parent.dtype != torch.int32 or token.dtype != torch.long or score.dtype != _f32 or ended.dtype != torch.uint8 \
+            or valid.dtype != torch.uint8 or ncons.dtype != torch.int32 or ncons.shape != (B,) \
+            or any(t.shape != parent.shape for t in (token, score, ended, valid)) or SB != int(S) * int(b):
+        raise _lib.CapmiError('cbs_finalize: parent int32, token int64, score float32, ended / valid uint8, all [L, B, S * b]; '
+                              'ncons int32 [B]')
+    if len_div is not None and (len_div.dtype != torch.float64 or len_div.shape != (L,)):
+        raise _lib.CapmiError('cbs_finalize: len_div float64 [L]')
+    dev = parent.device
+    seq = torch.empty(B, L, dtype=torch.long, device=dev)
+    lineage = torch.empty(L, B, dtype=torch.int32, device=dev)
+    length = torch.empty(B, dtype=torch.int32, device=dev)
+    state = torch.empty(B, dtype=torch.int32, device=dev)
+    out_score = torch.empty(B, dtype=_f32, device=dev)
+    check(lib.capmi_cbs_finalize(ptr(parent), ptr(token), ptr(score), ptr(ended), ptr(valid), ptr(ncons), ptr(len_div), B, int(b),
+                                 int(S), L, ptr(seq), ptr(lineage), ptr(length), ptr(state), ptr(out_score), stream_ptr()),
+          'capmi_cbs_finalize')
+    return seq, lineage, length, state, out_score

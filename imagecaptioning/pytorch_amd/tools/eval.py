@@ -20,6 +20,13 @@ box per word) and /top_box (the top region's own box); one device-to-host transf
 replacement in one search: N distinct captions; the predictions carry 'perplexity' and, with --verbose_beam 1, the caption's
 importance weight 'log_w'.
 
+--constraints_json FILE (constrained beam search, imagecaptioning/pytorch_amd/cbs.py) holds {"<image id>": [["zebra", "zebras"],
+["grass"]], ...}: the caption of such an image must contain one word of each list (at most 4 lists of at most 8 words; 2^lists *
+beam_size <= 64); images the file does not name are decoded without constraints.  --constraints_oov error (default) stops at a word
+that is not in the vocabulary, drop leaves such words -- and the lists they empty -- out and prints how many.  Every prediction
+gains 'constraints_satisfied' / 'constraints_total'; <eval_results_dir>/<id>_<split>_cbs.json holds the share of images whose
+constraints were all satisfied and the mean satisfied fraction.
+
 --rerank mbr_ciderd | mbr_bleu4 with --sample_n N (2..32) and --sample_n_method sample / gumbel / top<k|p> / sbs / bs decodes N captions per
 image and keeps the one with the highest expected CIDEr-D / BLEU-4 against the others (imagecaptioning/pytorch_amd/mbr.py;
 --rerank_prior model weighs them by the model's own probabilities): that caption is the image's prediction, scored and written
@@ -165,6 +172,66 @@ class RerankDump:
         return path
 
 
+class ConstraintSet:
+    """--constraints_json: the file's lists by image id, checked against the vocabulary when it is loaded; the satisfied / total
+    counts of the decoded images, and their summary"""
+
+    def __init__(self, by_id, vocab, oov='error'):
+        if oov not in ('error', 'drop'):
+            raise ValueError("--constraints_oov is 'error' or 'drop', got %r" % (oov,))
+        known = set(vocab.values())
+        self.by_id, self.dropped_words, self.dropped_constraints, self.rows = {}, 0, 0, []
+        missing = sorted({w for cons in by_id.values() for ws in cons for w in ws if w not in known})
+        if missing and oov == 'error':
+            raise ValueError('--constraints_json: words that are not in the vocabulary (--constraints_oov drop leaves them out): %s'
+                             % ', '.join(repr(w) for w in missing))
+        for key, cons in by_id.items():
+            kept = []
+            for ws in cons:
+                ok = [w for w in ws if w in known]
+                self.dropped_words += len(ws) - len(ok)
+                if ok:
+                    kept.append(ok)
+                else:
+                    self.dropped_constraints += 1
+            self.by_id[str(key)] = kept
+        if oov == 'drop':
+            print('--constraints_oov drop: %d words outside the vocabulary dropped, %d constraints left empty and dropped'
+                  % (self.dropped_words, self.dropped_constraints))
+
+    @classmethod
+    def load(cls, opt, vocab):
+        path = getattr(opt, 'constraints_json', '')
+        if not path:
+            return None
+        with open(path) as f:
+            return cls(json.load(f), vocab, getattr(opt, 'constraints_oov', 'error'))
+
+    def for_batch(self, infos):
+        return [self.by_id.get(str(info['id']), []) for info in infos]
+
+    def add_batch(self, last, infos, keep):
+        sat, total = last['satisfied'].tolist(), last['total'].tolist()                 # one small transfer each per batch
+        self.rows += [(info['id'], sat[i], total[i]) for i, info in enumerate(infos[:keep])]
+        return sat, total
+
+    def summary(self):
+        con = [(s, t) for _, s, t in self.rows if t > 0]
+        return {'images': len(self.rows), 'constrained_images': len(con),
+                'fully_satisfied': (sum(1 for s, t in con if s == t) / len(con)) if con else 1.0,
+                'mean_satisfied_fraction': (sum(s / t for s, t in con) / len(con)) if con else 1.0,
+                'dropped_words': self.dropped_words, 'dropped_constraints': self.dropped_constraints}
+
+    def write(self, opt, split):
+        out_dir = getattr(opt, 'eval_results_dir', 'eval_results')
+        os.makedirs(out_dir, exist_ok=True)
+        path = os.path.join(out_dir, '%s_%s_cbs.json' % (getattr(opt, 'id', 'capmi'), split))
+        with open(path, 'w') as f:
+            json.dump({'overall': self.summary(),
+                       'images': [{'image_id': i, 'constraints_satisfied': s, 'constraints_total': t} for i, s, t in self.rows]}, f)
+        return path
+
+
 class AttentionDump:
     """--dump_attention: the first caption row of every image of a batch, as ONE device-to-host transfer (every array of
     model.last_attention packed into one float32 block), kept by image id and written as one .npz"""
@@ -231,6 +298,9 @@ def eval_split(model, crit, loader, opt):
         from imagecaptioning.pytorch_amd.sentstats import SentenceStats
         sent = SentenceStats.for_loader(loader, split, dev, model, sample_n)
     dump = AttentionDump() if getattr(opt, 'dump_attention', 0) else None
+    cons = ConstraintSet.load(opt, model.vocab)
+    if cons is not None and (rerank_kw or opt.sample_n > 1):
+        raise NotImplementedError('--constraints_json decodes one caption per image: it does not combine with --sample_n > 1 or --rerank')
     if hasattr(loader, 'reset_iterator'):
         loader.reset_iterator(split)                                                                           # eval_utils.py:145
     num_images = opt.num_images
@@ -246,6 +316,8 @@ def eval_split(model, crit, loader, opt):
         kw = eval_kwargs_of(opt)
         kw['sample_n'] = 1                                                                                     # :169-170
         kw.update(rerank_kw)
+        if cons is not None:
+            kw['constraints'] = cons.for_batch(data['infos'])
         if dump is not None:
             kw['return_attention'] = 1
             boxes = batch_boxes(loader, opt, data, att.shape[1], dev)
@@ -261,6 +333,8 @@ def eval_split(model, crit, loader, opt):
             redump.add_batch(model.last_rerank, data['infos'], max(0, min(len(data['infos']), num_images - n)))
             mbr_choice = model.last_rerank['choice'].tolist()
             mbr_expected = model.last_rerank['expected'].gather(1, model.last_rerank['choice'].long().unsqueeze(1)).squeeze(1).tolist()
+        if cons is not None:
+            cbs_sat, cbs_total = cons.add_batch(model.last_cbs, data['infos'], max(0, min(len(data['infos']), num_images - n)))
         loss_sum += loss
         loss_n += 1
         if seq_logp.dim() == 3:
@@ -271,7 +345,7 @@ def eval_split(model, crit, loader, opt):
             entropy, perplexity = ops.caption_stats(seq_logp.contiguous(), seq.contiguous())
         else:                                  # _diverse_sample returns the chosen tokens' log-probs only (AttModel.py:449)
             entropy = perplexity = torch.full((seq.shape[0],), float('nan'))
-        if opt.beam_size > 1 and getattr(opt, 'verbose_beam', 0):                                              # :177-181
+        if opt.beam_size > 1 and getattr(opt, 'verbose_beam', 0) and cons is None:                                             # :177-181
             for i in range(fc.shape[0]):
                 print('\n'.join(misc.decode_sequence(model.vocab, b['seq'].unsqueeze(0))[0] for b in model.done_beams[i]))
                 print('--' * 10)
@@ -289,6 +363,8 @@ def eval_split(model, crit, loader, opt):
                           'entropy': entropy[k].item()})
             if redump is not None:
                 preds[-1].update(mbr_choice=mbr_choice[k], mbr_expected=mbr_expected[k])
+            if cons is not None:
+                preds[-1].update(constraints_satisfied=cbs_sat[k], constraints_total=cbs_total[k])
         if sample_n > 1:                                                                                       # :199-200
             first = len(n_preds)
             rows = eval_split_n(model, n_preds, fc, att, att_masks, data, opt)                                # :198
@@ -305,6 +381,8 @@ def eval_split(model, crit, loader, opt):
         print('attention written to', dump.write(opt, split))
     if redump is not None:
         print('reranking written to', redump.write(opt, split))
+    if cons is not None:
+        print('constraints: %s written to %s' % (cons.summary(), cons.write(opt, split)))
     model.n_predictions = n_preds
     model.train()                                                                                              # :224-225
     preds = preds[:num_images * max(1, len(preds) // max(n, 1))]

@@ -1901,6 +1901,39 @@ int capmi_sbs_select(const float *logp, const float *phi, const float *g, const 
 int capmi_sbs_backtrack(const int32_t *parent, const int64_t *token, const uint8_t *alive, int B, int bd, int L, int64_t *seq,
                         int32_t *length, int32_t *lineage, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Constrained beam search (cbs.hip; opt['constraints'], beam.constrained_beam_search_steps): captions that must contain given
+ * words (Anderson, Fernando, Johnson and Gould 2017).  An image has C <= 4 constraints, each a set of <= 8 token ids that is
+ * satisfied once one of them is emitted; a hypothesis's state is the bitmask of its satisfied constraints, and the image keeps one
+ * beam of b slots per state: S = 2^C states (of the batch's largest C), slot = state * b + j, S * b <= 64.
+ * capmi_cbs_select: one step.  logp [B * cur, V1] rows, image-major (cur = 1: the root, in state 0; else cur = S * b, row = slot);
+ *          sums [B, S * b], a value that is not > -inf marks an empty slot, which is never a source whatever its row holds;
+ *          words [B, 4, 8] int32 padded with -1, ncons [B] int32.  sat(v) = the mask of every constraint c < ncons whose set holds
+ *          v.  The candidates of target state s' are all (valid source slot r in state s, token v) with s | sat(v) == s' and a
+ *          score = sums[r] + logp[r, v] (one float32 add) > -inf.  Outputs [B, S * b]: per target state its b best by descending
+ *          score, equal scores by the lower flat index r * V1 + v: parent (r), token, score, ended = token == 0 or force_end,
+ *          next_sums = ended ? score - 1000 : score, valid = 1; a state with fewer candidates fills its other slots with
+ *          parent 0, token 0, score / next_sums -inf, ended 0, valid 0.  With S = 1 this is capmi_beam_select bit for bit.
+ *          scratch: capmi_cbs_scratch_bytes(B, cur, b, V1) bytes, 4-byte aligned (the per-chunk candidate lists).
+ *          Two launches, no float atomics, bit-identical from run to run.  CAPMI_EINVAL, before anything is launched: a NULL
+ *          pointer, a dimension <= 0, S no power of two <= 16, S * b > 64, cur not in {1, S * b}, a scratch that is too small,
+ *          ceil((V1 + 3) / 1024) * b above 2048.  The tables are trusted to hold ids in [1, V1) and 2^ncons <= S (ops.cbs_tables
+ *          checks them on the host before they are uploaded); an entry outside is skipped, a larger ncons is cut.
+ * capmi_cbs_finalize: the [L][B, S * b] tables of L steps (the last one with force_end) -> per image the best recorded (ended
+ *          and valid) candidate by (a) its state being the image's full mask 2^ncons - 1, else the larger popcount of the state,
+ *          (b) the larger (double)score / len_div[t] (len_div NULL: the score), (c) the lower step, then the lower slot; seq [B, L]
+ *          (0 behind the end), lineage [L][B] and length [B] with the conventions of capmi_beam_finalize (rows_src = S * b per
+ *          image), state [B] the candidate's mask, score_out [B] its key (b).  One launch.  CAPMI_EINVAL: a NULL pointer
+ *          (len_div excepted), the shape rules above, L * S * b > 4096.
+ * ------------------------------------------------------------------------------------------- */
+int64_t capmi_cbs_scratch_bytes(int B, int cur, int b, int V1);
+int capmi_cbs_select(const float *logp, const float *sums, const int32_t *words, const int32_t *ncons, int B, int cur, int b, int S,
+                     int V1, int force_end, void *scratch, int64_t scratch_bytes, int32_t *parent, int64_t *token, float *score,
+                     float *next_sums, uint8_t *ended, uint8_t *valid, void *stream);
+int capmi_cbs_finalize(const int32_t *parent, const int64_t *token, const float *score, const uint8_t *ended, const uint8_t *valid,
+                       const int32_t *ncons, const double *len_div, int B, int b, int S, int L, int64_t *seq, int32_t *lineage,
+                       int32_t *length, int32_t *state, float *score_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
