@@ -472,6 +472,8 @@ SIGNATURES = {
     'capmi_cbs_scratch_bytes': [_I, _I, _I, _I],
     'capmi_cbs_select': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I64, _P, _P, _P, _P, _P, _P, _P],
     'capmi_cbs_finalize': [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    'capmi_score_step': [_P, _I64, _I, _I, _P, _P, _P, _P, _P, _F, _I, _P],
+    'capmi_retrieval_rank': [_P, _I64, _I, _I, _P, _P, _P, _P],
 }
 
 

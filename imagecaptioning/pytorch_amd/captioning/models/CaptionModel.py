@@ -36,6 +36,17 @@ class CaptionModel(nn.Module):
     _cbs_req = None             # cbs.Request (the checked host tables) while such a call runs
     _cbs_refusal = 'the model has no single-step decoder for the beam driver'
 
+    # ---- mode='score' (imagecaptioning.pytorch_amd.score): log p(caption | image) of GIVEN captions; test-time only, no gradient
+    last_score = None           # dict of device tensors (logp, len, tok_logp, perplexity) after such a call
+
+    def _score(self, fc_feats, att_feats, seqs, att_masks=None, opt=None):
+        """``model(fc_feats, att_feats, seqs, att_masks, mode='score', opt={...})``: the joint log-probability of the given captions,
+        [B, n] for seqs [B, n, L] / [B * n, L], or S [C, B] for seqs [C, L] with opt['pairing'] = 'cross' (score.score_captions:
+        'score_norm', 'score_rows', 'temperature', 'suppress_UNK').  Every family with a single-step decoder; AttEnsemble, train
+        mode and output_logsoftmax=0 are refused before any device work."""
+        from imagecaptioning.pytorch_amd import score
+        return score.score_captions(self, fc_feats, att_feats, att_masks, seqs, opt)
+
     def _sample_entry(self, *args, **kwargs):
         opt = kwargs.get('opt') or (args[3] if len(args) > 3 else None)
         if self.last_cbs is not None:

@@ -56,6 +56,11 @@ DEFAULTS = dict(
     # names a file {"<image id>": [["zebra", "zebras"], ["grass"]], ...} of words the image's caption must contain (one of each
     # list); constraints_oov: 'error' stops at a word outside the vocabulary, 'drop' leaves such words out
     constraints_json='', constraints_oov='error',
+    # scoring given captions (imagecaptioning/pytorch_amd/score.py; not flags of the reference).  self_retrieval 1: after decoding, every
+    # image's first caption is scored against all images of its pool (consecutive blocks of retrieval_pool images) -> R@1/5/10,
+    # median rank; score_json names a file {"<image id>": ["a caption", ...]} of captions to score under the model (words outside
+    # the vocabulary: UNK, or dropped under constraints_oov drop); score_norm: 'none' the joint log-probability, 'length' per token
+    self_retrieval=0, retrieval_pool=1000, score_norm='none', score_json='',
     # data (synthetic only: the reference's h5/lmdb loaders are outside the hot path)
     input_synthetic=1, vocab_size=9487, synthetic_regions=36, synthetic_images=200,
     # real precomputed features (captioning/data/feature_loader.py; opts.py:23-37 of the reference)

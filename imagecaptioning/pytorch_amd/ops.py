@@ -1402,3 +1402,46 @@ def cbs_finalize(parent, token, score, ended, valid, ncons, b, S, len_div=None):
                                  int(S), L, ptr(seq), ptr(lineage), ptr(length), ptr(state), ptr(out_score), stream_ptr()),
           'capmi_cbs_finalize')
     return seq, lineage, length, state, out_score
+
+
+# ---- scoring given captions (score.score_captions; capmi.h capmi_score_step / capmi_retrieval_rank, score.hip) ----------------------
+def _rows_of(x, what):
+    """a float32 device matrix whose rows are contiguous (any row stride >= the width) -> its row stride"""
+    if not x.is_cuda:
+        raise _lib.CapmiError('capmi ops need device tensors (got %s)' % x.device)
+    if x.dtype != _f32 or x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1) or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        raise _lib.CapmiError('%s: a float32 matrix with contiguous rows' % what)
+    return x.stride(0) if x.shape[0] > 1 else max(x.stride(0), x.shape[1])
+
+
+def score_step(logits, tok, live, acc, cnt, tok_logp=None, inv_temperature=1.0, unk_col=-1):
+    """capmi_score_step, in place: logits float32 [rows, V1] (rows may be strided), tok int64 [rows], live uint8 [rows], acc float32
+    [rows], cnt int32 [rows], tok_logp float32 [rows] or None.  Live rows: acc += log p(tok), cnt += 1, tok_logp = it, live = 0
+    behind token 0; dead rows are untouched.  The tokens are trusted to lie in [0, V1) (score.py checks them on the host)."""
+    ld = _rows_of(logits, 'score_step: logits')
+    _chk(tok, live, acc, cnt, tok_logp)
+    rows, V1 = logits.shape
+    if tok.dtype != torch.long or live.dtype != torch.uint8 or acc.dtype != _f32 or cnt.dtype != torch.int32 \
+            or any(t.shape != (rows,) for t in (tok, live, acc, cnt)) \
+            or (tok_logp is not None and (tok_logp.dtype != _f32 or tok_logp.shape != (rows,))):
+        raise _lib.CapmiError('score_step: tok int64, live uint8, acc float32, cnt int32[, tok_logp float32], all [rows]')
+    check(lib.capmi_score_step(ptr(logits), ld, rows, V1, ptr(tok), ptr(live), ptr(acc), ptr(cnt), ptr(tok_logp),
+                               float(inv_temperature), int(unk_col), stream_ptr()), 'capmi_score_step')
+
+
+def retrieval_rank(S, target, log_post=True):
+    """capmi_retrieval_rank: S float32 [C, I] (rows may be strided), target [C] (host or device; checked on the host to lie in
+    [0, I)) -> (rank int32 [C], log_post float32 [C] or None): 1 + the images that score higher than the caption's own, ties to the
+    lower image index, and the log-posterior of the own image under a uniform prior."""
+    ld = _rows_of(S, 'retrieval_rank: S')
+    C, I = S.shape
+    target = torch.as_tensor(target)
+    if target.shape != (C,) or target.dtype.is_floating_point:
+        raise _lib.CapmiError('retrieval_rank: target holds one image index per caption')
+    if C and (int(target.min()) < 0 or int(target.max()) >= I):
+        raise _lib.CapmiError('retrieval_rank: a target outside [0, %d) (EINVAL)' % I)
+    target = target.to(device=S.device, dtype=torch.int32).contiguous()
+    rank = torch.empty(C, dtype=torch.int32, device=S.device)
+    post = torch.empty(C, dtype=_f32, device=S.device) if log_post else None
+    check(lib.capmi_retrieval_rank(ptr(S), ld, C, I, ptr(target), ptr(rank), ptr(post), stream_ptr()), 'capmi_retrieval_rank')
+    return rank, post

@@ -27,6 +27,17 @@ that is not in the vocabulary, drop leaves such words -- and the lists they empt
 gains 'constraints_satisfied' / 'constraints_total'; <eval_results_dir>/<id>_<split>_cbs.json holds the share of images whose
 constraints were all satisfied and the mean satisfied fraction.
 
+--self_retrieval 1 [--retrieval_pool 1000] [--score_norm none|length] (imagecaptioning/pytorch_amd/score.py): after decoding, the first
+caption of every evaluated image is scored against every image of its pool -- consecutive blocks of retrieval_pool images, the last
+one possibly smaller -- by log p(caption | image) (divided by the scored length under --score_norm length); every prediction gains
+'retrieval_rank' (1: the caption picks its own image; ties go to the lower image) and 'retrieval_log_post', and
+<eval_results_dir>/<id>_<split>_ret.json holds R@1, R@5, R@10, the median and mean rank, MRR, the pool size and the pools.  It does
+not combine with --constraints_json, or with --sample_n > 1 without --rerank.
+--score_json FILE holds {"<image id>": ["a caption", ...]}: the captions are scored under the model for their image; words outside
+the vocabulary become UNK, or are dropped with --constraints_oov drop; captions are cut at seq_length words.
+<eval_results_dir>/<id>_<split>_scores.json holds per caption 'logp', 'len' (scored tokens, the end token included), 'perplexity'
+and the words it lacked, and lists the image ids of the file that the evaluated split did not hold.
+
 --rerank mbr_ciderd | mbr_bleu4 with --sample_n N (2..32) and --sample_n_method sample / gumbel / top<k|p> / sbs / bs decodes N captions per
 image and keeps the one with the highest expected CIDEr-D / BLEU-4 against the others (imagecaptioning/pytorch_amd/mbr.py;
 --rerank_prior model weighs them by the model's own probabilities): that caption is the image's prediction, scored and written
@@ -232,6 +243,136 @@ class ConstraintSet:
         return path
 
 
+def _results_path(opt, split, suffix):
+    out_dir = getattr(opt, 'eval_results_dir', 'eval_results')
+    os.makedirs(out_dir, exist_ok=True)
+    return os.path.join(out_dir, '%s_%s_%s' % (getattr(opt, 'id', 'capmi'), split, suffix))
+
+
+class SelfRetrieval:
+    """--self_retrieval: the evaluated images are collected into pools of `pool` consecutive images (features and first captions
+    stay on the device); a full pool -- and at the end the rest -- is scored caption by image (score.score_captions, pairing
+    'cross') and ranked (capmi_retrieval_rank).  The predictions of the pool gain their rank and log-posterior then."""
+
+    def __init__(self, pool, norm='none'):
+        from imagecaptioning.pytorch_amd import score
+        if int(pool) < 1:
+            raise ValueError('--retrieval_pool is a number of images >= 1, got %r' % (pool,))
+        if norm not in score.NORMS:
+            raise ValueError("--score_norm is 'none' or 'length', got %r" % (norm,))
+        self.pool, self.norm = int(pool), norm
+        self.pending, self.ranks, self.sizes = [], [], []
+
+    @classmethod
+    def load(cls, opt, cons, rerank_kw):
+        if not getattr(opt, 'self_retrieval', 0):
+            return None
+        if cons is not None:
+            raise NotImplementedError('--self_retrieval does not combine with --constraints_json: a caption that was made to contain '
+                                      'given words says nothing about how well the model tells the images apart')
+        if opt.sample_n > 1 and not rerank_kw:
+            raise NotImplementedError('--self_retrieval ranks ONE caption per image: with --sample_n > 1 say which one with --rerank '
+                                      '(the first of sample_n sampled captions is an arbitrary one)')
+        return cls(getattr(opt, 'retrieval_pool', 1000), getattr(opt, 'score_norm', 'none'))
+
+    def add_batch(self, model, fc, att, att_masks, seq_first, preds):
+        """the kept images of a batch: their features, first captions [keep, L] and prediction dicts, in order"""
+        for k, p in enumerate(preds):
+            self.pending.append((fc[k], att[k], None if att_masks is None else att_masks[k], seq_first[k], p))
+            if len(self.pending) == self.pool:
+                self._flush(model)
+
+    def finish(self, model):
+        if self.pending:
+            self._flush(model)
+
+    def _flush(self, model):
+        from imagecaptioning.pytorch_amd import ops, score
+        items, self.pending = self.pending, []
+        k, K = len(items), max(it[1].shape[0] for it in items)
+        fc = torch.stack([it[0] for it in items])
+        att = torch.stack([torch.nn.functional.pad(it[1], (0, 0, 0, K - it[1].shape[0])) for it in items])
+        masks = None
+        if any(it[2] is not None or it[1].shape[0] != K for it in items):       # ragged pools: the loader's masks, padded
+            masks = att.new_zeros(k, K)
+            for j, it in enumerate(items):
+                if it[2] is None:
+                    masks[j, :it[1].shape[0]] = 1
+                else:
+                    masks[j, :it[2].shape[0]] = it[2]
+        seqs = torch.stack([it[3] for it in items]).long()
+        S = score.score_captions(model, fc, att, masks, seqs, {'pairing': 'cross', 'score_norm': self.norm})
+        rank, post = ops.retrieval_rank(S, torch.arange(k))
+        rank, post = rank.tolist(), post.tolist()                                # one transfer each per pool
+        for j, it in enumerate(items):
+            it[4].update(retrieval_rank=rank[j], retrieval_log_post=post[j])
+        self.ranks += rank
+        self.sizes.append(k)
+
+    def summary(self):
+        from imagecaptioning.pytorch_amd import score
+        return dict(score.retrieval_summary(self.ranks, self.pool, len(self.sizes)), pool_sizes=self.sizes, score_norm=self.norm)
+
+    def write(self, opt, split):
+        path = _results_path(opt, split, 'ret.json')
+        with open(path, 'w') as f:
+            json.dump({'overall': self.summary(), 'ranks': self.ranks}, f)
+        return path
+
+
+class CaptionScores:
+    """--score_json: the file's captions by image id as token rows; the scores of the images the pass met, and those it did not"""
+
+    def __init__(self, by_id, vocab, L, oov='error', norm='none'):
+        from imagecaptioning.pytorch_amd import score
+        if norm not in score.NORMS:
+            raise ValueError("--score_norm is 'none' or 'length', got %r" % (norm,))
+        self.norm, self.by_id, self.done, self.L = norm, {}, {}, L
+        for key, caps in by_id.items():
+            caps = [caps] if isinstance(caps, str) else list(caps)
+            if not caps:
+                continue
+            rows, missing = score.encode_captions(caps, vocab, L, 'drop' if oov == 'drop' else 'unk')
+            self.by_id[str(key)] = (caps, rows, missing)
+
+    @classmethod
+    def load(cls, opt, vocab, L):
+        path = getattr(opt, 'score_json', '')
+        if not path:
+            return None
+        with open(path) as f:
+            return cls(json.load(f), vocab, L, getattr(opt, 'constraints_oov', 'error'), getattr(opt, 'score_norm', 'none'))
+
+    def add_batch(self, model, fc, att, att_masks, infos, keep):
+        idx = [k for k in range(keep) if str(infos[k]['id']) in self.by_id and str(infos[k]['id']) not in self.done]
+        if not idx:
+            return
+        n = max(self.by_id[str(infos[k]['id'])][1].shape[0] for k in idx)
+        seqs = torch.zeros(len(idx), n, self.L, dtype=torch.long)          # images with fewer captions: empty rows, not reported
+        for j, k in enumerate(idx):
+            rows = self.by_id[str(infos[k]['id'])][1]
+            seqs[j, :rows.shape[0]] = rows
+        sel = torch.tensor(idx, device=fc.device)
+        out = model(fc[sel], att[sel], seqs.to(fc.device), None if att_masks is None else att_masks[sel], mode='score',
+                    opt={'score_norm': self.norm})
+        last = model.last_score
+        val, logp, ln, ppl = out.tolist(), last['logp'].tolist(), last['len'].tolist(), last['perplexity'].tolist()
+        for j, k in enumerate(idx):
+            caps, rows, missing = self.by_id[str(infos[k]['id'])]
+            self.done[str(infos[k]['id'])] = [
+                {'caption': c, 'score': val[j][i], 'logp': logp[j][i], 'len': ln[j][i], 'perplexity': ppl[j][i], 'oov_words': missing[i]}
+                for i, c in enumerate(caps)]
+
+    def missing_ids(self):
+        return sorted(k for k in self.by_id if k not in self.done)
+
+    def write(self, opt, split):
+        path = _results_path(opt, split, 'scores.json')
+        with open(path, 'w') as f:
+            json.dump({'score_norm': self.norm, 'images': self.done, 'missing_image_ids': self.missing_ids()}, f)
+        return path
+
+
 class AttentionDump:
     """--dump_attention: the first caption row of every image of a batch, as ONE device-to-host transfer (every array of
     model.last_attention packed into one float32 block), kept by image id and written as one .npz"""
@@ -301,6 +442,8 @@ def eval_split(model, crit, loader, opt):
     cons = ConstraintSet.load(opt, model.vocab)
     if cons is not None and (rerank_kw or opt.sample_n > 1):
         raise NotImplementedError('--constraints_json decodes one caption per image: it does not combine with --sample_n > 1 or --rerank')
+    retr = SelfRetrieval.load(opt, cons, rerank_kw)
+    given = CaptionScores.load(opt, model.vocab, model.seq_length)
     if hasattr(loader, 'reset_iterator'):
         loader.reset_iterator(split)                                                                           # eval_utils.py:145
     num_images = opt.num_images
@@ -358,6 +501,7 @@ def eval_split(model, crit, loader, opt):
             lang.add_batch(data['infos'][:keep], seq[::rows_per_image][:keep])
             if sent is not None:
                 sent.add_first(seq[::rows_per_image][:keep], perplexity[::rows_per_image][:keep], entropy[::rows_per_image][:keep])
+        first_pred = len(preds)
         for k, s in enumerate(sents):
             preds.append({'image_id': data['infos'][k // rows_per_image]['id'], 'caption': s, 'perplexity': perplexity[k].item(),
                           'entropy': entropy[k].item()})
@@ -365,6 +509,12 @@ def eval_split(model, crit, loader, opt):
                 preds[-1].update(mbr_choice=mbr_choice[k], mbr_expected=mbr_expected[k])
             if cons is not None:
                 preds[-1].update(constraints_satisfied=cbs_sat[k], constraints_total=cbs_total[k])
+        if retr is not None or given is not None:
+            kept = max(0, min(len(data['infos']), num_images - n))
+            if retr is not None:
+                retr.add_batch(model, fc, att, att_masks, seq[::rows_per_image][:kept], preds[first_pred::rows_per_image][:kept])
+            if given is not None:
+                given.add_batch(model, fc, att, att_masks, data['infos'], kept)
         if sample_n > 1:                                                                                       # :199-200
             first = len(n_preds)
             rows = eval_split_n(model, n_preds, fc, att, att_masks, data, opt)                                # :198
@@ -383,6 +533,14 @@ def eval_split(model, crit, loader, opt):
         print('reranking written to', redump.write(opt, split))
     if cons is not None:
         print('constraints: %s written to %s' % (cons.summary(), cons.write(opt, split)))
+    if retr is not None:
+        retr.finish(model)
+        print('self-retrieval: %s written to %s' % (retr.summary(), retr.write(opt, split)))
+    if given is not None:
+        if given.missing_ids():
+            print('--score_json: %d image ids of the file are not among the evaluated images of split %r: %s'
+                  % (len(given.missing_ids()), split, ', '.join(given.missing_ids())))
+        print('caption scores written to', given.write(opt, split))
     model.n_predictions = n_preds
     model.train()                                                                                              # :224-225
     preds = preds[:num_images * max(1, len(preds) // max(n, 1))]

@@ -1934,6 +1934,33 @@ int capmi_cbs_finalize(const int32_t *parent, const int64_t *token, const float 
                        const int32_t *ncons, const double *len_div, int B, int b, int S, int L, int64_t *seq, int32_t *lineage,
                        int32_t *length, int32_t *state, float *score_out, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Scoring given captions (score.hip; score.score_captions, model(..., mode='score'), tools/eval.py --self_retrieval /
+ * --score_json): log p(caption | image) of captions that came from elsewhere, one decoder row per (image, caption) pair.
+ * capmi_score_step: one step.  logits [rows, ld] (ld >= V1 floats between rows; neither ld nor V1 need be a multiple of 4), tok
+ *          int64 [rows] the row's given token, live uint8 [rows].  For every row with live != 0:
+ *              lse = logsumexp_v(logits[row, v] * inv_temperature) over all V1 columns,
+ *              lp  = logits[row, tok] * inv_temperature - lse, 1000 lower when tok == unk_col (capmi_beam_logsoftmax's
+ *                    suppress_UNK: the row is normalised over every column, then that column is pushed down; -1: none),
+ *              acc[row] += lp, cnt[row] += 1, tok_logp[row] = lp (tok_logp may be NULL), and live[row] = 0 when tok == 0: the end
+ *              token is scored, then the row is dead.
+ *          Rows with live == 0 are not read and nothing of theirs is written.  One pass over the row (an online max / sum), 16-byte
+ *          loads between the row's own 16-byte boundaries; a wave per row up to 1024 columns, a workgroup per row above; fixed
+ *          reduction order, bit-identical from run to run.  Reads rows * V1 * 4 bytes, writes O(rows).  A token outside [0, V1) is
+ *          the caller's error (score.py checks the captions on the host, once per call): such a row reads no logit and gets NaN.
+ *          CAPMI_EINVAL, before anything is launched: a NULL pointer (tok_logp excepted), rows <= 0, V1 <= 0, ld < V1,
+ *          inv_temperature not in (0, inf).
+ * capmi_retrieval_rank: S [C, ld] (ld >= I), S[c, i] the score of caption c against image i of a pool, target int32 [C] the
+ *          caption's own image t.  rank[c] = 1 + #{i : S[c, i] > S[c, t]} + #{i < t : S[c, i] == S[c, t]} (ties go to the lower
+ *          image index), log_post[c] (may be NULL) = S[c, t] - logsumexp_i S[c, i], the posterior of the right image under a
+ *          uniform prior.  One workgroup per caption.  A target outside [0, I) (ops.retrieval_rank refuses it) gives rank 0 and
+ *          NaN.  CAPMI_EINVAL: a NULL pointer (log_post excepted), C <= 0, I <= 0, ld < I.
+ * ------------------------------------------------------------------------------------------- */
+int capmi_score_step(const float *logits, int64_t ld, int rows, int V1, const int64_t *tok, uint8_t *live, float *acc, int32_t *cnt,
+                     float *tok_logp, float inv_temperature, int unk_col, void *stream);
+int capmi_retrieval_rank(const float *S, int64_t ld, int C, int I, const int32_t *target, int32_t *rank, float *log_post,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif
