@@ -72,12 +72,7 @@ def _native_search(model, P, pr, bd, L, opt, drop_xt=None, drop_out=None, train=
     b.B, b.bd, b.K, b.A, b.R, b.E, b.V1, b.L = B, bd, K, A, R, E, V1, L
     b.fc, b.att, b.p_att, b.att_mask = ptr(pr.fc), ptr(pr.att), ptr(pr.p_att), ptr(pr.att_masks)
     b.temperature = float(opt.get('temperature', 1))
-    unk = -1
-    if opt.get('suppress_UNK', 0) and hasattr(model, 'vocab') and model.vocab.get(str(V1 - 1)) == 'UNK':
-        unk = V1 - 1                                              # CaptionModel.py:159-160
-    elif getattr(model, 'unk_idx', None) is not None:
-        unk = int(model.unk_idx)                                  # :161-162
-    b.unk_col = unk
+    b.unk_col = unk_column(model, opt, V1)
     for k, t in bufs.items():
         setattr(b, k, t.data_ptr())
     b.partial, b.partial_capacity = ws.buf.data_ptr(), ws.capacity
@@ -331,6 +326,78 @@ def _decode_flags(model, opt, dev):
     return flags, bad
 
 
+def _normaliser(model, opt, V1, dev, root_temperature=1.0, renormalise=False):
+    """-> normalise(t, logits, out, rows, prev_token): out[:rows] = log_softmax(logits / T) with the UNK column pushed down
+    (CaptionModel.py:159-162), T = root_temperature at t = 0 and opt['temperature'] afterwards (:203-204); from t = 1 on
+    capmi_decode_constrain against the previous tokens when decoding_constraint / remove_bad_endings are set (:152-155).
+    renormalise (sbs): edited rows go through a second log_softmax, so that they are distributions again."""
+    temperature = float(opt.get('temperature', 1))
+    unk = unk_column(model, opt, V1)
+    flags, bad = _decode_flags(model, opt, dev)
+    st = stream_ptr()
+    edited = [None]
+
+    def normalise(t, logits, out, rows, prev_token):
+        dst = out
+        if renormalise and (flags or unk >= 0):
+            if edited[0] is None:
+                edited[0] = torch.empty(out.shape[0], V1, dtype=_f32, device=dev)
+            dst = edited[0]
+        check(lib.capmi_beam_logsoftmax(ptr(logits), ptr(dst), rows, V1, temperature if t else root_temperature, unk, st),
+              'beam_logsoftmax')
+        if flags and t > 0:
+            check(lib.capmi_decode_constrain(ptr(dst), rows, V1, ptr(prev_token), 1, flags, ptr(bad), bad.numel(), None, 0, t, 0, st),
+                  'decode_constrain')
+        if dst is not out:
+            check(lib.capmi_beam_logsoftmax(ptr(dst), ptr(out), rows, V1, 1.0, -1, st), 'beam_logsoftmax')
+    return normalise
+
+
+def _search_loop(model, make_decoder, B, W, V1, L, opt, dev, select, trace=True, root_temperature=1.0, renormalise=False):
+    """The loop that the beam search, the stochastic and the constrained beam search share, W rows per image: step the decoder
+    (from BOS on one row per image, then on B * W rows), normalise the rows (root_temperature, renormalise: _normaliser's),
+    select(t, logp_t [B * cur, V1], cur, parent_t, token_t) -- it fills the step's [B, W] slices -- and reorder the decoder's
+    state; the last step only selects.  The caller makes the tables its select writes before it calls, so their zero fills precede
+    the decoder's construction on the stream.  Nothing reads the device.  Returns (logp_rows [L, B * W, V1], parent int32 / token int64 [L, B, W], and the
+    recorders of att_trace.recording when the model wants the attention and `trace` allows it, else None)."""
+    recs = None
+    if trace and getattr(model, '_trace_req', None) is not None:
+        from . import att_trace
+        make_decoder, recs = att_trace.recording(make_decoder, L)
+    dec = make_decoder(W)
+    N = B * W
+    normalise = _normaliser(model, opt, V1, dev, root_temperature, renormalise)
+    logp_rows = torch.zeros(L, N, V1, dtype=_f32, device=dev)
+    parent = torch.zeros(L, B, W, dtype=torch.int32, device=dev)
+    token = torch.zeros(L, B, W, dtype=torch.long, device=dev)
+    it, rows, cur = torch.zeros(B, dtype=torch.long, device=dev), B, 1       # BOS
+    for t in range(L):
+        logits = dec.step(t, it, cur)
+        normalise(t, logits, logp_rows[t], rows, token[t - 1] if t else None)
+        select(t, logp_rows[t, :rows], cur, parent[t], token[t])
+        if t == L - 1:
+            break
+        dec.reorder(parent[t], cur)
+        it, rows, cur = token[t].reshape(N), N, W
+    return logp_rows, parent, token, recs
+
+
+def _publish_trace(model, recs, lineage, length, n):
+    """return_attention of a search that backtracks on the device: the recorded weights along the lineage, n captions per image"""
+    if recs is not None:
+        from . import att_trace
+        att_trace.publish(model, att_trace.beam(recs[0].buf, lineage, length, model._trace_req.Kout), n)
+
+
+def seq_logp_from_lineage(logp_rows, lineage):
+    """seqLogprobs [rows, L, V1] of the paths of lineage [L, rows] (beam.finalize's convention): step t's row lineage[t, i] of
+    logp_rows [L, N, V1], zeros where lineage < 0 (behind a path's end)."""
+    L, _, V1 = logp_rows.shape
+    live = (lineage >= 0).unsqueeze(2)
+    gathered = logp_rows.gather(1, lineage.clamp(min=0).long().unsqueeze(2).expand(L, lineage.shape[1], V1))
+    return torch.where(live, gathered, gathered.new_zeros(())).permute(1, 0, 2).contiguous()
+
+
 def beam_search_steps(model, make_decoder, B, V1, L, opt, dev, tables_only=False):
     """CaptionModel.beam_search (CaptionModel.py:35-209) for any decoder given as a single-step object (step.py
     protocol): the selection / reordering / normalisation / constraint / diversity kernels are native, only the decoder
@@ -347,44 +414,21 @@ def beam_search_steps(model, make_decoder, B, V1, L, opt, dev, tables_only=False
     if int(opt.get('group_size', 1)) != 1:
         return diverse_beam_search_steps(model, make_decoder, B, V1, L, opt, dev)
     assert sample_n == 1 or sample_n == beam_size, 'when beam search, sample_n == 1 or beam search'
-    trace = None if tables_only else getattr(model, '_trace_req', None)
-    if trace is not None:
-        from . import att_trace
-        make_decoder, recs = att_trace.recording(make_decoder, L)
-    dec = make_decoder(beam_size)
-    step, reorder = dec.step, dec.reorder
     bd = beam_size
-    N = B * bd
-    temperature = float(opt.get('temperature', 1))
-    unk = unk_column(model, opt, V1)
-    flags, bad = _decode_flags(model, opt, dev)
-    logp_rows = torch.zeros(L, N, V1, dtype=_f32, device=dev)
-    parent = torch.zeros(L, B, bd, dtype=torch.int32, device=dev)
-    token = torch.zeros(L, B, bd, dtype=torch.long, device=dev)
     score = torch.zeros(L, B, bd, dtype=_f32, device=dev)
     ended = torch.zeros(L, B, bd, dtype=torch.uint8, device=dev)
     sums = torch.zeros(2, B, bd, dtype=_f32, device=dev)
     st = stream_ptr()
-    it = torch.zeros(B, dtype=torch.long, device=dev)                       # BOS
-    logits = step(0, it, 1)
+
+    def select(t, logp_t, cur, parent_t, token_t):
+        check(lib.capmi_beam_select(ptr(logp_t), ptr(sums[t & 1]), B, cur, bd, V1, 1 if t == L - 1 else 0, ptr(parent_t),
+                                    ptr(token_t), ptr(score[t]), ptr(sums[(t + 1) & 1]), ptr(ended[t]), st), 'beam_select')
     # the first distribution is the model's own log_softmax; the temperature enters at CaptionModel.py:203-204 only
-    check(lib.capmi_beam_logsoftmax(ptr(logits), ptr(logp_rows[0]), B, V1, 1.0, unk, st), 'beam_logsoftmax')
-    cur = 1
-    for t in range(L):
-        check(lib.capmi_beam_select(ptr(logp_rows[t]), ptr(sums[t & 1]), B, cur, bd, V1, 1 if t == L - 1 else 0, ptr(parent[t]),
-                                    ptr(token[t]), ptr(score[t]), ptr(sums[(t + 1) & 1]), ptr(ended[t]), st), 'beam_select')
-        if t == L - 1:
-            break
-        reorder(parent[t], cur)
-        logits = step(t + 1, token[t].reshape(N), bd)
-        check(lib.capmi_beam_logsoftmax(ptr(logits), ptr(logp_rows[t + 1]), N, V1, temperature, unk, st), 'beam_logsoftmax')
-        if flags:                                                           # CaptionModel.py:152-155
-            check(lib.capmi_decode_constrain(ptr(logp_rows[t + 1]), N, V1, ptr(token[t]), 1, flags, ptr(bad), bad.numel(), None, 0,
-                                             t + 1, 0, st), 'decode_constrain')
-        cur = bd
+    logp_rows, parent, token, recs = _search_loop(model, make_decoder, B, bd, V1, L, opt, dev, select, trace=not tables_only)
     if tables_only:                                                         # the training search finalises on the device
         return parent, token, score, ended, logp_rows
-    if trace is not None:
+    if recs is not None:
+        from . import att_trace
         att_trace.from_beam(model, recs[0], parent, token, score, ended, sample_n if sample_n == beam_size else 1, B * sample_n, opt)
     return assemble_done_beams(model, parent, token, score, ended, logp_rows, B, bd, L, V1, sample_n, beam_size, opt)
 
@@ -404,56 +448,26 @@ def stochastic_beam_search_steps(model, make_decoder, B, V1, L, opt, dev):
     k = sbs.check_options(model, opt)
     if k > V1:
         raise ValueError("sample_method 'sbs': sample_n = %d captions need a vocabulary of at least as many words (%d)" % (k, V1))
-    trace = getattr(model, '_trace_req', None)
-    if trace is not None:
-        from . import att_trace
-        make_decoder, recs = att_trace.recording(make_decoder, L)
-    dec = make_decoder(k)
-    N = B * k
-    temperature = float(opt.get('temperature', 1))
-    unk = unk_column(model, opt, V1)
-    flags, bad = _decode_flags(model, opt, dev)
     gumbel = opt.get('_gumbel')
     seed = model._next_seed()
-    logp_rows = torch.zeros(L, N, V1, dtype=_f32, device=dev)
-    edited = torch.empty(N, V1, dtype=_f32, device=dev) if (flags or unk >= 0) else None
-    parent = torch.zeros(L, B, k, dtype=torch.int32, device=dev)
-    token = torch.zeros(L, B, k, dtype=torch.long, device=dev)
     alive = torch.zeros(L, B, k, dtype=torch.uint8, device=dev)
     phi = torch.zeros(2, B, k, dtype=_f32, device=dev)
     g = torch.zeros(2, B, k, dtype=_f32, device=dev)
     root, zero = torch.ones(B, 1, dtype=torch.uint8, device=dev), torch.zeros(B, 1, dtype=_f32, device=dev)     # the root: phi 0
-    st = stream_ptr()
-    it, rows, cur = torch.zeros(B, dtype=torch.long, device=dev), B, 1       # BOS
-    for t in range(L):
-        logits = dec.step(t, it, cur)
-        out = logp_rows[t]
-        if edited is None:
-            check(lib.capmi_beam_logsoftmax(ptr(logits), ptr(out), rows, V1, temperature, -1, st), 'beam_logsoftmax')
-        else:
-            check(lib.capmi_beam_logsoftmax(ptr(logits), ptr(edited), rows, V1, temperature, unk, st), 'beam_logsoftmax')
-            if flags and t > 0:
-                check(lib.capmi_decode_constrain(ptr(edited), rows, V1, ptr(token[t - 1]), 1, flags, ptr(bad), bad.numel(), None, 0,
-                                                 t, 0, st), 'decode_constrain')
-            check(lib.capmi_beam_logsoftmax(ptr(edited), ptr(out), rows, V1, 1.0, -1, st), 'beam_logsoftmax')
+
+    def select(t, logp_t, cur, parent_t, token_t):
         i, o = t & 1, (t + 1) & 1
         state = (zero, zero, root) if t == 0 else (phi[i], g[i], alive[t - 1])
-        ops.sbs_select(out[:rows], *state, k, step0=t == 0, force_end=t == L - 1,
-                       gumbel=None if gumbel is None else gumbel[t, :rows], seed=seed, offset=t,
-                       out=(parent[t], token[t], phi[o], g[o], alive[t]))
-        if t == L - 1:
-            break
-        dec.reorder(parent[t], cur)
-        it, rows, cur = token[t].reshape(N), N, k
+        ops.sbs_select(logp_t, *state, k, step0=t == 0, force_end=t == L - 1,
+                       gumbel=None if gumbel is None else gumbel[t, :logp_t.shape[0]], seed=seed, offset=t,
+                       out=(parent_t, token_t, phi[o], g[o], alive[t]))
+    logp_rows, parent, token, recs = _search_loop(model, make_decoder, B, k, V1, L, opt, dev, select,
+                                                  root_temperature=float(opt.get('temperature', 1)), renormalise=True)
     seq, length, lineage = ops.sbs_backtrack(parent, token, alive)
-    live = (lineage >= 0).unsqueeze(2)
-    gathered = logp_rows.gather(1, lineage.clamp(min=0).long().unsqueeze(2).expand(L, N, V1))
-    seq_logp = torch.where(live, gathered, gathered.new_zeros(())).permute(1, 0, 2).contiguous()
+    seq_logp = seq_logp_from_lineage(logp_rows, lineage)
     phi_k, g_k = phi[L & 1].clone(), g[L & 1].clone()
     model.last_sbs = dict(phi=phi_k, g=g_k, log_w=sbs.log_weights(phi_k, g_k))
-    if trace is not None:
-        att = att_trace.beam(recs[0].buf, lineage, length, trace.Kout)
-        att_trace.publish(model, att, k)
+    _publish_trace(model, recs, lineage, length, k)
     return seq, seq_logp
 
 
@@ -474,51 +488,23 @@ def constrained_beam_search_steps(model, make_decoder, B, V1, L, opt, dev):
     if V1 < 2:
         raise ValueError("opt['constraints'] needs a vocabulary")
     tables = ops.cbs_tables(req.words, req.ncons, V1, S, dev)
-    trace = getattr(model, '_trace_req', None)
-    if trace is not None:
-        from . import att_trace
-        make_decoder, recs = att_trace.recording(make_decoder, L)
-    dec = make_decoder(SB)
-    N = B * SB
-    temperature = float(opt.get('temperature', 1))
-    unk = unk_column(model, opt, V1)
-    flags, bad = _decode_flags(model, opt, dev)
-    logp_rows = torch.zeros(L, N, V1, dtype=_f32, device=dev)
-    parent = torch.zeros(L, B, SB, dtype=torch.int32, device=dev)
-    token = torch.zeros(L, B, SB, dtype=torch.long, device=dev)
     score = torch.zeros(L, B, SB, dtype=_f32, device=dev)
     ended = torch.zeros(L, B, SB, dtype=torch.uint8, device=dev)
     valid = torch.zeros(L, B, SB, dtype=torch.uint8, device=dev)
     sums = torch.zeros(2, B, SB, dtype=_f32, device=dev)
-    st = stream_ptr()
-    it = torch.zeros(B, dtype=torch.long, device=dev)                       # BOS
-    logits = dec.step(0, it, 1)
-    check(lib.capmi_beam_logsoftmax(ptr(logits), ptr(logp_rows[0]), B, V1, 1.0, unk, st), 'beam_logsoftmax')
-    rows, cur = B, 1
-    for t in range(L):
-        ops.cbs_select(logp_rows[t, :rows], sums[t & 1], tables, b, S, force_end=t == L - 1,
-                       out=(parent[t], token[t], score[t], sums[(t + 1) & 1], ended[t], valid[t]))
-        if t == L - 1:
-            break
-        dec.reorder(parent[t], cur)
-        logits = dec.step(t + 1, token[t].reshape(N), SB)
-        check(lib.capmi_beam_logsoftmax(ptr(logits), ptr(logp_rows[t + 1]), N, V1, temperature, unk, st), 'beam_logsoftmax')
-        if flags:
-            check(lib.capmi_decode_constrain(ptr(logp_rows[t + 1]), N, V1, ptr(token[t]), 1, flags, ptr(bad), bad.numel(), None, 0,
-                                             t + 1, 0, st), 'decode_constrain')
-        rows, cur = N, SB
+
+    def select(t, logp_t, cur, parent_t, token_t):
+        ops.cbs_select(logp_t, sums[t & 1], tables, b, S, force_end=t == L - 1,
+                       out=(parent_t, token_t, score[t], sums[(t + 1) & 1], ended[t], valid[t]))
+    logp_rows, parent, token, recs = _search_loop(model, make_decoder, B, SB, V1, L, opt, dev, select)
     seq, lineage, length, state, p = ops.cbs_finalize(parent, token, score, ended, valid, tables.ncons, b, S,
                                                       length_divisors(opt.get('length_penalty', ''), L, dev))
-    live = (lineage >= 0).unsqueeze(2)
-    gathered = logp_rows.gather(1, lineage.clamp(min=0).long().unsqueeze(2).expand(L, B, V1))
-    seq_logp = torch.where(live, gathered, gathered.new_zeros(())).permute(1, 0, 2).contiguous()
+    seq_logp = seq_logp_from_lineage(logp_rows, lineage)
     cbs.publish(model, state, tables.ncons, p)
     if isinstance(opt.get('_cbs_tables'), dict):                            # test hook: the per-step tables and rows
         opt['_cbs_tables'].update(parent=parent, token=token, score=score, ended=ended, valid=valid, logp_rows=logp_rows,
                                   lineage=lineage, length=length, words=req.words, ncons=req.ncons, b=b, S=S)
-    if trace is not None:
-        att = att_trace.beam(recs[0].buf, lineage, length, trace.Kout)
-        att_trace.publish(model, att, 1)
+    _publish_trace(model, recs, lineage, length, 1)
     return seq, seq_logp
 
 
@@ -539,9 +525,7 @@ def diverse_beam_search_steps(model, make_decoder, B, V1, L, opt, dev):
     bd = beam_size // G
     assert sample_n == 1 or sample_n == bd, 'when beam search, sample_n == 1 or beam search'
     W, n = G * bd, B * bd
-    temperature = float(opt.get('temperature', 1))
-    unk = unk_column(model, opt, V1)
-    flags, bad = _decode_flags(model, opt, dev)
+    normalise = _normaliser(model, opt, V1, dev)
     trace = getattr(model, '_trace_req', None)
     if trace is not None:
         # the returned caption of an image is the best beam of group 0 (CaptionModel.py:207-208 concatenates the groups in order):
@@ -561,8 +545,7 @@ def diverse_beam_search_steps(model, make_decoder, B, V1, L, opt, dev):
     st = stream_ptr()
     it0 = torch.zeros(B, dtype=torch.long, device=dev)                      # BOS
     for g in range(G):                                                      # logprobs_table = [init_logprobs.clone() ...] (:136)
-        logits = decs[g].step(0, it0, 1)
-        check(lib.capmi_beam_logsoftmax(ptr(logits), ptr(cur_logp[g]), B, V1, 1.0, unk, st), 'beam_logsoftmax')
+        normalise(0, decs[g].step(0, it0, 1), cur_logp[g], B, None)
     logp_rows[0, :B] = cur_logp[0, :B]
     for t in range(L + G - 1):
         for g in range(G):
@@ -588,11 +571,7 @@ def diverse_beam_search_steps(model, make_decoder, B, V1, L, opt, dev):
             if last:
                 continue
             decs[g].reorder(lparent[g, lt], cur)
-            logits = decs[g].step(lt + 1, ltoken[g, lt].reshape(n), bd)
-            check(lib.capmi_beam_logsoftmax(ptr(logits), ptr(cur_logp[g]), n, V1, temperature, unk, st), 'beam_logsoftmax')
-            if flags:
-                check(lib.capmi_decode_constrain(ptr(cur_logp[g]), n, V1, ptr(ltoken[g, lt]), 1, flags, ptr(bad), bad.numel(), None,
-                                                 0, lt + 1, 0, st), 'decode_constrain')
+            normalise(lt + 1, decs[g].step(lt + 1, ltoken[g, lt].reshape(n), bd), cur_logp[g], n, ltoken[g, lt])
             logp_rows[lt + 1].view(B, G, bd, V1)[:, g] = cur_logp[g].view(B, bd, V1)
     # image-major global tables for the shared assembly: beam j of group g is column g*bd + j
     offs = (torch.arange(G, device=dev, dtype=torch.int32) * bd).view(G, 1, 1, 1)

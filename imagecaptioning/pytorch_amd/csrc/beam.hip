@@ -1,23 +1,13 @@
 // Device-side batched beam search for the UpDown decoder (gfx950).
 // Reference: AttModel._sample_beam (AttModel.py:218-256) + CaptionModel.beam_search
 // (CaptionModel.py:35-209, group_size 1).  See include/capmi.h for what each kernel replaces.
-#include "host_common.h"
+#include "search_common.h"
 
 using namespace capmi;
 
 namespace {
 
 constexpr int SEL_T = 1024;
-constexpr int BD_MAX = 16;
-
-struct Cand {
-    float v;
-    int i;
-};
-__device__ __forceinline__ Cand best_of(Cand a, Cand b) {
-    if (b.v > a.v || (b.v == a.v && b.i < a.i)) return b;
-    return a;
-}
 
 // one workgroup per image.  ONE pass over the cur*V1 candidates (~46 per thread at beam 5, V1 = 9488): every thread keeps
 // the best BDP >= bd of its own candidates in a sorted register list (compare-exchange chain, fully unrolled: no dynamic
@@ -39,7 +29,7 @@ __global__ __launch_bounds__(SEL_T) void beam_select_kernel(const float *__restr
     const float *lp = logp + (size_t)b * cur * V1;
     Cand top[BDP];
 #pragma unroll
-    for (int q = 0; q < BDP; ++q) top[q] = Cand{-INFINITY, 0x7fffffff};
+    for (int q = 0; q < BDP; ++q) top[q] = Cand{-INFINITY, NO_CAND};
     for (int r = 0; r < cur; ++r) {
         const float base = sums[(size_t)b * bd + r];
         const float *row = lp + (size_t)r * V1;
@@ -82,7 +72,7 @@ __global__ __launch_bounds__(SEL_T) void beam_select_kernel(const float *__restr
         if (top[0].i == s_win) {                          // flat indices are unique: exactly one thread pops
 #pragma unroll
             for (int q = 0; q + 1 < BDP; ++q) top[q] = top[q + 1];
-            top[BDP - 1] = Cand{-INFINITY, 0x7fffffff};
+            top[BDP - 1] = Cand{-INFINITY, NO_CAND};
         }
         __syncthreads();                                  // s_win / s_v reused next round
     }
@@ -247,28 +237,9 @@ __global__ __launch_bounds__(FIN_T) void beam_finalize_kernel(const int32_t *__r
     if (tid < sample_n) {
         const int rows = B * sample_n, row = b * sample_n + tid;
         const int c = s_out[tid];
-        int len = 0;
-        float pv = 0.f;
-        if (c >= 0) {
-            const int t = c / bd;
-            int jj = c - t * bd;
-            len = t + 1;
-            pv = (float)s_key[c];
-            for (int s = t; s >= 0; --s) {
-                const size_t o = ((size_t)s * B + b) * bd + jj;
-                seq[(size_t)row * L + s] = token[o];
-                int par = parent[o];
-                par = par < 0 ? 0 : (par >= bd ? bd - 1 : par);
-                lineage[(size_t)s * rows + row] = s == 0 ? b : b * bd + par;
-                jj = par;
-            }
-        }
-        for (int s = len; s < L; ++s) {
-            seq[(size_t)row * L + s] = 0;
-            lineage[(size_t)s * rows + row] = -1;
-        }
-        length[row] = len;
-        p[row] = pv;
+        const int t = c >= 0 ? c / bd : -1;                // no finished candidate: an empty path
+        length[row] = backtrack_path(parent, token, nullptr, B, bd, L, b, t, c - t * bd, seq + (size_t)row * L, lineage + row, rows);
+        p[row] = c >= 0 ? (float)s_key[c] : 0.f;
     }
 }
 

@@ -14,14 +14,12 @@
 //                     the listed tokens v with s | sat(v) == s' -- and the b best of both, ranked by counting.
 // Order everywhere: larger score first, equal scores by the lower flat index row * V1 + token.  Plain stores, no float atomics:
 // bit-identical from run to run.
-#include "host_common.h"
+#include "search_common.h"
 
 using namespace capmi;
 
 namespace {
 
-constexpr int ROW_T = 256;
-constexpr int CHUNK = 4 * ROW_T;           // floats of a row-kernel workgroup: one 16-byte piece per thread
 constexpr int MERGE_T = 256;
 constexpr int C_MAX = 4, W_MAX = 8, NW = C_MAX * W_MAX;
 constexpr int SB_MAX = 64;                 // slots per image
@@ -30,26 +28,12 @@ constexpr int CAND_MAX = 4096;             // S = 1: b * b <= 4096; S > 1 (b <= 
 constexpr int FIN_T = 256;
 constexpr int FIN_MAX = 4096;              // L * S * b finished candidates of an image
 
-struct Cand {
-    float v;
-    int i;
-};
-__device__ __forceinline__ bool before(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
-__device__ __forceinline__ Cand best_of(Cand a, Cand b) { return before(b.v, b.i, a.v, a.i) ? b : a; }
-__device__ __forceinline__ void order2(Cand &a, Cand &b) {
-    if (before(b.v, b.i, a.v, a.i)) {
-        const Cand t = a;
-        a = b;
-        b = t;
-    }
-}
 __device__ __forceinline__ int clamp_ncons(int n, int S) {
     n = n < 0 ? 0 : (n > C_MAX ? C_MAX : n);
     while ((1 << n) > S) --n;
     return n;
 }
 
-// scratch layout: cand_s [rows][C][b] float, then cand_tok [rows][C][b] int32; rows = B * cur
 __global__ __launch_bounds__(ROW_T) void cbs_row_kernel(const float *__restrict__ logp, const float *__restrict__ sums,
                                                         const int32_t *__restrict__ words, const int32_t *__restrict__ ncons,
                                                         int cur, int b, int S, int V1, int C, float *__restrict__ cand_s,
@@ -62,7 +46,6 @@ __global__ __launch_bounds__(ROW_T) void cbs_row_kernel(const float *__restrict_
     const float base = sums[(size_t)img * S * b + slot];
     if (!(base > -INFINITY)) return;                       // an empty slot is never a source (the merge tests the same value)
     const int state = cur == 1 ? 0 : slot / b;
-    const int lane = tid & 63, wid = tid >> 6;
     const float *lp = logp + (size_t)row * V1;
     const int a = (int)((reinterpret_cast<uintptr_t>(lp) >> 2) & 3);       // floats from the 16-byte grid to the row's start
     if (tid < CHUNK / 32) s_out[tid] = 0u;
@@ -89,32 +72,10 @@ __global__ __launch_bounds__(ROW_T) void cbs_row_kernel(const float *__restrict_
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const float s = base + x[k];
-        c[k] = (((out4 >> k) & 1u) || !(s > -INFINITY)) ? Cand{-INFINITY, 0x7fffffff} : Cand{s, v0 + k};
+        c[k] = (((out4 >> k) & 1u) || !(s > -INFINITY)) ? Cand{-INFINITY, NO_CAND} : Cand{s, v0 + k};
     }
-    order2(c[0], c[1]); order2(c[2], c[3]); order2(c[0], c[2]); order2(c[1], c[3]); order2(c[1], c[2]);
     const size_t o0 = ((size_t)row * C + chunk) * b;
-    for (int round = 0; round < b; ++round) {
-        Cand best = c[0];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) best = best_of(best, Cand{__shfl_xor(best.v, o, 64), __shfl_xor(best.i, o, 64)});
-        if (lane == 0) {
-            s_v[wid] = best.v;
-            s_i[wid] = best.i;
-        }
-        __syncthreads();
-        Cand t{s_v[0], s_i[0]};
-#pragma unroll
-        for (int i = 1; i < ROW_T / 64; ++i) t = best_of(t, Cand{s_v[i], s_i[i]});
-        if (tid == 0) {
-            cand_s[o0 + round] = t.v;
-            cand_tok[o0 + round] = t.i;
-        }
-        if (t.v > -INFINITY && c[0].i == t.i) {            // token indices are unique: exactly one thread pops
-            c[0] = c[1]; c[1] = c[2]; c[2] = c[3];
-            c[3] = Cand{-INFINITY, 0x7fffffff};
-        }
-        __syncthreads();                                   // s_v / s_i are rewritten next round
-    }
+    select_rounds(c, b, s_v, s_i, cand_s + o0, cand_tok + o0);
 }
 
 __global__ __launch_bounds__(MERGE_T) void cbs_merge_kernel(const float *__restrict__ logp, const float *__restrict__ sums,
@@ -144,7 +105,7 @@ __global__ __launch_bounds__(MERGE_T) void cbs_merge_kernel(const float *__restr
     if (tid == 0) s_n = 0;
     for (int e = tid; e < n; e += MERGE_T) {
         l_s[e] = -INFINITY;
-        l_i[e] = 0x7fffffff;
+        l_i[e] = NO_CAND;
     }
     // phase A: per row of the state, the b largest of its C chunk lists
     for (int j = 0; j < nrows; ++j) {
@@ -157,17 +118,7 @@ __global__ __launch_bounds__(MERGE_T) void cbs_merge_kernel(const float *__restr
             st_i[e] = cand_tok[src + e];
         }
         __syncthreads();
-        for (int e = tid; e < per_row; e += MERGE_T) {
-            const float s = st_s[e];
-            if (!(s > -INFINITY)) continue;
-            const int tok = st_i[e];
-            int rank = 0;
-            for (int e2 = 0; e2 < per_row; ++e2) rank += before(st_s[e2], st_i[e2], s, tok) ? 1 : 0;
-            if (rank < b) {
-                l_s[j * b + rank] = s;
-                l_i[j * b + rank] = r * V1 + tok;
-            }
-        }
+        best_of_lists<MERGE_T>(st_s, st_i, 1, per_row, b, l_s + j * b, l_i + j * b, r * V1);
     }
     __syncthreads();
     // phase B: the moving candidates, enumerated.  A token listed twice (one set twice, or two sets) is taken at its first listing.
@@ -190,17 +141,13 @@ __global__ __launch_bounds__(MERGE_T) void cbs_merge_kernel(const float *__restr
     }
     __syncthreads();
     // phase C: the b largest, by counting
-    int mine = 0;
-    for (int e = tid; e < n; e += MERGE_T) {
-        const float s = l_s[e];
-        if (!(s > -INFINITY)) continue;
-        ++mine;
-        const int fl = l_i[e];
-        int rank = 0;
-        for (int e2 = 0; e2 < n; ++e2) rank += before(l_s[e2], l_i[e2], s, fl) ? 1 : 0;
-        if (rank < b) {
-            const size_t o = (size_t)img * SB + tgt * b + rank;
-            const int par = fl / V1, tok = fl - par * V1;
+    const size_t o0 = (size_t)img * SB + tgt * b;
+    best_of_candidates<MERGE_T>(
+        l_s, l_i, n, b, &s_n,
+        [&](int rank, int e) {
+            const size_t o = o0 + rank;
+            const float s = l_s[e];
+            const int fl = l_i[e], par = fl / V1, tok = fl - par * V1;
             const bool end = tok == 0 || force_end;
             parent[o] = par;
             token[o] = tok;
@@ -208,20 +155,16 @@ __global__ __launch_bounds__(MERGE_T) void cbs_merge_kernel(const float *__restr
             next_sums[o] = end ? s - 1000.f : s;           // as capmi_beam_select
             ended[o] = end ? 1 : 0;
             valid[o] = 1;
-        }
-    }
-    if (mine) atomicAdd(&s_n, mine);                       // an integer count: the order of arrival does not show
-    __syncthreads();
-    const int nvalid = s_n;
-    if (tid < b && tid >= nvalid) {
-        const size_t o = (size_t)img * SB + tgt * b + tid;
-        parent[o] = 0;
-        token[o] = 0;
-        score[o] = -INFINITY;
-        next_sums[o] = -INFINITY;
-        ended[o] = 0;
-        valid[o] = 0;
-    }
+        },
+        [&](int slot) {
+            const size_t o = o0 + slot;
+            parent[o] = 0;
+            token[o] = 0;
+            score[o] = -INFINITY;
+            next_sums[o] = -INFINITY;
+            ended[o] = 0;
+            valid[o] = 0;
+        });
 }
 
 // one workgroup per image: every recorded (ended and valid) candidate gets the key (class, penalised score, step, slot), the
@@ -275,34 +218,15 @@ __global__ __launch_bounds__(FIN_T) void cbs_finalize_kernel(const int32_t *__re
     }
     if (tid == 0) {
         const int c = s_c[0];
-        int len = 0, st = 0;
-        float pv = 0.f;
-        if (c >= 0) {
-            const int t = c / SB;
-            int jj = c - t * SB;
-            len = t + 1;
-            st = jj / b;
-            pv = (float)s_key[0];
-            for (int s = t; s >= 0; --s) {
-                const size_t o = ((size_t)s * B + img) * SB + jj;
-                seq[(size_t)img * L + s] = token[o];
-                int par = parent[o];
-                par = par < 0 ? 0 : (par >= SB ? SB - 1 : par);
-                lineage[(size_t)s * B + img] = s == 0 ? img : img * SB + par;
-                jj = par;
-            }
-        }
-        for (int s = len; s < L; ++s) {
-            seq[(size_t)img * L + s] = 0;
-            lineage[(size_t)s * B + img] = -1;
-        }
-        length[img] = len;
-        state_out[img] = st;
-        score_out[img] = pv;
+        const int t = c >= 0 ? c / SB : -1;                // nothing recorded: an empty path
+        const int slot = c - t * SB;
+        length[img] = backtrack_path(parent, token, nullptr, B, SB, L, img, t, slot, seq + (size_t)img * L, lineage + img, B);
+        state_out[img] = c >= 0 ? slot / b : 0;
+        score_out[img] = c >= 0 ? (float)s_key[0] : 0.f;
     }
 }
 
-inline int chunks_of(int V1) { return (V1 + 3 + CHUNK - 1) / CHUNK; }      // + 3: the row may start 3 floats into its first piece
+constexpr int LEAD = 3;                    // a row may start 3 floats into its first 16-byte piece
 inline bool shape_ok(int B, int b, int S) {
     return B > 0 && b > 0 && S > 0 && S <= 16 && (S & (S - 1)) == 0 && (long long)S * b <= SB_MAX;
 }
@@ -311,10 +235,7 @@ inline bool shape_ok(int B, int b, int S) {
 
 extern "C" {
 
-int64_t capmi_cbs_scratch_bytes(int B, int cur, int b, int V1) {
-    if (B <= 0 || cur <= 0 || b <= 0 || V1 <= 0) return 0;
-    return (int64_t)B * cur * chunks_of(V1) * b * 8;
-}
+int64_t capmi_cbs_scratch_bytes(int B, int cur, int b, int V1) { return chunk_lists_bytes(B, cur, b, V1, LEAD); }
 
 int capmi_cbs_select(const float *logp, const float *sums, const int32_t *words, const int32_t *ncons, int B, int cur, int b, int S,
                      int V1, int force_end, void *scratch, int64_t scratch_bytes, int32_t *parent, int64_t *token, float *score,
@@ -322,19 +243,17 @@ int capmi_cbs_select(const float *logp, const float *sums, const int32_t *words,
     if (!logp || !sums || !words || !ncons || !scratch || !parent || !token || !score || !next_sums || !ended || !valid)
         return CAPMI_EINVAL;
     if (!shape_ok(B, b, S) || V1 <= 0 || (cur != 1 && cur != S * b)) return CAPMI_EINVAL;
-    const int C = chunks_of(V1);
+    const int C = chunks_of(V1, LEAD);
+    ChunkLists cand;
     if ((long long)B * cur > 0x7fffffffLL || B > 65535 || C > 65535 || (long long)C * b > STAGE_MAX ||
         (long long)SB_MAX * V1 > 0x7fffffffLL || (reinterpret_cast<uintptr_t>(logp) & 3))
         return CAPMI_EINVAL;
-    if (scratch_bytes < capmi_cbs_scratch_bytes(B, cur, b, V1) || (reinterpret_cast<uintptr_t>(scratch) & 3)) return CAPMI_EINVAL;
-    const size_t n_cand = (size_t)B * cur * C * b;
-    float *cand_s = static_cast<float *>(scratch);
-    int *cand_tok = reinterpret_cast<int *>(cand_s + n_cand);
+    if (!chunk_lists(scratch, scratch_bytes, B, cur, b, V1, LEAD, &cand)) return CAPMI_EINVAL;
     hipLaunchKernelGGL(cbs_row_kernel, dim3(B * cur, C), dim3(ROW_T), 0, (hipStream_t)stream, logp, sums, words, ncons, cur, b, S,
-                       V1, C, cand_s, cand_tok);
+                       V1, C, cand.s, cand.tok);
     CAPMI_CHECK_LAUNCH();
-    hipLaunchKernelGGL(cbs_merge_kernel, dim3(S, B), dim3(MERGE_T), 0, (hipStream_t)stream, logp, sums, words, ncons, cand_s,
-                       cand_tok, cur, b, S, V1, C, force_end, parent, token, score, next_sums, ended, valid);
+    hipLaunchKernelGGL(cbs_merge_kernel, dim3(S, B), dim3(MERGE_T), 0, (hipStream_t)stream, logp, sums, words, ncons, cand.s,
+                       cand.tok, cur, b, S, V1, C, force_end, parent, token, score, next_sums, ended, valid);
     CAPMI_CHECK_LAUNCH();
     return 0;
 }

@@ -3,7 +3,7 @@
 // noise on phi, each parent's children conditioned on having the parent's perturbed value as their maximum -- returns bd distinct
 // sequences distributed as a sample without replacement from the model.  See include/capmi.h for the arithmetic.
 //
-// A step is two launches:
+// A step is two launches (the chunk-list scheme of search_common.h):
 //   sbs_row_kernel    one workgroup per (search row, chunk of 1024 tokens): s = phi + logp + Gumbel for the chunk -- ONE Philox
 //                     quad or one 16-byte load of injected noise per thread, the four values never leave its registers -- and
 //                     the chunk's bd largest s, in order, to scratch.  B*cur*ceil(V1/1024) workgroups: 500 .. 5000 at the
@@ -12,38 +12,20 @@
 //                     conditional transform is monotone in s within a row, so nothing else can be kept), the transform on those
 //                     cur*bd candidates, and the bd largest results.
 // Both rank by counting (value descending, then the lower token / flat index), so the result does not depend on any arrival
-// order: plain stores, no atomics, bit-identical from run to run.
-#include "host_common.h"
+// order: plain stores, no float atomics, bit-identical from run to run.
+#include "search_common.h"
 
 using namespace capmi;
 
 namespace {
 
-constexpr int BD_MAX = 16;                 // = beam.hip
-constexpr int ROW_T = 256;
-constexpr int CHUNK = 4 * ROW_T;           // tokens of a row-kernel workgroup: one quad per thread
 constexpr int MERGE_T = 256;               // >= BD_MAX * BD_MAX: one thread per transformed candidate
 constexpr int MERGE_LDS = 48 * 1024;       // the chunk lists of as many rows as fit are staged at once
 constexpr uint64_t SBS_STREAM = 0x73627300ull;      // "sbs": the high counter word, apart from the sampling kernels' streams
 
-struct Cand {
-    float v;
-    int i;
-};
-__device__ __forceinline__ bool before(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
-__device__ __forceinline__ Cand best_of(Cand a, Cand b) { return before(b.v, b.i, a.v, a.i) ? b : a; }
-__device__ __forceinline__ void order2(Cand &a, Cand &b) {
-    if (before(b.v, b.i, a.v, a.i)) {
-        const Cand t = a;
-        a = b;
-        b = t;
-    }
-}
-
 // log(1 - exp(d)) for d <= 0 without the cancellation of log1p(-exp(d)) near d = 0
 __device__ __forceinline__ float log1mexp(float d) { return d > -0.6931472f ? logf(-expm1f(d)) : log1pf(-expf(d)); }
 
-// scratch layout: cand_s [rows][C][bd] float, then cand_tok [rows][C][bd] int32; rows = B * cur, C = ceil(V1 / CHUNK)
 __global__ __launch_bounds__(ROW_T) void sbs_row_kernel(const float *__restrict__ logp, const float *__restrict__ phi,
                                                         const uint8_t *__restrict__ alive, const float *__restrict__ gumbel,
                                                         uint64_t seed, uint32_t offset, const uint64_t *__restrict__ epoch,
@@ -53,7 +35,6 @@ __global__ __launch_bounds__(ROW_T) void sbs_row_kernel(const float *__restrict_
     __shared__ int s_i[ROW_T / 64];
     const int row = blockIdx.x, chunk = blockIdx.y;
     if (!alive[row]) return;                               // an ended hypothesis has one candidate, made by the merge
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int q = chunk * ROW_T + threadIdx.x, v0 = 4 * q;
     const float base = phi[row];
     const float *lp = logp + (size_t)row * V1;
@@ -81,34 +62,12 @@ __global__ __launch_bounds__(ROW_T) void sbs_row_kernel(const float *__restrict_
 #pragma unroll
         for (int k = 0; k < 4; ++k) gn[k] = gumbel_u32(o[k]);
     }
-    // the thread's four candidates, best first; a -inf log-prob (a decoding constraint, or a column past V1) stays -inf
+    // the thread's four candidates; a -inf log-prob (a decoding constraint, or a column past V1) stays -inf and keeps its token
     Cand c[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) c[k] = Cand{x[k] == -INFINITY ? -INFINITY : (base + x[k]) + gn[k], v0 + k};
-    order2(c[0], c[1]); order2(c[2], c[3]); order2(c[0], c[2]); order2(c[1], c[3]); order2(c[1], c[2]);
     const size_t o0 = ((size_t)row * C + chunk) * bd;
-    for (int round = 0; round < bd; ++round) {
-        Cand best = c[0];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) best = best_of(best, Cand{__shfl_xor(best.v, o, 64), __shfl_xor(best.i, o, 64)});
-        if (lane == 0) {
-            s_v[wid] = best.v;
-            s_i[wid] = best.i;
-        }
-        __syncthreads();
-        Cand t{s_v[0], s_i[0]};
-#pragma unroll
-        for (int i = 1; i < ROW_T / 64; ++i) t = best_of(t, Cand{s_v[i], s_i[i]});
-        if (threadIdx.x == 0) {
-            cand_s[o0 + round] = t.v;
-            cand_tok[o0 + round] = t.i;
-        }
-        if (c[0].i == t.i) {                               // token indices are unique: exactly one thread pops
-            c[0] = c[1]; c[1] = c[2]; c[2] = c[3];
-            c[3] = Cand{-INFINITY, 0x7fffffff};
-        }
-        __syncthreads();                                   // s_v / s_i are rewritten next round
-    }
+    select_rounds(c, bd, s_v, s_i, cand_s + o0, cand_tok + o0);
 }
 
 __global__ __launch_bounds__(MERGE_T) void sbs_merge_kernel(const float *__restrict__ logp, const float *__restrict__ phi,
@@ -123,8 +82,8 @@ __global__ __launch_bounds__(MERGE_T) void sbs_merge_kernel(const float *__restr
     __shared__ int r_tok[BD_MAX * BD_MAX];
     __shared__ float t_g[BD_MAX * BD_MAX];                 // the transformed candidates
     __shared__ float t_ph[BD_MAX * BD_MAX];
-    __shared__ long long t_flat[BD_MAX * BD_MAX];
-    __shared__ uint8_t t_ok[BD_MAX * BD_MAX];
+    __shared__ int t_flat[BD_MAX * BD_MAX];                // row * V1 + token < 2^23: C * bd * 8 <= MERGE_LDS bounds cur * V1
+    __shared__ int s_n;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int per_row = C * bd, n = cur * bd;
     float *l_s = reinterpret_cast<float *>(smem);
@@ -133,6 +92,7 @@ __global__ __launch_bounds__(MERGE_T) void sbs_merge_kernel(const float *__restr
         r_s[tid] = -INFINITY;
         r_tok[tid] = 0;
     }
+    if (tid == 0) s_n = 0;
     // phase A: per row, the bd largest of its C chunk lists (rows_fit rows at a time in LDS)
     for (int j0 = 0; j0 < cur; j0 += rows_fit) {
         const int nr = min(rows_fit, cur - j0), cnt = nr * per_row;
@@ -141,20 +101,10 @@ __global__ __launch_bounds__(MERGE_T) void sbs_merge_kernel(const float *__restr
         for (int e = tid; e < cnt; e += MERGE_T) {
             const bool live = alive[(size_t)b * cur + j0 + e / per_row] != 0;      // an ended row's lists were never written
             l_s[e] = live ? cand_s[src + e] : -INFINITY;
-            l_tok[e] = live ? cand_tok[src + e] : 0x7fffffff;
+            l_tok[e] = live ? cand_tok[src + e] : NO_CAND;
         }
         __syncthreads();
-        for (int e = tid; e < cnt; e += MERGE_T) {
-            const float s = l_s[e];
-            if (s == -INFINITY) continue;
-            const int jr = e / per_row, tok = l_tok[e], lo = jr * per_row;
-            int rank = 0;
-            for (int e2 = lo; e2 < lo + per_row; ++e2) rank += before(l_s[e2], l_tok[e2], s, tok) ? 1 : 0;
-            if (rank < bd) {
-                r_s[(j0 + jr) * bd + rank] = s;
-                r_tok[(j0 + jr) * bd + rank] = tok;
-            }
-        }
+        best_of_lists<MERGE_T>(l_s, l_tok, nr, per_row, bd, r_s + j0 * bd, r_tok + j0 * bd, 0);
     }
     __syncthreads();
     // phase B: the conditional transform on the cur * bd survivors
@@ -183,44 +133,33 @@ __global__ __launch_bounds__(MERGE_T) void sbs_merge_kernel(const float *__restr
                 gt = gj - fmaxf(0.f, u) - log1pf(expf(-fabsf(u)));
             }
         }
-        t_g[tid] = gt;
-        t_flat[tid] = (long long)j * V1 + tok;
-        t_ok[tid] = ok ? 1 : 0;
+        t_g[tid] = ok ? gt : -INFINITY;                    // what is no candidate: {-inf, NO_CAND}
+        t_flat[tid] = ok ? j * V1 + tok : NO_CAND;
         t_ph[tid] = ph;
         r_tok[tid] = tok;                                  // read by this thread alone from here on
     }
     __syncthreads();
     // phase C: the bd largest, ties to the lower flat index
-    int nvalid = 0;
-    if (tid < bd)
-        for (int e = 0; e < n; ++e) nvalid += t_ok[e];
-    if (tid < n && t_ok[tid]) {
-        const float gt = t_g[tid];
-        const long long fl = t_flat[tid];
-        int rank = 0;
-        for (int e = 0; e < n; ++e) {
-            const float g2 = t_g[e];
-            rank += (t_ok[e] && (g2 > gt || (g2 == gt && t_flat[e] < fl))) ? 1 : 0;
-        }
-        if (rank < bd) {
+    best_of_candidates<MERGE_T>(
+        t_g, t_flat, n, bd, &s_n,
+        [&](int rank, int e) {                             // e == tid: one candidate per thread
             const size_t o = (size_t)b * bd + rank;
-            const int tok = r_tok[tid];
-            const bool was = alive[(size_t)b * cur + tid / bd] != 0;
-            parent[o] = tid / bd;
+            const int tok = r_tok[e];
+            const bool was = alive[(size_t)b * cur + e / bd] != 0;
+            parent[o] = e / bd;
             token[o] = tok;
-            phi_out[o] = t_ph[tid];
-            g_out[o] = gt;
+            phi_out[o] = t_ph[e];
+            g_out[o] = t_g[e];
             alive_out[o] = (was && tok != 0 && !force_end) ? 1 : 0;
-        }
-    }
-    if (tid < bd && tid >= nvalid) {                       // fewer than bd finite candidates (not visible from the arguments)
-        const size_t o = (size_t)b * bd + tid;
-        parent[o] = 0;
-        token[o] = 0;
-        phi_out[o] = -INFINITY;
-        g_out[o] = -INFINITY;
-        alive_out[o] = 0;
-    }
+        },
+        [&](int slot) {                                    // fewer than bd finite candidates (not visible from the arguments)
+            const size_t o = (size_t)b * bd + slot;
+            parent[o] = 0;
+            token[o] = 0;
+            phi_out[o] = -INFINITY;
+            g_out[o] = -INFINITY;
+            alive_out[o] = 0;
+        });
 }
 
 __global__ void sbs_backtrack_kernel(const int32_t *__restrict__ parent, const int64_t *__restrict__ token,
@@ -229,33 +168,15 @@ __global__ void sbs_backtrack_kernel(const int32_t *__restrict__ parent, const i
     const int rows = B * bd, row = blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= rows) return;
     const int b = row / bd;
-    int jj = row - b * bd, len = L;
-    for (int s = L - 1; s >= 0; --s) {
-        const size_t o = ((size_t)s * B + b) * bd + jj;
-        seq[(size_t)row * L + s] = token[o];
-        if (!alive[o]) len = s + 1;                        // the earliest step of the path that is not alive is its end
-        int par = parent[o];
-        par = par < 0 ? 0 : (par >= bd ? bd - 1 : par);
-        lineage[(size_t)s * rows + row] = s == 0 ? b : b * bd + par;
-        jj = par;
-    }
-    for (int s = len; s < L; ++s) {
-        seq[(size_t)row * L + s] = 0;
-        lineage[(size_t)s * rows + row] = -1;
-    }
-    length[row] = len;
+    // the whole length: the earliest step of the path that is not alive is its end
+    length[row] = backtrack_path(parent, token, alive, B, bd, L, b, L - 1, row - b * bd, seq + (size_t)row * L, lineage + row, rows);
 }
-
-inline int chunks_of(int V1) { return (V1 + CHUNK - 1) / CHUNK; }
 
 }  // namespace
 
 extern "C" {
 
-int64_t capmi_sbs_scratch_bytes(int B, int cur, int bd, int V1) {
-    if (B <= 0 || cur <= 0 || bd <= 0 || V1 <= 0) return 0;
-    return (int64_t)B * cur * chunks_of(V1) * bd * 8;
-}
+int64_t capmi_sbs_scratch_bytes(int B, int cur, int bd, int V1) { return chunk_lists_bytes(B, cur, bd, V1, 0); }
 
 int capmi_sbs_select(const float *logp, const float *phi, const float *g, const uint8_t *alive, const float *gumbel,
                      uint64_t seed, uint32_t offset, int B, int cur, int bd, int V1, int step0, int force_end, void *scratch,
@@ -264,21 +185,19 @@ int capmi_sbs_select(const float *logp, const float *phi, const float *g, const 
     if (!logp || !phi || !g || !alive || !scratch || !parent || !token || !phi_out || !g_out || !alive_out) return CAPMI_EINVAL;
     if (B <= 0 || cur <= 0 || cur > bd || bd > BD_MAX || V1 <= 0 || (long long)cur * V1 < bd || (step0 && cur != 1))
         return CAPMI_EINVAL;
-    const int C = chunks_of(V1);
+    const int C = chunks_of(V1, 0);
     const long long per_row = (long long)C * bd;
+    ChunkLists cand;
     if ((long long)B * cur > 0x7fffffffLL || C > 65535 || per_row * 8 > MERGE_LDS) return CAPMI_EINVAL;
-    if (scratch_bytes < capmi_sbs_scratch_bytes(B, cur, bd, V1) || (reinterpret_cast<uintptr_t>(scratch) & 3)) return CAPMI_EINVAL;
-    const size_t n_cand = (size_t)B * cur * per_row;
-    float *cand_s = static_cast<float *>(scratch);
-    int *cand_tok = reinterpret_cast<int *>(cand_s + n_cand);
+    if (!chunk_lists(scratch, scratch_bytes, B, cur, bd, V1, 0, &cand)) return CAPMI_EINVAL;
     const int vec = (V1 % 4 == 0 && aligned16(logp, gumbel)) ? 1 : 0;
     hipLaunchKernelGGL(sbs_row_kernel, dim3(B * cur, C), dim3(ROW_T), 0, (hipStream_t)stream, logp, phi, alive, gumbel, seed,
-                       offset, gumbel ? nullptr : rng_epoch(), bd, V1, C, vec, cand_s, cand_tok);
+                       offset, gumbel ? nullptr : rng_epoch(), bd, V1, C, vec, cand.s, cand.tok);
     CAPMI_CHECK_LAUNCH();
     int rows_fit = (int)(MERGE_LDS / (per_row * 8));
     if (rows_fit > cur) rows_fit = cur;
     hipLaunchKernelGGL(sbs_merge_kernel, dim3(B), dim3(MERGE_T), (size_t)rows_fit * per_row * 8, (hipStream_t)stream, logp, phi,
-                       g, alive, cand_s, cand_tok, cur, bd, V1, C, rows_fit, step0, force_end, parent, token, phi_out, g_out,
+                       g, alive, cand.s, cand.tok, cur, bd, V1, C, rows_fit, step0, force_end, parent, token, phi_out, g_out,
                        alive_out);
     CAPMI_CHECK_LAUNCH();
     return 0;

@@ -1278,7 +1278,13 @@ def df_finalize(count_keys, counts, keys, vals, meta):
 
 
 # ---- stochastic beam search (beam.stochastic_beam_search_steps; capmi.h capmi_sbs_*, sbs.hip) ------------------------------------
-SBS_BD_MAX = 16       # = BD_MAX of beam.hip / sbs.hip
+SBS_BD_MAX = 16       # = BD_MAX of csrc/search_common.h, the one definition beam.hip and sbs.hip share
+
+
+def _chunk_list_scratch(scratch_bytes, B, cur, b, V1, dev):
+    """the chunk lists between the row kernel and the merge kernel of a select step (csrc/search_common.h) -> (buffer, its bytes)"""
+    nbytes = max(int(scratch_bytes(B, cur, b, V1)), 4)
+    return torch.empty(nbytes // 4, dtype=torch.int32, device=dev), nbytes
 
 
 def sbs_select(logp, phi, g, alive, bd, step0=False, force_end=False, gumbel=None, seed=0, offset=0, out=None):
@@ -1299,8 +1305,7 @@ def sbs_select(logp, phi, g, alive, bd, step0=False, force_end=False, gumbel=Non
                torch.empty(B, bd, dtype=_f32, device=dev), torch.empty(B, bd, dtype=_f32, device=dev),
                torch.empty(B, bd, dtype=torch.uint8, device=dev))
     _chk(*out)
-    nbytes = max(int(lib.capmi_sbs_scratch_bytes(B, cur, bd, V1)), 4)
-    scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+    scratch, nbytes = _chunk_list_scratch(lib.capmi_sbs_scratch_bytes, B, cur, bd, V1, dev)
     check(lib.capmi_sbs_select(ptr(logp), ptr(phi), ptr(g), ptr(alive), ptr(gumbel), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                int(offset) & 0xFFFFFFFF, B, cur, int(bd), V1, int(bool(step0)), int(bool(force_end)), ptr(scratch),
                                nbytes, *[ptr(t) for t in out], stream_ptr()), 'capmi_sbs_select')
@@ -1373,8 +1378,7 @@ def cbs_select(logp, sums, tables, b, S, force_end=False, out=None):
         e = lambda dt: torch.empty(B, SB, dtype=dt, device=dev)      # noqa: E731
         out = (e(torch.int32), e(torch.long), e(_f32), e(_f32), e(torch.uint8), e(torch.uint8))
     _chk(*out)
-    nbytes = max(int(lib.capmi_cbs_scratch_bytes(B, cur, b, V1)), 4)
-    scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+    scratch, nbytes = _chunk_list_scratch(lib.capmi_cbs_scratch_bytes, B, cur, b, V1, dev)
     check(lib.capmi_cbs_select(ptr(logp), ptr(sums), ptr(tables.words), ptr(tables.ncons), B, cur, b, S, V1, int(bool(force_end)),
                                ptr(scratch), nbytes, *[ptr(t) for t in out], stream_ptr()), 'capmi_cbs_select')
     return out

@@ -16,7 +16,7 @@ After such a call ``model.last_sbs = {'phi', 'g', 'log_w'}``, each [B, k] on the
 """
 import torch
 
-K_MAX = 16            # BD_MAX of sbs.hip / beam.hip
+K_MAX = 16            # BD_MAX of csrc/search_common.h
 
 
 def wanted(opt):

@@ -132,6 +132,16 @@ def test_select_against_the_replay(b, V1):
     print('cbs_select b=%d V1=%d: %d cases, %d needed a later seed, worst |score err| %.3g' % (b, V1, n, later, worst))
 
 
+def test_select_with_long_chunk_lists():
+    """V1 = 52999 at b = 5: 52 chunks, so a row's staged lists hold 260 entries -- more than one pass of the merge kernel's 256
+    threads, where V1 = 1031 gives 10 -- and, V1 being odd, rows that start off the 16-byte grid.  B = 1, one constraint: 10 rows"""
+    b, V1, C, W = 5, 52999, 1, 3
+    for variant in ('plain', 'inf'):
+        i, inputs, ref = _fixture(1, b, C, W, V1, variant)
+        err = _compare(_run_select(inputs, b, 1 << C, False), ref, (1, b, C, W, V1, variant, i))
+        print('cbs_select b=%d V1=%d %s: seed index %d, worst |score err| %.3g' % (b, V1, variant, i, err))
+
+
 def test_select_order_ties_and_errors():
     """equal scores go to the lower flat index; a token in two sets moves once, to the state with both bits; bad tables are refused"""
     from imagecaptioning.pytorch_amd import _lib, ops
