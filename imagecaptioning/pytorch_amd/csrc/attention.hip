@@ -1056,6 +1056,7 @@ int capmi_attention_bwd_batched_ws(const float *d_ctx_all, int ld_dctx, const fl
                                    int R, float *dw_partial, void *stream) {
     if (!d_ctx_all || !att_h_all || !alpha_all || !d_e_all || !p_att || !w || !d_att || !d_p_att || !d_b) return CAPMI_EINVAL;
     if (!d_w && !dw_partial) return CAPMI_EINVAL;
+    if (T <= 0 || n <= 0 || (size_t)T * n * KCH * sizeof(float) > 64 * 1024) return CAPMI_EINVAL;   // attn_datt_kernel's LDS
     hipStream_t st = (hipStream_t)stream;
     const int N = N_stride > 0 ? N_stride : B * n;
     hipLaunchKernelGGL(attn_datt_kernel, dim3(B, (K + KCH - 1) / KCH, (R + DATT_T - 1) / DATT_T), dim3(DATT_T),

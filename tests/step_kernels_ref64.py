@@ -1,5 +1,5 @@
 """Float64 restatements, on the CPU, of the per-step kernels (LSTM / maxout / att2in2 / adaatt cells, additive attention forward,
-backward and time-batched pass) plus the case tables and input builders that test_step_kernels_host.py and
+backward and time-batched pass, the same three for AdaAtt's sentinel attention) plus the case tables and input builders that test_step_kernels_host.py and
 test_step_kernels_gpu.py share.  Nothing of the package is imported here: the operand semantics are those of include/capmi.h and of
 the Python models (AttModel.py, NewFCModel.py, Att2in2Model.py, AdaAttModel.py); backward is torch.autograd on the forward."""
 import torch
@@ -355,3 +355,153 @@ def maxout_rows():
     rows += [('maxout', c[0], c[1], 1, 0, 'bih', 200 + i) for i, c in enumerate(MAXOUT_BWD)]
     rows += [('adaattmo', c[0], c[1], c[3], 0, c[4], 300 + i) for i, c in enumerate(ADAATT) if c[2]]
     return rows
+
+
+# ------------------------------------------------------------------------------------------------ sentinel attention (AdaAtt)
+def sentinel_fwd(fre, hoe, fr, ho, p_att, att, mask, w, b, tile, img):
+    """AdaAtt_attention.forward (AttModel.py:565-602) from the two projections fr_e / ho_e on, for rows whose image is img[r]:
+    pi [M,K+1] (sentinel first), ctx [M,R] (residual ho included), scores e [M,K+1], the dropped tanh tile hA [M,K+1,A]"""
+    hA = torch.tanh(torch.cat([fre.unsqueeze(1), p_att[img]], 1) + hoe.unsqueeze(1))
+    if tile is not None:
+        hA = hA * tile
+    e = hA @ w + b
+    pi = torch.softmax(e, 1)
+    if mask is not None:
+        m = mask[img]
+        pi = pi * torch.cat([m[:, :1], m], 1)                 # the sentinel takes the mask of region 0
+        pi = pi / pi.sum(1, keepdim=True)
+    ctx = (pi.unsqueeze(2) * torch.cat([fr.unsqueeze(1), att[img]], 1)).sum(1) + ho
+    return pi, ctx, e, hA
+
+
+def sentinel_case(T, B, n, K, A, R, fre_splits, hoe_splits, flags, seed):
+    """float32 operands of one sentinel-attention case over T steps of N = B * n image-major rows + the float64 forward, its autograd
+    backward and the time-batched results.  fre / hoe come as `splits` slabs [S, T*N*A + pad] (+ bias) or, with splits == 0, as one
+    finished buffer (slab 0).  flags: mask, tile, hpad, hodd, nobias; noout and off:X only concern the caller."""
+    fl = _flags(flags)
+    g = gen(seed)
+    N, K1 = B * n, K + 1
+    M = T * N
+    img = (torch.arange(M) % N) // n
+    pad = 3 if 'hodd' in fl else (8 if 'hpad' in fl else 0)
+    rnd = lambda *s: torch.randn(*s, generator=g).float()       # noqa: E731
+    d = {'N': N, 'img': img, 'fre_stride': M * A + pad, 'hoe_stride': M * A + pad}
+    for k, s in (('fre', fre_splits), ('hoe', hoe_splits)):
+        S_ = max(s, 1)
+        d[k + '_slabs'] = (torch.randn(S_, M * A + pad, generator=g) / S_ ** 0.5).float()
+        d[k + '_bias'] = rnd(A) if (s > 0 and 'nobias' not in fl) else None
+    d.update(fr=rnd(T, N, R), ho=rnd(T, N, R), p_att=rnd(B, K, A), att=rnd(B, K, R),
+             w=(torch.randn(A, generator=g) * (2.0 / A ** 0.5)).float(), b=rnd(1), d_ctx=rnd(T, N, R), mask=None, tile=None)
+    if 'mask' in fl:
+        lens = torch.randint(1, K + 1, (B,), generator=g)
+        lens[0] = 1                                           # an image with ONE unmasked region
+        lens[B - 1] = K
+        d['mask'] = (torch.arange(K).unsqueeze(0) < lens.unsqueeze(1)).float()
+    if 'tile' in fl:
+        d['tile'] = (torch.rand(T, N, K1, A, generator=g) < 0.5).float() * 2
+    x = {}
+    for k in ('fre', 'hoe'):
+        v = d64(d[k + '_slabs'])[:, :M * A].sum(0).view(M, A)
+        if d[k + '_bias'] is not None:
+            v = v + d64(d[k + '_bias'])
+        x[k] = v
+    x.update(fr=d64(d['fr']).view(M, R), p_att=d64(d['p_att']), att=d64(d['att']), w=d64(d['w']), b=d64(d['b']))
+    ref_in = {k: v.clone() for k, v in x.items()}
+    x = {k: v.requires_grad_(True) for k, v in x.items()}
+    tile = None if d['tile'] is None else d64(d['tile']).view(M, K1, A)
+    pi, ctx, e, hA = sentinel_fwd(x['fre'], x['hoe'], x['fr'], d64(d['ho']).view(M, R), x['p_att'], x['att'], d64(d['mask']), x['w'],
+                                  x['b'], tile, img)
+    e.retain_grad()
+    (ctx * d64(d['d_ctx']).view(M, R)).sum().backward()
+    # alpha_net's weight gradient, one row per (image, score row): what dw_partial receives
+    dw_rows = torch.einsum('tbnk,tbnka->bka', e.grad.view(T, B, n, K1), hA.detach().view(T, B, n, K1, A))
+    d.update(fre=ref_in['fre'].view(T, N, A), hoe=ref_in['hoe'].view(T, N, A), pi=pi.detach().view(T, N, K1),
+             ctx=ctx.detach().view(T, N, R), d_e=e.grad.view(T, N, K1), d_hoe=x['hoe'].grad.view(T, N, A),
+             d_fre=x['fre'].grad.view(T, N, A), d_fr=x['fr'].grad.view(T, N, R), d_att=x['att'].grad, d_p_att=x['p_att'].grad,
+             dw_rows=dw_rows, d_w=x['w'].grad, d_b=x['b'].grad)
+    return d
+
+
+# The last column of a sentinel row names its arm twice: `key=value` tokens, which test_step_kernels_host.py recomputes from the
+# row with a mirror of the dispatcher's arithmetic, then ' | ' and words.  Forward keys: rpb (rows per workgroup), ragged (last chunk
+# of an image shorter: 0/1), padwg (B % 8 != 0: padding workgroups), vecA / vecR (16-byte score / context arm), G (region groups of
+# the context phase), idle (threads of the 512 outside the G * R/4 working ones), trips (trips of G * 6 regions a group makes),
+# passes (score passes of 8 waves x 4 rows), lanes (softmax entries per lane), ftrips / htrips (8-slab trips of fr_e / ho_e).
+# forward: (B, n, K, A, R, fre_splits, hoe_splits, flags, arm), one step
+SENT_FWD = [
+    (3, 2, 7, 12, 36, 0, 0, '', 'ftrips=0 htrips=0 rpb=1 padwg=1 vecA=1 vecR=1 G=4 | both projections finished, copied to fre_out / hoe_out'),
+    (3, 2, 7, 12, 36, 1, 1, '', 'ftrips=1 htrips=1 G=4 trips=1 passes=1 lanes=1 | the product shape: one slab each + bias + rows out'),
+    (3, 2, 7, 12, 36, 3, 3, 'hpad', 'ftrips=1 htrips=1 | 3 slabs, partly filled trip, slab stride N * A + 8'),
+    (3, 2, 7, 12, 36, 8, 8, '', 'ftrips=1 htrips=1 | 8 slabs: exactly one trip'),
+    (3, 2, 7, 12, 36, 9, 9, '', 'ftrips=2 htrips=2 | 9 slabs: one into the second trip'),
+    (3, 2, 7, 12, 36, 17, 17, '', 'ftrips=3 htrips=3 | 17 slabs: third trip'),
+    (3, 2, 7, 12, 36, 3, 9, '', 'ftrips=1 htrips=2 | the two operands at different slab counts'),
+    (3, 2, 7, 12, 36, 0, 3, '', 'ftrips=0 htrips=1 | fr_e finished, ho_e as slabs'),
+    (3, 2, 7, 12, 36, 8, 0, '', 'ftrips=1 htrips=0 | fr_e as slabs, ho_e finished'),
+    (3, 2, 7, 12, 36, 3, 3, 'hodd', 'ftrips=1 vecA=1 | slab stride N * A + 3: the slab loads are scalar, the score arm stays 16-byte'),
+    (3, 2, 7, 12, 36, 3, 1, 'nobias', 'ftrips=1 htrips=1 | slabs without biases'),
+    (3, 2, 7, 12, 36, 3, 3, 'noout', 'ftrips=1 htrips=1 | fre_out / hoe_out NULL'),
+    (3, 2, 7, 10, 36, 1, 1, '', 'vecA=0 vecR=1 | A % 4 != 0: scalar score loop'),
+    (3, 2, 7, 12, 36, 1, 1, 'off:p_att', 'vecA=0 vecR=1 | p_att one float off'),
+    (3, 2, 7, 12, 36, 1, 1, 'off:w', 'vecA=0 vecR=1 | w one float off'),
+    (3, 2, 7, 12, 36, 1, 1, 'tile off:tile', 'vecA=0 vecR=1 | the tile mask one float off'),
+    (3, 2, 7, 12, 31, 1, 1, '', 'vecA=1 vecR=0 G=1 | R % 4 != 0: scalar context loop'),
+    (2, 3, 7, 12, 2052, 1, 1, '', 'vecA=1 vecR=0 G=1 | R > 2048: scalar context loop, five columns per thread'),
+    (3, 2, 7, 12, 36, 1, 1, 'off:att', 'vecA=1 vecR=0 | att one float off'),
+    (3, 2, 7, 12, 36, 1, 1, 'off:fr', 'vecA=1 vecR=0 | fr one float off'),
+    (3, 2, 7, 12, 36, 1, 1, 'off:ho', 'vecA=1 vecR=0 | ho one float off'),
+    (3, 2, 7, 12, 36, 1, 1, 'off:ctx', 'vecA=1 vecR=0 | ctx one float off'),
+    (2, 3, 7, 12, 516, 1, 1, '', 'vecR=1 G=3 idle=125 | R = 516: 129 quads, three groups'),
+    (2, 3, 7, 12, 1000, 1, 1, '', 'vecR=1 G=2 idle=12 | R = 1000, the configured width: 250 quads, two groups, 12 threads idle'),
+    (2, 3, 7, 12, 2048, 1, 1, '', 'vecR=1 G=1 idle=0 | R = 2048: one group, no LDS partials'),
+    (2, 3, 1, 12, 36, 1, 1, '', 'G=1 trips=1 | K = 1 clamps G to 1'),
+    (2, 3, 2, 12, 36, 1, 1, '', 'G=2 trips=1 | K = 2 clamps G to 2'),
+    (2, 3, 3, 12, 36, 1, 1, '', 'G=3 trips=1 | K = 3 clamps G to 3'),
+    (103, 5, 7, 12, 36, 1, 1, '', 'rpb=3 ragged=1 G=2 padwg=1 | 515 rows: three per workgroup (3, 2), G = 2 by rows'),
+    (2, 3, 24, 12, 36, 1, 1, '', 'G=4 trips=1 | K = 24 = G * 6: one full trip'),
+    (2, 3, 25, 12, 36, 1, 1, '', 'G=4 trips=2 | K = 25: one region into the second trip'),
+    (2, 3, 31, 12, 36, 1, 1, '', 'passes=1 lanes=1 | K + 1 = 32: one full score pass'),
+    (2, 3, 32, 12, 36, 1, 1, '', 'passes=2 lanes=1 | K + 1 = 33: one score row into the second pass'),
+    (2, 3, 64, 12, 36, 1, 1, '', 'passes=3 lanes=2 | K + 1 = 65: lane 0 takes two softmax entries'),
+    (52, 5, 7, 12, 36, 1, 1, '', 'rpb=2 ragged=1 G=4 padwg=1 | 260 rows: two per workgroup, ragged last chunk (2, 2, 1)'),
+    (225, 8, 7, 12, 36, 1, 1, '', 'rpb=8 ragged=0 G=2 padwg=1 | 1800 rows: NMAX = 8 per workgroup'),
+    (16, 3, 7, 12, 36, 1, 1, '', 'rpb=1 padwg=0 | B a multiple of 8: no padding workgroup'),
+    (5, 2, 9, 12, 36, 1, 1, 'mask', 'vecA=1 vecR=1 | mask, small: one image with a single unmasked region'),
+    (5, 2, 36, 512, 512, 1, 1, 'mask', 'vecA=1 vecR=1 G=4 trips=2 passes=2 | mask at K = 36, A = 512, R = 512'),
+    (3, 2, 7, 12, 36, 1, 1, 'tile', 'vecA=1 | tile drop through 16-byte mask loads'),
+    (3, 2, 7, 10, 36, 1, 1, 'tile', 'vecA=0 | tile drop through scalar mask loads'),
+    (52, 5, 7, 12, 36, 3, 3, 'tile mask', 'rpb=2 ragged=1 vecA=1 | tile drop and mask with two rows per workgroup'),
+]
+# backward keys: T, rpb, ragged, coltrips (trips of 4 x 64 columns of the d_pi dot product), apasses (passes of the 512 threads over A),
+# kmod (K % 12, the region group CG of the score-gradient loop).  backward: (T, B, n, K, A, R, flags, arm)
+SENT_BWD = [
+    (1, 3, 2, 7, 12, 36, '', 'T=1 rpb=1 coltrips=1 apasses=1 | one step'),
+    (3, 3, 2, 7, 12, 36, 'tile', 'T=3 rpb=1 | three steps (blockIdx.y), the tile mask of every step'),
+    (1, 103, 5, 7, 12, 36, '', 'rpb=2 ragged=1 | 515 rows round DOWN to two per workgroup, ragged last chunk'),
+    (2, 103, 5, 7, 12, 36, 'tile mask', 'T=2 rpb=2 ragged=1 | the same with tile drop, mask and two steps'),
+    (1, 256, 8, 7, 12, 36, '', 'rpb=8 ragged=0 | 2048 rows: NMAX = 8 per workgroup'),
+    (1, 3, 2, 7, 12, 256, '', 'coltrips=1 | R = 256: exactly one trip of 4 x 64 columns'),
+    (1, 3, 2, 7, 12, 257, '', 'coltrips=2 | R = 257: one column into the second trip'),
+    (1, 2, 3, 7, 12, 1000, '', 'coltrips=4 | R = 1000, the configured width'),
+    (1, 3, 2, 7, 516, 36, '', 'apasses=2 | A = 516: four columns into the second pass of the threads'),
+    (1, 3, 2, 11, 12, 36, '', 'kmod=11 | K = 11: one below the region group'),
+    (1, 3, 2, 12, 12, 36, '', 'kmod=0 | K = 12: exactly one region group'),
+    (1, 3, 2, 13, 12, 36, 'tile', 'kmod=1 | K = 13: one region into the second group, tile drop'),
+    (1, 5, 2, 9, 12, 36, 'mask', 'rpb=1 | pi of a masked forward: zero weights and a single-region image'),
+    (1, 3, 2, 7, 12, 36, 'off:att off:fr off:d_ctx', 'rpb=1 | operands one float off: the kernel is scalar, nothing may change'),
+]
+# batched keys: kchunks / kfill (chunks of KCH = 12 regions, K % 12), rblocks (column blocks of 128), rows (T * n), trips4 / trips8 (the
+# 4-row trips of sentinel_datt_kernel, the 8-row trips of sentinel_dpatt_kernel), threads (of sentinel_dpatt_kernel), sumtrips (trips
+# of sum_all_kernel: 8 x 1024 values each).  batched: (T, B, n, K, A, R, flags, arm)
+SENT_BATCHED = [
+    (1, 3, 1, 11, 12, 127, '', 'kchunks=1 kfill=11 rblocks=1 rows=1 trips4=1 trips8=1 threads=256 | one row: every clamped index is 0'),
+    (3, 3, 1, 12, 12, 128, '', 'kchunks=1 kfill=0 rblocks=1 rows=3 trips4=1 | exactly one chunk and one column block'),
+    (2, 2, 2, 13, 20, 129, '', 'kchunks=2 kfill=1 rblocks=2 rows=4 trips4=1 | exactly one trip of 4 rows'),
+    (5, 3, 1, 7, 12, 36, '', 'rows=5 trips4=2 trips8=1 | one row into the second 4-row trip'),
+    (7, 3, 1, 7, 12, 36, '', 'rows=7 trips8=1 | one below the 8-row trip'),
+    (4, 3, 2, 7, 12, 36, '', 'rows=8 trips4=2 trips8=1 | exactly one 8-row trip'),
+    (3, 2, 3, 7, 12, 36, 'tile', 'rows=9 trips4=3 trips8=2 | one row into the second 8-row trip; tile drop over steps and rows'),
+    (1, 2, 2, 7, 512, 36, '', 'threads=512 | A = 512: 512-thread workgroups'),
+    (2, 3, 2, 7, 516, 36, 'tile', 'threads=512 | A = 516: second pass of the threads'),
+    (3, 50, 3, 20, 12, 36, '', 'sumtrips=2 kchunks=2 | T * N * (K + 1) = 9450 > 8192: second trip of sum_all_kernel'),
+]

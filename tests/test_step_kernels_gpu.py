@@ -3,7 +3,9 @@
 tables there say which branch a row is meant to reach.  Metric and bounds are those of test_kernels_gpu.py: rel_err =
 max|got - ref| / max|ref| with cell forward 2e-6, cell backward 5e-6, attention forward 5e-6, attention backward 2e-5; the planted
 row of extremes of every cell case is left out of that maximum (its 1e4 entries would set the scale) and compared elementwise as
-|got - ref| <= tol * (1 + |ref|) instead."""
+|got - ref| <= tol * (1 + |ref|) instead.  The sentinel attention of AdaAtt (three entry points, each fed float64-derived inputs so that
+no kernel absorbs another's error) holds the plain attention's bounds unwidened; every output of those tests is NaN-filled and
+followed by a guard tail that the launch must leave alone."""
 import numpy as np
 import pytest
 import torch
@@ -480,3 +482,249 @@ def test_layernorm_fwd(dev, M, D):
     check('mean', mean.view(M, 1), mu, CELL_FWD)
     check('inv', inv.view(M, 1), 1.0 / (sd + eps), CELL_FWD)
     check('y', y, a.double() * (xd - mu) / (sd + eps) + b.double(), CELL_BWD)
+
+
+# ------------------------------------------------------------------------------------------------ sentinel attention (AdaAtt)
+# Each of the three entry points alone against S.sentinel_case: the backward is fed the float32 rounding of the float64 pi, the
+# time-batched pass those of pi and d_e, so no kernel's error is absorbed by the next.  Bounds: ATT_FWD for pi, ctx, fre_out, hoe_out,
+# ATT_BWD for every gradient -- those of the plain attention, the same operation over K instead of K + 1 rows.
+GUARD = 777.0
+
+
+class Out:
+    """an output: NaN where the kernel must write, a guard value in the 8 floats behind it (and in the float before it with off,
+    where the output starts one float past a 16-byte boundary)"""
+    def __init__(self, dev, *shape, off=False):
+        cnt = int(np.prod(shape))
+        self.buf = torch.full((cnt + 9,), GUARD, device=dev)
+        assert self.buf.data_ptr() % 16 == 0
+        self.lo, self.hi = (1 if off else 0), (1 if off else 0) + cnt
+        self.buf[self.lo:self.hi] = float('nan')
+        self.t = self.buf[self.lo:self.hi].view(shape)
+
+    @property
+    def p(self):
+        return self.t.data_ptr()
+
+    def guarded(self):
+        torch.cuda.synchronize()
+        b = self.buf.cpu()
+        return bool((b[:self.lo] == GUARD).all()) and bool((b[self.hi:] == GUARD).all()) and b[self.hi:].numel() >= 8
+
+    def untouched(self):
+        return self.guarded() and bool(torch.isnan(self.t).all())
+
+
+def check_out(name, out, ref, tol):
+    check(name, out.t, ref, tol)
+    assert out.guarded(), name + ': wrote outside its buffer'
+
+
+def tile_drop(mask=None, p=0.0, seed=0, row0=0):
+    import ctypes
+    td = L().TileDrop()
+    td.mask, td.p, td.seed, td.row0 = ptr(mask), float(p), int(seed), int(row0)
+    return ctypes.byref(td)
+
+
+def sent_fwd(dev, t, drop, pi, ctx, fo, ho_, fs, hs, strides, B, n, K, A, R):
+    return L().lib.capmi_sentinel_attention_fwd(ptr(t['fre_slabs']), fs, strides[0], ptr(t.get('fre_bias')), ptr(t['hoe_slabs']), hs, strides[1],
+                                                ptr(t.get('hoe_bias')), fo and fo.p, ho_ and ho_.p, ptr(t['fr']), ptr(t['ho']), ptr(t['p_att']),
+                                                ptr(t['att']), ptr(t.get('mask')), ptr(t['w']), ptr(t['b']), drop, pi.p, ctx.p, B, n, K, A, R,
+                                                L().stream_ptr())
+
+
+@pytest.mark.parametrize('i', range(len(S.SENT_FWD)))
+def test_sentinel_fwd(dev, i):
+    B, n, K, A, R, fs, hs, flags, _ = S.SENT_FWD[i]
+    fl = set(flags.split())
+    d = S.sentinel_case(1, B, n, K, A, R, fs, hs, flags, seed=1000 + i)
+    N = d['N']
+    t = {k: put(dev, d[k], 'off:' + k in fl) for k in ('fre_slabs', 'hoe_slabs', 'fre_bias', 'hoe_bias', 'fr', 'ho', 'p_att', 'att', 'w', 'b',
+                                                         'mask', 'tile')}
+    pi, ctx = Out(dev, N, K + 1), Out(dev, N, R, off='off:ctx' in fl)
+    fo, ho_ = (None, None) if 'noout' in fl else (Out(dev, N, A), Out(dev, N, A))
+    L().check(sent_fwd(dev, t, tile_drop(t['tile']), pi, ctx, fo, ho_, fs, hs, (d['fre_stride'], d['hoe_stride']), B, n, K, A, R), 'sentinel_fwd')
+    if fo is not None:
+        check_out('fre_out', fo, d['fre'][0], ATT_FWD)
+        check_out('hoe_out', ho_, d['hoe'][0], ATT_FWD)
+    check_out('pi', pi, d['pi'][0], ATT_FWD)
+    check_out('ctx', ctx, d['ctx'][0], ATT_FWD)
+    if d['mask'] is not None:      # dead regions get exactly nothing; the single-region image splits its weight between sentinel and region 0
+        got = pi.t.cpu()
+        m = d['mask'][d['img']]
+        assert float(got[torch.cat([m[:, :1], m], 1) == 0].abs().max()) == 0.0
+        assert float((got[d['img'] == 0, :2].sum(1) - 1).abs().max()) < 1e-6
+
+
+@pytest.mark.parametrize('i', range(len(S.SENT_BWD)))
+def test_sentinel_bwd(dev, i):
+    T, B, n, K, A, R, flags, _ = S.SENT_BWD[i]
+    fl = set(flags.split())
+    d = S.sentinel_case(T, B, n, K, A, R, 0, 0, flags, seed=1100 + i)
+    N = d['N']
+    src = dict(d, fre=d['fre'].float(), hoe=d['hoe'].float(), pi=d['pi'].float())        # fre / hoe were float32 to begin with: exact
+    t = {k: put(dev, src[k], 'off:' + k in fl) for k in ('d_ctx', 'fr', 'fre', 'hoe', 'pi', 'p_att', 'att', 'w', 'tile')}
+    de, dh, df, dfr = Out(dev, T, N, K + 1), Out(dev, T, N, A), Out(dev, T, N, A), Out(dev, T, N, R)
+    L().check(L().lib.capmi_sentinel_attention_bwd(ptr(t['d_ctx']), ptr(t['fr']), ptr(t['fre']), ptr(t['hoe']), ptr(t['pi']), ptr(t['p_att']),
+                                                   ptr(t['att']), ptr(t['w']), tile_drop(t['tile']), de.p, dh.p, df.p, dfr.p, T, B, n, K, A, R,
+                                                   L().stream_ptr()), 'sentinel_bwd')
+    for name, out in (('d_e', de), ('d_hoe', dh), ('d_fre', df), ('d_fr', dfr)):
+        check_out(name, out, d[name], ATT_BWD)
+
+
+def d_b_bound(count, d_e):
+    """d_b = sum(d_e) is zero in exact arithmetic; sum_all_kernel adds ceil(count / 1024) values per thread, then a ten-level tree:
+    (that run length + 16) roundings of 2^-24 each, relative to sum|d_e|"""
+    return (-(-count // 1024) + 16) * 2.0 ** -24 * float(d_e.double().abs().sum())
+
+
+@pytest.mark.parametrize('i', range(len(S.SENT_BATCHED)))
+def test_sentinel_bwd_batched(dev, i):
+    T, B, n, K, A, R, flags, _ = S.SENT_BATCHED[i]
+    d = S.sentinel_case(T, B, n, K, A, R, 0, 0, flags, seed=1200 + i)
+    src = dict(d, fre=d['fre'].float(), hoe=d['hoe'].float(), pi=d['pi'].float(), d_e=d['d_e'].float())
+    t = {k: put(dev, src[k]) for k in ('d_ctx', 'fre', 'hoe', 'pi', 'd_e', 'p_att', 'w', 'tile')}
+    assert float(d['d_b'].abs()) < 1e-12
+    for partial in (True, False):      # dw_partial rows, then d_w by atomicAdd (any order: compared by bound only)
+        o_att, o_patt, o_w, o_b, o_rows = Out(dev, B, K, R), Out(dev, B, K, A), Out(dev, A), Out(dev, 1), Out(dev, B, K + 1, A)
+        L().check(L().lib.capmi_sentinel_attention_bwd_batched(ptr(t['d_ctx']), ptr(t['fre']), ptr(t['hoe']), ptr(t['pi']), ptr(t['d_e']),
+                                                               ptr(t['p_att']), ptr(t['w']), tile_drop(t['tile']), o_att.p, o_patt.p,
+                                                               None if partial else o_w.p, o_b.p, T, B, n, K, A, R,
+                                                               o_rows.p if partial else None, L().stream_ptr()), 'sentinel_bwd_batched')
+        check_out('d_att', o_att, d['d_att'], ATT_BWD)
+        check_out('d_p_att', o_patt, d['d_p_att'], ATT_BWD)
+        if partial:
+            check_out('dw_partial', o_rows, d['dw_rows'], ATT_BWD)
+            e = rel_err(o_rows.t.double().cpu().sum((0, 1)), d['d_w'])
+            print('column sum of dw_partial rel_err %.2e (bound %.0e)' % (e, ATT_BWD))
+            assert e < ATT_BWD and o_w.untouched()
+        else:
+            check_out('d_w (atomic)', o_w, d['d_w'], ATT_BWD)
+            assert o_rows.untouched()
+        bound = d_b_bound(T * B * n * (K + 1), src['d_e'])
+        got = abs(float(o_b.t.cpu()))
+        print('|d_b| %.2e (bound %.2e)' % (got, bound))
+        assert got <= bound and o_b.guarded()
+
+
+def sent_chain(dev, t, T, B, n, K, A, R, tile=None, p=0.0, seed=0):
+    """forward of every step (row0 = step * N), backward and time-batched pass of all steps, each fed by the one before"""
+    N = B * n
+    o = {k: Out(dev, *s) for k, s in (('pi', (T, N, K + 1)), ('ctx', (T, N, R)), ('d_e', (T, N, K + 1)), ('d_hoe', (T, N, A)), ('d_fre', (T, N, A)),
+                                      ('d_fr', (T, N, R)), ('d_att', (B, K, R)), ('d_p_att', (B, K, A)), ('dw_rows', (B, K + 1, A)), ('d_b', (1,)))}
+    lib = L().lib
+    for s in range(T):
+        drop = tile_drop(None if tile is None else tile[s], p, seed, s * N)
+        L().check(lib.capmi_sentinel_attention_fwd(ptr(t['fre'][s]), 0, 0, None, ptr(t['hoe'][s]), 0, 0, None, None, None, ptr(t['fr'][s]),
+                                                   ptr(t['ho'][s]), ptr(t['p_att']), ptr(t['att']), None, ptr(t['w']), ptr(t['b']), drop,
+                                                   o['pi'].t[s].data_ptr(), o['ctx'].t[s].data_ptr(), B, n, K, A, R, L().stream_ptr()), 'fwd')
+    drop = tile_drop(tile, p, seed, 0)
+    L().check(lib.capmi_sentinel_attention_bwd(ptr(t['d_ctx']), ptr(t['fr']), ptr(t['fre']), ptr(t['hoe']), o['pi'].p, ptr(t['p_att']),
+                                               ptr(t['att']), ptr(t['w']), drop, o['d_e'].p, o['d_hoe'].p, o['d_fre'].p, o['d_fr'].p, T, B, n, K,
+                                               A, R, L().stream_ptr()), 'bwd')
+    L().check(lib.capmi_sentinel_attention_bwd_batched(ptr(t['d_ctx']), ptr(t['fre']), ptr(t['hoe']), o['pi'].p, o['d_e'].p, ptr(t['p_att']),
+                                                       ptr(t['w']), drop, o['d_att'].p, o['d_p_att'].p, None, o['d_b'].p, T, B, n, K, A, R,
+                                                       o['dw_rows'].p, L().stream_ptr()), 'batched')
+    assert all(v.guarded() for v in o.values())
+    return {k: v.t for k, v in o.items()}
+
+
+# (B, K, A, R): vec draw forward and scalar draw backward; scalar draw of words 1..3 of the 4-tuple; forward rpb = 2 (258 rows)
+@pytest.mark.parametrize('B,K,A,R', [(4, 5, 64, 16), (4, 5, 10, 16), (86, 3, 12, 8)])
+def test_sentinel_philox_row_numbering(dev, B, K, A, R):
+    """p > 0 without a mask at n = 3 rows per image and T = 2 steps.  The draw index is (row, score row, column), so a launch of B * n
+    single-row images with p_att / att repeated per row draws the same bits; there, step by step, the backward kernels expose every
+    bit (d_fre != 0: the sentinel's row, d_p_att != 0: a region's row).  Those bits, injected as a mask, must reproduce the Philox run of
+    all three kernels at (B, n): a wrong row number in any of them, or in the chunks of rpb > 1, draws other bits."""
+    T, n, p, seed = 2, 3, 0.5, 4321
+    N, K1 = B * n, K + 1
+    d = S.sentinel_case(T, B, n, K, A, R, 0, 0, '', seed=1300 + A + B)
+    src = dict(d, fre=d['fre'].float(), hoe=d['hoe'].float())
+    t = {k: put(dev, src[k]) for k in ('fre', 'hoe', 'fr', 'ho', 'p_att', 'att', 'w', 'b', 'd_ctx')}
+    tile = torch.zeros(T, N, K1, A, device=dev)
+    rep = dict(t, p_att=t['p_att'].repeat_interleave(n, 0).contiguous(), att=t['att'].repeat_interleave(n, 0).contiguous())
+    for s in range(T):
+        one = {k: (v if k in ('p_att', 'att', 'w', 'b') else v[s:s + 1].contiguous()) for k, v in rep.items()}
+        N1 = N
+        o = {k: Out(dev, *sh) for k, sh in (('pi', (N1, K1)), ('ctx', (N1, R)), ('d_e', (N1, K1)), ('d_hoe', (N1, A)), ('d_fre', (N1, A)),
+                                            ('d_fr', (N1, R)), ('d_att', (N1, K, R)), ('d_p_att', (N1, K, A)), ('dw', (N1, K1, A)), ('d_b', (1,)))}
+        drop = tile_drop(None, p, seed, s * N)
+        lib = L().lib
+        L().check(lib.capmi_sentinel_attention_fwd(ptr(one['fre']), 0, 0, None, ptr(one['hoe']), 0, 0, None, None, None, ptr(one['fr']),
+                                                   ptr(one['ho']), ptr(one['p_att']), ptr(one['att']), None, ptr(one['w']), ptr(one['b']), drop,
+                                                   o['pi'].p, o['ctx'].p, N1, 1, K, A, R, L().stream_ptr()), 'fwd')
+        L().check(lib.capmi_sentinel_attention_bwd(ptr(one['d_ctx']), ptr(one['fr']), ptr(one['fre']), ptr(one['hoe']), o['pi'].p,
+                                                   ptr(one['p_att']), ptr(one['att']), ptr(one['w']), drop, o['d_e'].p, o['d_hoe'].p, o['d_fre'].p,
+                                                   o['d_fr'].p, 1, N1, 1, K, A, R, L().stream_ptr()), 'bwd')
+        L().check(lib.capmi_sentinel_attention_bwd_batched(ptr(one['d_ctx']), ptr(one['fre']), ptr(one['hoe']), o['pi'].p, o['d_e'].p,
+                                                           ptr(one['p_att']), ptr(one['w']), drop, o['d_att'].p, o['d_p_att'].p, None, o['d_b'].p,
+                                                           1, N1, 1, K, A, R, o['dw'].p, L().stream_ptr()), 'batched')
+        assert all(v.guarded() for v in o.values())
+        tile[s, :, 0] = (o['d_fre'].t != 0).float() * 2
+        tile[s, :, 1:] = (o['d_p_att'].t != 0).float() * 2
+    rate = float((tile != 0).float().mean())
+    assert abs(rate - (1 - p)) < 5 * (p * (1 - p) / tile.numel()) ** 0.5, rate           # five binomial sigmas
+    assert not torch.equal(tile[0], tile[1])
+    drawn = sent_chain(dev, t, T, B, n, K, A, R, p=p, seed=seed)
+    given = sent_chain(dev, t, T, B, n, K, A, R, tile=tile.contiguous())
+    for k in drawn:
+        if k == 'd_b':
+            continue
+        check(k, drawn[k], given[k].double().cpu(), ATT_FWD if k in ('pi', 'ctx') else ATT_BWD)
+    # and the injected run is the float64 forward under those bits
+    ref = S.sentinel_fwd(*(S.d64(src[k]).flatten(0, 1) for k in ('fre', 'hoe', 'fr', 'ho')), S.d64(d['p_att']), S.d64(d['att']), None,
+                         S.d64(d['w']), S.d64(d['b']), tile.double().cpu().flatten(0, 1), d['img'])
+    check('pi vs float64', drawn['pi'].flatten(0, 1), ref[0], ATT_FWD)
+    check('ctx vs float64', drawn['ctx'].flatten(0, 1), ref[1], ATT_FWD)
+
+
+def test_sentinel_refusals(dev):
+    """each refused before any launch: CAPMI_EINVAL and not one output element written"""
+    B, n, K, A, R = 2, 2, 3, 8, 8
+    d = S.sentinel_case(1, B, n, K, A, R, 1, 1, '', seed=1400)
+    N = B * n
+    t = {k: put(dev, d[k]) for k in ('fre_slabs', 'hoe_slabs', 'fre_bias', 'hoe_bias', 'fr', 'ho', 'p_att', 'att', 'w', 'b', 'd_ctx')}
+    st = (d['fre_stride'], d['hoe_stride'])
+    outs = [Out(dev, N, K + 1), Out(dev, N, R), Out(dev, N, A), Out(dev, N, A)]
+    assert sent_fwd(dev, t, tile_drop(None, 1.0, 1, 0), *outs, 1, 1, st, B, n, K, A, R) == L().EINVAL         # p = 1 without a mask
+    assert all(o.untouched() for o in outs)
+    # forward LDS: 1800 rows go eight to a workgroup, and at A = 1024 those need 8 * (2 * 1024 + K + 1) floats > 64 KB
+    Bw, nw, Aw, Rw = 225, 8, 1024, 4
+    z = lambda *s: torch.zeros(*s, device=dev)          # noqa: E731
+    wide = {'fre_slabs': z(Bw * nw, Aw), 'hoe_slabs': z(Bw * nw, Aw), 'fr': z(Bw * nw, Rw), 'ho': z(Bw * nw, Rw), 'p_att': z(Bw, 1, Aw),
+            'att': z(Bw, 1, Rw), 'w': z(Aw), 'b': z(1)}
+    outs = [Out(dev, Bw * nw, 2), Out(dev, Bw * nw, Rw), Out(dev, Bw * nw, Aw), Out(dev, Bw * nw, Aw)]
+    assert sent_fwd(dev, wide, None, *outs, 0, 0, (0, 0), Bw, nw, 1, Aw, Rw) == L().EINVAL
+    assert all(o.untouched() for o in outs)
+    lib = L().lib
+    x = {k: put(dev, d[k].float()) for k in ('fre', 'hoe', 'pi', 'd_e')}
+    bw = [Out(dev, N, K + 1), Out(dev, N, A), Out(dev, N, A), Out(dev, N, R)]
+    assert lib.capmi_sentinel_attention_bwd(ptr(t['d_ctx']), ptr(t['fr']), ptr(x['fre']), ptr(x['hoe']), ptr(x['pi']), ptr(t['p_att']),
+                                            ptr(t['att']), ptr(t['w']), None, *(o.p for o in bw), 65536, B, n, K, A, R,
+                                            L().stream_ptr()) == L().EINVAL                                      # T past the grid's y limit
+    assert all(o.untouched() for o in bw)
+    bt = [Out(dev, B, K, R), Out(dev, B, K, A), Out(dev, A), Out(dev, 1), Out(dev, B, K + 1, A)]
+
+    def batched(T, n_, d_w, rows):
+        return lib.capmi_sentinel_attention_bwd_batched(ptr(t['d_ctx']), ptr(x['fre']), ptr(x['hoe']), ptr(x['pi']), ptr(x['d_e']),
+                                                        ptr(t['p_att']), ptr(t['w']), None, bt[0].p, bt[1].p, d_w, bt[3].p, T, B, n_, K, A, R,
+                                                        rows, L().stream_ptr())
+    assert batched(1366, 1, bt[2].p, bt[4].p) == L().EINVAL              # T * n * 12 floats of pi pass 64 KB of LDS
+    assert batched(1, n, None, None) == L().EINVAL                       # nowhere to put d_w
+    assert all(o.untouched() for o in bt)
+
+
+def test_attention_bwd_batched_refuses_more_rows_than_lds_holds(dev):
+    """T * n * 12 floats of alpha go through LDS: 1366 rows pass 64 KB.  CAPMI_EINVAL before any launch, as the sentinel twin"""
+    T, A, R = 1366, 4, 4
+    z = torch.zeros(T, 4, device=dev)
+    al = torch.ones(T, 1, device=dev)
+    o = [Out(dev, 1, 1, R), Out(dev, 1, 1, A), Out(dev, A), Out(dev, 1), Out(dev, 1, A)]
+    lib = L().lib
+    for d_w, rows in ((o[2].p, None), (None, o[4].p), (o[2].p, o[4].p)):
+        assert lib.capmi_attention_bwd_batched_ws(ptr(z), R, ptr(z), ptr(al), ptr(al), ptr(z), ptr(z), o[0].p, o[1].p, d_w, o[3].p, T, 1, 1, 0, 1,
+                                                  A, R, rows, L().stream_ptr()) == L().EINVAL
+    assert lib.capmi_attention_bwd_batched(ptr(z), R, ptr(z), ptr(al), ptr(al), ptr(z), ptr(z), o[0].p, o[1].p, o[2].p, o[3].p, T, 1, 1, 0, 1, A, R,
+                                           L().stream_ptr()) == L().EINVAL
+    assert all(v.untouched() for v in o)
