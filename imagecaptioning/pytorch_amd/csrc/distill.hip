@@ -2,12 +2,13 @@
 // teacher-forced pass.  No reference counterpart; see include/capmi.h (capmi_distill_loss_fwd / _bwd) for the normative formula and
 // the edge cases.  Forward: one workgroup per (i, t) row reads the student and the teacher row once, in one sweep, then one
 // workgroup folds the masked means in double.  Backward: one workgroup per row reads both rows once and writes the dense gradient
-// once (plain stores: the teacher-forced backward reads it next).
+// once (plain stores: the teacher-forced backward reads it next).  Rows are cut and swept, and the means folded, as row_sweep.h has
+// it; a teacher row is addressed through t_rows, so whether a row pair shares its alignment is decided per row, in the kernel.
 #include <float.h>
 #include <math.h>
 
-#include "capmi_common.h"
-#include "../../../include/capmi.h"
+#include "host_common.h"
+#include "row_sweep.h"
 
 using namespace capmi;
 
@@ -57,16 +58,6 @@ __device__ __forceinline__ void push4(Run &r, f32x4 a, f32x4 b) {
     r.mA = nA, r.mB = nB;
 }
 
-// scalar head up to the 16-byte boundary of `p`, float4 body, scalar tail; everything scalar unless `vec`
-__device__ __forceinline__ void row_split(const void *p, int V1, bool vec, int &head, int &nv) {
-    head = V1, nv = 0;
-    if (vec) {
-        head = (int)(((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) >> 2);
-        head = head < V1 ? head : V1;
-        nv = (V1 - head) >> 2;
-    }
-}
-
 __global__ __launch_bounds__(KD_T) void distill_rows_kernel(const KdArgs a) {
     __shared__ float s_red[32];
     const int row = blockIdx.x, tid = threadIdx.x;
@@ -79,9 +70,7 @@ __global__ __launch_bounds__(KD_T) void distill_rows_kernel(const KdArgs a) {
     const float *ls = a.lp_s + (size_t)row * a.ld_s;
     const float *lt = a.lp_t + ((size_t)i * a.t_rows + t) * a.ld_t;
     const int V1 = a.V1;
-    int head, nv;
-    row_split(ls, V1, ((reinterpret_cast<uintptr_t>(ls) ^ reinterpret_cast<uintptr_t>(lt)) & 15) == 0, head, nv);
-    const int tail = head + 4 * nv;
+    const RowSplit sp = row_split(ls, V1, same16(ls, lt));
     // the target's entry: loaded before the sweep, so its latency hides behind it
     float nll = 0.f;
     if (tid == 0) {
@@ -90,13 +79,14 @@ __global__ __launch_bounds__(KD_T) void distill_rows_kernel(const KdArgs a) {
     }
     const float it = a.inv_tau;
     Run r;
-    for (int q = tid; q < nv; q += KD_T) {
-        const f32x4 x = *reinterpret_cast<const f32x4 *>(ls + head + 4 * q);
-        const f32x4 y = *reinterpret_cast<const f32x4 *>(lt + head + 4 * q);
+    // sweep()'s order, written out: with the payload in lambdas this kernel compiles to other code (by reference x * it is fused
+    // into push4's b - a, an fma with other bits; by value it costs a register)
+    for (int q = tid; q < sp.nv; q += KD_T) {
+        const f32x4 x = ld4(ls + sp.head + 4 * q), y = ld4(lt + sp.head + 4 * q);
         push4(r, x * it, y * it);
     }
-    for (int v = tid; v < head; v += KD_T) push1(r, ls[v] * it, lt[v] * it);
-    for (int v = tail + tid; v < V1; v += KD_T) push1(r, ls[v] * it, lt[v] * it);
+    for (int v = tid; v < sp.head; v += KD_T) push1(r, ls[v] * it, lt[v] * it);
+    for (int v = sp.tail + tid; v < V1; v += KD_T) push1(r, ls[v] * it, lt[v] * it);
     // across the workgroup: the two maxima, then the sums rescaled to them (fixed trees: two runs are bit-equal)
     const float MA = block_max(r.mA, s_red), MB = block_max(r.mB, s_red);
     const float fB = __expf(r.mB - MB);
@@ -114,20 +104,20 @@ __global__ __launch_bounds__(KD_T) void distill_rows_kernel(const KdArgs a) {
 // the masked means of one launch's rows: double accumulators, a fixed order (deterministic).  The global sums take one row per
 // thread (independent loads); the per-sample losses of per_row walk each sample's steps in order.
 __global__ __launch_bounds__(FIN_T) void distill_finish_kernel(const KdArgs a) {
-    __shared__ double s_red[4][FIN_T / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    __shared__ double s_red[4 * (FIN_T / 64)];
+    const int tid = threadIdx.x;
     const int R = a.N * a.T;
     const double w_lm = 1.0 - (double)a.lambda, w_kd = (double)a.lambda * (double)a.tau * (double)a.tau;
-    double sm = 0.0, snll = 0.0, skl = 0.0, sc = 0.0;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};                      // mask, nll, kl, the mixed loss
     for (int row = tid; row < R; row += FIN_T) {
         const int i = row / a.T, t = row - i * a.T;
         const double m = a.mask[(size_t)i * a.mask_ld + t];
         if (m == 0.0) continue;
         const double nll = a.nll[row], kl = a.kl[row];
-        sm += m;
-        snll += m * nll;
-        skl += m * kl;
-        sc += m * (w_lm * nll + w_kd * kl);
+        s[0] += m;
+        s[1] += m * nll;
+        s[2] += m * kl;
+        s[3] += m * (w_lm * nll + w_kd * kl);
     }
     if (a.per_row) {
         for (int i = tid; i < a.N; i += FIN_T) {
@@ -143,17 +133,11 @@ __global__ __launch_bounds__(FIN_T) void distill_finish_kernel(const KdArgs a) {
             a.msum[i] = (float)m_i;
         }
     }
-    sm = wave_sum_d(sm), snll = wave_sum_d(snll), skl = wave_sum_d(skl), sc = wave_sum_d(sc);
-    if (lane == 0) s_red[0][wid] = sm, s_red[1][wid] = snll, s_red[2][wid] = skl, s_red[3][wid] = sc;
-    __syncthreads();
-    if (tid != 0) return;
-    double t4[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int k = 0; k < 4; ++k)
-        for (int w = 0; w < FIN_T / 64; ++w) t4[k] += s_red[k][w];
-    const float M = (float)t4[0];
-    a.out[0] = (float)t4[1] / M;
-    a.out[1] = (float)t4[2] / M;
-    a.out[2] = (float)t4[3] / M;
+    if (!fold_d<4, FIN_T>(s, s_red)) return;
+    const float M = (float)s[0];
+    a.out[0] = (float)s[1] / M;
+    a.out[1] = (float)s[2] / M;
+    a.out[2] = (float)s[3] / M;
     if (!a.per_row) a.msum[0] = M;
 }
 
@@ -166,12 +150,8 @@ __global__ __launch_bounds__(KD_T) void distill_bwd_kernel(const KdArgs a) {
     const float *lt = a.lp_t + ((size_t)i * a.t_rows + t) * a.ld_t;
     const int V1 = a.V1;
     const float m = a.mask[(size_t)i * a.mask_ld + t];
-    const bool sweep = m != 0.f && a.lambda != 0.f;          // else the rows are not read
-    const uintptr_t ug = reinterpret_cast<uintptr_t>(g);
-    const bool vec = !sweep || (((ug ^ reinterpret_cast<uintptr_t>(ls)) | (ug ^ reinterpret_cast<uintptr_t>(lt))) & 15) == 0;
-    int head, nv;
-    row_split(g, V1, vec, head, nv);
-    const int tail = head + 4 * nv;
+    const bool soft = m != 0.f && a.lambda != 0.f;           // else the rows are not read
+    const RowSplit sp = row_split(g, V1, !soft || (same16(g, ls) && same16(g, lt)));
     const int k = a.per_row ? i : 0;
     float ch = 0.f;
     int64_t s = -1;
@@ -179,39 +159,24 @@ __global__ __launch_bounds__(KD_T) void distill_bwd_kernel(const KdArgs a) {
         const float c = a.g_out[k] * m / a.msum[k];
         ch = -(1.f - a.lambda) * c;
         s = a.tok[(size_t)i * a.tok_ld + t];       // (a token outside [0, V1) matches no column: no hard-label term anywhere)
-        if (sweep) {
+        if (soft) {
             const float ck = a.lambda * a.tau * c, it = a.inv_tau;
             const float lse_s = a.lse_s[row], lse_t = a.lse_t[row];
-            for (int q = tid; q < nv; q += KD_T) {
-                const int v0 = head + 4 * q;
-                const f32x4 x = *reinterpret_cast<const f32x4 *>(ls + v0);
-                const f32x4 y = *reinterpret_cast<const f32x4 *>(lt + v0);
-                f32x4 o;
-                o.x = ck * (__expf(x.x * it - lse_s) - __expf(y.x * it - lse_t)) + (v0 == s ? ch : 0.f);
-                o.y = ck * (__expf(x.y * it - lse_s) - __expf(y.y * it - lse_t)) + (v0 + 1 == s ? ch : 0.f);
-                o.z = ck * (__expf(x.z * it - lse_s) - __expf(y.z * it - lse_t)) + (v0 + 2 == s ? ch : 0.f);
-                o.w = ck * (__expf(x.w * it - lse_s) - __expf(y.w * it - lse_t)) + (v0 + 3 == s ? ch : 0.f);
-                *reinterpret_cast<f32x4 *>(g + v0) = o;
-            }
-            for (int v = tid; v < head; v += KD_T)
-                g[v] = ck * (__expf(ls[v] * it - lse_s) - __expf(lt[v] * it - lse_t)) + (v == s ? ch : 0.f);
-            for (int v = tail + tid; v < V1; v += KD_T)
-                g[v] = ck * (__expf(ls[v] * it - lse_s) - __expf(lt[v] * it - lse_t)) + (v == s ? ch : 0.f);
+            const auto g1 = [&](float x, float y, int v) {
+                return ck * (__expf(x * it - lse_s) - __expf(y * it - lse_t)) + (v == s ? ch : 0.f);
+            };
+            sweep<KD_T>(
+                sp, tid,
+                [&](int v0) {
+                    const f32x4 x = ld4(ls + v0), y = ld4(lt + v0);
+                    st4(g + v0, f32x4{g1(x.x, y.x, v0), g1(x.y, y.y, v0 + 1), g1(x.z, y.z, v0 + 2), g1(x.w, y.w, v0 + 3)});
+                },
+                [&](int v) { g[v] = g1(ls[v], lt[v], v); });
             return;
         }
     }
-    // masked rows: zeros; lambda == 0: the hard-label term alone
-    for (int q = tid; q < nv; q += KD_T) {
-        const int v0 = head + 4 * q;
-        f32x4 o;
-        o.x = v0 == s ? ch : 0.f, o.y = v0 + 1 == s ? ch : 0.f, o.z = v0 + 2 == s ? ch : 0.f, o.w = v0 + 3 == s ? ch : 0.f;
-        *reinterpret_cast<f32x4 *>(g + v0) = o;
-    }
-    for (int v = tid; v < head; v += KD_T) g[v] = v == s ? ch : 0.f;
-    for (int v = tail + tid; v < V1; v += KD_T) g[v] = v == s ? ch : 0.f;
+    sweep_one_hot<KD_T>(sp, tid, g, s, ch);                  // masked rows: zeros; lambda == 0: the hard-label term alone
 }
-
-bool off4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; }
 
 int common_args(const capmi_distill *p, KdArgs &a) {
     if (!p || p->N < 0 || p->T < 1 || p->V1 < 1) return CAPMI_EINVAL;
@@ -220,7 +185,7 @@ int common_args(const capmi_distill *p, KdArgs &a) {
     if (!(p->tau > 0.f) || p->tau == INFINITY) return CAPMI_EINVAL;
     if (!(p->lambda >= 0.f && p->lambda <= 1.f)) return CAPMI_EINVAL;
     if (!p->lp_s || !p->lp_t || !p->tok || !p->mask || !p->row_stats || !p->msum) return CAPMI_EINVAL;
-    if (off4(p->lp_s) || off4(p->lp_t) || off4(p->mask) || off4(p->row_stats) || off4(p->msum)) return CAPMI_EINVAL;
+    if (!aligned4(p->lp_s, p->lp_t, p->mask, p->row_stats, p->msum)) return CAPMI_EINVAL;
     a = KdArgs{};
     a.lp_s = p->lp_s, a.lp_t = p->lp_t, a.tok = p->tok, a.mask = p->mask;
     const size_t R = (size_t)p->N * p->T;
@@ -252,7 +217,7 @@ extern "C" int capmi_distill_loss_fwd(const capmi_distill *p, void *stream) {
 extern "C" int capmi_distill_loss_bwd(const capmi_distill *p, void *stream) {
     KdArgs a;
     if (common_args(p, a) != 0) return CAPMI_EINVAL;
-    if (p->ld_grad < p->V1 || !p->grad || !p->g_out || off4(p->grad) || off4(p->g_out)) return CAPMI_EINVAL;
+    if (p->ld_grad < p->V1 || !p->grad || !p->g_out || !aligned4(p->grad, p->g_out)) return CAPMI_EINVAL;
     if (p->N == 0) return 0;
     hipLaunchKernelGGL(distill_bwd_kernel, dim3(p->N * p->T), dim3(KD_T), 0, (hipStream_t)stream, a);
     CAPMI_CHECK_LAUNCH();

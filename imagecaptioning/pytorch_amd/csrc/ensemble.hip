@@ -1,8 +1,9 @@
 // Test-time ensemble (gfx950): the mixture log-probability of M members' rows.
 // Reference: AttEnsemble.get_logprobs_state (AttEnsemble.py:45-53), log(sum_i w_i softmax(logit_i) / sum_i w_i), here in
-// log space.  See include/capmi.h (capmi_ensemble_logprobs) for the contract and the edge cases.
-#include "capmi_common.h"
-#include "../../../include/capmi.h"
+// log space.  See include/capmi.h (capmi_ensemble_logprobs) for the contract and the edge cases.  The member rows are cut as row_sweep.h has
+// it; both passes spell its sweep order out (see the kernel).
+#include "host_common.h"
+#include "row_sweep.h"
 
 using namespace capmi;
 
@@ -101,30 +102,25 @@ __global__ __launch_bounds__(ENS_T) void ensemble_logprobs_kernel(const EnsArgs 
 #pragma unroll
     for (int i = 0; i < M; ++i) row[i] = e.in[i] + r * (size_t)e.ld_in;
     float *o = e.out + r * (size_t)e.ld_out;
-    // [0, head) scalar, [head, head + 4 nv) float4, [head + 4 nv, V1) scalar; head aligns member 0's row, hence all of them
-    int head = V1, nv = 0;
-    if (e.vec) {
-        head = (int)(((16 - (reinterpret_cast<uintptr_t>(row[0]) & 15)) & 15) >> 2);
-        head = head < V1 ? head : V1;
-        nv = (V1 - head) >> 2;
-    }
-    const int tail = head + 4 * nv;
+    const RowSplit sp = row_split(row[0], V1, e.vec);        // the cut aligns member 0's row, hence all of them
 
+    // Both passes spell sweep()'s order (body, head, tail) out: with the payloads in lambdas the kernels compile to other code,
+    // M = 5 with two registers more, and at 50 rows M = 5, 6, 7 ran 1-2 % slower.
     // pass 1: per member online max and sum of exp over the row
     float m[M], s[M];
 #pragma unroll
     for (int i = 0; i < M; ++i) m[i] = -INFINITY, s[i] = 0.f;
-    for (int q = tid; q < nv; q += ENS_T) {
+    for (int q = tid; q < sp.nv; q += ENS_T) {
         f32x4 x[M];
 #pragma unroll
-        for (int i = 0; i < M; ++i) x[i] = *reinterpret_cast<const f32x4 *>(row[i] + head + 4 * q);
+        for (int i = 0; i < M; ++i) x[i] = ld4(row[i] + sp.head + 4 * q);
 #pragma unroll
         for (int i = 0; i < M; ++i) online4(m[i], s[i], x[i]);
     }
-    for (int v = tid; v < head; v += ENS_T)
+    for (int v = tid; v < sp.head; v += ENS_T)
 #pragma unroll
         for (int i = 0; i < M; ++i) online1(m[i], s[i], row[i][v]);
-    for (int v = tail + tid; v < V1; v += ENS_T)
+    for (int v = sp.tail + tid; v < V1; v += ENS_T)
 #pragma unroll
         for (int i = 0; i < M; ++i) online1(m[i], s[i], row[i][v]);
     block_lse<M>(m, s, s_red);
@@ -133,11 +129,11 @@ __global__ __launch_bounds__(ENS_T) void ensemble_logprobs_kernel(const EnsArgs 
     for (int i = 0; i < M; ++i) c[i] = __logf(s[i]) - e.log_w[i];
 
     // pass 2: re-read the member rows, write the mixture
-    const bool out_vec = ((reinterpret_cast<uintptr_t>(o) ^ reinterpret_cast<uintptr_t>(row[0])) & 15) == 0;
-    for (int q = tid; q < nv; q += ENS_T) {
+    const bool out_vec = same16(o, row[0]);
+    for (int q = tid; q < sp.nv; q += ENS_T) {
         f32x4 x[M];
 #pragma unroll
-        for (int i = 0; i < M; ++i) x[i] = *reinterpret_cast<const f32x4 *>(row[i] + head + 4 * q);
+        for (int i = 0; i < M; ++i) x[i] = ld4(row[i] + sp.head + 4 * q);
         f32x4 y;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -146,23 +142,21 @@ __global__ __launch_bounds__(ENS_T) void ensemble_logprobs_kernel(const EnsArgs 
             for (int i = 0; i < M; ++i) xk[i] = x[i][k];
             y[k] = mix<M>(xk, m, c);
         }
-        float *op = o + head + 4 * q;
+        float *op = o + sp.head + 4 * q;
         if (out_vec) {
-            *reinterpret_cast<f32x4 *>(op) = y;
+            st4(op, y);
         } else {
             op[0] = y.x; op[1] = y.y; op[2] = y.z; op[3] = y.w;
         }
     }
-    for (int v = tid; v < head; v += ENS_T) o[v] = mix_at<M>(row, v, m, c);
-    for (int v = tail + tid; v < V1; v += ENS_T) o[v] = mix_at<M>(row, v, m, c);
+    for (int v = tid; v < sp.head; v += ENS_T) o[v] = mix_at<M>(row, v, m, c);
+    for (int v = sp.tail + tid; v < V1; v += ENS_T) o[v] = mix_at<M>(row, v, m, c);
 }
 
 template <int M>
 void launch(const EnsArgs &a, hipStream_t st) {
     hipLaunchKernelGGL(ensemble_logprobs_kernel<M>, dim3(a.rows), dim3(ENS_T), 0, st, a);
 }
-
-bool overlaps(const float *a, size_t na, const float *b, size_t nb) { return a < b + nb && b < a + na; }
 
 }  // namespace
 
@@ -176,22 +170,21 @@ extern "C" int capmi_ensemble_logprobs(const capmi_ensemble *e, void *stream) {
     a.ld_in = e->ld_in;
     a.ld_out = e->ld_out;
     a.vec = 1;
-    const size_t span_in = (size_t)(e->rows > 0 ? e->rows - 1 : 0) * e->ld_in + e->V1;
-    const size_t span_out = (size_t)(e->rows > 0 ? e->rows - 1 : 0) * e->ld_out + e->V1;
+    const size_t span_in = span(e->rows, e->ld_in, e->V1), span_out = span(e->rows, e->ld_out, e->V1);
     int n = 0;
     for (int i = 0; i < e->M; ++i) {
         const float w = e->w[i];
         if (!e->in[i] || !(w >= 0.f) || w == INFINITY) return CAPMI_EINVAL;      // (also NaN)
-        if ((reinterpret_cast<uintptr_t>(e->in[i]) & 3) != 0) return CAPMI_EINVAL;
+        if (!aligned4(e->in[i])) return CAPMI_EINVAL;
         if (overlaps(e->in[i], span_in, e->out, span_out)) return CAPMI_EINVAL;
         if (w == 0.f) continue;
         a.in[n] = e->in[i];
         a.log_w[n] = logf(w);
-        if (((reinterpret_cast<uintptr_t>(a.in[n]) ^ reinterpret_cast<uintptr_t>(a.in[0])) & 15) != 0) a.vec = 0;
+        if (!same_phase16(a.in[n], e->ld_in, a.in[0], e->ld_in)) a.vec = 0;
         ++n;
     }
     if (n == 0) return CAPMI_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(e->out) & 3) != 0) return CAPMI_EINVAL;
+    if (!aligned4(e->out)) return CAPMI_EINVAL;
     if (e->rows == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     switch (n) {

@@ -32,6 +32,27 @@ inline bool aligned16(P... p) {
     return ((... | reinterpret_cast<uintptr_t>(p)) & 15) == 0;
 }
 
+// all (possibly null) pointers 4-byte aligned
+template <typename... P>
+inline bool aligned4(P... p) {
+    return ((... | reinterpret_cast<uintptr_t>(p)) & 3) == 0;
+}
+
+// bytes from the first to past the last element of a [rows, V1] float matrix of leading dimension ld
+inline size_t span(int rows, int ld, int V1) { return ((size_t)(rows > 0 ? rows - 1 : 0) * ld + V1) * sizeof(float); }
+
+// the byte ranges [a, a + na) and [b, b + nb) meet
+inline bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
+    const char *pa = static_cast<const char *>(a), *pb = static_cast<const char *>(b);
+    return pa < pb + nb && pb < pa + na;
+}
+
+// every row of p (leading dimension ld_p floats) sits at the same offset mod 16 bytes as the same row of q: one cut of a row
+// (row_sweep.h) aligns both, so a kernel may sweep them with float4
+inline bool same_phase16(const void *p, int64_t ld_p, const void *q, int64_t ld_q) {
+    return ((reinterpret_cast<uintptr_t>(p) ^ reinterpret_cast<uintptr_t>(q)) & 15) == 0 && (ld_p - ld_q) % 4 == 0;
+}
+
 // one K segment of a capmi_gemm_f32 call; a_row_div <= 0 means 1
 struct SegSpec {
     const float *A;

@@ -1,9 +1,10 @@
 // PPO structure loss (gfx950): clipped policy ratio + KL(old || new) of the sampled rollout against a frozen old policy.
 // Reference: PPOLoss.forward (captioning/modules/losses.py:267-357).  See include/capmi.h (capmi_ppo_loss_fwd / _bwd) for the
 // contract and the edge cases.  Forward: one workgroup per (n, t) row reads the new and the old row once, then one workgroup folds
-// the masked means.  Backward: one workgroup per row reads the old row once and writes the dense gradient once.
-#include "capmi_common.h"
-#include "../../../include/capmi.h"
+// the masked means.  Backward: one workgroup per row reads the old row once and writes the dense gradient once.  Rows are cut and
+// swept, and the means folded, as row_sweep.h has it.
+#include "host_common.h"
+#include "row_sweep.h"
 
 using namespace capmi;
 
@@ -46,13 +47,7 @@ __global__ __launch_bounds__(PPO_T) void ppo_rows_kernel(const PpoArgs a) {
     const float *ln = a.lp_new + (size_t)row * a.ld_new;
     const float *lo = a.lp_old + (size_t)row * a.ld_old;
     const int V1 = a.V1;
-    int head = V1, nv = 0;
-    if (a.vec) {
-        head = (int)(((16 - (reinterpret_cast<uintptr_t>(ln) & 15)) & 15) >> 2);
-        head = head < V1 ? head : V1;
-        nv = (V1 - head) >> 2;
-    }
-    const int tail = head + 4 * nv;
+    const RowSplit sp = row_split(ln, V1, a.vec);
     // the sampled token's two entries and the image's scores: loaded before the sweep, so their latency hides behind it
     const int64_t s = a.seq[(size_t)i * a.L + t];
     const bool s_in = s >= 0 && s < V1;
@@ -64,13 +59,13 @@ __global__ __launch_bounds__(PPO_T) void ppo_rows_kernel(const PpoArgs a) {
         si = a.scores[i];
     }
     float acc = 0.f;
-    for (int q = tid; q < nv; q += PPO_T) {
-        const f32x4 x = *reinterpret_cast<const f32x4 *>(ln + head + 4 * q);
-        const f32x4 y = *reinterpret_cast<const f32x4 *>(lo + head + 4 * q);
-        acc += (kl1(y.x, x.x) + kl1(y.y, x.y)) + (kl1(y.z, x.z) + kl1(y.w, x.w));
-    }
-    for (int v = tid; v < head; v += PPO_T) acc += kl1(lo[v], ln[v]);
-    for (int v = tail + tid; v < V1; v += PPO_T) acc += kl1(lo[v], ln[v]);
+    sweep<PPO_T>(
+        sp, tid,
+        [&](int v0) {
+            const f32x4 x = ld4(ln + v0), y = ld4(lo + v0);
+            acc += (kl1(y.x, x.x) + kl1(y.y, x.y)) + (kl1(y.z, x.z) + kl1(y.w, x.w));
+        },
+        [&](int v) { acc += kl1(lo[v], ln[v]); });
     const float kl = block_sum(acc, s_red);
     if (tid != 0) return;
     // the advantage of sample i against the mean score of its image's other samples (new_self_critical's baseline)
@@ -96,17 +91,17 @@ __global__ __launch_bounds__(PPO_T) void ppo_rows_kernel(const PpoArgs a) {
 // the masked means of one launch's rows: double accumulators, a fixed order (deterministic).  The global sums take one row per
 // thread (independent loads); the per-sample losses of per_row walk each sample's steps in order.
 __global__ __launch_bounds__(FIN_T) void ppo_finish_kernel(const PpoArgs a) {
-    __shared__ double s_red[4][FIN_T / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    __shared__ double s_red[4 * (FIN_T / 64)];
+    const int tid = threadIdx.x;
     const int R = a.N * a.L;
-    double sm = 0.0, spg = 0.0, skl = 0.0, sclip = 0.0;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};                      // rows on, pg, kl, clipped
     for (int row = tid; row < R; row += FIN_T) {
         const int i = row / a.L, t = row - i * a.L;
         if (!row_on(a.seq, a.L, i, t)) continue;
-        sm += 1.0;
-        spg += a.pg[row];
-        skl += a.kl[row];
-        sclip += fabsf(a.r[row] - 1.f) > a.eps ? 1.0 : 0.0;
+        s[0] += 1.0;
+        s[1] += a.pg[row];
+        s[2] += a.kl[row];
+        s[3] += fabsf(a.r[row] - 1.f) > a.eps ? 1.0 : 0.0;
     }
     if (a.per_row) {
         for (int i = tid; i < a.N; i += FIN_T) {
@@ -121,18 +116,12 @@ __global__ __launch_bounds__(FIN_T) void ppo_finish_kernel(const PpoArgs a) {
             a.msum[i] = m_i;
         }
     }
-    sm = wave_sum_d(sm), spg = wave_sum_d(spg), skl = wave_sum_d(skl), sclip = wave_sum_d(sclip);
-    if (lane == 0) s_red[0][wid] = sm, s_red[1][wid] = spg, s_red[2][wid] = skl, s_red[3][wid] = sclip;
-    __syncthreads();
-    if (tid != 0) return;
-    double t4[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int k = 0; k < 4; ++k)
-        for (int w = 0; w < FIN_T / 64; ++w) t4[k] += s_red[k][w];
-    const float M = (float)t4[0];
-    const float pg_loss = (float)t4[1] / M, kl_loss = (float)t4[2] / M;
+    if (!fold_d<4, FIN_T>(s, s_red)) return;
+    const float M = (float)s[0];
+    const float pg_loss = (float)s[1] / M, kl_loss = (float)s[2] / M;
     a.out[0] = pg_loss;
     a.out[1] = kl_loss;
-    a.out[2] = (float)t4[3] / M;
+    a.out[2] = (float)s[3] / M;
     a.out[3] = pg_loss + a.kl_coef * kl_loss;
     if (!a.per_row) a.msum[0] = M;
 }
@@ -144,18 +133,9 @@ __global__ __launch_bounds__(PPO_T) void ppo_bwd_kernel(const PpoArgs a) {
     float *g = a.grad + (size_t)row * a.ld_grad;
     const int V1 = a.V1;
     const bool on = row_on(a.seq, a.L, i, t);
-    int head = V1, nv = 0;
-    if (a.vec) {
-        head = (int)(((16 - (reinterpret_cast<uintptr_t>(g) & 15)) & 15) >> 2);
-        head = head < V1 ? head : V1;
-        nv = (V1 - head) >> 2;
-    }
-    const int tail = head + 4 * nv;
+    const RowSplit sp = row_split(g, V1, a.vec);
     if (!on) {                                               // masked rows: zeros, the old row is not read
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        for (int q = tid; q < nv; q += PPO_T) *reinterpret_cast<f32x4 *>(g + head + 4 * q) = z;
-        for (int v = tid; v < head; v += PPO_T) g[v] = 0.f;
-        for (int v = tail + tid; v < V1; v += PPO_T) g[v] = 0.f;
+        sweep_one_hot<PPO_T>(sp, tid, g, -1, 0.f);
         return;
     }
     const float c = a.per_row ? a.g_out[i] / a.msum[i] : a.g_out[0] / a.msum[0];
@@ -163,30 +143,21 @@ __global__ __launch_bounds__(PPO_T) void ppo_bwd_kernel(const PpoArgs a) {
     const float cs = c * a.gpg[row];
     const int64_t s = a.seq[(size_t)i * a.L + t];   // (a token outside [0, V1) matches no column: no extra term anywhere)
     const float *lo = a.lp_old + (size_t)row * a.ld_old;
-    for (int q = tid; q < nv; q += PPO_T) {
-        const int v0 = head + 4 * q;
-        const f32x4 y = *reinterpret_cast<const f32x4 *>(lo + v0);
-        f32x4 o;
-        o.x = ck * __expf(y.x) + (v0 == s ? cs : 0.f);
-        o.y = ck * __expf(y.y) + (v0 + 1 == s ? cs : 0.f);
-        o.z = ck * __expf(y.z) + (v0 + 2 == s ? cs : 0.f);
-        o.w = ck * __expf(y.w) + (v0 + 3 == s ? cs : 0.f);
-        *reinterpret_cast<f32x4 *>(g + v0) = o;
-    }
-    for (int v = tid; v < head; v += PPO_T) g[v] = ck * __expf(lo[v]) + (v == s ? cs : 0.f);
-    for (int v = tail + tid; v < V1; v += PPO_T) g[v] = ck * __expf(lo[v]) + (v == s ? cs : 0.f);
-}
-
-bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
-    const char *pa = static_cast<const char *>(a), *pb = static_cast<const char *>(b);
-    return pa < pb + nb && pb < pa + na;
+    const auto g1 = [&](float y, int v) { return ck * __expf(y) + (v == s ? cs : 0.f); };
+    sweep<PPO_T>(
+        sp, tid,
+        [&](int v0) {
+            const f32x4 y = ld4(lo + v0);
+            st4(g + v0, f32x4{g1(y.x, v0), g1(y.y, v0 + 1), g1(y.z, v0 + 2), g1(y.w, v0 + 3)});
+        },
+        [&](int v) { g[v] = g1(lo[v], v); });
 }
 
 int common_args(const capmi_ppo *p, PpoArgs &a) {
     if (!p || p->N < 0 || p->L < 1 || p->V1 < 1 || p->n < 2 || (p->N % p->n) != 0 || p->ld_old < p->V1 || !p->lp_old || !p->seq)
         return CAPMI_EINVAL;
     if ((int64_t)p->N * p->L > 0x7fffffff) return CAPMI_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(p->lp_old) & 3) != 0) return CAPMI_EINVAL;
+    if (!aligned4(p->lp_old)) return CAPMI_EINVAL;
     if (!(p->eps >= 0.f) || !(p->kl_coef >= 0.f) || p->eps == INFINITY || p->kl_coef == INFINITY) return CAPMI_EINVAL;
     a = PpoArgs{};
     a.lp_new = p->lp_new, a.lp_old = p->lp_old, a.seq = p->seq, a.scores = p->scores;
@@ -199,8 +170,6 @@ int common_args(const capmi_ppo *p, PpoArgs &a) {
     return 0;
 }
 
-size_t span(int rows, int ld, int V1) { return ((size_t)(rows > 0 ? rows - 1 : 0) * ld + V1) * sizeof(float); }
-
 }  // namespace
 
 extern "C" int capmi_ppo_loss_fwd(const capmi_ppo *p, void *stream) {
@@ -208,13 +177,12 @@ extern "C" int capmi_ppo_loss_fwd(const capmi_ppo *p, void *stream) {
     if (common_args(p, a) != 0) return CAPMI_EINVAL;
     if (p->ld_new < p->V1 || !p->lp_new || !p->scores || !p->row_stats || !p->msum || !p->out || (p->per_row && !p->loss_rows))
         return CAPMI_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(p->lp_new) & 3) != 0) return CAPMI_EINVAL;
+    if (!aligned4(p->lp_new)) return CAPMI_EINVAL;
     const int R = p->N * p->L;
     if (overlaps(p->row_stats, (size_t)4 * R * sizeof(float), p->lp_new, span(R, p->ld_new, p->V1)) ||
         overlaps(p->row_stats, (size_t)4 * R * sizeof(float), p->lp_old, span(R, p->ld_old, p->V1)))
         return CAPMI_EINVAL;
-    const int64_t d = (int64_t)((reinterpret_cast<uintptr_t>(p->lp_new) ^ reinterpret_cast<uintptr_t>(p->lp_old)) & 15);
-    a.vec = (d == 0 && ((int64_t)p->ld_new - p->ld_old) % 4 == 0) ? 1 : 0;
+    a.vec = same_phase16(p->lp_new, p->ld_new, p->lp_old, p->ld_old) ? 1 : 0;
     if (p->N == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(ppo_rows_kernel, dim3(R), dim3(PPO_T), 0, st, a);
@@ -228,11 +196,10 @@ extern "C" int capmi_ppo_loss_bwd(const capmi_ppo *p, void *stream) {
     PpoArgs a;
     if (common_args(p, a) != 0) return CAPMI_EINVAL;
     if (p->ld_grad < p->V1 || !p->grad || !p->row_stats || !p->msum || !p->g_out) return CAPMI_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(p->grad) & 3) != 0) return CAPMI_EINVAL;
+    if (!aligned4(p->grad)) return CAPMI_EINVAL;
     const int R = p->N * p->L;
     if (overlaps(p->grad, span(R, p->ld_grad, p->V1), p->lp_old, span(R, p->ld_old, p->V1))) return CAPMI_EINVAL;
-    const int64_t d = (int64_t)((reinterpret_cast<uintptr_t>(p->grad) ^ reinterpret_cast<uintptr_t>(p->lp_old)) & 15);
-    a.vec = (d == 0 && ((int64_t)p->ld_grad - p->ld_old) % 4 == 0) ? 1 : 0;
+    a.vec = same_phase16(p->grad, p->ld_grad, p->lp_old, p->ld_old) ? 1 : 0;
     if (p->N == 0) return 0;
     hipLaunchKernelGGL(ppo_bwd_kernel, dim3(R), dim3(PPO_T), 0, (hipStream_t)stream, a);
     CAPMI_CHECK_LAUNCH();

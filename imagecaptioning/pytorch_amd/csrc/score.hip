@@ -6,14 +6,14 @@
 //                      -- an online logsumexp -- and the pairs are merged by a wave / block max followed by a wave / block sum of
 //                      the rescaled sums, both in the fixed order of capmi_common.h: no atomics, the same bits from run to run.
 //                      Nothing of the row's size is written; the step is bound by the rows * V1 * 4 bytes it reads.
-//                      The row is cut on its OWN alignment: scalar loads up to the first 16-byte boundary, 16-byte loads, a scalar
-//                      tail -- so ld and V1 need not be multiples of 4.
+//                      The row is cut on its OWN alignment (row_sweep.h), so ld and V1 need not be multiples of 4.
 //                      Launch shape by V1: up to WAVE_V1 columns one WAVE per row (four rows per 256-thread workgroup, no LDS, no
 //                      barrier: a 4 KB row is 4 loads per lane); above, one 256-thread WORKGROUP per row (a 37 KB row of the 9488
 //                      word vocabulary is 9-10 16-byte loads per thread, all in flight at once; 8000 rows are 8000 workgroups).
 // retrieval_rank_kernel  one workgroup per caption over its row of I scores: integer counts (order-free) and the same online
 //                      logsumexp for the posterior.
 #include "host_common.h"
+#include "row_sweep.h"
 
 using namespace capmi;
 
@@ -41,20 +41,18 @@ __device__ __forceinline__ void lse_add4(LSE &a, float y0, float y1, float y2, f
     }
 }
 
-// this thread's share of x[0, n) * scale; tid of nthr threads
+// this thread's share of x[0, n) * scale; tid of nthr threads (a wave or a workgroup).  The cut is row_sweep.h's; the order is this
+// file's own -- head, body, tail, the head and the tail one guarded element each (at most 3 columns) -- and stays: the payload is
+// not associative in float, so row_sweep.h's sweep (body, head, tail) would give other bits.
 __device__ __forceinline__ LSE lse_scan(const float *__restrict__ x, int n, float scale, int tid, int nthr) {
     LSE a{-INFINITY, 0.f};
-    int head = (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(x) & 15u)) & 15u) >> 2);
-    if (head > n) head = n;
-    const int nvec = (n - head) >> 2;
-    const int tail0 = head + 4 * nvec;
-    if (tid < head) lse_add(a, x[tid] * scale);
-    const f32x4 *xv = reinterpret_cast<const f32x4 *>(x + head);
-    for (int i = tid; i < nvec; i += nthr) {
-        const f32x4 v = xv[i];
+    const RowSplit sp = row_split(x, n, true);
+    if (tid < sp.head) lse_add(a, x[tid] * scale);
+    for (int i = tid; i < sp.nv; i += nthr) {
+        const f32x4 v = ld4(x + sp.head + 4 * i);
         lse_add4(a, v.x * scale, v.y * scale, v.z * scale, v.w * scale);
     }
-    if (tid < n - tail0) lse_add(a, x[tail0 + tid] * scale);
+    if (tid < n - sp.tail) lse_add(a, x[sp.tail + tid] * scale);
     return a;
 }
 

@@ -6,8 +6,8 @@
 // writes the sparse gradient (capmi_sparse_logp_grad); nothing dense is produced.
 #include <math.h>
 
-#include "capmi_common.h"
-#include "../../../include/capmi.h"
+#include "host_common.h"
+#include "row_sweep.h"
 
 using namespace capmi;
 
@@ -41,8 +41,8 @@ __global__ __launch_bounds__(XE_T) void xe_nll_kernel(const XeArgs a) {
     a.pos[row] = v;
 }
 
-// smoothing > 0: pos[n, t] = (ent - off * sum_v logp[n, t, v] - (conf - off) * logp[n, t, tok]) * mask, one workgroup per row.
-// Row bases fall off 16-byte boundaries (V1 is odd in general): scalar head up to the boundary, float4 body, scalar tail.
+// smoothing > 0: pos[n, t] = (ent - off * sum_v logp[n, t, v] - (conf - off) * logp[n, t, tok]) * mask, one workgroup per row,
+// the row cut and swept as row_sweep.h has it.
 __global__ __launch_bounds__(XE_T) void xe_smooth_kernel(const XeArgs a) {
     __shared__ double s_red[XE_W];
     const int row = blockIdx.x, tid = threadIdx.x;
@@ -54,31 +54,21 @@ __global__ __launch_bounds__(XE_T) void xe_smooth_kernel(const XeArgs a) {
     }
     const float *lp = a.logp + (size_t)row * a.V1;
     const int V1 = a.V1;
-    int head = (int)(((16 - (reinterpret_cast<uintptr_t>(lp) & 15)) & 15) >> 2);
-    head = head < V1 ? head : V1;
-    const int nv = (V1 - head) >> 2;
-    const int tail = head + 4 * nv;
+    const RowSplit sp = row_split(lp, V1, true);
     float sel = 0.f;                                         // loaded before the sweep, so its latency hides behind it
     if (tid == 0) sel = gather1(lp, a.tok[(size_t)n * a.tok_ld + t], V1);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int q = tid; q < nv; q += XE_T) acc += *reinterpret_cast<const f32x4 *>(lp + head + 4 * q);
     float edge = 0.f;
-    for (int v = tid; v < head; v += XE_T) edge += lp[v];
-    for (int v = tail + tid; v < V1; v += XE_T) edge += lp[v];
+    sweep<XE_T>(sp, tid, [&](int v0) { acc += ld4(lp + v0); }, [&](int v) { edge += lp[v]; });
     // a thread holds at most a few terms per lane of `acc`; everything across threads is added in double, in a fixed tree
-    double s = ((double)acc.x + (double)acc.y) + ((double)acc.z + (double)acc.w) + (double)edge;
-    s = wave_sum_d(s);
-    if ((tid & 63) == 0) s_red[tid >> 6] = s;
-    __syncthreads();
-    if (tid != 0) return;
-    double tot = 0.0;
-    for (int w = 0; w < XE_W; ++w) tot += s_red[w];
-    a.pos[row] = (float)(a.ent - (a.off * tot + a.cmo * (double)sel)) * m;
+    double s[1] = {((double)acc.x + (double)acc.y) + ((double)acc.z + (double)acc.w) + (double)edge};
+    if (!fold_d<1, XE_T>(s, s_red)) return;
+    a.pos[row] = (float)(a.ent - (a.off * s[0] + a.cmo * (double)sel)) * m;
 }
 
 // stage 2: the masked means of one launch's positions.  Double accumulators, a fixed order: two runs are bit-equal.
 __global__ __launch_bounds__(XE_T) void xe_fold_kernel(const XeArgs a) {
-    __shared__ double s_red[2][XE_W];
+    __shared__ double s_red[2 * XE_W];
     const int tid = threadIdx.x;
     if (a.per_row) {                                         // 'none': each row's steps in order
         for (int n = tid; n < a.N; n += XE_T) {
@@ -93,20 +83,15 @@ __global__ __launch_bounds__(XE_T) void xe_fold_kernel(const XeArgs a) {
         return;
     }
     const int R = a.N * a.T;
-    double sv = 0.0, sm = 0.0;
+    double s[2] = {0.0, 0.0};                                // value, mask
     for (int row = tid; row < R; row += XE_T) {
         const int n = row / a.T, t = row - n * a.T;
-        sv += a.pos[row];
-        sm += a.mask[(size_t)n * a.mask_ld + t];
+        s[0] += a.pos[row];
+        s[1] += a.mask[(size_t)n * a.mask_ld + t];
     }
-    sv = wave_sum_d(sv), sm = wave_sum_d(sm);
-    if ((tid & 63) == 0) s_red[0][tid >> 6] = sv, s_red[1][tid >> 6] = sm;
-    __syncthreads();
-    if (tid != 0) return;
-    double tv = 0.0, tm = 0.0;
-    for (int w = 0; w < XE_W; ++w) tv += s_red[0][w], tm += s_red[1][w];
-    a.msum[0] = (float)tm;
-    a.loss[0] = (float)tv / (float)tm;
+    if (!fold_d<2, XE_T>(s, s_red)) return;
+    a.msum[0] = (float)s[1];
+    a.loss[0] = (float)s[0] / (float)s[1];
 }
 
 // g_sel[n, t] = -(conf - off) * mask / msum * u,  g_sum[n, t] = -off * mask / msum * u  (u: the row's upstream value, or 1)
@@ -149,7 +134,7 @@ extern "C" int capmi_xe_loss_fwd(const capmi_xe_loss *p, void *stream) {
     XeArgs a;
     if (common_args(p, a) != 0) return CAPMI_EINVAL;
     if (!p->logp || !p->tok || !p->pos || !p->loss) return CAPMI_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(p->logp) & 3) != 0) return CAPMI_EINVAL;
+    if (!aligned4(p->logp)) return CAPMI_EINVAL;
     const int R = p->N * p->T;
     hipStream_t st = (hipStream_t)stream;
     if (p->smoothing > 0.0)

@@ -21,10 +21,11 @@ N, T, LD, TT = 6, 5, 9, 7          # B 3 x n 2 rows, T = 5 steps out of tok_ld =
 
 
 # ---------------------------------------------------------------------------------------------------------------- the kernels
-def _inputs(V1, layout, seed):
+def _inputs(V1, layout, seed, N=N, T=T):
     """fp32 device inputs: the student near the teacher; layout 'cut': the teacher is the [:, :T] part of a [N, TT, V1 + 3] buffer
     (row stride above V1, a longer sample pitch; rows off the student's alignment), 'plain': [N, T, V1] contiguous (the float4 body
     wherever V1 allows).  Masks with zero positions mid-row and a fully masked sample."""
+    LD, TT = T + 4, T + 2
     g = torch.Generator().manual_seed(seed)
     lt = torch.log_softmax(2 * torch.randn(N, TT, V1, generator=g), 2)
     ls = torch.log_softmax(lt[:, :T] + 0.5 * torch.randn(N, T, V1, generator=g), 2)
@@ -47,7 +48,7 @@ def _check_kernel(ls, lt, tok, mask, lam, tau, per_row):
     """the tolerances of tests/test_ppo_gpu.py for its KL rows (2e-5 of the sum of |terms| + 1e-6), its losses (2e-5 of the scale of
     the summed terms) and its dense gradient (2e-5 relative + 1e-6 of the largest entry)"""
     from imagecaptioning.pytorch_amd import ops
-    u = torch.linspace(0.5, 1.5, N, device=DEV) if per_row else torch.tensor([0.7], device=DEV)
+    u = torch.linspace(0.5, 1.5, ls.shape[0], device=DEV) if per_row else torch.tensor([0.7], device=DEV)
     out, loss_rows, rs, msum = ops.distill_loss_fwd(ls, lt, tok, mask, lam, tau, per_row)
     grad = torch.full_like(ls, float('nan'))                 # NaN-filled: every entry must be overwritten
     ops.distill_loss_bwd(ls, lt, tok, mask, rs, msum, u, lam, tau, per_row, out=grad)
@@ -89,6 +90,16 @@ def test_kernel_against_fp64(V1, layout, per_row):
     for lam in (0.0, 0.3, 1.0):
         for tau in (0.5, 1.0, 2.0):
             _check_kernel(ls, lt, tok, mask, lam, tau, per_row)
+
+
+@pytest.mark.parametrize('per_row', (False, True))
+@pytest.mark.parametrize('layout', ('cut', 'plain'))
+@pytest.mark.parametrize('V1', (3, 31))
+def test_kernel_against_fp64_more_rows_than_fold_threads(V1, layout, per_row):
+    """N * T = 1100: the finish kernel's 1024 threads take a second trip over the rows; a fully masked sample as above"""
+    ls, lt, tok, mask = _inputs(V1, layout, seed=V1 * 11 + per_row, N=50, T=22)
+    for lam in (0.0, 0.3, 1.0):
+        _check_kernel(ls, lt, tok, mask, lam, 2.0, per_row)
 
 
 def test_two_runs_are_bit_equal_and_identity_is_zero():

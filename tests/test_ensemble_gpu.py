@@ -26,7 +26,7 @@ def mixture64(xs, w):
 
 # ---------------------------------------------------------------------------------------------------------------- the kernel
 @pytest.mark.parametrize('M', (1, 2, 3, 8))
-@pytest.mark.parametrize('V1', (31, 9487, 9488))
+@pytest.mark.parametrize('V1', (1, 3, 31, 9487, 9488))
 def test_kernel_against_fp64(M, V1):
     from imagecaptioning.pytorch_amd import ops
     from imagecaptioning.pytorch_amd._lib import lib, ptr, stream_ptr

@@ -75,7 +75,7 @@ def _check_kernel(ln, lo, seq, scores, n, eps, klc, per_row):
 
 
 @pytest.mark.parametrize('per_row', (False, True))
-@pytest.mark.parametrize('N,L,V1', [(6, 1, 1), (6, 1, 11), (9, 4, 11), (640, 21, 11), (12, 5, 4097), (50, 20, 9488)])
+@pytest.mark.parametrize('N,L,V1', [(6, 1, 1), (6, 2, 3), (50, 22, 5), (6, 1, 11), (9, 4, 11), (640, 21, 11), (12, 5, 4097), (50, 20, 9488)])
 def test_kernel_against_fp64(N, L, V1, per_row):
     for eps, klc in ((0.2, 0.02), (0.05, 0.5)):
         ln, lo, seq, scores = _inputs(N, L, V1, 3 if N % 3 == 0 else 2, seed=N * 31 + V1)

@@ -47,7 +47,7 @@ def _strided(x, ld):
 # ---------------------------------------------------------------------------------------------------------------------------
 # capmi_score_step
 # ---------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('V1', (5, 67, 1024, 1025, 9488))        # 1024 / 1025: the last wave-per-row and the first workgroup-per-row width
+@pytest.mark.parametrize('V1', (3, 5, 67, 1024, 1025, 9488))    # 1024 / 1025: the last wave-per-row and the first workgroup-per-row width
 def test_score_step_against_float64(V1):
     from imagecaptioning.pytorch_amd import ops
     worst = 0.0

@@ -133,12 +133,12 @@ def within_rule(got, aten, ref, what):
     assert e_k <= max(4.0 * e_a, 4.0 * ulp), (what, e_k, e_a, ulp)
 
 
-SHAPES = [(1, 1), (3, 7), (40, 7)]                 # N * T = 280 > one 256-thread workgroup of the fold
+SHAPES = [(1, 1), (3, 7), (40, 7), (50, 22)]       # N * T = 280 > one 256-thread workgroup of the fold; 1100 > 1024
 
 
 @pytest.mark.parametrize('smoothing', [0.0, 0.1])
 @pytest.mark.parametrize('NT', SHAPES)
-@pytest.mark.parametrize('V1', [9, 67, 257, 1027, 128])
+@pytest.mark.parametrize('V1', [3, 9, 67, 257, 1027, 128])
 def test_parity(V1, NT, smoothing, monkeypatch):
     N, T = NT
     for layout in ('tight', 'wide', '3d'):
