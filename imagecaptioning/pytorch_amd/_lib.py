@@ -240,6 +240,16 @@ class Ensemble(C.Structure):
                 ('w', C.c_float * ENSEMBLE_MAX), ('out', c_f)])
 
 
+DISC_MAX = 8           # capmi.h CAPMI_DISC_MAX
+DISC_SUPPRESS, DISC_LISTENER = 0, 1
+
+
+class Disc(C.Structure):
+    """capmi_disc (include/capmi.h): the slot rows of B * cur hypotheses -> their pragmatic rows"""
+    _fields_ = ([(k, C.c_int) for k in ('B', 'D1', 'cur', 'V1', 'ld_in', 'ld_out', 'mode')] + [('lambda', C.c_float)] +
+                [(k, c_f) for k in ('in', 'present', 'out')])
+
+
 class Ppo(C.Structure):
     """capmi_ppo (include/capmi.h): the PPO structure loss of one rollout, forward and backward"""
     _fields_ = ([(k, C.c_int) for k in ('N', 'L', 'V1', 'n', 'ld_new', 'ld_old', 'ld_grad', 'per_row')] +
@@ -429,6 +439,7 @@ SIGNATURES = {
                                  C.POINTER(AdaAttGrads), _P],
     'capmi_adaatt_decode_step': [C.POINTER(AdaAttWeights), C.POINTER(AdaAttStep), _I, _I, _P, _P, _P, _P, _P],
     'capmi_ensemble_logprobs': [C.POINTER(Ensemble), _P],
+    'capmi_disc_combine': [C.POINTER(Disc), _P],
     'capmi_ppo_loss_fwd': [C.POINTER(Ppo), _P],
     'capmi_ppo_loss_bwd': [C.POINTER(Ppo), _P],
     'capmi_xe_loss_fwd': [C.POINTER(XeLoss), _P],

@@ -2,7 +2,7 @@
 import torch
 import torch.nn as nn
 
-from imagecaptioning.pytorch_amd import att_trace, cbs, mbr, sbs
+from imagecaptioning.pytorch_amd import att_trace, cbs, disc, mbr, sbs
 
 BAD_ENDINGS = ['a', 'an', 'the', 'in', 'for', 'at', 'of', 'with', 'before', 'after', 'on', 'upon', 'near', 'to', 'is',
                'are', 'am', 'the']       # AttModel.py:27
@@ -39,6 +39,9 @@ class CaptionModel(nn.Module):
     # ---- mode='score' (imagecaptioning.pytorch_amd.score): log p(caption | image) of GIVEN captions; test-time only, no gradient
     last_score = None           # dict of device tensors (logp, len, tok_logp, perplexity) after such a call
 
+    # ---- opt['distractors'] (imagecaptioning.pytorch_amd.disc): discriminative decoding against other images of the batch
+    last_disc = None            # {'distractors' (device int64 [B, D]), 'lambda', 'mode'} after such a call
+
     def _score(self, fc_feats, att_feats, seqs, att_masks=None, opt=None):
         """``model(fc_feats, att_feats, seqs, att_masks, mode='score', opt={...})``: the joint log-probability of the given captions,
         [B, n] for seqs [B, n, L] / [B * n, L], or S [C, B] for seqs [C, L] with opt['pairing'] = 'cross' (score.score_captions:
@@ -49,6 +52,10 @@ class CaptionModel(nn.Module):
 
     def _sample_entry(self, *args, **kwargs):
         opt = kwargs.get('opt') or (args[3] if len(args) > 3 else None)
+        if self.last_disc is not None:
+            self.last_disc = None
+        if disc.wanted(opt):
+            return self._sample_disc(opt, *args[:3], **{k: v for k, v in kwargs.items() if k != 'opt'})
         if self.last_cbs is not None:
             self.last_cbs = None
         if cbs.wanted(opt):
@@ -67,6 +74,38 @@ class CaptionModel(nn.Module):
             return self._sample_traced(*args, **kwargs)
         mbr.check_options(self, opt)                        # every refusal, before any device work
         return mbr.apply(self, opt, self._sample_traced(*args, **kwargs))
+
+    def _sample_disc(self, opt, fc_feats, att_feats, att_masks=None):
+        """A sample call with opt['distractors'] (disc.py): every refusal first, then the stepper-driven search the options ask for
+        -- constrained, stochastic or plain / diverse beam search, else the host-stepped samplers -- on a DiscStepper over the
+        family's single-step decoder.  The families' one-call rollouts are not used.  Eval numerics, no gradient."""
+        from imagecaptioning.pytorch_amd import beam
+        B = (att_feats if torch.is_tensor(att_feats) and att_feats.dim() > 1 else fc_feats).shape[0]
+        req = disc.check_options(self, opt, B)                  # cbs.prepare's refusals included, before any device work
+        method = opt.get('sample_method', 'greedy')
+        if method == 'sbs':
+            sbs.check_options(self, opt)
+        if mbr.wanted(opt):
+            mbr.check_options(self, opt)
+        for name in ('last_cbs', 'last_rerank', 'last_sbs', 'last_attention'):
+            if getattr(self, name) is not None:
+                setattr(self, name, None)
+        self._cbs_req = req.cbs
+        try:
+            with torch.no_grad():
+                make = disc.make_stepper(self, req, fc_feats, att_feats, att_masks, self.seq_length)
+                if req.cbs is not None:
+                    out = self._sample_cbs(make, B, opt)
+                elif method == 'sbs':
+                    out = self._sample_sbs(make, B, opt)
+                elif opt.get('beam_size', 1) > 1 and method in ('greedy', 'beam_search'):
+                    out = beam.beam_search_steps(self, make, B, self.vocab_size + 1, self.seq_length, opt, req.device)
+                else:
+                    out = self._sample_with_options(make, B, opt)
+        finally:
+            self._cbs_req = None
+        self.last_disc = {'distractors': req.distractors_dev, 'lambda': req.lam, 'mode': req.mode}
+        return mbr.apply(self, opt, out) if mbr.wanted(opt) else out
 
     def _sample_traced(self, *args, **kwargs):
         opt = kwargs.get('opt') or (args[3] if len(args) > 3 else None)

@@ -61,6 +61,11 @@ DEFAULTS = dict(
     # median rank; score_json names a file {"<image id>": ["a caption", ...]} of captions to score under the model (words outside
     # the vocabulary: UNK, or dropped under constraints_oov drop); score_norm: 'none' the joint log-probability, 'length' per token
     self_retrieval=0, retrieval_pool=1000, score_norm='none', score_json='',
+    # discriminative decoding (opt['distractors'], imagecaptioning/pytorch_amd/disc.py; not flags of the reference).  disc_lambda in
+    # [0, 1] turns it on (below 0, the default: off; 1 is the plain decoder): every image of an eval batch is decoded against
+    # disc_distractors (1..7) other images of the batch, picked by disc_pick 'nearest' (cosine similarity of the mean-pooled region
+    # features) or 'random' (seeded by seed); disc_mode: 'suppress' | 'listener'
+    disc_lambda=-1.0, disc_distractors=1, disc_mode='suppress', disc_pick='nearest',
     # data (synthetic only: the reference's h5/lmdb loaders are outside the hot path)
     input_synthetic=1, vocab_size=9487, synthetic_regions=36, synthetic_images=200,
     # real precomputed features (captioning/data/feature_loader.py; opts.py:23-37 of the reference)

@@ -3,6 +3,7 @@
 // log space.  See include/capmi.h (capmi_ensemble_logprobs) for the contract and the edge cases.  The member rows are cut as row_sweep.h has
 // it; both passes spell its sweep order out (see the kernel).
 #include "host_common.h"
+#include "lse_online.h"
 #include "row_sweep.h"
 
 using namespace capmi;
@@ -21,51 +22,6 @@ struct EnsArgs {
     int rows, V1, ld_in, ld_out;
     int vec;                           // every member's rows share one alignment mod 16 bytes: float4 body
 };
-
-// (max, sum exp(x - max)) folded with x.  A NaN x leaves the max alone and reaches the sum; while the max is still -inf the
-// sum stays 0 without forming -inf - -inf.
-__device__ __forceinline__ void online1(float &m, float &s, float x) {
-    const float nm = fmaxf(m, x);
-    const float base = nm == -INFINITY ? 0.f : nm;
-    s = s * __expf(m - base) + __expf(x - base);
-    m = nm;
-}
-__device__ __forceinline__ void online4(float &m, float &s, f32x4 x) {
-    const float nm = fmaxf(m, fmaxf(fmaxf(x.x, x.y), fmaxf(x.z, x.w)));
-    const float base = nm == -INFINITY ? 0.f : nm;
-    s = s * __expf(m - base) + ((__expf(x.x - base) + __expf(x.y - base)) + (__expf(x.z - base) + __expf(x.w - base)));
-    m = nm;
-}
-
-// block-wide max of M values at once (one barrier pair instead of M), then the rescaled sums likewise
-template <int M>
-__device__ __forceinline__ void block_lse(float (&m)[M], float (&s)[M], float *scratch /* [2][M][ENS_W] */) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-        const float wm = wave_max(m[i]);
-        if (lane == 0) scratch[i * ENS_W + wid] = wm;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-        float r = scratch[i * ENS_W];
-#pragma unroll
-        for (int q = 1; q < ENS_W; ++q) r = fmaxf(r, scratch[i * ENS_W + q]);
-        const float base = r == -INFINITY ? 0.f : r;
-        const float ws = wave_sum(s[i] * __expf(m[i] - base));
-        if (lane == 0) scratch[(M + i) * ENS_W + wid] = ws;
-        m[i] = r;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-        float r = 0.f;
-#pragma unroll
-        for (int q = 0; q < ENS_W; ++q) r += scratch[(M + i) * ENS_W + q];
-        s[i] = r;
-    }
-}
 
 // out = log sum_i exp(a_i) with a_i = (x_i - max_i) - c_i, c_i = log(sum_i) - log w_i, as m + log sum_i exp(a_i - m).
 // x_i - max_i is exact for inputs near the row maximum (logits offset by 1e4 keep their digits); all a_i = -inf gives -inf.
@@ -123,7 +79,7 @@ __global__ __launch_bounds__(ENS_T) void ensemble_logprobs_kernel(const EnsArgs 
     for (int v = sp.tail + tid; v < V1; v += ENS_T)
 #pragma unroll
         for (int i = 0; i < M; ++i) online1(m[i], s[i], row[i][v]);
-    block_lse<M>(m, s, s_red);
+    block_lse<M, ENS_W>(m, s, s_red);
     float c[M];
 #pragma unroll
     for (int i = 0; i < M; ++i) c[i] = __logf(s[i]) - e.log_w[i];

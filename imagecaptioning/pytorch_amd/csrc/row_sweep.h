@@ -1,5 +1,5 @@
 // What the kernels that walk a [rows, V1] float matrix one workgroup per row share (xe_loss.hip, ppo.hip, distill.hip, ensemble.hip,
-// score.hip): the cut of a row on its own 16-byte grid, the sweep over that cut, and the fixed-order double fold of a finish kernel.
+// score.hip, disc.hip): the cut of a row on its own 16-byte grid, the sweep over that cut, and the fixed-order double fold of a finish kernel.
 // Internal, device side.  The payloads stay with their kernels, the three running-logsumexp conventions among them.
 //
 // A row base does not sit on a 16-byte boundary (V1 is odd in general), so a row is cut into [0, head) scalar, [head, tail) as nv

@@ -1449,3 +1449,41 @@ def retrieval_rank(S, target, log_post=True):
     post = torch.empty(C, dtype=_f32, device=S.device) if log_post else None
     check(lib.capmi_retrieval_rank(ptr(S), ld, C, I, ptr(target), ptr(rank), ptr(post), stream_ptr()), 'capmi_retrieval_rank')
     return rank, post
+
+
+# ---- discriminative decoding (disc.DiscStepper; capmi.h capmi_disc_combine, disc.hip) ---------------------------------------------
+DISC_MODES = {'suppress': _lib.DISC_SUPPRESS, 'listener': _lib.DISC_LISTENER}
+
+
+def disc_combine(logits, present, lam, mode, B, D1, cur, out=None):
+    """capmi_disc_combine: logits float32 [B * D1 * cur, V1] (slot-major: row (b * D1 + d) * cur + j; rows may be strided), present
+    uint8 [B, D1] (column 0 the target) -> out float32 [B * cur, V1], the pragmatic row of every hypothesis (capmi.h has the
+    formulas of mode 'suppress' / 'listener' and the edge cases).  One launch, nothing reads the device."""
+    if mode not in DISC_MODES:
+        raise _lib.CapmiError("disc_combine: mode is 'suppress' or 'listener' (got %r)" % (mode,))
+    B, D1, cur, lam = int(B), int(D1), int(cur), float(lam)
+    if not 1 <= D1 <= _lib.DISC_MAX:
+        raise _lib.CapmiError('disc_combine: 1..%d slots per image (got %d)' % (_lib.DISC_MAX, D1))
+    if not 0.0 <= lam <= 1.0:
+        raise _lib.CapmiError('disc_combine: lambda lies in [0, 1] (got %r)' % (lam,))
+    ld_in = _rows_of(logits, 'disc_combine: logits')
+    rows, V1 = logits.shape
+    if B < 0 or cur < 0 or rows != B * D1 * cur or V1 < 1:
+        raise _lib.CapmiError('disc_combine: logits [B * D1 * cur, V1] = [%d, V1 >= 1] expected (got %s)' % (B * D1 * cur, tuple(logits.shape)))
+    _chk(present)
+    if present.dtype != torch.uint8 or tuple(present.shape) != (B, D1):
+        raise _lib.CapmiError('disc_combine: present uint8 [B, D1] = [%d, %d] expected (got %s %s)' % (B, D1, present.dtype, tuple(present.shape)))
+    if out is None:
+        out = torch.empty(B * cur, V1, dtype=_f32, device=logits.device)
+    ld_out = _rows_of(out, 'disc_combine: out')
+    if tuple(out.shape) != (B * cur, V1):
+        raise _lib.CapmiError('disc_combine: out [B * cur, V1] = [%d, %d] expected (got %s)' % (B * cur, V1, tuple(out.shape)))
+    if rows == 0:
+        return out
+    d = _lib.Disc()
+    d.B, d.D1, d.cur, d.V1, d.ld_in, d.ld_out, d.mode = B, D1, cur, V1, ld_in, ld_out, DISC_MODES[mode]
+    setattr(d, 'lambda', lam)
+    setattr(d, 'in', logits.data_ptr())
+    d.present, d.out = present.data_ptr(), out.data_ptr()
+    check(lib.capmi_disc_combine(C.byref(d), stream_ptr()), 'capmi_disc_combine')
+    return out

@@ -15,6 +15,8 @@ The fast paths (one native call per rollout / per beam search) do not go through
   Att2in2Stepper  capmi_att2in2_decode_step (Att2in2Core.forward, AttModel.py:750-790, eval numerics)
   AdaAttStepper   capmi_adaatt_decode_step  (AdaAttCore.forward, AttModel.py:604-613, eval numerics)
   EnsembleStepper M member steppers + capmi_ensemble_logprobs (AttEnsemble.get_logprobs_state, AttEnsemble.py:45-53)
+
+disc.DiscStepper (discriminative decoding, opt['distractors']) wraps any of them the way EnsembleStepper wraps its members.
 """
 import ctypes as C
 

@@ -44,6 +44,15 @@ image and keeps the one with the highest expected CIDEr-D / BLEU-4 against the o
 as for --sample_n 1; every prediction gains 'mbr_choice' and 'mbr_expected', and <eval_results_dir>/<id>_<split>_mbr.npz holds
 image_id, choice [images], expected [images, N] and candidates [images, N, L].
 
+--disc_lambda X [--disc_distractors D] [--disc_mode suppress|listener] [--disc_pick nearest|random] (discriminative decoding,
+imagecaptioning/pytorch_amd/disc.py): every image of an eval batch is decoded against D <= 7 other images of the same batch, so that
+its caption tells it from them -- opt['distractors'] with lambda = X in [0, 1] (1: the plain decoder; the flag absent: off).  nearest
+picks the D images whose mean-pooled region features have the highest cosine similarity to the image's, random draws them with
+--seed; a batch with fewer than D + 1 images leaves the missing slots empty.  Every prediction gains 'distractors' (image ids);
+<eval_results_dir>/<id>_<split>_disc.json holds the settings and the distractors per image.  It combines with --language_eval,
+--beam_size, --sample_n_method sbs, --constraints_json and --self_retrieval 1 (one command then shows what the option is for: the
+R@1 of the captions it decodes), not with --dump_attention.
+
     python -m imagecaptioning.pytorch_amd.tools.eval --caption_model updown --beam_size 5 --num_images 20 [--start_from DIR | --model FILE]
 """
 import json
@@ -66,13 +75,15 @@ def eval_kwargs_of(opt):
     return {k: getattr(opt, k) for k in SAMPLE_KEYS if hasattr(opt, k)}
 
 
-def eval_split_n(model, n_predictions, fc, att, att_masks, data, opt):
+def eval_split_n(model, n_predictions, fc, att, att_masks, data, opt, extra=None):
     """eval_utils.eval_split_n (eval_utils.py:228-290): sample_n captions per image by beam search ('bs'), sampling
     ('sample' / 'gumbel' / 'top<k|p>'), stochastic beam search ('sbs': distinct captions, drawn without replacement), diverse beam
     search ('dbs') or diverse sampling ('d<method>').  Returns the token rows of
-    what it decoded, int64 [B, sample_n, L] on the device (finished beams padded with 0), in the order of the appended predictions."""
+    what it decoded, int64 [B, sample_n, L] on the device (finished beams padded with 0), in the order of the appended predictions.
+    extra: further options of every decode of the batch (--disc_lambda: the batch's distractors)."""
     from captioning.utils import misc
     kw = eval_kwargs_of(opt)
+    kw.update(extra or {})
     sample_n, method, beam_size = opt.sample_n, opt.sample_n_method, opt.beam_size
     with torch.no_grad():
         if method == 'bs':                                                  # :243-252
@@ -240,6 +251,56 @@ class ConstraintSet:
         with open(path, 'w') as f:
             json.dump({'overall': self.summary(),
                        'images': [{'image_id': i, 'constraints_satisfied': s, 'constraints_total': t} for i, s, t in self.rows]}, f)
+        return path
+
+
+class Distractors:
+    """--disc_lambda: the distractors of every eval batch (disc.pick_nearest / disc.pick_random), the decode options that carry them,
+    and the image ids they stand for, per evaluated image"""
+
+    PICKS = ('nearest', 'random')
+
+    def __init__(self, lam, D=1, mode='suppress', pick='nearest', seed=1234):
+        from imagecaptioning.pytorch_amd import disc
+        if not 0.0 <= float(lam) <= 1.0:
+            raise ValueError('--disc_lambda lies in [0, 1], got %r' % (lam,))
+        if not 1 <= int(D) <= disc.D_MAX:
+            raise ValueError('--disc_distractors is a number of images in 1..%d, got %r' % (disc.D_MAX, D))
+        if mode not in disc.MODES:
+            raise ValueError("--disc_mode is 'suppress' or 'listener', got %r" % (mode,))
+        if pick not in self.PICKS:
+            raise ValueError("--disc_pick is 'nearest' or 'random', got %r" % (pick,))
+        self.lam, self.D, self.mode, self.pick, self.seed = float(lam), int(D), mode, pick, int(seed)
+        self.gen = torch.Generator().manual_seed(self.seed)
+        self.rows = {}
+
+    @classmethod
+    def load(cls, opt):
+        lam = getattr(opt, 'disc_lambda', -1.0)
+        if lam is None or lam < 0:
+            return None
+        return cls(lam, getattr(opt, 'disc_distractors', 1), getattr(opt, 'disc_mode', 'suppress'), getattr(opt, 'disc_pick', 'nearest'),
+                   getattr(opt, 'seed', 1234))
+
+    def for_batch(self, att, att_masks, infos, keep):
+        """-> the decode options of this batch; the kept images' distractor ids are noted (one small transfer per batch)"""
+        from imagecaptioning.pytorch_amd import disc
+        if self.pick == 'nearest':
+            table = disc.pick_nearest(att, att_masks, self.D)
+        else:
+            table = disc.pick_random(att.shape[0], self.D, self.gen)
+        for k, row in enumerate(table.tolist()[:keep]):
+            self.rows[infos[k]['id']] = [infos[j]['id'] for j in row if j >= 0]
+        return dict(distractors=table, disc_lambda=self.lam, disc_mode=self.mode)
+
+    def settings(self):
+        return {'disc_lambda': self.lam, 'disc_distractors': self.D, 'disc_mode': self.mode, 'disc_pick': self.pick, 'seed': self.seed}
+
+    def write(self, opt, split):
+        path = _results_path(opt, split, 'disc.json')
+        with open(path, 'w') as f:
+            json.dump({'settings': self.settings(),
+                       'images': [{'image_id': i, 'distractors': d} for i, d in self.rows.items()]}, f)
         return path
 
 
@@ -444,6 +505,10 @@ def eval_split(model, crit, loader, opt):
         raise NotImplementedError('--constraints_json decodes one caption per image: it does not combine with --sample_n > 1 or --rerank')
     retr = SelfRetrieval.load(opt, cons, rerank_kw)
     given = CaptionScores.load(opt, model.vocab, model.seq_length)
+    dist = Distractors.load(opt)
+    if dist is not None and dump is not None:
+        raise NotImplementedError('--dump_attention does not combine with --disc_lambda: a discriminative call steps every '
+                                  'hypothesis under several images and keeps no per-word attention')
     if hasattr(loader, 'reset_iterator'):
         loader.reset_iterator(split)                                                                           # eval_utils.py:145
     num_images = opt.num_images
@@ -461,6 +526,10 @@ def eval_split(model, crit, loader, opt):
         kw.update(rerank_kw)
         if cons is not None:
             kw['constraints'] = cons.for_batch(data['infos'])
+        disc_kw = {}
+        if dist is not None:
+            disc_kw = dist.for_batch(att, att_masks, data['infos'], max(0, min(len(data['infos']), num_images - n)))
+            kw.update(disc_kw)
         if dump is not None:
             kw['return_attention'] = 1
             boxes = batch_boxes(loader, opt, data, att.shape[1], dev)
@@ -509,6 +578,8 @@ def eval_split(model, crit, loader, opt):
                 preds[-1].update(mbr_choice=mbr_choice[k], mbr_expected=mbr_expected[k])
             if cons is not None:
                 preds[-1].update(constraints_satisfied=cbs_sat[k], constraints_total=cbs_total[k])
+            if dist is not None:
+                preds[-1]['distractors'] = dist.rows.get(preds[-1]['image_id'], [])
         if retr is not None or given is not None:
             kept = max(0, min(len(data['infos']), num_images - n))
             if retr is not None:
@@ -517,7 +588,10 @@ def eval_split(model, crit, loader, opt):
                 given.add_batch(model, fc, att, att_masks, data['infos'], kept)
         if sample_n > 1:                                                                                       # :199-200
             first = len(n_preds)
-            rows = eval_split_n(model, n_preds, fc, att, att_masks, data, opt)                                # :198
+            rows = eval_split_n(model, n_preds, fc, att, att_masks, data, opt, disc_kw)                       # :198
+            if dist is not None:
+                for p in n_preds[first:]:
+                    p['distractors'] = dist.rows.get(p['image_id'], [])
             if div is not None:          # the same cut at num_images as the single-caption pass; the rows stay on the device
                 div.add_batch(data['infos'][:keep], rows[:keep])
                 if sent is not None:
@@ -533,6 +607,8 @@ def eval_split(model, crit, loader, opt):
         print('reranking written to', redump.write(opt, split))
     if cons is not None:
         print('constraints: %s written to %s' % (cons.summary(), cons.write(opt, split)))
+    if dist is not None:
+        print('discriminative decoding: %s written to %s' % (dist.settings(), dist.write(opt, split)))
     if retr is not None:
         retr.finish(model)
         print('self-retrieval: %s written to %s' % (retr.summary(), retr.write(opt, split)))

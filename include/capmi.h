@@ -1398,6 +1398,33 @@ typedef struct capmi_ensemble {
 int capmi_ensemble_logprobs(const capmi_ensemble *e, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Discriminative decoding (disc.py): the row a search sees for a hypothesis whose token history was stepped under the target image
+ * (slot 0) and under up to CAPMI_DISC_MAX - 1 distractor images (slots 1 .. D1 - 1).  For hypothesis (b, j), j < cur, with
+ *   l_i[v] = in[(b * D1 + i) * cur + j, v] - logsumexp_v in[(b * D1 + i) * cur + j, v]     (every slot is normalised here)
+ *   lt = l_0, P = {i >= 1 : present[b, i]}, D' = |P|, w = 1 - lambda:
+ *   mode 0 (suppress): out[b * cur + j, v] = lt[v] - w * (logsumexp_{i in P} l_i[v] - log D')
+ *   mode 1 (listener): out[b * cur + j, v] = lt[v] + w * (lt[v] - logsumexp_{i in P or i = 0} l_i[v])
+ *   D' = 0 or lambda = 1: out = lt (the slots behind the target are not read).
+ * The sum over the slots runs in log space, m + log sum_i exp(l_i - m): a column that is tiny under every distractor stays finite,
+ * and for finite inputs the output is finite.  lt[v] = -inf gives -inf.  A column that is -inf under every distractor of P (and
+ * finite under the target) gives +inf in mode 0 -- no distractor can say the word -- and lt[v] in mode 1.  NaN propagates.
+ * Absent slots (present == 0) are not read; present[b, 0] is taken as 1.
+ * rows == 0 (B or cur 0): success, nothing launched.  CAPMI_EINVAL: D1 outside 1..CAPMI_DISC_MAX, a negative B or cur, V1 <= 0,
+ * ld_in or ld_out below V1, a mode other than 0 / 1, a NULL pointer, lambda outside [0, 1] or not finite, out overlapping in.
+ * One workgroup per hypothesis, two sweeps over its present slot rows (float4 loads when the slot rows share their alignment mod
+ * 16 bytes, i.e. cur * ld_in is a multiple of 4 or D1 = 1); no atomics, the result does not depend on arrival order.
+ * ------------------------------------------------------------------------------------------- */
+#define CAPMI_DISC_MAX 8
+typedef struct capmi_disc {
+    int B, D1, cur, V1, ld_in, ld_out, mode;   /* D1 = 1 + D slots per image; mode 0 suppress, 1 listener */
+    float lambda;
+    const float *in;          /* [B * D1 * cur, V1] logits, slot-major as above, row stride ld_in */
+    const uint8_t *present;   /* [B, D1]; column 0 is the target and must be 1 */
+    float *out;               /* [B * cur, V1], row stride ld_out; may not overlap in */
+} capmi_disc;
+int capmi_disc_combine(const capmi_disc *d, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * PPO structure loss (PPOLoss.forward, captioning/modules/losses.py:267-357): a clipped policy ratio plus a KL penalty against a
  * frozen old policy, over the N = B * n sampled rows of one rollout (n samples per image, image-major).  Row (i, t), t < L:
  *   m[i,t]  = 1 for t == 0, else (seq[i, t-1] > 0)                           (the end step still counts)
