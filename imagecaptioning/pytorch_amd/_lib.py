@@ -411,6 +411,7 @@ SIGNATURES = {
     'capmi_mha_fwd_qslabs': [_P, _I, _I, _I64, _P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     'capmi_mha_bwd_slabs': [_P, _I, _I64, _I, _P, _I, _P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     'capmi_gemm_group_tn': [_P, _I, _P, _I64, _P],
+    'capmi_mha_plan': [_I] * 7 + [_P] * 4,
     'capmi_split_halves': [_P, _I, _I64, _P, _P, _P, _P, _I, _I, _P],
     'capmi_meanpool_fwd': [_P, _P, _P, _I, _I, _I, _P],
     'capmi_meanpool_bwd': [_P, _P, _P, _I, _I, _I, _I, _P],

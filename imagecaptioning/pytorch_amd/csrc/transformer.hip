@@ -1281,6 +1281,20 @@ int capmi_mha_bwd_slabs(const float *d_o, int do_splits, int64_t do_stride, int 
     return 0;
 }
 
+int capmi_mha_plan(int bwd, int Nq, int q_per_kv, int Tq, int Tk, int h, int dk, int *CH, int *threads, int *mfma, int64_t *lds) {
+    // the launch shape capmi_mha_fwd* / capmi_mha_bwd* take for these sizes: the same three functions, nothing launched
+    if (!CH || !threads || !mfma || !lds || Nq <= 0 || q_per_kv <= 0 || Nq % q_per_kv || Tq <= 0 || Tk <= 0 || h <= 0 || dk <= 0 || dk % 4)
+        return CAPMI_EINVAL;
+    const int64_t fixed = (int64_t)(bwd ? 4 : 2) * Tk * (dk + 4);
+    const int64_t per = bwd ? (int64_t)2 * (dk + 4) + 3 * (Tk + 1) + 1 : (int64_t)(dk + 4) + (Tk + 1) + 2;
+    const int ch = mha_chunk(q_per_kv * Tq, fixed, per);
+    *CH = ch;
+    *threads = mha_threads(ch, Tk, (int64_t)(Nq / q_per_kv) * h);
+    *mfma = mha_on_mfma(ch);
+    *lds = (fixed + (int64_t)ch * per) * (int64_t)sizeof(float);
+    return *lds > 160 * 1024 ? CAPMI_EINVAL : 0;
+}
+
 int capmi_embed_pe_fwd(const int64_t *tok, int tok_ld, const float *E, const float *pe, const float *drop, float *x, int N,
                        int T, int D, int pos0, void *stream) {
     if (!tok || !E || !pe || !x || N <= 0 || T <= 0 || D <= 0 || pos0 < 0) return CAPMI_EINVAL;

@@ -1020,6 +1020,10 @@ int capmi_mha_bwd_slabs(const float *d_o, int do_splits, int64_t do_stride, int 
                         const float *v, int ldkv, int kstride, const float *p, const float *drop, float *dq, int dq_stride,
                         float *dk_out, float *dv_out, int dkv_ld, int dkv_stride, int accumulate, int Nq, int q_per_kv, int Tq,
                         int Tk, int h, int dk, void *stream);
+/* Host only, launches nothing: the launch shape the forward (bwd = 0) or backward (bwd = 1) entry points above choose for these
+ * sizes -- CH query rows per LDS pass, threads per workgroup, mfma (1: contractions on the matrix pipe), lds bytes of dynamic
+ * LDS.  Returns CAPMI_EINVAL where the launchers refuse the sizes (more than 160 KB of LDS, dk % 4, Nq % q_per_kv). */
+int capmi_mha_plan(int bwd, int Nq, int q_per_kv, int Tq, int Tk, int h, int dk, int *CH, int *threads, int *mfma, int64_t *lds);
 /* x[r,t,:] = E[tok[r,t]]*sqrt(D) + pe[pos0+t,:], then * drop (TransformerModel.py:215, 231-233) */
 int capmi_embed_pe_fwd(const int64_t *tok, int tok_ld, const float *E, const float *pe, const float *drop, float *x,
                        int N, int T, int D, int pos0, void *stream);
