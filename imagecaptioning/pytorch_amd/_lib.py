@@ -310,6 +310,7 @@ _I, _F, _P, _U64, _I64 = C.c_int, C.c_float, C.c_void_p, C.c_uint64, C.c_int64
 DECODE_NO_REPEAT, DECODE_NO_BAD_ENDING, DECODE_BLOCK_TRIGRAMS = 1, 2, 4      # capmi.h CAPMI_DECODE_*
 ROWS_L2NORM_DMAX = 8192       # capmi.h CAPMI_ROWS_L2NORM_DMAX
 ROWS_F32, ROWS_BF16, ROWS_FP16 = 0, 1, 2      # capmi.h CAPMI_ROWS_*: the element format of the resident store's rows
+TRUNCATE_MINP, TRUNCATE_EPS, TRUNCATE_ETA, TRUNCATE_TYP, TRUNCATE_STREAM = 0, 1, 2, 3, 256      # capmi.h CAPMI_TRUNCATE_*
 SELECT_RAW = 256       # capmi.h CAPMI_SELECT_RAW: OR into the select `mode` -- the stored rows are the logits, not the log-probabilities
 
 # name -> argtypes (restype is always int unless noted).  Must list EVERY symbol of include/capmi.h:
@@ -393,6 +394,7 @@ SIGNATURES = {
     'capmi_beam_diversity': [_P, _P, _I, _I, _I, _P, _I, _I, _F, _P],
     'capmi_column_penalty': [_P, _I, _I, _P, _I, _I, _F, _P],
     'capmi_select_logp': [_P, _I, _I, _I, _I, _I, _F, _P, _U64, _P, _I, _P, _P, _P, _P, _I, _P, _P],
+    'capmi_truncate_rows': [_P, _I, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _I64, _P, _P],
     'capmi_layernorm_fwd': [_P] * 6 + [_I, _I, _F, _P],
     'capmi_layernorm_bwd': [_P] * 6 + [_I, _P, _I, _I, _F, _P],
     'capmi_layernorm_bwd_parts_rows': [_I],

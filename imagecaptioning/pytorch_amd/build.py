@@ -35,7 +35,8 @@ def _newest_dep():
 # reward_mix: the reward mix must round like numpy's cw * cider + bw * bleu, likewise.
 # region_rows: the box area is a sort key and must round like numpy's separate float32 operations, likewise.
 # resident: the row norm of norm_att_feat must round like numpy's x * x followed by its float32 add.reduce, likewise.
-EXTRA_FLAGS = {'region_rows.hip': ['-ffp-contract=off'], 'resident.hip': ['-ffp-contract=off'],'gemm_x3.hip': ['-fno-slp-vectorize'], 'gemm_x3w.hip': ['-fno-slp-vectorize'], 'gemm_lc.hip': ['-fno-slp-vectorize'], 'sampler.hip': ['-fno-slp-vectorize'], 'decode_opts.hip': ['-ffp-contract=off'], 'reward_mix.hip': ['-ffp-contract=off']}
+# truncate: x / T - max must be exactly 0 at the row maximum (the token every rule keeps) and the same bits in both arms, likewise.
+EXTRA_FLAGS = {'truncate.hip': ['-ffp-contract=off'],'region_rows.hip': ['-ffp-contract=off'], 'resident.hip': ['-ffp-contract=off'],'gemm_x3.hip': ['-fno-slp-vectorize'], 'gemm_x3w.hip': ['-fno-slp-vectorize'], 'gemm_lc.hip': ['-fno-slp-vectorize'], 'sampler.hip': ['-fno-slp-vectorize'], 'decode_opts.hip': ['-ffp-contract=off'], 'reward_mix.hip': ['-ffp-contract=off']}
 
 
 def build(force=False, verbose=True):

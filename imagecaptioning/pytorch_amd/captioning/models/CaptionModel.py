@@ -52,6 +52,9 @@ class CaptionModel(nn.Module):
 
     def _sample_entry(self, *args, **kwargs):
         opt = kwargs.get('opt') or (args[3] if len(args) > 3 else None)
+        if opt:
+            from imagecaptioning.pytorch_amd import decode
+            decode.check_truncation(self, opt)                  # min-p / epsilon / eta / typical sampling: every refusal first
         if self.last_disc is not None:
             self.last_disc = None
         if disc.wanted(opt):

@@ -12,6 +12,11 @@ class LossWrapper(torch.nn.Module):
         super().__init__()
         self.opt = opt
         self.model = model
+        from ..models.utils import parse_truncation
+        if parse_truncation(getattr(opt, 'train_sample_method', 'sample')) is not None:
+            raise NotImplementedError('train_sample_method %r: min-p, epsilon, eta and typical sampling are test-time options '
+                                      '(sample_method / sample_n_method); training rollouts have no truncation hook and no '
+                                      'gradient through one' % opt.train_sample_method)
         if getattr(opt, 'label_smoothing', 0) > 0:
             self.crit = losses.LabelSmoothing(smoothing=opt.label_smoothing)
         else:

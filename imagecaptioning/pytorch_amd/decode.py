@@ -23,7 +23,34 @@ _MODES = {'greedy': 0, 'sample': 1}
 def wants_options(opt):
     """True when `opt` asks for something only the host-stepped samplers implement."""
     return bool(opt.get('decoding_constraint', 0) or opt.get('block_trigrams', 0) or opt.get('remove_bad_endings', 0)
-                or opt.get('group_size', 1) > 1)
+                or opt.get('group_size', 1) > 1 or truncation(opt) is not None)
+
+
+_KINDS = {'minp': _lib.TRUNCATE_MINP, 'eps': _lib.TRUNCATE_EPS, 'eta': _lib.TRUNCATE_ETA, 'typ': _lib.TRUNCATE_TYP}
+
+
+def truncation(opt):
+    """(rule, parameter) when opt['sample_method'] names min-p, epsilon, eta or typical sampling, else None"""
+    from .captioning.models.utils import parse_truncation
+    return parse_truncation(opt.get('sample_method', 'greedy')) if opt else None
+
+
+def check_truncation(model, opt):
+    """the refusals of a sample call with a truncation rule, before any device work"""
+    if truncation(opt) is None:
+        return
+    name = opt['sample_method']
+    if model.training:
+        raise NotImplementedError('sample_method %r is a test-time option: call model.eval() first' % name)
+    if not opt.get('output_logsoftmax', 1):
+        raise NotImplementedError('output_logsoftmax=0 is only used by margin structure losses; sample_method %r truncates '
+                                  'log-probabilities' % name)
+
+
+def _truncate(trunc, x, q, rows, V1, temperature, store, store_ld, unf, st):
+    """q = the renormalised truncated distribution of the rows of x (capmi_truncate_rows); store: the rows of x times the flags"""
+    check(lib.capmi_truncate_rows(ptr(x), V1, ptr(q), V1, rows, V1, _KINDS[trunc[0]], float(trunc[1]), float(temperature), None,
+                                  None, store, store_ld, unf, st), 'capmi_truncate_rows')
 
 
 def _filter(top_k, top_p):
@@ -63,6 +90,8 @@ def sample_steps(model, stepper, B, L, opt, dev, seed=0):
     bad = torch.tensor(sorted(getattr(model, 'bad_endings_ix', [])), dtype=torch.long, device=dev)
     gumbel = opt.get('_gumbel')                                              # test hook: injected noise [L,N,V1]
     flt = _filter(top_k, top_p)
+    trunc = truncation(opt)
+    q = torch.empty(N, V1, dtype=_f32, device=dev) if trunc else None
     any_flags = False
     st = stream_ptr()
     for t in range(L):
@@ -75,6 +104,13 @@ def sample_steps(model, stepper, B, L, opt, dev, seed=0):
             # first B rows are ever blocked (AttModel.py:310, 322); kept
             check(lib.capmi_decode_constrain(ptr(logp), N, V1, _prev(seq, t), L, flags, ptr(bad), bad.numel(), ptr(seq), L, t, B,
                                              st), 'capmi_decode_constrain')
+        if trunc:
+            # the rule on softmax(logp / T), then a plain draw from q; seqLogprobs keeps the constrained rows, as for every sampler
+            _truncate(trunc, logp, q, N, V1, temperature, seq_logp.data_ptr() + 4 * t * V1, L * V1, ptr(unf), st)
+            check(lib.capmi_select_logp(ptr(q), N, V1, t, L, 1, 1.0, None if gumbel is None else ptr(gumbel[t]),
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(seq), L, ptr(it), ptr(unf), None, None, 0, None, st),
+                  'capmi_select_logp')
+            continue
         check(lib.capmi_select_logp(ptr(logp), N, V1, t, L, _MODES[mode], float(temperature),
                                     None if gumbel is None else ptr(gumbel[t]), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(seq), L,
                                     ptr(it), ptr(unf), ptr(seq_logp), None, 0, flt, st), 'capmi_select_logp')
@@ -109,6 +145,8 @@ def diverse_sample_steps(model, stepper, B, L, opt, dev, seed=0):
     bad = torch.tensor(sorted(getattr(model, 'bad_endings_ix', [])), dtype=torch.long, device=dev)
     gumbel = opt.get('_gumbel')                                              # test hook [L,G,B,V1]
     flt = _filter(top_k, top_p)
+    trunc = truncation(opt)
+    q = torch.empty(B, V1, dtype=_f32, device=dev) if trunc else None
     st = stream_ptr()
     for t in range(L):
         it = it_tab.t().reshape(N)                                           # rows image-major: b*G + g
@@ -125,7 +163,11 @@ def diverse_sample_steps(model, stepper, B, L, opt, dev, seed=0):
             if flags:
                 check(lib.capmi_decode_constrain(ptr(x), B, V1, _prev(seq_tab[g], t), L, flags, ptr(bad), bad.numel(),
                                                  ptr(seq_tab[g]), L, t, B, st), 'capmi_decode_constrain')
-            check(lib.capmi_select_logp(ptr(x), B, V1, t, L, _MODES[mode], 1.0, None if gumbel is None else ptr(gumbel[t, g]),
+            if trunc:
+                # per group, after the column penalties; T = 1, the rows are tempered already.  sel_logp = q[token], the nucleus
+                # convention (CaptionModel.py:396-398)
+                _truncate(trunc, x, q, B, V1, 1.0, None, 0, None, st)
+            check(lib.capmi_select_logp(ptr(q if trunc else x), B, V1, t, L, _MODES[mode], 1.0, None if gumbel is None else ptr(gumbel[t, g]),
                                         (int(seed) + 0x9E3779B97F4A7C15 * g) & 0xFFFFFFFFFFFFFFFF, ptr(seq_tab[g]), L,
                                         ptr(it_tab[g]), ptr(unf[g]), None, ptr(slp_tab[g]), 1, flt, st), 'capmi_select_logp')
     return seq_tab.transpose(0, 1).reshape(N, L), slp_tab.transpose(0, 1).reshape(N, L)

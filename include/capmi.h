@@ -952,6 +952,30 @@ int capmi_select_logp(const float *logp, int N, int V1, int step, int L, int mod
                       uint64_t seed, int64_t *seq, int seq_ld, int64_t *it_next, uint8_t *unfinished, float *seq_logp,
                       float *sel_logp, int sel_unmasked, const capmi_sample_filter *filter, void *stream);
 
+/* Truncation samplers: min-p, epsilon and eta sampling (Hewitt et al. 2022), locally typical sampling (Meister et al. 2022).
+ * x = row r of logp [N, ld] (already constrained log-probabilities, any per-row shift), p = softmax(x / temperature),
+ * H = -sum p log p (0 log 0 = 0), p_max = max p.  The kept set of `kind` with parameter `param`:
+ *   MINP (0 < a <= 1)   p_v >= a p_max
+ *   EPS  (0 < e < 1)    p_v >= e, and every token with p_v == p_max
+ *   ETA  (0 < e < 1)    p_v >= min(e, sqrt(e) exp(-H)), and every token with p_v == p_max
+ *   TYP  (0 < tau < 1)  s_v <= s*, where s_v = |-log p_v - H| and s* is the smallest score with mass{v : s_v <= s*} >= tau
+ *                       (tokens tied at s* are all kept)
+ * Entries at -inf have p = 0 and are never kept; a row needs one finite entry.  q [N, ld_q], q != logp and no overlap:
+ * q_v = log(p_v / sum_kept p) on the kept set, -inf elsewhere, so a draw of the rule is capmi_select_logp on q in mode 1 at
+ * temperature 1 with no filter.  kept [N] (optional): the size of the kept set; kept_mass [N] (optional): sum_kept p.
+ * store (optional): store[r * store_ld + v] = logp[r, v] * unfinished[r] (unfinished NULL: the row as it is; a finished row
+ * holds x * 0, -inf * 0 = NaN, AttModel.py:345), the flag as it stands BEFORE this step's select -- what capmi_select_logp
+ * writes through seq_logp.  Rows with V1 <= 12288 whose logp rows are all 16-byte aligned stay in registers across the passes;
+ * any other row, and every row with CAPMI_TRUNCATE_STREAM OR-ed into `kind`, is re-read from memory per pass.  On the same row
+ * (same alignment) the two arms give the same bits. */
+#define CAPMI_TRUNCATE_MINP 0
+#define CAPMI_TRUNCATE_EPS 1
+#define CAPMI_TRUNCATE_ETA 2
+#define CAPMI_TRUNCATE_TYP 3
+#define CAPMI_TRUNCATE_STREAM 256
+int capmi_truncate_rows(const float *logp, int ld, float *q, int ld_q, int N, int V1, int kind, float param, float temperature,
+                        int *kept, float *kept_mass, float *store, int64_t store_ld, const uint8_t *unfinished, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Transformer captioner building blocks (BASELINE configs[3]; TransformerModel.py).  The contractions
  * (QKV / output projections, FFN, generator) run on capmi_gemm_f32 with fused bias / ReLU / dropout /
