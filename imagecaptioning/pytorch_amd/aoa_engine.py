@@ -686,11 +686,3 @@ class BeamDecoder:
         from . import beam
         beam.reorder_rows(self.state, self.state_alt, parent, self.B, cur, self.N // self.B)
         self.state, self.state_alt = self.state_alt, self.state
-
-
-def sample_beam(model, P, att_feats, att_masks, h, L, opt, fc_feats=None):
-    from . import beam
-    g = AoAGraph(P, {}, h, 0.0, 0.0, False, 0, variant=getattr(model, 'variant', None))
-    g.prepare(att_feats, att_masks, fc_feats)     # refined features are shared by every decoder (diverse groups)
-    return beam.beam_search_steps(model, lambda rows: BeamDecoder(g, rows), g.B, P['embed.0.weight'].shape[0], L, opt,
-                                  att_feats.device)

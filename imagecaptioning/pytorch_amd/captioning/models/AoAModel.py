@@ -11,7 +11,6 @@ from .CaptionModel import CaptionModel
 from .TransformerModel import _FF, _LayerNorm, _Sublayer, _clones
 from imagecaptioning.pytorch_amd import aoa_engine as engine
 from imagecaptioning.pytorch_amd._lib import CapmiError
-from imagecaptioning.pytorch_amd.ops import clip_len
 
 
 FF_HIDDEN = 2048         # PositionwiseFeedForward(rnn_size, 2048, 0.1): constants of the reference (AoAModel.py:119)
@@ -65,10 +64,10 @@ class _Core(nn.Module):
 class _Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, cfg, fc_feats, att_feats, att_masks, *params):
-        P = dict(zip(model._param_names, [p.detach() for p in params]))
+        P = model._params()
         ctx.sink = cfg.pop('_sink', None)
         ctx.set_materialize_grads(False)        # the dense log-prob gradient may be undefined (sparse route)
-        grads = model._flat.grad_views if model._flat is not None else {k: torch.empty_like(v) for k, v in P.items()}
+        grads = model._grad_targets(P)
         g = engine.AoAGraph(P, grads, model.num_heads, model.drop_prob_lm, model.dropout_aoa, model.training, model._next_seed(),
                             variant=model.variant)
         g.prepare(att_feats, att_masks, fc_feats)
@@ -121,7 +120,6 @@ class AoAModel(CaptionModel):
         self.dropout_aoa = getattr(opt, 'dropout_aoa', 0.3)
         self.seq_length = getattr(opt, 'max_length', 20) or opt.seq_length
         self.vocab = opt.vocab
-        self.ss_prob = 0.0
         R = self.rnn_size
         self.embed = nn.Sequential(nn.Embedding(self.vocab_size + 1, self.input_encoding_size), nn.ReLU(),
                                    nn.Dropout(self.drop_prob_lm))
@@ -140,17 +138,19 @@ class AoAModel(CaptionModel):
         blocks = sorted({n[:n.index('.self_attn.') + len('.self_attn')] for n in names if n.startswith('refiner.') and '.self_attn.linears.' in n})
         return [['%s.linears.%d.%s' % (b, i, kind) for i in range(3)] for b in blocks for kind in ('weight', 'bias')]
 
+    _rollout_filters = True         # top<k|p> run inside the rollout's select launch
+
+    def _feeds(self, fc_feats, att_feats, att_masks):
+        return att_feats, att_masks, fc_feats
+
     def _run(self, cfg, att_feats, att_masks, clipped=False, fc_feats=None):
-        if not att_feats.is_cuda:
-            raise CapmiError('the capmi backend runs on a HIP device only; there is no CPU path')
-        if att_masks is not None and not clipped:
-            ml = clip_len(att_masks)
-            att_feats, att_masks = att_feats[:, :ml], att_masks[:, :ml].float().contiguous()
-        params = self._param_list()
+        self._device_check(att_feats)
+        if not clipped:
+            att_feats, att_masks = self._clip_regions(att_feats, att_masks)
         from imagecaptioning.pytorch_amd import sparse_logp
         cfg = dict(cfg)
         cfg['_sink'] = sink = sparse_logp.LogpSink()
-        seq, logp = _Fn.apply(self, cfg, self._fc(fc_feats), att_feats.float().contiguous(), att_masks, *params)
+        seq, logp = _Fn.apply(self, cfg, self._fc(fc_feats), att_feats, att_masks, *self._param_list())
         return seq, sparse_logp.attach(logp, sink)
 
     def _fc(self, fc_feats):
@@ -162,100 +162,38 @@ class AoAModel(CaptionModel):
         return fc_feats.float().contiguous()
 
     def _forward(self, fc_feats, att_feats, seq, att_masks=None):
-        B = att_feats.size(0)
-        if seq.ndim == 3:
-            seq = seq.reshape(-1, seq.shape[2])
-        seq = seq.long().contiguous()
+        seq, T_eff = self._labels(seq)
         N, T = seq.shape
-        zero_cols = (seq[:, 1:].sum(0) == 0).nonzero()
-        T_eff = int(zero_cols[0]) + 1 if zero_cols.numel() else T
-        cfg = dict(n=N // B, T=T_eff, L=T, forced=seq, teacher=True)
-        if self.training and self.ss_prob > 0.0:
-            # AttModel.py:145-154: the coin flips of all steps here, the draws inside the rollout (_ss_coin / _ss_gumbel: test hooks)
-            coin = self._ss_coin if getattr(self, '_ss_coin', None) is not None else \
-                torch.rand(T_eff, N, device=att_feats.device) < self.ss_prob
-            cfg['ss_mode'] = torch.where(coin, 1, 2).to(torch.uint8).contiguous()
-            cfg['seed'] = self._next_seed()
-            if getattr(self, '_ss_gumbel', None) is not None:
-                cfg['gumbel'] = self._ss_gumbel
+        cfg = dict(n=N // att_feats.size(0), T=T_eff, L=T, forced=seq, teacher=True)
+        cfg.update(self._scheduled_sampling(T_eff, N, att_feats.device))
         _, logp = self._run(cfg, att_feats, att_masks, fc_feats=fc_feats)
         return logp
 
     def _decode_stepper(self, fc_feats, att_feats, att_masks, L):
-        """make(rows_per_image) -> aoa_engine.BeamDecoder, the factory _sample builds inline for the decode options (masks clipped to
-        the longest row).  Used by AttEnsemble; L is the caller's decode length (the decoder has none)."""
-        if not att_feats.is_cuda:
-            raise CapmiError('the capmi backend runs on a HIP device only; there is no CPU path')
-        if att_masks is not None:
-            ml = clip_len(att_masks)
-            att_feats, att_masks = att_feats[:, :ml], att_masks[:, :ml].float().contiguous()
-        P = dict(zip(self._param_names, [p.detach() for p in self._param_list()]))
-        att_feats = att_feats.float().contiguous()
-        fc = self._fc(fc_feats)
+        """make(rows_per_image) -> aoa_engine.BeamDecoder on features refined once, here: every decoder of the factory shares them
+        (diverse groups).  Masks clipped to the longest row; L is the caller's decode length (the decoder has none)."""
+        self._device_check(att_feats)
+        g = engine.AoAGraph(self._params(), {}, self.num_heads, 0.0, 0.0, False, 0, variant=self.variant)
+        with torch.no_grad():
+            g.prepare(*self._clip_regions(att_feats, att_masks), self._fc(fc_feats))
+        return lambda rows: engine.BeamDecoder(g, rows)
 
-        def make(rows):
-            g = engine.AoAGraph(P, {}, self.num_heads, 0.0, 0.0, False, 0, variant=self.variant)
-            g.prepare(att_feats, att_masks, fc)
-            return engine.BeamDecoder(g, rows)
-        return make
-
-    def _sample(self, fc_feats, att_feats, att_masks=None, opt={}):
-        method = opt.get('sample_method', 'greedy')
-        from imagecaptioning.pytorch_amd import decode
-        raw = not opt.get('output_logsoftmax', 1)
-        if raw and ((opt.get('beam_size', 1) > 1 and method in ('greedy', 'beam_search')) or decode.wants_options(opt)):
-            # AttModel.py:171-175: the margin structure losses read raw LOGITS (loss_wrapper.py:31-37 samples them with sample_n and no
-            # decode-time option); the sampled / greedy rollout stores them (r5, CAPMI_SELECT_RAW), beam search and the option
-            # samplers return log-probabilities -- refuse rather than hand those to a margin loss
-            raise NotImplementedError('output_logsoftmax=0 is implemented for the sampled / greedy rollout; beam search and the '
-                                      'decode-time options of %s return log-probabilities' % type(self).__name__)
-        cbs = self._cbs_req is not None
-        if not cbs and opt.get('beam_size', 1) > 1 and method in ('greedy', 'beam_search'):
-            if not att_feats.is_cuda:
-                raise CapmiError('the capmi backend runs on a HIP device only; there is no CPU path')
-            from imagecaptioning.pytorch_amd import beam
-            beam.refuse_train_beam(self, opt)       # train_beam_size > 1: no log-probs without a graph
-            if att_masks is not None:
-                ml = clip_len(att_masks)
-                att_feats, att_masks = att_feats[:, :ml], att_masks[:, :ml].float().contiguous()
-            with torch.no_grad():
-                P = dict(zip(self._param_names, [p.detach() for p in self._param_list()]))
-                return engine.sample_beam(self, P, att_feats.float().contiguous(), att_masks, self.num_heads, self.seq_length, opt,
-                                          self._fc(fc_feats))
-        from .utils import parse_sample_method
-        if cbs or method == 'sbs' or decode.wants_options(opt):
-            if not att_feats.is_cuda:
-                raise CapmiError('the capmi backend runs on a HIP device only; there is no CPU path')
-            if att_masks is not None:
-                ml = clip_len(att_masks)
-                att_feats, att_masks = att_feats[:, :ml], att_masks[:, :ml].float().contiguous()
-            P = dict(zip(self._param_names, [p.detach() for p in self._param_list()]))
-
-            def make(rows):
-                g = engine.AoAGraph(P, {}, self.num_heads, 0.0, 0.0, False, 0, variant=self.variant)
-                g.prepare(att_feats.float().contiguous(), att_masks, self._fc(fc_feats))
-                return engine.BeamDecoder(g, rows)
-            return (self._sample_cbs if cbs else self._sample_sbs if method == 'sbs' else self._sample_with_options)(
-                make, att_feats.size(0), opt)
-        mode, temperature, top_k, top_p = parse_sample_method(method, opt.get('temperature', 1.0))
+    def _rollout(self, fc_feats, att_feats, att_masks, opt, how, raw):
+        mode, temperature, top_k, top_p = how
         L = self.seq_length
         cfg = dict(n=int(opt.get('sample_n', 1)), T=L, L=L, mode=mode, temperature=temperature,
                    seed=self._next_seed(), gumbel=opt.get('_gumbel'), top_k=top_k, top_p=top_p)
         if raw:
             cfg['raw'] = True
-        if mode == 'greedy' and not self.training and not torch.is_grad_enabled() and opt.get('_graph', True) and att_feats.is_cuda:
+        if mode == 'greedy' and not self.training and not torch.is_grad_enabled() and opt.get('_graph', True):
             # deterministic, no gradient, launch-bound on the host: replay a captured hipGraph (graphs.py)
             if not hasattr(self, '_graphs'):
                 from imagecaptioning.pytorch_amd.graphs import GraphedDecode
                 self._graphs = GraphedDecode()
             gcfg = dict(cfg, seed=0)
-            if att_masks is not None:                 # the data-dependent clip (a host sync) stays outside the graph
-                ml = clip_len(att_masks)
-                att_feats, att_masks = att_feats[:, :ml], att_masks[:, :ml].float().contiguous()
-            fc = self._fc(fc_feats)
-            if fc is None:
-                return self._graphs(('greedy', cfg['n'], L, raw), lambda a, m: self._run(gcfg, a, m, clipped=True),
-                                    (att_feats.float().contiguous(), att_masks))
-            return self._graphs(('greedy', cfg['n'], L, raw), lambda a, m, f: self._run(gcfg, a, m, clipped=True, fc_feats=f),
-                                (att_feats.float().contiguous(), att_masks, fc))
+            feeds = self._clip_regions(att_feats, att_masks)    # the data-dependent clip (a host sync) stays outside the graph
+            if not self.variant.mean_feats:
+                feeds += (self._fc(fc_feats),)
+            return self._graphs(('greedy', cfg['n'], L, raw),
+                                lambda a, m, f=None: self._run(gcfg, a, m, clipped=True, fc_feats=f), feeds)
         return self._run(cfg, att_feats, att_masks, fc_feats=fc_feats)

@@ -55,10 +55,6 @@ class AttEnsemble(CaptionModel):
         if torch.is_grad_enabled():
             raise RuntimeError('AttEnsemble is evaluation only: run it under torch.no_grad()')
 
-    def _next_seed(self):
-        self._rng_calls += 1
-        return (torch.initial_seed() * 0x9E3779B97F4A7C15 + self._rng_calls * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
-
     def _w(self):
         return self.weights.tolist()
 
@@ -76,12 +72,8 @@ class AttEnsemble(CaptionModel):
         """Teacher-forced mixture log-probs [N,T,V1] (AttModel._forward, AttModel.py:126-164, over get_logprobs_state :45-53):
         each member's own forward, then one launch; from the first all-pad column on (:158-159) the rows stay exactly 0."""
         self._eval_only()
-        if seq.ndim == 3:
-            seq = seq.reshape(-1, seq.shape[2])
-        seq = seq.long().contiguous()
+        seq, T_eff = self._labels(seq)
         N, T = seq.shape
-        zero_cols = (seq[:, 1:].sum(0) == 0).nonzero()
-        T_eff = int(zero_cols[0]) + 1 if zero_cols.numel() else T
         V1 = self.vocab_size + 1
         members = [m._forward(fc_feats, att_feats, seq, att_masks).detach().contiguous() for m in self.models]
         for lp in members:

@@ -22,7 +22,7 @@ from imagecaptioning.pytorch_amd import updown_engine as engine
 from imagecaptioning.pytorch_amd import ops
 from imagecaptioning.pytorch_amd import sparse_logp
 
-from .utils import parse_sample_method, clip_len      # noqa: E402
+from .utils import clip_len      # noqa: E402
 
 
 class Attention(nn.Module):
@@ -78,6 +78,10 @@ class UpDownCore(nn.Module):
 class AttModel(StepAPI, RecurrentModel):
     _use_bn_refusal = None
     _trace_refusal = None           # return_attention: alpha of the rollouts / steppers
+    _rollout_filters = True         # top<k|p> run inside the rollout's select kernel
+    # output_logsoftmax=0 with beam search or the decode options is not refused here: the searches and diverse sampling return
+    # log-probabilities all the same, decode.sample_steps raises
+    _raw_refusal = False
 
     def __init__(self, opt):
         super().__init__()
@@ -185,47 +189,22 @@ class AttModel(StepAPI, RecurrentModel):
                             None if att_masks is None else att_masks.float(), bn=self._region_bn(False))
         return pr.fc, pr.att, pr.p_att, pr.att_masks
 
-    def _sample(self, fc_feats, att_feats, att_masks=None, opt={}):
-        """Greedy / sampling rollout (AttModel.py:258-352)."""
-        self._device_check(fc_feats)
-        sample_method = opt.get('sample_method', 'greedy')
-        beam_size = opt.get('beam_size', 1)
-        temperature = opt.get('temperature', 1.0)
-        sample_n = int(opt.get('sample_n', 1))
-        group_size = opt.get('group_size', 1)
-        if self._cbs_req is not None:
-            return self._sample_cbs(self._stepper(fc_feats, att_feats, att_masks), fc_feats.size(0), opt)
-        if beam_size > 1 and sample_method in ('greedy', 'beam_search'):
-            from imagecaptioning.pytorch_amd import beam
-            if beam.wants_train_beam(self, opt):
-                if self._trace_req is not None:
-                    raise NotImplementedError('return_attention is not implemented for the training beam search (train_beam_size > 1)')
-                # train mode with gradients (loss_wrapper.py, train_beam_size > 1): search, finalise on the device, forced replay
-                return beam.updown_beam_train(self, fc_feats, att_feats, att_masks, opt)
-            return self._sample_beam(fc_feats, att_feats, att_masks, opt)
-        from imagecaptioning.pytorch_amd import decode
-        if sample_method == 'sbs':
-            return self._sample_sbs(self._stepper(fc_feats, att_feats, att_masks), fc_feats.size(0), opt)
-        if decode.wants_options(opt):
-            # _diverse_sample (AttModel.py:270-271) / decoding constraints (:293-330): host-stepped, same kernels
-            return self._sample_with_options(self._stepper(fc_feats, att_feats, att_masks), fc_feats.size(0), opt)
-        mode, temperature, top_k, top_p = parse_sample_method(sample_method, temperature)
-        B = fc_feats.size(0)
-        N = B * sample_n
-        L = self.seq_length
-        K = clip_len(att_masks, att_feats.shape[1])
-        cfg = dict(n=sample_n, T=L, L=L, mode=mode, temperature=temperature, seed=self._next_seed(), top_k=top_k, top_p=top_p)
-        if not opt.get('output_logsoftmax', 1):   # AttModel.py:171-175, 265: seqLogprobs holds the LOGITS (margin structure losses)
-            cfg['raw'] = True
-        cfg.update(self._dropout_masks(B, K, N, L, fc_feats.device))
+    def _sample_beam(self, fc_feats, att_feats, att_masks=None, opt={}):
+        """The native search (beam.sample_beam), or in train mode with gradients the training beam search"""
+        from imagecaptioning.pytorch_amd import beam
+        if beam.wants_train_beam(self, opt):
+            if self._trace_req is not None:
+                raise NotImplementedError('return_attention is not implemented for the training beam search (train_beam_size > 1)')
+            # loss_wrapper.py, train_beam_size > 1: search, finalise on the device, forced replay
+            return beam.updown_beam_train(self, fc_feats, att_feats, att_masks, opt)
+        return beam.sample_beam(self, fc_feats, att_feats, att_masks, opt)
+
+    def _rollout(self, fc_feats, att_feats, att_masks, opt, how, raw):
+        more = dict(top_k=how[2], top_p=how[3])
         forced = opt.get('_forced_seq')           # test hook: teacher-force a sampled sequence
         if forced is not None:
-            cfg.update(mode='forced', forced=forced.long().contiguous())
-        gumbel = opt.get('_gumbel')               # test hook: injected noise
-        if gumbel is not None:
-            cfg['gumbel'] = gumbel
-        seq, logp = self._run(cfg, fc_feats, att_feats, att_masks)
-        return seq, logp
+            more.update(mode='forced', forced=forced.long().contiguous())
+        return super()._rollout(fc_feats, att_feats, att_masks, opt, how, raw, **more)
 
     def scst_rollouts(self, fc_feats, att_feats, att_masks=None, sample_n=5, temperature=1.0, _gumbel=None):
         """Both rollouts of one self-critical step in ONE pass (MI355X-first: the decode GEMMs run on
@@ -263,10 +242,6 @@ class AttModel(StepAPI, RecurrentModel):
             hyp_img = torch.cat([torch.arange(N, device=dev) // n, torch.arange(B, device=dev)]).to(torch.int32)
             cache[key] = (row_img, row_mode, hyp_img)
         return cache[key][:2]
-
-    def _sample_beam(self, fc_feats, att_feats, att_masks=None, opt={}):
-        from imagecaptioning.pytorch_amd.beam import sample_beam
-        return sample_beam(self, fc_feats, att_feats, att_masks, opt)
 
 
 class UpDownModel(AttModel):

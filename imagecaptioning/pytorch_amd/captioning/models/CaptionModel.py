@@ -3,6 +3,7 @@ import torch
 import torch.nn as nn
 
 from imagecaptioning.pytorch_amd import att_trace, cbs, disc, mbr, sbs
+from imagecaptioning.pytorch_amd.ops import clip_len
 
 BAD_ENDINGS = ['a', 'an', 'the', 'in', 'for', 'at', 'of', 'with', 'before', 'after', 'on', 'upon', 'near', 'to', 'is',
                'are', 'am', 'the']       # AttModel.py:27
@@ -211,6 +212,94 @@ class CaptionModel(nn.Module):
     @bad_endings_ix.setter
     def bad_endings_ix(self, ix):
         self.__dict__['_bad_endings_ix'] = [int(i) for i in ix]
+
+    # ---- the one sample dispatch of the single-model families ("Adding a decode option").  A family states what differs:
+    #     _feeds(fc_feats, att_feats, att_masks)               the inputs it reads, the one whose device and batch size count first
+    #     _rollout_filters                                     its one-call rollout applies top<k|p> itself (else: host-stepped)
+    #     _raw_refusal                                         output_logsoftmax=0 outside the plain rollout is refused
+    #     _decode_stepper(fc_feats, att_feats, att_masks, L)   the factory of every stepper-driven arm: rows_per_image -> stepper
+    #     _sample_beam(fc_feats, att_feats, att_masks, opt)    beam search (default: the stepper-driven one, eval / no_grad only)
+    #     _rollout(fc_feats, att_feats, att_masks, opt, how, raw)
+    #                                                          its free-running rollout; how = parse_sample_method's tuple
+    ss_prob = 0.0
+    _rollout_filters = False
+    _raw_refusal = True
+
+    def _feeds(self, fc_feats, att_feats, att_masks):
+        return fc_feats, att_feats, att_masks
+
+    def _device_check(self, t):
+        if not t.is_cuda:
+            from imagecaptioning.pytorch_amd._lib import CapmiError
+            raise CapmiError('the capmi backend runs on a HIP device only (got a %s tensor); there is no CPU path' % t.device.type)
+
+    def _sample(self, fc_feats, att_feats, att_masks=None, opt={}):
+        """AttModel._sample (AttModel.py:258-352): constrained, stochastic or plain beam search and the host-stepped options on the
+        family's single-step decoder, else its one-call rollout.  Every decode option is classified here, once."""
+        from .utils import parse_sample_method
+        from imagecaptioning.pytorch_amd import decode
+        method = opt.get('sample_method', 'greedy')
+        stochastic = method == 'sbs'
+        is_beam = opt.get('beam_size', 1) > 1 and method in ('greedy', 'beam_search')
+        how = (None, 1.0, 0, 0.0) if (is_beam or stochastic) else parse_sample_method(method, opt.get('temperature', 1.0))
+        stepped = decode.wants_options(opt) or (not self._rollout_filters and bool(how[2] or how[3]))
+        raw = not opt.get('output_logsoftmax', 1)
+        if raw and self._raw_refusal and (is_beam or stepped):
+            # AttModel.py:171-175: the margin structure losses read raw LOGITS (loss_wrapper.py:31-37 samples them with sample_n and no
+            # decode-time option); the one-call rollout stores them (r5, CAPMI_SELECT_RAW), beam search and the host-stepped option
+            # samplers return log-probabilities -- refuse rather than hand those to a margin loss
+            raise NotImplementedError('output_logsoftmax=0 is implemented for the sampled / greedy rollout; beam search and the '
+                                      'decode-time options of %s return log-probabilities' % type(self).__name__)
+        first = self._feeds(fc_feats, att_feats, att_masks)[0]
+        self._device_check(first)
+        if self._cbs_req is not None or stochastic or (stepped and not is_beam):
+            make = self._decode_stepper(fc_feats, att_feats, att_masks, self.seq_length)
+            return (self._sample_cbs if self._cbs_req is not None else self._sample_sbs if stochastic else self._sample_with_options)(
+                make, first.size(0), opt)
+        if is_beam:
+            return self._sample_beam(fc_feats, att_feats, att_masks, opt)
+        return self._rollout(fc_feats, att_feats, att_masks, opt, how, raw)
+
+    def _sample_beam(self, fc_feats, att_feats, att_masks=None, opt={}):
+        """AttModel._sample_beam (AttModel.py:218-256) on the family's single-step decoder"""
+        from imagecaptioning.pytorch_amd import beam
+        beam.refuse_train_beam(self, opt)           # train_beam_size > 1: no log-probs without a graph
+        first = self._feeds(fc_feats, att_feats, att_masks)[0]
+        with torch.no_grad():
+            return beam.beam_search_steps(self, self._decode_stepper(fc_feats, att_feats, att_masks, self.seq_length), first.size(0),
+                                          self.vocab_size + 1, self.seq_length, opt, first.device)
+
+    def _clip_regions(self, att_feats, att_masks):
+        """(att_feats, att_masks) cut to the longest mask row, float32 and contiguous (Transformer, AoA).  The cut reads the device:
+        callers keep it outside a captured graph."""
+        if att_masks is not None:
+            ml = clip_len(att_masks)
+            att_feats, att_masks = att_feats[:, :ml], att_masks[:, :ml].float().contiguous()
+        return att_feats.float().contiguous(), att_masks
+
+    # ---- the prologue of a teacher-forced _forward (AttModel.py:126-164)
+    @staticmethod
+    def _labels(seq):
+        """seq [B, n, T] / [N, T] -> (int64 [N, T], T_eff).  AttModel.py:158-159: stop at the first all-pad column.  The labels are an
+        INPUT, so this is one host decision per batch made before anything is enqueued, not a per-step sync."""
+        if seq.ndim == 3:
+            seq = seq.reshape(-1, seq.shape[2])
+        seq = seq.long().contiguous()
+        zero_cols = (seq[:, 1:].sum(0) == 0).nonzero()
+        return seq, int(zero_cols[0]) + 1 if zero_cols.numel() else seq.shape[1]
+
+    def _scheduled_sampling(self, T_eff, N, dev):
+        """the rollout keywords of scheduled sampling (AttModel.py:145-154), {} when it is off: from step 1 on each row feeds, with
+        probability ss_prob, a draw from the model's previous distribution instead of the ground-truth word.  The coin flips are
+        made here for all steps at once (they do not depend on the model), the draws happen inside the rollout."""
+        if not (self.training and self.ss_prob > 0.0):
+            return {}
+        coin = self._ss_coin if getattr(self, '_ss_coin', None) is not None else \
+            torch.rand(T_eff, N, device=dev) < self.ss_prob            # _ss_coin / _ss_gumbel: test hooks
+        cfg = dict(ss_mode=torch.where(coin, 1, 2).to(torch.uint8).contiguous(), seed=self._next_seed())
+        if getattr(self, '_ss_gumbel', None) is not None:
+            cfg['gumbel'] = self._ss_gumbel
+        return cfg
 
     def _sample_sbs(self, make_stepper, B, opt):
         """sample_method 'sbs' on the family's single-step decoder (beam.stochastic_beam_search_steps).  Eval numerics, no gradient."""

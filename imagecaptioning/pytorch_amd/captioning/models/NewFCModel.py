@@ -1,7 +1,6 @@
 """NewFCModel (reference AttModel.py:904-945 over FCModel.LSTMCore 13-42) on the HIP backend -- BASELINE
 configs[0] (configs/fc.yml).  Same parameter names as the reference: embed.weight, fc_embed.{weight,bias},
 _core.i2h/h2h.{weight,bias}, logit.{weight,bias}."""
-import torch
 import torch.nn as nn
 
 from .RecurrentModel import RecurrentModel
@@ -59,37 +58,10 @@ class NewFCModel(RecurrentModel):
         P = self._params()
         return lambda rows: NewFCStepper(P, fc_feats, rows)
 
-    def _sample(self, fc_feats, att_feats, att_masks=None, opt={}):
-        method = opt.get('sample_method', 'greedy')
-        from .utils import parse_sample_method
-        from imagecaptioning.pytorch_amd import decode, beam
-        raw = not opt.get('output_logsoftmax', 1)
-        is_beam = opt.get('beam_size', 1) > 1 and method in ('greedy', 'beam_search')
-        mode, temperature, top_k, top_p = (None, 1.0, 0, 0.0) if (is_beam or method == 'sbs') else parse_sample_method(method, opt.get('temperature', 1.0))
-        if raw and (is_beam or decode.wants_options(opt) or top_k or top_p):
-            # AttModel.py:171-175: the margin structure losses read raw LOGITS (loss_wrapper.py:31-37 samples them with sample_n and no
-            # decode-time option); the one-call rollout stores them (r5, CAPMI_SELECT_RAW), beam search and the host-stepped option
-            # samplers return log-probabilities -- refuse rather than hand those to a margin loss
-            raise NotImplementedError('output_logsoftmax=0 is implemented for the sampled / greedy rollout; beam search and the '
-                                      'decode-time options of %s return log-probabilities' % type(self).__name__)
-        self._device_check(fc_feats)
-        if method == 'sbs' or self._cbs_req is not None:
-            return (self._sample_sbs if method == 'sbs' else self._sample_cbs)(self._stepper(fc_feats), fc_feats.size(0), opt)
-        if is_beam and beam.wants_train_beam(self, opt):
+    def _sample_beam(self, fc_feats, att_feats, att_masks=None, opt={}):
+        from imagecaptioning.pytorch_amd import beam
+        if beam.wants_train_beam(self, opt):
             # train mode with gradients (loss_wrapper.py, train_beam_size > 1): search, finalise on the device, forced replay
             return beam.newfc_beam_train(self, fc_feats, opt)
-        if is_beam:
-            # AttModel._sample_beam on the single-step decoder (the image step is taken once per image, AttModel.py:925-927)
-            with torch.no_grad():
-                return beam.beam_search_steps(self, self._stepper(fc_feats), fc_feats.size(0), self.vocab_size + 1,
-                                              self.seq_length, opt, fc_feats.device)
-        if decode.wants_options(opt) or top_k or top_p:
-            # options the one-call rollout has no hooks for: host-stepped (eval numerics, no gradient)
-            return self._sample_with_options(self._stepper(fc_feats), fc_feats.size(0), opt)
-        cfg = dict(n=int(opt.get('sample_n', 1)), T=self.seq_length, L=self.seq_length, mode=mode,
-                   temperature=temperature, seed=self._next_seed())
-        if raw:
-            cfg['raw'] = True
-        if opt.get('_gumbel') is not None:         # test hook: injected noise [L, N, V1]
-            cfg['gumbel'] = opt['_gumbel']
-        return self._run(cfg, fc_feats)
+        # AttModel._sample_beam on the single-step decoder (the image step is taken once per image, AttModel.py:925-927)
+        return super()._sample_beam(fc_feats, att_feats, att_masks, opt)

@@ -1,10 +1,11 @@
 """RecurrentModel: the host side the LSTM families (UpDown, NewFC, Att2in2, AdaAtt) share -- one autograd.Function around a
-family's one-call rollout, the teacher-forced _forward and the free-running _sample -- and StepAPI, the reference's single-step
-API (init_hidden, get_logprobs_state) for the attention families: NewFC has neither, and callers probe for them with hasattr.
+family's one-call rollout, the teacher-forced _forward and the free-running _rollout of CaptionModel._sample -- and StepAPI, the
+reference's single-step API (init_hidden, get_logprobs_state) for the attention families: NewFC has neither, and callers probe for
+them with hasattr.
 
 A family holds its parameters (nn.Module tree with the reference's names) and states, by overriding:
 
-    _feeds(fc_feats, att_feats, att_masks)    which of the three its rollout reads, as a tuple (default: all)
+    _feeds(fc_feats, att_feats, att_masks)    which of the three its rollout reads, as a tuple (CaptionModel's default: all)
     _make_rollout(P, cfg, *feeds)             cfg -> (engine Rollout, whatever its _rollout_backward wants back)
     _dropout_masks(B, K, N, T, dev)           the keep masks of its dropout sites as Rollout keywords ({} in eval mode)
     _rollout_masks(B, N, T, att_feats, att_masks, dev)
@@ -13,12 +14,13 @@ A family holds its parameters (nn.Module tree with the reference's names) and st
     _stepper(*feeds)                          rows_per_image -> single-step decoder on features prepared once
     _row_stepper(P, pr, fc_feats)             the same for one row per already embedded feature (StepAPI.get_logprobs_state)
 
-and, where it differs, _rollout_backward / _publish_rollout / _sample ("Adding a recurrent family").
+and, where it differs, _rollout_backward / _publish_rollout and the hooks of the sample dispatch: _rollout_filters, _raw_refusal,
+_sample_beam, _rollout (DESIGN.md, "Adding a recurrent family").
 """
 import torch
 
 from .CaptionModel import CaptionModel
-from .utils import parse_sample_method, clip_len
+from .utils import clip_len
 from imagecaptioning.pytorch_amd import _lib, sparse_logp
 from imagecaptioning.pytorch_amd.engine_common import Prepared, RegionBN
 
@@ -96,15 +98,7 @@ class RecurrentModel(CaptionModel):
         steppers, _prepare_feature, beam search, get_logprobs_state and ensemble members are eval-mode prefills."""
         return RegionBN.of_module(self.att_embed, self.use_bn, train) if self.use_bn else None
 
-    def _device_check(self, t):
-        if not t.is_cuda:
-            raise _lib.CapmiError('the capmi backend runs on a HIP device only (got a %s tensor); there is no CPU path'
-                                  % t.device.type)
-
     # ------------------------------------------------------------------ the family's hooks
-    def _feeds(self, fc_feats, att_feats, att_masks):
-        return fc_feats, att_feats, att_masks
-
     def _dropout_masks(self, B, K, N, T, dev):
         return {}
 
@@ -131,62 +125,28 @@ class RecurrentModel(CaptionModel):
         """Teacher-forced log-probs [N,T,V1] (AttModel.py:126-164), scheduled sampling included."""
         feeds = self._feeds(fc_feats, att_feats, att_masks)
         B, dev = feeds[0].size(0), feeds[0].device
-        if seq.ndim == 3:
-            seq = seq.reshape(-1, seq.shape[2])
-        seq = seq.long().contiguous()
+        seq, T_eff = self._labels(seq)
         N, T = seq.shape
-        # AttModel.py:158-159: stop at the first all-pad column.  The labels are an INPUT, so this is one
-        # host decision per batch made before anything is enqueued, not a per-step sync.
-        zero_cols = (seq[:, 1:].sum(0) == 0).nonzero()
-        T_eff = int(zero_cols[0]) + 1 if zero_cols.numel() else T
         cfg = dict(n=N // B, T=T_eff, L=T, mode='forced', forced=seq, teacher=True)
         cfg.update(self._rollout_masks(B, N, T_eff, att_feats, att_masks, dev))
-        if self.training and self.ss_prob > 0.0:
-            # scheduled sampling (AttModel.py:145-154): from step 1 on each row feeds, with probability ss_prob, a draw from
-            # the model's previous distribution instead of the ground-truth word.  The coin flips are made here for all
-            # steps at once (they do not depend on the model), the draws happen inside the rollout.
-            coin = self._ss_coin if getattr(self, '_ss_coin', None) is not None else \
-                torch.rand(T_eff, N, device=dev) < self.ss_prob            # _ss_coin / _ss_gumbel: test hooks
-            cfg['ss_mode'] = torch.where(coin, 1, 2).to(torch.uint8).contiguous()
-            cfg['seed'] = self._next_seed()
-            if getattr(self, '_ss_gumbel', None) is not None:
-                cfg['gumbel'] = self._ss_gumbel
+        cfg.update(self._scheduled_sampling(T_eff, N, dev))
         _, logp = self._run(cfg, *feeds)
         return logp
 
-    def _sample(self, fc_feats, att_feats, att_masks=None, opt={}):
-        """Greedy / sampling rollout (AttModel.py:258-352); beam search and the decode-time options on the stepper."""
-        from imagecaptioning.pytorch_amd import decode, beam
-        self._device_check(att_feats)
-        beam.refuse_train_beam(self, opt)           # train_beam_size > 1: no log-probs without a graph
-        method = opt.get('sample_method', 'greedy')
-        if method == 'sbs' or self._cbs_req is not None:
-            return (self._sample_sbs if method == 'sbs' else self._sample_cbs)(
-                self._stepper(*self._feeds(fc_feats, att_feats, att_masks)), att_feats.size(0), opt)
-        raw = not opt.get('output_logsoftmax', 1)
-        is_beam = opt.get('beam_size', 1) > 1 and method in ('greedy', 'beam_search')
-        mode, temperature, top_k, top_p = (None, 1.0, 0, 0.0) if is_beam else parse_sample_method(method, opt.get('temperature', 1.0))
-        if raw and (is_beam or decode.wants_options(opt) or top_k or top_p):
-            raise NotImplementedError('output_logsoftmax=0 is implemented for the sampled / greedy rollout; beam search and the '
-                                      'decode-time options of %s return log-probabilities' % type(self).__name__)
-        B, feeds = att_feats.size(0), self._feeds(fc_feats, att_feats, att_masks)
-        if is_beam:
-            with torch.no_grad():
-                return beam.beam_search_steps(self, self._stepper(*feeds), B, self.vocab_size + 1, self.seq_length, opt,
-                                              att_feats.device)
-        if decode.wants_options(opt) or top_k or top_p:
-            return self._sample_with_options(self._stepper(*feeds), B, opt)
-        n, L = int(opt.get('sample_n', 1)), self.seq_length
-        cfg = dict(n=n, T=L, L=L, mode=mode, temperature=temperature, seed=self._next_seed(), raw=raw)
-        cfg.update(self._rollout_masks(B, B * n, L, att_feats, att_masks, att_feats.device))
+    def _rollout(self, fc_feats, att_feats, att_masks, opt, how, raw, **more):
+        """Greedy / sampling rollout (AttModel.py:258-352).  more: what a family adds to the rollout's keywords."""
+        feeds = self._feeds(fc_feats, att_feats, att_masks)
+        B, n, L = feeds[0].size(0), int(opt.get('sample_n', 1)), self.seq_length
+        cfg = dict(n=n, T=L, L=L, mode=how[0], temperature=how[1], seed=self._next_seed(), raw=raw)
+        cfg.update(self._rollout_masks(B, B * n, L, att_feats, att_masks, feeds[0].device))
+        cfg.update(more)
         if opt.get('_gumbel') is not None:         # test hook: injected noise [L, N, V1]
             cfg['gumbel'] = opt['_gumbel']
         return self._run(cfg, *feeds)
 
     # ------------------------------------------------------------------ single steps
     def _decode_stepper(self, fc_feats, att_feats, att_masks, L):
-        """make(rows_per_image) -> the family's stepper (= _stepper).  Used by AttEnsemble; L is the caller's decode length (the
-        stepper has none)."""
+        """make(rows_per_image) -> the family's stepper (= _stepper); L is the caller's decode length (the stepper has none)"""
         feeds = self._feeds(fc_feats, att_feats, att_masks)
         self._device_check(feeds[0])
         return self._stepper(*feeds)

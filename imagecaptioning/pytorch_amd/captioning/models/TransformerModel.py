@@ -9,8 +9,6 @@ import torch.nn as nn
 
 from .CaptionModel import CaptionModel
 from imagecaptioning.pytorch_amd import transformer_engine as engine
-from imagecaptioning.pytorch_amd._lib import CapmiError
-from imagecaptioning.pytorch_amd.ops import clip_len
 
 
 def _clones(m, n):
@@ -104,7 +102,7 @@ class _Fn(torch.autograd.Function):
     def forward(ctx, model, att_feats, att_masks, seq, n, sink, seed, raw, *params):
         """seed / raw: None / False for the reference's _forward; _sample's teacher-forced gradient pass hands in the seed its
         rollout drew under and whether that rollout returned logits (explicit arguments: nothing is left on the model)."""
-        P = model._pdict(params)
+        P = model._params()
         ctx.sink = sink
         ctx.set_materialize_grads(False)        # the dense log-prob gradient may be undefined (sparse route)
         grads = model._grad_targets(P)
@@ -155,7 +153,6 @@ class TransformerModel(CaptionModel):
         self.h = getattr(opt, 'num_att_heads', 8)
         self.dropout = getattr(opt, 'dropout', 0.1)
         self.vocab = opt.vocab
-        self.ss_prob = 0.0
         if getattr(opt, 'use_bn', 0):
             raise NotImplementedError('use_bn is outside the BASELINE configs')
         self.att_embed = nn.Sequential(nn.Linear(self.att_feat_size, self.d_model), nn.ReLU(), nn.Dropout(self.drop_prob_lm))
@@ -169,8 +166,13 @@ class TransformerModel(CaptionModel):
         self.tie_encoder_dropout = bool(getattr(opt, 'tie_encoder_dropout', 0)) or os.environ.get('CAPMI_TIE_ENC') == '1'
 
     # ---- plumbing
-    def _pdict(self, params):
-        P = dict(zip(self._param_names, [p.detach() for p in params]))
+    _rollout_filters = True         # top<k|p> run inside transformer_engine.sample's select launch
+
+    def _feeds(self, fc_feats, att_feats, att_masks):
+        return att_feats, att_masks
+
+    def _params(self):
+        P = super()._params()
         P['model.tgt_embed.1.pe'] = self.model.tgt_embed[1].pe[0].contiguous()      # [max_len, D]
         return P
 
@@ -200,21 +202,14 @@ class TransformerModel(CaptionModel):
     def init_hidden(self, bsz):
         return []
 
-    def _clip(self, att_feats, att_masks):
-        if att_masks is not None:
-            ml = clip_len(att_masks)
-            att_feats, att_masks = att_feats[:, :ml].contiguous(), att_masks[:, :ml].contiguous().float()
-        return att_feats.float().contiguous(), att_masks
-
     # ---- reference API
     def _forward(self, fc_feats, att_feats, seq, att_masks=None, _seed=None, _raw=False):
         """TransformerModel._forward (:340-348): log-probs [N,T,V1]."""
-        if not att_feats.is_cuda:
-            raise CapmiError('the capmi backend runs on a HIP device only; there is no CPU path')
-        if seq.ndim == 3:
+        self._device_check(att_feats)
+        if seq.ndim == 3:               # (not _labels: every column runs, and its look at the labels would be a sync in a captured step)
             seq = seq.reshape(-1, seq.shape[2])
         seq = seq.long().contiguous()
-        att_feats, att_masks = self._clip(att_feats, att_masks)
+        att_feats, att_masks = self._clip_regions(att_feats, att_masks)
         n = seq.shape[0] // att_feats.shape[0]
         params = self._param_list()
         from imagecaptioning.pytorch_amd import sparse_logp
@@ -222,15 +217,13 @@ class TransformerModel(CaptionModel):
         return sparse_logp.attach(_Fn.apply(self, att_feats, att_masks, seq, n, sink, _seed, bool(_raw), *params), sink)
 
     def _decode_stepper(self, fc_feats, att_feats, att_masks, L):
-        """make(rows_per_image) -> transformer_engine.Decoder sized for L steps, the factory _sample builds inline for the decode
-        options (masks clipped by _clip).  Used by AttEnsemble, whose seq_length is the L given here."""
-        if not att_feats.is_cuda:
-            raise CapmiError('the capmi backend runs on a HIP device only; there is no CPU path')
-        att_feats, att_masks = self._clip(att_feats, att_masks)
-        P = self._pdict(self._param_list())
+        """make(rows_per_image) -> transformer_engine.Decoder sized for L steps, masks clipped to the longest row"""
+        self._device_check(att_feats)
+        att_feats, att_masks = self._clip_regions(att_feats, att_masks)
+        P = self._params()
         return lambda rows: engine.Decoder(P, att_feats, att_masks, self.h, self.N_enc, self.N_dec, int(L), rows)
 
-    def _sample(self, fc_feats, att_feats, att_masks=None, opt={}):
+    def _rollout(self, fc_feats, att_feats, att_masks, opt, how, raw):
         """AttModel._sample for the Transformer.  Tokens are drawn with the KV-cached decoder under no_grad; when a
         gradient is needed (SCST) the log-probs of the drawn tokens are recomputed by ONE teacher-forced pass.  In train
         mode both run under ONE dropout realisation (same Philox seed; step t of the rollout applies position t's rows of the
@@ -239,42 +232,16 @@ class TransformerModel(CaptionModel):
         step, TransformerModel.py:351-362, and so redraws the masks of earlier positions each step; here a position keeps its
         masks for the whole rollout -- the KV cache's meaning -- which is the same policy-gradient estimator for a slightly
         different, equally valid, noise model.)"""
-        method = opt.get('sample_method', 'greedy')
-        from imagecaptioning.pytorch_amd import decode
-        raw = not opt.get('output_logsoftmax', 1)
-        if raw and ((opt.get('beam_size', 1) > 1 and method in ('greedy', 'beam_search')) or decode.wants_options(opt)):
-            # AttModel.py:171-175: the margin structure losses read raw LOGITS (loss_wrapper.py:31-37 samples them with sample_n and no
-            # decode-time option); the sampled / greedy rollout and its teacher-forced gradient pass return them (r5), beam search
-            # and the option samplers return log-probabilities -- refuse rather than hand those to a margin loss
-            raise NotImplementedError('output_logsoftmax=0 is implemented for the sampled / greedy rollout; beam search and the '
-                                      'decode-time options of %s return log-probabilities' % type(self).__name__)
-        if not att_feats.is_cuda:
-            raise CapmiError('the capmi backend runs on a HIP device only; there is no CPU path')
-        from imagecaptioning.pytorch_amd import beam
-        beam.refuse_train_beam(self, opt)           # train_beam_size > 1: no log-probs without a graph
-        cbs = self._cbs_req is not None
-        if not cbs and opt.get('beam_size', 1) > 1 and method in ('greedy', 'beam_search'):
-            att_feats, att_masks = self._clip(att_feats, att_masks)
-            with torch.no_grad():
-                P = self._pdict(self._param_list())
-                return engine.sample_beam(self, P, att_feats, att_masks, self.h, self.N_enc, self.N_dec, self.seq_length, opt)
-        from .utils import parse_sample_method
-        if cbs or method == 'sbs' or decode.wants_options(opt):
-            att_feats, att_masks = self._clip(att_feats, att_masks)
-            P = self._pdict(self._param_list())
-            return (self._sample_cbs if cbs else self._sample_sbs if method == 'sbs' else self._sample_with_options)(
-                lambda rows: engine.Decoder(P, att_feats, att_masks, self.h, self.N_enc, self.N_dec, self.seq_length, rows),
-                att_feats.size(0), opt)
-        mode, temperature, top_k, top_p = parse_sample_method(method, opt.get('temperature', 1.0))
+        mode, temperature, top_k, top_p = how
         n = int(opt.get('sample_n', 1))
-        att_feats, att_masks = self._clip(att_feats, att_masks)
+        att_feats, att_masks = self._clip_regions(att_feats, att_masks)
         want_grad = torch.is_grad_enabled() and self.training
         drop, drop_seed = None, None
         if want_grad and (self.dropout > 0 or self.drop_prob_lm > 0):
             drop_seed = self._next_seed()
             drop = (self.drop_prob_lm, self.dropout, drop_seed)
         with torch.no_grad():
-            P = self._pdict(self._param_list())
+            P = self._params()
             if mode == 'greedy' and opt.get('_graph', True) and not self.training:
                 # deterministic and launch-bound on the host (~1300 launches): replay a captured hipGraph
                 if not hasattr(self, '_graphs'):
@@ -283,7 +250,7 @@ class TransformerModel(CaptionModel):
                 seq, logp = self._graphs(('greedy', n, self.seq_length, raw),
                                          lambda a, m: engine.sample(P, a, m, self.h, self.N_enc, self.N_dec, self.seq_length,
                                                                     sample_n=n, mode='greedy', raw=raw),
-                                         (att_feats.contiguous(), att_masks))
+                                         (att_feats, att_masks))
             else:
                 seq, logp = engine.sample(P, att_feats, att_masks, self.h, self.N_enc, self.N_dec, self.seq_length, sample_n=n,
                                           mode=mode, temperature=temperature, seed=self._next_seed(),

@@ -8,6 +8,9 @@ A stepper holds the recurrent state of ``B * rows_per_image_max`` hypotheses (im
 
 which is the protocol the Transformer ``Decoder`` and the AoA ``BeamDecoder`` already implement; the host-stepped
 samplers of ``decode.py`` / ``beam.py`` (constrained decoding, diverse sampling, diverse beam search) drive any of them.
+A model hands them out through one factory, ``model._decode_stepper(fc_feats, att_feats, att_masks, L)`` -> ``make(rows_per_image)``:
+the features are prepared once when the factory is made and shared by every stepper it makes.  ``CaptionModel._sample`` builds no
+other; AttEnsemble, score.py and disc.py call the same one.
 The fast paths (one native call per rollout / per beam search) do not go through here.
 
   UpDownStepper   capmi_updown_decode_step  (UpDownCore.forward, AttModel.py:615-640, eval numerics)

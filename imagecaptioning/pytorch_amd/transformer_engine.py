@@ -602,12 +602,3 @@ def sample(P, att_feats, att_masks, h, n_enc, n_dec, L, sample_n=1, mode='greedy
         ops.logsoftmax_select(logits, t, L, mode_i, temperature, None if gumbel is None else gumbel[t], seed, forced, 0, seq, it, unf,
                               seq_logp, sel, live, top_k, top_p)
     return seq, seq_logp
-
-
-def sample_beam(model, P, att_feats, att_masks, h, n_enc, n_dec, L, opt):
-    """AttModel._sample_beam (AttModel.py:218-256) for the Transformer: beam_size hypotheses per image share the image's
-    encoder memory (no repeat_tensors copy), the KV caches follow the beams by parent pointer."""
-    from . import beam
-    B, V1 = att_feats.shape[0], P['model.generator.proj.weight'].shape[0]
-    return beam.beam_search_steps(model, lambda rows: Decoder(P, att_feats, att_masks, h, n_enc, n_dec, L, rows), B, V1, L, opt,
-                                  att_feats.device)
