@@ -311,6 +311,7 @@ DECODE_NO_REPEAT, DECODE_NO_BAD_ENDING, DECODE_BLOCK_TRIGRAMS = 1, 2, 4      # c
 ROWS_L2NORM_DMAX = 8192       # capmi.h CAPMI_ROWS_L2NORM_DMAX
 ROWS_F32, ROWS_BF16, ROWS_FP16 = 0, 1, 2      # capmi.h CAPMI_ROWS_*: the element format of the resident store's rows
 TRUNCATE_MINP, TRUNCATE_EPS, TRUNCATE_ETA, TRUNCATE_TYP, TRUNCATE_STREAM = 0, 1, 2, 3, 256      # capmi.h CAPMI_TRUNCATE_*
+CONTRASTIVE_KMAX = 32      # capmi.h CAPMI_CONTRASTIVE_KMAX
 SELECT_RAW = 256       # capmi.h CAPMI_SELECT_RAW: OR into the select `mode` -- the stored rows are the logits, not the log-probabilities
 
 # name -> argtypes (restype is always int unless noted).  Must list EVERY symbol of include/capmi.h:
@@ -395,6 +396,8 @@ SIGNATURES = {
     'capmi_column_penalty': [_P, _I, _I, _P, _I, _I, _F, _P],
     'capmi_select_logp': [_P, _I, _I, _I, _I, _I, _F, _P, _U64, _P, _I, _P, _P, _P, _P, _I, _P, _P],
     'capmi_truncate_rows': [_P, _I, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _I64, _P, _P],
+    'capmi_contrastive_topk': [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I64, _P],
+    'capmi_contrastive_select': [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _I, _P, _P, _P],
     'capmi_layernorm_fwd': [_P] * 6 + [_I, _I, _F, _P],
     'capmi_layernorm_bwd': [_P] * 6 + [_I, _P, _I, _I, _F, _P],
     'capmi_layernorm_bwd_parts_rows': [_I],

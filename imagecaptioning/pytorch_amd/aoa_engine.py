@@ -682,6 +682,13 @@ class BeamDecoder:
         self._keep = (xt, qn, mu, inv, q, att_o, pre2)           # scratch stays alive until the stream has used it
         return logits
 
+    def hidden(self, rows):
+        """the rows the logit of the last step read, [rows, R] (a view of the carried context; out_res 0 only: with out_res the
+        operand is output + h_att, formed inside the GEMM)"""
+        if self.g.v.out_res:
+            raise CapmiError('BeamDecoder keeps no pre-logit row with out_res 1')
+        return self.state[2, :rows]
+
     def reorder(self, parent, cur):
         from . import beam
         beam.reorder_rows(self.state, self.state_alt, parent, self.B, cur, self.N // self.B)

@@ -96,6 +96,7 @@ class _Fn(torch.autograd.Function):
 class AoAModel(CaptionModel):
     _sbs_refusal = None             # sample_method 'sbs': BeamDecoder is a stepper
     _cbs_refusal = None             # opt['constraints']: likewise
+    _contrastive_refusal = None     # sample_method 'contrastive': the carried context is the logit operand (out_res 1: refused per model)
     graph_step = True      # graph_step.TrainStep captures this family's training iteration into a hipGraph (no host sync in it)
 
     def __init__(self, opt):
@@ -111,6 +112,9 @@ class AoAModel(CaptionModel):
                                       refine=int(bool(getattr(opt, 'refine', 1))), refine_aoa=int(bool(getattr(opt, 'refine_aoa', 1))),
                                       use_ff=int(bool(getattr(opt, 'use_ff', 0))))
         v = self.variant
+        if v.out_res:
+            # logit(output + h_att): the BeamDecoder adds h_att as a second K segment of the logit GEMM, the sum is no kept row
+            self._contrastive_refusal = 'out_res 1 forms the logit operand inside the GEMM, the decoder keeps no pre-logit row'
         self.vocab_size = opt.vocab_size
         self.rnn_size = opt.rnn_size
         self.input_encoding_size = opt.input_encoding_size

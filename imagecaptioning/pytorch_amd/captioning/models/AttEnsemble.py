@@ -25,6 +25,7 @@ from imagecaptioning.pytorch_amd._lib import CapmiError
 class AttEnsemble(CaptionModel):
     _sbs_refusal = 'it is implemented for the single-model families; decode the members one by one'
     _cbs_refusal = _sbs_refusal
+    _contrastive_refusal = 'a mixture has no single hidden state; decode the members one by one'
 
     def __init__(self, models, weights=None):
         super().__init__()

@@ -32,6 +32,10 @@ class CaptionModel(nn.Module):
     # why a model has no stochastic beam search (None: it has one -- every family that runs beam.beam_search_steps on a stepper)
     _sbs_refusal = 'the model has no single-step decoder for the beam driver'
 
+    # ---- opt['sample_method'] = 'contrastive' (decode.contrastive_steps): why a model has no contrastive search (None: it has one --
+    # every family whose stepper keeps the pre-logit rows of its last step, stepper.hidden)
+    _contrastive_refusal = 'its single-step decoder keeps no pre-logit row after a step'
+
     # ---- opt['constraints'] (imagecaptioning.pytorch_amd.cbs): constrained beam search, captions that must contain given words
     last_cbs = None             # dict of device tensors (state, satisfied, total, score), each [B], after such a call
     _cbs_req = None             # cbs.Request (the checked host tables) while such a call runs
@@ -56,6 +60,7 @@ class CaptionModel(nn.Module):
         if opt:
             from imagecaptioning.pytorch_amd import decode
             decode.check_truncation(self, opt)                  # min-p / epsilon / eta / typical sampling: every refusal first
+            decode.check_contrastive(self, opt)                 # contrastive search: likewise
         if self.last_disc is not None:
             self.last_disc = None
         if disc.wanted(opt):
@@ -241,7 +246,7 @@ class CaptionModel(nn.Module):
         method = opt.get('sample_method', 'greedy')
         stochastic = method == 'sbs'
         is_beam = opt.get('beam_size', 1) > 1 and method in ('greedy', 'beam_search')
-        how = (None, 1.0, 0, 0.0) if (is_beam or stochastic) else parse_sample_method(method, opt.get('temperature', 1.0))
+        how = (None, 1.0, 0, 0.0) if (is_beam or stochastic or decode.contrastive(opt)) else parse_sample_method(method, opt.get('temperature', 1.0))
         stepped = decode.wants_options(opt) or (not self._rollout_filters and bool(how[2] or how[3]))
         raw = not opt.get('output_logsoftmax', 1)
         if raw and self._raw_refusal and (is_beam or stepped):
@@ -325,6 +330,9 @@ class CaptionModel(nn.Module):
             # return_attention: the stepper keeps every step's weights, laid out like a rollout's alpha [L, rows, K]
             make_stepper, made = att_trace.recording(make_stepper, self.seq_length)
         with torch.no_grad():
+            if decode.contrastive(opt):
+                # one look-ahead step over contrastive_k candidate rows per image and token (check_contrastive ran first)
+                return decode.contrastive_steps(self, make_stepper(decode.contrastive_params(opt)[1]), B, self.seq_length, opt, dev)
             if opt.get('group_size', 1) > 1:
                 st = make_stepper(int(opt['group_size']))
                 out = decode.diverse_sample_steps(self, st, B, self.seq_length, opt, dev, seed=self._next_seed())

@@ -67,6 +67,7 @@ class _RolloutFn(torch.autograd.Function):
 class RecurrentModel(CaptionModel):
     _sbs_refusal = None             # sample_method 'sbs': every family here has a stepper
     _cbs_refusal = None             # opt['constraints']: likewise
+    _contrastive_refusal = None     # sample_method 'contrastive': every stepper here keeps its pre-logit rows (stepper.hidden)
     ss_prob = 0.0
 
     # why a family refuses use_bn (None: it runs it).  models.setup gives the same reasons for the families outside this base.

@@ -138,6 +138,7 @@ class _Fn(torch.autograd.Function):
 class TransformerModel(CaptionModel):
     _sbs_refusal = None             # sample_method 'sbs': the KV-cached Decoder is a stepper
     _cbs_refusal = None             # opt['constraints']: likewise
+    _contrastive_refusal = "the KV-cached Decoder's pre-logit row (the final LayerNorm output) is a per-step temporary, not a kept buffer"
     graph_step = True      # graph_step.TrainStep captures this family's training iteration into a hipGraph (no host sync in it)
 
     def __init__(self, opt):

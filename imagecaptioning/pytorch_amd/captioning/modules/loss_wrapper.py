@@ -17,6 +17,9 @@ class LossWrapper(torch.nn.Module):
             raise NotImplementedError('train_sample_method %r: min-p, epsilon, eta and typical sampling are test-time options '
                                       '(sample_method / sample_n_method); training rollouts have no truncation hook and no '
                                       'gradient through one' % opt.train_sample_method)
+        if getattr(opt, 'train_sample_method', 'sample') == 'contrastive':
+            raise NotImplementedError("train_sample_method 'contrastive': contrastive search is a test-time option (sample_method); it "
+                                      'is deterministic and carries no gradient, a training rollout needs samples')
         if getattr(opt, 'label_smoothing', 0) > 0:
             self.crit = losses.LabelSmoothing(smoothing=opt.label_smoothing)
         else:

@@ -66,6 +66,9 @@ DEFAULTS = dict(
     # disc_distractors (1..7) other images of the batch, picked by disc_pick 'nearest' (cosine similarity of the mean-pooled region
     # features) or 'random' (seeded by seed); disc_mode: 'suppress' | 'listener'
     disc_lambda=-1.0, disc_distractors=1, disc_mode='suppress', disc_pick='nearest',
+    # contrastive search (sample_method 'contrastive', decode.contrastive_steps; not flags of the reference): the weight of the
+    # degeneration penalty in [0, 1] (0: greedy) and the number of candidates per step, 1..32
+    penalty_alpha=0.6, contrastive_k=4,
     # data (synthetic only: the reference's h5/lmdb loaders are outside the hot path)
     input_synthetic=1, vocab_size=9487, synthetic_regions=36, synthetic_images=200,
     # real precomputed features (captioning/data/feature_loader.py; opts.py:23-37 of the reference)

@@ -4,7 +4,9 @@
                                                                           block_trigrams (+ every sample_method)
     diverse_sample_steps  AttModel._diverse_sample   AttModel.py:354-447  group_size > 1 without beam search
 
-Both drive a stepper (step.py protocol; any model family) and keep every per-step edit on the device: normalisation,
+    contrastive_steps     (none: Su et al. 2022)                          sample_method 'contrastive'
+
+All drive a stepper (step.py protocol; any model family) and keep every per-step edit on the device: normalisation,
 constraints (capmi_decode_constrain), group penalties (capmi_column_penalty) and the token choice
 (capmi_select_logp) are kernels of libcapmi, the finished flags never leave the device, there is no `.item()` in the loop.
 Results follow the reference value for value, including its quirks (noted inline).
@@ -23,7 +25,7 @@ _MODES = {'greedy': 0, 'sample': 1}
 def wants_options(opt):
     """True when `opt` asks for something only the host-stepped samplers implement."""
     return bool(opt.get('decoding_constraint', 0) or opt.get('block_trigrams', 0) or opt.get('remove_bad_endings', 0)
-                or opt.get('group_size', 1) > 1 or truncation(opt) is not None)
+                or opt.get('group_size', 1) > 1 or truncation(opt) is not None or contrastive(opt))
 
 
 _KINDS = {'minp': _lib.TRUNCATE_MINP, 'eps': _lib.TRUNCATE_EPS, 'eta': _lib.TRUNCATE_ETA, 'typ': _lib.TRUNCATE_TYP}
@@ -45,6 +47,55 @@ def check_truncation(model, opt):
     if not opt.get('output_logsoftmax', 1):
         raise NotImplementedError('output_logsoftmax=0 is only used by margin structure losses; sample_method %r truncates '
                                   'log-probabilities' % name)
+
+
+def contrastive(opt):
+    """True when opt['sample_method'] names contrastive search"""
+    return bool(opt) and opt.get('sample_method', 'greedy') == 'contrastive'
+
+
+def contrastive_params(opt):
+    """(penalty_alpha, contrastive_k) of a contrastive-search call, range-checked"""
+    alpha, k = opt.get('penalty_alpha', 0.6), opt.get('contrastive_k', 4)
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0 <= alpha <= 1:
+        raise ValueError("sample_method 'contrastive': penalty_alpha must satisfy 0 <= alpha <= 1, got %r" % (alpha,))
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _lib.CONTRASTIVE_KMAX:
+        raise ValueError("sample_method 'contrastive': contrastive_k must be an integer in [1, %d], got %r" % (_lib.CONTRASTIVE_KMAX, k))
+    return float(alpha), int(k)
+
+
+def check_contrastive(model, opt):
+    """the refusals of a sample call with sample_method 'contrastive', before any device work"""
+    if not contrastive(opt):
+        return
+    name = "sample_method 'contrastive'"
+    if model.training:
+        raise NotImplementedError('%s is a test-time option: call model.eval() first' % name)
+    if not opt.get('output_logsoftmax', 1):
+        raise NotImplementedError('output_logsoftmax=0 is only used by margin structure losses; %s scores the candidates by their '
+                                  'probabilities' % name)
+    refusal = getattr(model, '_contrastive_refusal', None)
+    if refusal is not None:
+        raise NotImplementedError('%s is not implemented for %s: %s' % (name, type(model).__name__, refusal))
+    if int(opt.get('sample_n', 1)) > 1:
+        raise ValueError('%s is deterministic: sample_n = %d would return n identical rows per image' % (name, opt['sample_n']))
+    if opt.get('beam_size', 1) > 1:
+        raise ValueError('%s is a search of its own (one look-ahead step over contrastive_k candidates): beam_size must be 1, got %r'
+                         % (name, opt['beam_size']))
+    if opt.get('group_size', 1) > 1:
+        raise ValueError('%s has no groups: group_size must be 1, got %r' % (name, opt['group_size']))
+    contrastive_params(opt)
+    if float(opt.get('temperature', 1.0)) != 1.0:
+        raise ValueError("%s scores the candidates by the model's own probabilities: temperature must be 1, got %r"
+                         % (name, opt['temperature']))
+    if opt.get('distractors') is not None:
+        raise NotImplementedError("%s with opt['distractors']: the pragmatic row of discriminative decoding mixes 1 + D decoder rows "
+                                  'and has no single hidden state' % name)
+    if opt.get('constraints') is not None:
+        raise NotImplementedError("%s with opt['constraints']: constrained decoding is a beam search" % name)
+    if opt.get('return_attention', 0):
+        raise NotImplementedError('%s with return_attention: the recorder layout assumes one row per caption per step, the '
+                                  'look-ahead steps contrastive_k' % name)
 
 
 def _truncate(trunc, x, q, rows, V1, temperature, store, store_ld, unf, st):
@@ -171,3 +222,66 @@ def diverse_sample_steps(model, stepper, B, L, opt, dev, seed=0):
                                         (int(seed) + 0x9E3779B97F4A7C15 * g) & 0xFFFFFFFFFFFFFFFF, ptr(seq_tab[g]), L,
                                         ptr(it_tab[g]), ptr(unf[g]), None, ptr(slp_tab[g]), 1, flt, st), 'capmi_select_logp')
     return seq_tab.transpose(0, 1).reshape(N, L), slp_tab.transpose(0, 1).reshape(N, L)
+
+
+def contrastive_steps(model, stepper, B, L, opt, dev):
+    """Contrastive search (Su et al. 2022) on a stepper made with rows_per_image_max = contrastive_k.  Per generated token: the
+    constraints, capmi_contrastive_topk on the N rows, the reorder that fans the chosen state out to the k rows of every image, ONE
+    decoder step on the N * k candidate rows (the look-ahead: its pre-logit rows are the candidates' hidden states, its logits the
+    next step's), capmi_contrastive_select, and the gather + log-softmax of the chosen rows' logits -- plus the BOS step on N rows.
+    Returns (seq [B, L] int64, seqLogprobs [B, L, V1])."""
+    alpha, k = contrastive_params(opt)
+    V1, R, N = stepper.V1, stepper.R, B
+    if k > V1:
+        raise ValueError("sample_method 'contrastive': contrastive_k = %d exceeds the %d vocabulary rows" % (k, V1))
+    from . import beam
+    S = L + 1
+    i32 = torch.int32
+    seq = torch.zeros(N, L, dtype=torch.long, device=dev)
+    seq_logp = torch.zeros(N, L, V1, dtype=_f32, device=dev)
+    it = torch.zeros(N, dtype=torch.long, device=dev)                       # BOS
+    unf = torch.ones(N, dtype=torch.uint8, device=dev)
+    logp = torch.empty(N, V1, dtype=_f32, device=dev)
+    picked = torch.empty(1, N, V1, dtype=_f32, device=dev)                   # the chosen candidates' logits
+    hist = torch.empty(N, S, R, dtype=_f32, device=dev)
+    hist_inv = torch.empty(N, S, dtype=_f32, device=dev)
+    tok = torch.empty(N, k, dtype=torch.long, device=dev)
+    tok_logp = torch.empty(N, k, dtype=_f32, device=dev)
+    choice = torch.zeros(N, 1, dtype=i32, device=dev)
+    parent = torch.empty(N, dtype=i32, device=dev)
+    fan = torch.zeros(N, k, dtype=i32, device=dev)                           # zeros: the first reorder fans row b out to b * k + j
+    bad = torch.tensor(sorted(getattr(model, 'bad_endings_ix', [])), dtype=torch.long, device=dev)
+    st = stream_ptr()
+
+    def select(h, rows_k, hist_len, t, with_tokens):
+        # no `it` output: the look-ahead step takes its tokens from the top-k table, `it` feeds the BOS step alone
+        check(lib.capmi_contrastive_select(ptr(tok) if with_tokens else None, ptr(tok_logp) if with_tokens else None, ptr(h),
+                                           h.stride(0), ptr(hist), ptr(hist_inv), N, rows_k, R, S, hist_len, t, L, alpha,
+                                           ptr(choice), ptr(parent), ptr(fan) if with_tokens else None,
+                                           ptr(seq) if with_tokens else None, L, None,
+                                           ptr(unf) if with_tokens else None, st), 'capmi_contrastive_select')
+
+    logits = stepper.step(0, it, 1)
+    select(stepper.hidden(N), 1, 0, 0, False)                                # h_0 and its inverse norm
+    check(lib.capmi_log_softmax_rows(ptr(logits), ptr(logp), N, V1, st), 'capmi_log_softmax_rows')
+    any_flags = False
+    for t in range(L):
+        flags = _flags(opt, t)
+        if flags:
+            any_flags = True
+            check(lib.capmi_decode_constrain(ptr(logp), N, V1, _prev(seq, t), L, flags, ptr(bad), bad.numel(), ptr(seq), L, t, B,
+                                             st), 'capmi_decode_constrain')
+        check(lib.capmi_contrastive_topk(ptr(logp), V1, N, V1, k, ptr(unf), ptr(tok), ptr(tok_logp),
+                                         seq_logp.data_ptr() + 4 * t * V1, L * V1, st), 'capmi_contrastive_topk')
+        stepper.reorder(fan, 1 if t == 0 else k)                             # row i * cur + c -> all of i * k .. i * k + k - 1
+        logits_k = stepper.step(t + 1, tok.view(N * k), k)
+        select(stepper.hidden(N * k), k, t + 1, t, True)
+        if t + 1 < L:
+            beam.reorder_rows(logits_k.view(1, N * k, V1), picked, choice, N, k, 1)
+            check(lib.capmi_log_softmax_rows(ptr(picked), ptr(logp), N, V1, st), 'capmi_log_softmax_rows')
+    if any_flags:
+        # as in sample_steps: blank the columns the reference's loop would have left before writing them
+        alive = (seq != 0).cumprod(1).any(0)
+        written = torch.cat([alive.new_ones(1), alive[:-1]])
+        seq_logp = torch.where(written.view(1, L, 1), seq_logp, torch.zeros((), dtype=_f32, device=dev))
+    return seq, seq_logp

@@ -4,6 +4,7 @@ A stepper holds the recurrent state of ``B * rows_per_image_max`` hypotheses (im
 
     step(t, it, rows_per_image) -> logits [B*rows_per_image, V1]      # AttModel.get_logprobs_state up to the logits
     reorder(parent [B,bd] int32, cur)                                 # beam search: row b*cur+parent[b,j] -> b*bd+j
+    hidden(rows) -> [rows, R] view, no copy                           # the rows the logit of the last step read (contrastive search)
     snapshot() / restore(s)                                           # (scheduled host loops that fork the state)
 
 which is the protocol the Transformer ``Decoder`` and the AoA ``BeamDecoder`` already implement; the host-stepped
@@ -47,6 +48,12 @@ class _Stepper:
         src, dst = self.state[self.cur], self.state[1 - self.cur]
         beam.reorder_rows(src, dst, parent, self.B, cur, parent.shape[1])
         self.cur = 1 - self.cur
+
+    HIDDEN = 0                        # the slot of the state that the vocabulary projection reads
+
+    def hidden(self, rows):
+        """the pre-logit rows of the last step, [rows, R] (read-only view of the state; a reorder or the next step moves it)"""
+        return self.state[self.cur][self.HIDDEN, :rows]
 
 
 class _StructStepper(_Stepper):
@@ -99,6 +106,7 @@ class _OneLayerState:
 
 class UpDownStepper(_StructStepper):
     STEP = 'capmi_updown_decode_step'
+    HIDDEN = 2                        # h_lang
 
     def __init__(self, P, pr, rows_per_image_max):
         from . import updown_engine
@@ -155,6 +163,10 @@ class NewFCStepper(_Stepper):
         fc_emb = ops.linear(fc_feats.float().contiguous(), P['fc_embed.weight'], P['fc_embed.bias'], ws=self.ws)
         self._cell(fc_emb, B)                                           # one row per image, cur = 1 afterwards
 
+    def hidden(self, rows):
+        """the cell output the logit reads (under a train-mode mask: the dropped copy)"""
+        return self.state[self.cur][0, :rows] if self.drop_out is None else self.h_drop[:rows]
+
     def _cell(self, x, rows, out_mask=None):
         P, R, E = self.P, self.R, self.E
         src, dst = self.state[self.cur], self.state[1 - self.cur]
@@ -177,7 +189,7 @@ class NewFCStepper(_Stepper):
         x = ops.embed_fwd(it, self.P['embed.weight'], relu=False)      # plain Embedding (AttModel.py:908)
         mask = None if self.drop_out is None else self.drop_out[t, :rows]
         self._cell(x, rows, mask)
-        h = self.state[self.cur][0, :rows] if mask is None else self.h_drop[:rows]
+        h = self.hidden(rows)
         logits = self.logits[:rows]
         ops.gemm([(h, self.R, self.P['logit.weight'], self.R, self.R, 1)], rows, self.V1, logits, bias=self.P['logit.bias'],
                  ws=self.ws)
@@ -230,6 +242,10 @@ class AdaAttStepper(_OneLayerState, _StructStepper):
         self._bind(s, dict(xt=z(N, E), saved=z(N, W), h_drop=z(N, R), fake_drop=z(N, R), fr=z(N, E), ho_t=z(N, E), ho=z(N, E),
                            fr_e=z(N, A), ho_e=z(N, A), pi=z(N, K + 1), ctx=z(N, R), out_t=z(N, R), out_drop=z(N, R)), dev)
         self.w = adaatt_engine.weights_struct(P, ap.packs)
+
+    def hidden(self, rows):
+        """the attention output tanh(att2h(.)) the logit reads (eval numerics: out_drop is the undropped row)"""
+        return self.bufs['out_drop'][:rows]
 
 
 class EnsembleStepper:

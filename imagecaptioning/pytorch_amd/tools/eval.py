@@ -57,6 +57,13 @@ R@1 of the captions it decodes), not with --dump_attention.
 capmi_truncate_rows in front of the token choice of imagecaptioning/pytorch_amd/decode.py): wherever sample / top<k|p> are accepted,
 e.g. --sample_n 5 --sample_n_method typ0.9 --language_eval 1; the predictions and the _n.json carry no new fields.
 
+--sample_method contrastive [--penalty_alpha 0.6] [--contrastive_k 4] (contrastive search, Su et al. 2022: decode.contrastive_steps)
+decodes one caption per image that avoids repeating itself: at every step the contrastive_k most probable words are re-scored by
+(1 - penalty_alpha) p(word) - penalty_alpha max cos(hidden state after the word, hidden states so far).  updown / topdown, newfc,
+att2in2, adaatt, adaattmo, aoa (out_res 0); with --decoding_constraint, --remove_bad_endings, --block_trigrams and --language_eval, not with
+--beam_size, --sample_n_method contrastive, --temperature, --disc_lambda, --constraints_json or --dump_attention; tools/eval_ensemble.py
+reports that an ensemble has no single hidden state.
+
     python -m imagecaptioning.pytorch_amd.tools.eval --caption_model updown --beam_size 5 --num_images 20 [--start_from DIR | --model FILE]
 """
 import json
@@ -70,7 +77,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 
 
 SAMPLE_KEYS = ('sample_method', 'beam_size', 'temperature', 'suppress_UNK', 'length_penalty', 'group_size', 'diversity_lambda',
-               'decoding_constraint', 'block_trigrams', 'remove_bad_endings', 'max_length')
+               'decoding_constraint', 'block_trigrams', 'remove_bad_endings', 'max_length', 'penalty_alpha', 'contrastive_k')
 
 
 def eval_kwargs_of(opt):
@@ -89,6 +96,7 @@ def eval_split_n(model, n_predictions, fc, att, att_masks, data, opt, extra=None
     kw = eval_kwargs_of(opt)
     kw.update(extra or {})
     sample_n, method, beam_size = opt.sample_n, opt.sample_n_method, opt.beam_size
+    refuse_contrastive_n(method)
     with torch.no_grad():
         if method == 'bs':                                                  # :243-252
             kw.update(sample_n=1, beam_size=sample_n, group_size=1, sample_method='beam_search')
@@ -133,6 +141,13 @@ def eval_split_n(model, n_predictions, fc, att, att_masks, data, opt, extra=None
     return rows.to(torch.long).reshape(fc.shape[0], sample_n, -1)
 
 
+def refuse_contrastive_n(method):
+    """--sample_n_method contrastive: contrastive search is deterministic, there are no n captions to draw"""
+    if method == 'contrastive':
+        raise ValueError('sample_n_method %r: contrastive search is deterministic and would return sample_n identical captions per '
+                         'image; it is a --sample_method (with --penalty_alpha, --contrastive_k)' % method)
+
+
 def _is_truncation(method):
     """--sample_method / --sample_n_method minp<a>, eps<e>, eta<e>, typ<tau> (a parameter outside its range raises here)"""
     from imagecaptioning.pytorch_amd.captioning.models.utils import parse_truncation
@@ -171,6 +186,7 @@ def rerank_kwargs(opt):
     if not kind:
         return {}
     n, method = opt.sample_n, opt.sample_n_method
+    refuse_contrastive_n(method)
     kw = dict(rerank=kind, rerank_prior=getattr(opt, 'rerank_prior', 'uniform'), sample_n=n)
     if method == 'bs':
         kw.update(beam_size=n, group_size=1, sample_method='beam_search')

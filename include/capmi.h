@@ -976,6 +976,37 @@ int capmi_select_logp(const float *logp, int N, int V1, int step, int L, int mod
 int capmi_truncate_rows(const float *logp, int ld, float *q, int ld_q, int N, int V1, int kind, float param, float temperature,
                         int *kept, float *kept_mass, float *store, int64_t store_ld, const uint8_t *unfinished, void *stream);
 
+/* Contrastive search (Su et al. 2022), sample_method 'contrastive' (decode.contrastive_steps): at every step the k most probable
+ * tokens of a row are re-scored by  (1 - alpha) p(v) - alpha max_s cos(g_v, h_s),  g_v the pre-logit row of the decoder after it
+ * consumed candidate v and h_0 .. h_{len-1} the pre-logit rows the caption has produced so far (h_0: after BOS).
+ *
+ * capmi_contrastive_topk: tok [N, k] int64 / tok_logp [N, k] = the k largest entries of every row of logp [N, ld] in descending
+ * order, equal values by ascending token id; -inf entries are values like any other, so a row with fewer than k finite entries is
+ * filled with its lowest-numbered -inf columns.  1 <= k <= min(CAPMI_CONTRASTIVE_KMAX, V1).  store (optional):
+ * store[r * store_ld + v] = logp[r, v] * unfinished[r], as capmi_truncate_rows has it.
+ *
+ * capmi_contrastive_select, ONE launch per generated token.  In: cand_tok / cand_logp [N, k] (the top-k output), cand_h [N * k, R]
+ * with leading dimension ld (row i * k + j: candidate j of row i), hist [N, S_max, R] with hist_inv [N, S_max] = 1 / |h_s| (inf
+ * for a zero row) of which the first hist_len rows are valid, the step t of L, alpha in [0, 1].
+ *   score_j = (1 - alpha) exp(cand_logp_j) - alpha max_{s < hist_len} cos(g_j, h_s),   cos(a, b) = a.b / max(|a| |b|, 1e-8)
+ * (torch.nn.functional.cosine_similarity's clamp: a zero row gives 0); cand_logp_j = -inf scores -inf; hist_len = 0: no penalty.
+ * c = arg-max_j score_j, the lowest j on ties (all -inf: 0).  Out, each optional unless noted:
+ *   choice [N] = c, parent [N] = i * k + c, fan [N, k] = c in every column (the parent table that reorders the decoder state of
+ *   row i * k + c onto all k rows of image i, ready for the next look-ahead step);
+ *   seq[i * seq_ld + t] = it[i] = cand_tok[i, c] where unfinished[i], else 0; unfinished[i] &= token != 0;
+ *   hist[i, hist_len, :] = g_c and hist_inv[i, hist_len] = 1 / |g_c| (always written).
+ * cand_tok NULL: no token outputs; cand_logp NULL: every p is 0 -- with k = 1 and hist_len = 0 the call that files the BOS row h_0.
+ * Limits (CAPMI_EINVAL): 1 <= k <= CAPMI_CONTRASTIVE_KMAX, R >= 1 (no upper bound: rows are streamed), ld >= R, 0 <= t < L,
+ * S_max >= L + 1, 0 <= hist_len < S_max, cand_h and hist apart.  |g|^2 is summed in double (the stored inverse norm is good to a float ulp), the dots in fp32, with 16-byte loads when R % 4 == 0,
+ * ld % 4 == 0 and cand_h, hist sit on 16-byte boundaries, element by element otherwise. */
+#define CAPMI_CONTRASTIVE_KMAX 32
+int capmi_contrastive_topk(const float *logp, int ld, int N, int V1, int k, const uint8_t *unfinished, int64_t *tok,
+                           float *tok_logp, float *store, int64_t store_ld, void *stream);
+int capmi_contrastive_select(const int64_t *cand_tok, const float *cand_logp, const float *cand_h, int ld, float *hist,
+                             float *hist_inv, int N, int k, int R, int S_max, int hist_len, int t, int L, float alpha,
+                             int32_t *choice, int32_t *parent, int32_t *fan, int64_t *seq, int seq_ld, int64_t *it,
+                             uint8_t *unfinished, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Transformer captioner building blocks (BASELINE configs[3]; TransformerModel.py).  The contractions
  * (QKV / output projections, FFN, generator) run on capmi_gemm_f32 with fused bias / ReLU / dropout /
