@@ -324,7 +324,9 @@ int capmi_bn_stats(const float *x, const float *mask, int rows, int D, float *pa
 int capmi_bn_finalize(const float *partial, const float *x, const float *mask, int rows, int D, int train, float eps, float momentum,
                       float *running_mean, float *running_var, int64_t *num_batches_tracked, float *mean, float *rstd, float *count,
                       float *shift, void *stream) {
-    if (D <= 0 || !mean || !rstd || !shift || bad4(shift) || bad4(mean) || bad4(rstd) || bad4(running_mean) || bad4(running_var) || bad4(count)) return CAPMI_EINVAL;
+    if (D <= 0 || !mean || !rstd || !shift || bad4(shift) || bad4(mean) || bad4(rstd) || bad4(running_mean) || bad4(running_var) || bad4(count) ||
+        bad4(partial) || bad4(x) || bad4(mask))
+        return CAPMI_EINVAL;
     if (train && (!partial || !x || rows <= 0)) return CAPMI_EINVAL;
     if (!train && (!running_mean || !running_var)) return CAPMI_EINVAL;
     if (reinterpret_cast<uintptr_t>(num_batches_tracked) & 7) return CAPMI_EINVAL;
@@ -337,7 +339,9 @@ int capmi_bn_finalize(const float *partial, const float *x, const float *mask, i
 
 int capmi_bn_apply(const float *x, const float *mask, const float *shift, const float *rstd, const float *gamma, const float *beta,
                    float *y, int rows, int D, void *stream) {
-    if (!x || !shift || !rstd || !gamma || !beta || !y || rows <= 0 || D <= 0 || bad4(x) || bad4(y) || bad4(mask)) return CAPMI_EINVAL;
+    if (!x || !shift || !rstd || !gamma || !beta || !y || rows <= 0 || D <= 0 || bad4(x) || bad4(y) || bad4(mask) || bad4(shift) ||
+        bad4(rstd) || bad4(gamma) || bad4(beta))
+        return CAPMI_EINVAL;
     const size_t quads = (size_t)rows * ((D + 3) / 4);
     if (vec_ok(D) && aligned16(x, y))
         hipLaunchKernelGGL(bn_apply_kernel<true>, dim3(grid_for(quads)), dim3(256), 0, (hipStream_t)stream, x, mask, shift, rstd, gamma,
@@ -351,7 +355,8 @@ int capmi_bn_apply(const float *x, const float *mask, const float *shift, const 
 
 int capmi_bn_bwd_partial(const float *dy, const float *x, const float *mask, const float *mean, const float *rstd, int rows, int D,
                          float *partial, void *stream) {
-    if (!dy || !x || !mean || !rstd || !partial || rows <= 0 || D <= 0 || bad4(dy) || bad4(x) || bad4(mask) || bad4(partial))
+    if (!dy || !x || !mean || !rstd || !partial || rows <= 0 || D <= 0 || bad4(dy) || bad4(x) || bad4(mask) || bad4(partial) ||
+        bad4(mean) || bad4(rstd))
         return CAPMI_EINVAL;
     if (capmi_bn_row_blocks(rows) > 65535) return CAPMI_EINVAL;
     if (vec_ok(D) && aligned16(dy, x, partial))
@@ -373,7 +378,8 @@ int capmi_bn_colsum_parts(const float *partial, int nparts, int D, float *out0, 
 
 int capmi_bn_bwd_dx(const float *dy, const float *x, const float *mask, const float *mean, const float *rstd, const float *gamma,
                     const float *dgamma, const float *dbeta, const float *count, int train, float *dx, int rows, int D, void *stream) {
-    if (!dy || !x || !mean || !rstd || !gamma || !dx || rows <= 0 || D <= 0 || bad4(dy) || bad4(x) || bad4(dx) || bad4(mask))
+    if (!dy || !x || !mean || !rstd || !gamma || !dx || rows <= 0 || D <= 0 || bad4(dy) || bad4(x) || bad4(dx) || bad4(mask) ||
+        bad4(mean) || bad4(rstd) || bad4(gamma) || bad4(dgamma) || bad4(dbeta) || bad4(count))
         return CAPMI_EINVAL;
     if (train && (!dgamma || !dbeta || !count)) return CAPMI_EINVAL;
     const size_t quads = (size_t)rows * ((D + 3) / 4);
@@ -389,7 +395,8 @@ int capmi_bn_bwd_dx(const float *dy, const float *x, const float *mask, const fl
 
 int capmi_bn_linear_bwd(float *G, const float *db, const float *W, const float *mean, const float *rstd, const float *gamma,
                         const float *beta, int R, int D, float *partial, void *stream) {
-    if (!G || !db || !W || !mean || !rstd || !gamma || !beta || !partial || R <= 0 || D <= 0 || bad4(G) || bad4(W) || bad4(partial))
+    if (!G || !db || !W || !mean || !rstd || !gamma || !beta || !partial || R <= 0 || D <= 0 || bad4(G) || bad4(W) || bad4(partial) ||
+        bad4(db) || bad4(mean) || bad4(rstd) || bad4(gamma) || bad4(beta))
         return CAPMI_EINVAL;
     if (capmi_bn_row_blocks(R) > 65535) return CAPMI_EINVAL;
     if (vec_ok(D) && aligned16(G, W, partial))
