@@ -74,6 +74,14 @@ class SampleFilter(C.Structure):
     _fields_ = [('top_k', C.c_int), ('top_p', C.c_float)]
 
 
+LP_HIST_MAX, LP_NGRAM_MAX, LP_BAD_MAX, LP_BAD_LEN = 64, 8, 16, 4      # capmi.h CAPMI_LP_*
+
+
+class LogitsProc(C.Structure):
+    _fields_ = [('no_repeat_ngram_size', C.c_int), ('repetition_penalty', C.c_float), ('min_length', C.c_int), ('n_bad', C.c_int),
+                ('bad_len', C.c_int * LP_BAD_MAX), ('bad_words', C.c_int * (LP_BAD_MAX * LP_BAD_LEN))]
+
+
 class UpDownGrads(C.Structure):
     _fields_ = [(k, c_f) for k in (
         'embed', 'att_w_ih', 'att_w_hh', 'att_b_ih', 'att_b_hh', 'lang_w_ih', 'lang_w_hh', 'lang_b_ih', 'lang_b_hh',
@@ -394,6 +402,7 @@ SIGNATURES = {
     'capmi_decode_constrain': [_P, _I, _I, _P, _I, _I, _P, _I, _P, _I, _I, _I, _P],
     'capmi_beam_diversity': [_P, _P, _I, _I, _I, _P, _I, _I, _F, _P],
     'capmi_column_penalty': [_P, _I, _I, _P, _I, _I, _F, _P],
+    'capmi_logits_process': [_P, _I, _I, _I, _I, _I, C.POINTER(LogitsProc), _P, _I, _P, _P, _I, _I, _P, _I, _P],
     'capmi_select_logp': [_P, _I, _I, _I, _I, _I, _F, _P, _U64, _P, _I, _P, _P, _P, _P, _I, _P, _P],
     'capmi_truncate_rows': [_P, _I, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _I64, _P, _P],
     'capmi_contrastive_topk': [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I64, _P],

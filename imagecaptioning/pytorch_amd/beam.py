@@ -6,7 +6,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib, ops, updown_engine as engine
+from . import _lib, logits_proc, ops, updown_engine as engine
 from ._lib import lib, ptr, check, stream_ptr
 
 _f32 = torch.float32
@@ -37,8 +37,9 @@ def sample_beam(model, fc_feats, att_feats, att_masks, opt):
     pr = engine.prepare(P, fc_feats.float().contiguous(), att_feats.float().contiguous(),
                         None if att_masks is None else att_masks.float(), bn=model._region_bn(False))      # an eval-mode prefill
     dev = fc_feats.device
-    if group_size != 1 or opt.get('decoding_constraint', 0) or opt.get('remove_bad_endings', 0) or model._trace_req is not None:
-        # diverse groups / decoding constraints / return_attention: same kernels, host-stepped (the one-call search below has no
+    if group_size != 1 or opt.get('decoding_constraint', 0) or opt.get('remove_bad_endings', 0) or model._trace_req is not None \
+            or logits_proc.wanted(opt):
+        # diverse groups / decoding constraints / logits processors / return_attention: same kernels, host-stepped (the one-call search below has no
         # hooks and keeps no per-step weights)
         from .step import UpDownStepper
         return beam_search_steps(model, lambda rows: UpDownStepper(P, pr, rows), pr.att.shape[0], P['embed.0.weight'].shape[0],
@@ -326,11 +327,12 @@ def _decode_flags(model, opt, dev):
     return flags, bad
 
 
-def _normaliser(model, opt, V1, dev, root_temperature=1.0, renormalise=False):
+def _normaliser(model, opt, V1, dev, root_temperature=1.0, renormalise=False, edit=None):
     """-> normalise(t, logits, out, rows, prev_token): out[:rows] = log_softmax(logits / T) with the UNK column pushed down
     (CaptionModel.py:159-162), T = root_temperature at t = 0 and opt['temperature'] afterwards (:203-204); from t = 1 on
     capmi_decode_constrain against the previous tokens when decoding_constraint / remove_bad_endings are set (:152-155).
-    renormalise (sbs): edited rows go through a second log_softmax, so that they are distributions again."""
+    renormalise (sbs): edited rows go through a second log_softmax, so that they are distributions again.
+    edit(t, rows_tensor, rows) or None: one more in-place edit of the step's rows, after the others (the logits processors)."""
     temperature = float(opt.get('temperature', 1))
     unk = unk_column(model, opt, V1)
     flags, bad = _decode_flags(model, opt, dev)
@@ -339,7 +341,7 @@ def _normaliser(model, opt, V1, dev, root_temperature=1.0, renormalise=False):
 
     def normalise(t, logits, out, rows, prev_token):
         dst = out
-        if renormalise and (flags or unk >= 0):
+        if renormalise and (flags or unk >= 0 or edit is not None):
             if edited[0] is None:
                 edited[0] = torch.empty(out.shape[0], V1, dtype=_f32, device=dev)
             dst = edited[0]
@@ -348,17 +350,22 @@ def _normaliser(model, opt, V1, dev, root_temperature=1.0, renormalise=False):
         if flags and t > 0:
             check(lib.capmi_decode_constrain(ptr(dst), rows, V1, ptr(prev_token), 1, flags, ptr(bad), bad.numel(), None, 0, t, 0, st),
                   'decode_constrain')
+        if edit is not None:
+            edit(t, dst, rows)
         if dst is not out:
             check(lib.capmi_beam_logsoftmax(ptr(dst), ptr(out), rows, V1, 1.0, -1, st), 'beam_logsoftmax')
     return normalise
 
 
-def _search_loop(model, make_decoder, B, W, V1, L, opt, dev, select, trace=True, root_temperature=1.0, renormalise=False):
+def _search_loop(model, make_decoder, B, W, V1, L, opt, dev, select, trace=True, root_temperature=1.0, renormalise=False,
+                 exempt=None):
     """The loop that the beam search, the stochastic and the constrained beam search share, W rows per image: step the decoder
     (from BOS on one row per image, then on B * W rows), normalise the rows (root_temperature, renormalise: _normaliser's),
     select(t, logp_t [B * cur, V1], cur, parent_t, token_t) -- it fills the step's [B, W] slices -- and reorder the decoder's
     state; the last step only selects.  The caller makes the tables its select writes before it calls, so their zero fills precede
-    the decoder's construction on the stream.  Nothing reads the device.  Returns (logp_rows [L, B * W, V1], parent int32 / token int64 [L, B, W], and the
+    the decoder's construction on the stream.  With a logits processor on (logits_proc.py) every step's rows are edited once more
+    after the normaliser's own edits, from the histories that the parent / token tables below hold: capmi_logits_process walks the
+    parents itself (exempt int32 [B, n]: per image, words its n-gram rule spares).  Nothing reads the device.  Returns (logp_rows [L, B * W, V1], parent int32 / token int64 [L, B, W], and the
     recorders of att_trace.recording when the model wants the attention and `trace` allows it, else None)."""
     recs = None
     if trace and getattr(model, '_trace_req', None) is not None:
@@ -366,10 +373,12 @@ def _search_loop(model, make_decoder, B, W, V1, L, opt, dev, select, trace=True,
         make_decoder, recs = att_trace.recording(make_decoder, L)
     dec = make_decoder(W)
     N = B * W
-    normalise = _normaliser(model, opt, V1, dev, root_temperature, renormalise)
     logp_rows = torch.zeros(L, N, V1, dtype=_f32, device=dev)
     parent = torch.zeros(L, B, W, dtype=torch.int32, device=dev)
     token = torch.zeros(L, B, W, dtype=torch.long, device=dev)
+    proc = logits_proc.make(opt, L)                                          # None: the four options are at their defaults
+    edit = None if proc is None else (lambda t, x, rows: proc.search(x, rows, V1, t, token, parent, 1 if t == 0 else W, exempt))
+    normalise = _normaliser(model, opt, V1, dev, root_temperature, renormalise, edit)
     it, rows, cur = torch.zeros(B, dtype=torch.long, device=dev), B, 1       # BOS
     for t in range(L):
         logits = dec.step(t, it, cur)
@@ -496,7 +505,9 @@ def constrained_beam_search_steps(model, make_decoder, B, V1, L, opt, dev):
     def select(t, logp_t, cur, parent_t, token_t):
         ops.cbs_select(logp_t, sums[t & 1], tables, b, S, force_end=t == L - 1,
                        out=(parent_t, token_t, score[t], sums[(t + 1) & 1], ended[t], valid[t]))
-    logp_rows, parent, token, recs = _search_loop(model, make_decoder, B, SB, V1, L, opt, dev, select)
+    # no_repeat_ngram_size never blocks a word of the image's own constraint lists: a required word stays reachable
+    exempt = req.words.reshape(B, -1).to(dev).contiguous() if (logits_proc.wanted(opt) and B) else None
+    logp_rows, parent, token, recs = _search_loop(model, make_decoder, B, SB, V1, L, opt, dev, select, exempt=exempt)
     seq, lineage, length, state, p = ops.cbs_finalize(parent, token, score, ended, valid, tables.ncons, b, S,
                                                       length_divisors(opt.get('length_penalty', ''), L, dev))
     seq_logp = seq_logp_from_lineage(logp_rows, lineage)

@@ -36,7 +36,8 @@ def _newest_dep():
 # region_rows: the box area is a sort key and must round like numpy's separate float32 operations, likewise.
 # resident: the row norm of norm_att_feat must round like numpy's x * x followed by its float32 add.reduce, likewise.
 # truncate: x / T - max must be exactly 0 at the row maximum (the token every rule keeps) and the same bits in both arms, likewise.
-EXTRA_FLAGS = {'truncate.hip': ['-ffp-contract=off'],'region_rows.hip': ['-ffp-contract=off'], 'resident.hip': ['-ffp-contract=off'],'gemm_x3.hip': ['-fno-slp-vectorize'], 'gemm_x3w.hip': ['-fno-slp-vectorize'], 'gemm_lc.hip': ['-fno-slp-vectorize'], 'sampler.hip': ['-fno-slp-vectorize'], 'decode_opts.hip': ['-ffp-contract=off'], 'reward_mix.hip': ['-ffp-contract=off']}
+# logits_proc: the repetition penalty is one float32 multiply, the same bits as numpy's, likewise.
+EXTRA_FLAGS = {'logits_proc.hip': ['-ffp-contract=off'], 'truncate.hip': ['-ffp-contract=off'],'region_rows.hip': ['-ffp-contract=off'], 'resident.hip': ['-ffp-contract=off'],'gemm_x3.hip': ['-fno-slp-vectorize'], 'gemm_x3w.hip': ['-fno-slp-vectorize'], 'gemm_lc.hip': ['-fno-slp-vectorize'], 'sampler.hip': ['-fno-slp-vectorize'], 'decode_opts.hip': ['-ffp-contract=off'], 'reward_mix.hip': ['-ffp-contract=off']}
 
 
 def build(force=False, verbose=True):

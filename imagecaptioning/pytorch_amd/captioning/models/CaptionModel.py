@@ -52,13 +52,15 @@ class CaptionModel(nn.Module):
         [B, n] for seqs [B, n, L] / [B * n, L], or S [C, B] for seqs [C, L] with opt['pairing'] = 'cross' (score.score_captions:
         'score_norm', 'score_rows', 'temperature', 'suppress_UNK').  Every family with a single-step decoder; AttEnsemble, train
         mode and output_logsoftmax=0 are refused before any device work."""
-        from imagecaptioning.pytorch_amd import score
+        from imagecaptioning.pytorch_amd import logits_proc, score
+        logits_proc.refuse_score(opt)
         return score.score_captions(self, fc_feats, att_feats, att_masks, seqs, opt)
 
     def _sample_entry(self, *args, **kwargs):
         opt = kwargs.get('opt') or (args[3] if len(args) > 3 else None)
         if opt:
-            from imagecaptioning.pytorch_amd import decode
+            from imagecaptioning.pytorch_amd import decode, logits_proc
+            logits_proc.check_options(self, opt)                        # the logits processors: every refusal first
             decode.check_truncation(self, opt)                  # min-p / epsilon / eta / typical sampling: every refusal first
             decode.check_contrastive(self, opt)                 # contrastive search: likewise
         if self.last_disc is not None:

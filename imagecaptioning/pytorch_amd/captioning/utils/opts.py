@@ -34,6 +34,11 @@ DEFAULTS = dict(
     # eval
     beam_size=1, sample_method='greedy', temperature=1.0, suppress_UNK=1, length_penalty='', num_images=20, device='cuda',
     group_size=1, diversity_lambda=0.5, decoding_constraint=0, block_trigrams=0, remove_bad_endings=0, sample_n=1,
+    # logits processors (imagecaptioning/pytorch_amd/logits_proc.py; not flags of the reference): hard n-gram blocking (0 off, 1..8),
+    # the multiplicative penalty on words already emitted (1.0 off), the least caption length (0 off) and a JSON file of banned
+    # word sequences (a list of strings or of word lists; words outside the vocabulary as constraints_oov says); bad_words: the
+    # same on the command line, --bad_words "a man" top
+    no_repeat_ngram_size=0, repetition_penalty=1.0, min_length=0, bad_words=[], bad_words_json='',
     sample_n_method='sample', verbose_beam=0,                                # opts.py:288-330 add_eval_sample_opts
     split='test',                                                            # opts.py:314 add_eval_options
     model='',                                                                # tools/eval.py:25 --model: the state-dict file tools/eval.py loads (else <start_from>/model.pth)
@@ -83,7 +88,7 @@ DEFAULTS = dict(
 RESIDENT_DTYPES = ('fp32', 'bf16', 'fp16')
 
 
-LIST_ELEMENTS = dict(distill_from=str, distill_weights=float)      # the list-valued flags: --flag A B ...
+LIST_ELEMENTS = dict(distill_from=str, distill_weights=float, bad_words=str)      # the list-valued flags: --flag A B ...
 
 
 def add_flag(ap, k, v):

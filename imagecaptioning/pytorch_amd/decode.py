@@ -15,7 +15,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _lib, logits_proc
 from ._lib import lib, ptr, check, stream_ptr
 
 _f32 = torch.float32
@@ -25,7 +25,7 @@ _MODES = {'greedy': 0, 'sample': 1}
 def wants_options(opt):
     """True when `opt` asks for something only the host-stepped samplers implement."""
     return bool(opt.get('decoding_constraint', 0) or opt.get('block_trigrams', 0) or opt.get('remove_bad_endings', 0)
-                or opt.get('group_size', 1) > 1 or truncation(opt) is not None or contrastive(opt))
+                or opt.get('group_size', 1) > 1 or truncation(opt) is not None or contrastive(opt) or logits_proc.wanted(opt))
 
 
 _KINDS = {'minp': _lib.TRUNCATE_MINP, 'eps': _lib.TRUNCATE_EPS, 'eta': _lib.TRUNCATE_ETA, 'typ': _lib.TRUNCATE_TYP}
@@ -144,6 +144,7 @@ def sample_steps(model, stepper, B, L, opt, dev, seed=0):
     trunc = truncation(opt)
     q = torch.empty(N, V1, dtype=_f32, device=dev) if trunc else None
     any_flags = False
+    proc = logits_proc.make(opt, L)                                          # None: the four options are at their defaults
     st = stream_ptr()
     for t in range(L):
         logits = stepper.step(t, it, n)
@@ -155,6 +156,9 @@ def sample_steps(model, stepper, B, L, opt, dev, seed=0):
             # first B rows are ever blocked (AttModel.py:310, 322); kept
             check(lib.capmi_decode_constrain(ptr(logp), N, V1, _prev(seq, t), L, flags, ptr(bad), bad.numel(), ptr(seq), L, t, B,
                                              st), 'capmi_decode_constrain')
+        if proc is not None:
+            any_flags = True
+            proc.dense(logp, N, V1, t, seq, n)                               # all N rows, each from its own history seq[:, :t]
         if trunc:
             # the rule on softmax(logp / T), then a plain draw from q; seqLogprobs keeps the constrained rows, as for every sampler
             _truncate(trunc, logp, q, N, V1, temperature, seq_logp.data_ptr() + 4 * t * V1, L * V1, ptr(unf), st)

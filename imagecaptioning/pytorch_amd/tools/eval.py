@@ -27,6 +27,11 @@ that is not in the vocabulary, drop leaves such words -- and the lists they empt
 gains 'constraints_satisfied' / 'constraints_total'; <eval_results_dir>/<id>_<split>_cbs.json holds the share of images whose
 constraints were all satisfied and the mean satisfied fraction.
 
+--no_repeat_ngram_size N, --repetition_penalty X, --min_length M, --bad_words "a man" top ... and --bad_words_json FILE (a JSON list of
+strings or of word lists; words outside the vocabulary as --constraints_oov says) are the logits processors of
+imagecaptioning/pytorch_amd/logits_proc.py: they reach every decoder that keeps a history, and with --language_eval 1 the settings
+are recorded as 'logits_processors' in <eval_results_dir>/<id>_<split>.json (the key is absent when all are off).
+
 --self_retrieval 1 [--retrieval_pool 1000] [--score_norm none|length] (imagecaptioning/pytorch_amd/score.py): after decoding, the first
 caption of every evaluated image is scored against every image of its pool -- consecutive blocks of retrieval_pool images, the last
 one possibly smaller -- by log p(caption | image) (divided by the scored length under --score_norm length); every prediction gains
@@ -77,7 +82,8 @@ sys.path.insert(0, os.path.dirname(HERE))
 
 
 SAMPLE_KEYS = ('sample_method', 'beam_size', 'temperature', 'suppress_UNK', 'length_penalty', 'group_size', 'diversity_lambda',
-               'decoding_constraint', 'block_trigrams', 'remove_bad_endings', 'max_length', 'penalty_alpha', 'contrastive_k')
+               'decoding_constraint', 'block_trigrams', 'remove_bad_endings', 'max_length', 'penalty_alpha', 'contrastive_k',
+               'no_repeat_ngram_size', 'repetition_penalty', 'min_length', 'bad_words')
 
 
 def eval_kwargs_of(opt):
@@ -528,6 +534,14 @@ def eval_split(model, crit, loader, opt):
         sent = SentenceStats.for_loader(loader, split, dev, model, sample_n)
     dump = AttentionDump() if getattr(opt, 'dump_attention', 0) else None
     cons = ConstraintSet.load(opt, model.vocab)
+    if getattr(opt, 'bad_words_json', '') or getattr(opt, 'bad_words', None):
+        # --bad_words "a man" top ... and --bad_words_json FILE: word sequences -> opt['bad_words'], token-id sequences
+        from imagecaptioning.pytorch_amd import logits_proc
+        oov = getattr(opt, 'constraints_oov', 'error')
+        ids = logits_proc.bad_word_ids(list(getattr(opt, 'bad_words', None) or []), model.vocab, oov)
+        if getattr(opt, 'bad_words_json', ''):
+            ids = ids + [e for e in logits_proc.bad_words_from_file(opt.bad_words_json, model.vocab, oov) if e not in ids]
+        opt.bad_words = ids
     if cons is not None and (rerank_kw or opt.sample_n > 1):
         raise NotImplementedError('--constraints_json decodes one caption per image: it does not combine with --sample_n > 1 or --rerank')
     retr = SelfRetrieval.load(opt, cons, rerank_kw)
@@ -669,8 +683,13 @@ def language_eval(lang, preds, opt, split, sent=None):
             img_to_eval[p['image_id']] = {'image_id': p['image_id'], 'CIDEr': float(img_cider[pos]), 'caption': p['caption']}
     out_dir = getattr(opt, 'eval_results_dir', 'eval_results')
     os.makedirs(out_dir, exist_ok=True)
+    out = {'overall': lang_stats, 'imgToEval': img_to_eval}
+    from imagecaptioning.pytorch_amd import logits_proc
+    settings = {k: getattr(opt, k) for k in logits_proc.KEYS if hasattr(opt, k)}
+    if logits_proc.wanted(settings):
+        out['logits_processors'] = settings            # the settings the captions were decoded with; absent when all are off
     with open(os.path.join(out_dir, '%s_%s.json' % (getattr(opt, 'id', 'capmi'), split)), 'w') as f:
-        json.dump({'overall': lang_stats, 'imgToEval': img_to_eval}, f)
+        json.dump(out, f)
     return lang_stats
 
 

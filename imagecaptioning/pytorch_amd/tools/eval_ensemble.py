@@ -24,7 +24,8 @@ sys.path.insert(0, os.path.dirname(HERE))
 EVAL_KEYS = ('beam_size', 'sample_method', 'temperature', 'suppress_UNK', 'length_penalty', 'group_size', 'diversity_lambda',
              'decoding_constraint', 'block_trigrams', 'remove_bad_endings', 'max_length', 'num_images', 'device', 'sample_n',
              'sample_n_method', 'verbose_beam', 'split', 'language_eval', 'eval_results_dir', 'eval_oracle',
-             'sentence_stats', 'penalty_alpha', 'contrastive_k')
+             'sentence_stats', 'penalty_alpha', 'contrastive_k', 'no_repeat_ngram_size', 'repetition_penalty', 'min_length',
+             'bad_words', 'bad_words_json')
 
 
 def split_id(entry):

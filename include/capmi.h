@@ -940,6 +940,38 @@ int capmi_beam_diversity(const float *logp, float *out, int B, int cur, int V1, 
  * tokens[i*token_stride], i < n_tokens.  One call per earlier group. */
 int capmi_column_penalty(float *logp, int N, int V1, const int64_t *tokens, int n_tokens, int token_stride,
                          float diversity_lambda, void *stream);
+
+/* Logits processors (logits_proc.hip): hard n-gram blocking, repetition penalty, minimum length and banned word sequences, one
+ * launch per decode step, one wave per row, in place on logp [rows] rows of V1 floats with pitch ld.  h = the row's history of t
+ * tokens.  A row whose history holds the end token 0 is left untouched; the others get, in this order,
+ *   repetition_penalty theta > 1   logp[v] = logp[v] * theta (one fp32 multiply) for every DISTINCT word v != 0 of h
+ *   min_length m                   logp[0] = -inf while t < min(m, L - 1)
+ *   no_repeat_ngram_size n >= 1    logp[v] = -inf for every v != 0 with h[i .. i+n-2] == h[t-n+1 .. t-1] and h[i+n-1] == v for
+ *                                  some i <= t - n (n = 1: every word of h); words of exempt[img] are spared
+ *   bad_words                      entry e of bad_len[e] = k ids bad_words[e * CAPMI_LP_BAD_LEN + 0 .. k-1] (all >= 1): its last
+ *                                  id gets -inf when h ends with the k - 1 ids before it (k = 1: always) */
+#define CAPMI_LP_HIST_MAX 64
+#define CAPMI_LP_NGRAM_MAX 8
+#define CAPMI_LP_BAD_MAX 16
+#define CAPMI_LP_BAD_LEN 4
+#define CAPMI_LP_BAD_IDS 64            /* CAPMI_LP_BAD_MAX * CAPMI_LP_BAD_LEN */
+typedef struct {
+    int no_repeat_ngram_size;          /* 0 = off, else 1 .. CAPMI_LP_NGRAM_MAX */
+    float repetition_penalty;          /* 1 = off, else > 1 */
+    int min_length;                    /* 0 = off */
+    int n_bad;                         /* 0 .. CAPMI_LP_BAD_MAX */
+    int bad_len[CAPMI_LP_BAD_MAX];
+    int bad_words[CAPMI_LP_BAD_IDS];
+} capmi_logits_proc;
+/* The history is given in one of two forms.  Dense: seq [rows, seq_ld] int64, columns 0 .. t-1 (seq_ld >= t).  Back-pointer
+ * (seq NULL): the per-step tables of a search, token int64 / parent int32 [L][rows / cur at step 0 = B][W]; at t > 0 the rows are
+ * the W slots of step t - 1 (cur == W), row b * W + j has h[t-1] = token[t-1][b][j] and continues at slot parent[t-1][b][j] of step
+ * t - 2; at t = 0 the history is empty.  cur: rows per image at this step (rows % cur == 0), img = row / cur.
+ * exempt (or NULL) int32 [rows / cur][n_exempt]: per image, words the n-gram rule never blocks (entries < 1 are padding).
+ * 0 <= t < L <= CAPMI_LP_HIST_MAX, else CAPMI_EINVAL; with every option off nothing is launched. */
+int capmi_logits_process(float *logp, int ld, int rows, int V1, int t, int L, const capmi_logits_proc *p, const int64_t *seq,
+                         int seq_ld, const int64_t *token, const int32_t *parent, int W, int cur, const int32_t *exempt,
+                         int n_exempt, void *stream);
 /* Token choice from rows that ALREADY hold (constrained) log-probabilities: nothing is renormalised, the rows are
  * stored as they are times the unfinished flag (AttModel.py:333-347; -inf * 0 = NaN like there).  mode 0 arg-max,
  * 1 Categorical(logits = logp / temperature) with the optional top-k / nucleus filter.  sel_logp [N,L] (optional):
