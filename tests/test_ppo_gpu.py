@@ -39,12 +39,23 @@ def _near_clip(r, eps):
     return ((r - (1 - eps)).abs() < 1e-4) | ((r - (1 + eps)).abs() < 1e-4)
 
 
+def upstream(N, per_row):
+    """the upstream gradient the kernel tests feed the backward: [N] for per_row, else the scalar 0.7"""
+    return torch.linspace(0.5, 1.5, N, device=DEV) if per_row else torch.tensor([0.7], device=DEV)
+
+
 def _check_kernel(ln, lo, seq, scores, n, eps, klc, per_row):
     from imagecaptioning.pytorch_amd import ops
-    N = ln.shape[0]
-    u = (torch.linspace(0.5, 1.5, N, device=DEV) if per_row else torch.tensor([0.7], device=DEV))
+    u = upstream(ln.shape[0], per_row)
     out, loss_rows, rs, msum = ops.ppo_loss_fwd(ln, lo, seq, scores, n, eps, klc, per_row)
     grad = ops.ppo_loss_bwd(lo, seq, rs, msum, u, n, eps, klc, per_row)
+    check_against_ppo64(out, loss_rows, rs, grad, ln, lo, seq, scores, n, eps, klc, per_row, u)
+    return out, rs, grad
+
+
+def check_against_ppo64(out, loss_rows, rs, grad, ln, lo, seq, scores, n, eps, klc, per_row, u):
+    """what a forward and a backward launch returned (out [4], loss_rows [N] or None, row_stats [4, N, L], grad [N, L, V1], any
+    strides) against the fp64 restatement on the same inputs; u as upstream() gives it"""
     torch.cuda.synchronize()
     ref = ppo64(ln, lo, seq, scores, n, eps, klc, per_row, u=(u if per_row else 0.7))
     m = ref['mask'] > 0
@@ -71,7 +82,6 @@ def _check_kernel(ln, lo, seq, scores, n, eps, klc, per_row):
     err = (grad.double() - gref).abs()
     assert bool((err <= 2e-5 * gref.abs() + 1e-6 * float(gref.abs().max()) + 1e-30)[rowok.expand_as(err)].all()), 'grad'
     assert torch.equal(grad[~m], torch.zeros_like(grad[~m]))
-    return out, rs, grad
 
 
 @pytest.mark.parametrize('per_row', (False, True))

@@ -285,8 +285,9 @@ def test_adam_step(dev, i, name):
       clip   1.344e-07 1.117e-07 1.126e-07 -> 1e-6 (fixed), 4.47e-07, 4.50e-07
       decay  9.533e-08 4.369e-07 1.060e-07 -> 3.81e-07, 1.75e-06, 4.24e-07
       all    1.241e-07 1.452e-07 1.487e-07 -> 4.96e-07, 5.81e-07, 5.95e-07
-    The second trip of adam2_kernel's outer loop is NOT reached: grid_for caps the launch at 2048 workgroups of 256 threads, two quads
-    per thread and trip, so it takes more than 4 194 304 floats in each of p, g, m and v -- over 64 MB in total."""
+    The second trip of adam2_kernel's outer loop is not reached at these counts: grid_for caps the launch at 2048 workgroups of 256
+    threads, two quads per thread and trip, so it takes more than 4 194 304 floats in each of p, g, m and v.
+    test_grid_wrap_gpu.test_adam_wraps runs that trip (and adam_kernel's), with bounds measured on its own inputs."""
     count, arm = R.ADAM[i]
     s = R.ADAM_SETS[name]
     p0, grads = R.adam_inputs(count)
